@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: GP fit + estimate_many points/second on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c2|c3|c4] [--dump-outputs DIR] [--full]
 
 `--gpus N` with N > 1 may be started either under torch.distributed.run (one rank per GPU; RANK / WORLD_SIZE in the
 environment) or as a plain script: it then launches torch.distributed.run itself as a child process and forwards rank 0's line.
@@ -18,10 +18,18 @@ N>1 : one rank per GPU (torch.distributed over RCCL), config C4 (N=65536, d=16) 
 
 The JSON line also carries
   roofline     : the dominant kernel (fp64 MFMA GEMM) timed live with HIP events on the handle's stream
+and, with --full only (N=1; the --no-* options drop parts of it):
+  roofline.mfma_probe_tflops / vendor_dgemm_8192_tflops_same_box : the MFMA issue rate and the vendor DGEMM, timed after the steps
+  kernel_classes_from_untimed_profiling_step : every kernel class of one extra, untimed step
   cpu_baseline : the oracle (CPU restatement of the reference algorithm, "port") timed on the host
                  cores on the FULL workload when that fits --cpu-budget seconds (rank 0, N=1 only), and
   parity_vs_oracle : the GPU outputs of the timed workload compared with the oracle's.
   python_api   : the same workload through the user-facing classes, host arrays in and out.
+  propagate, likelihood_f1, spgp_c5_f3, c2, c4_one_gpu, multi_abi : the other configurations and entry points.
+
+--dump-outputs DIR (N=1) writes what the last timed step computed, the arrays gpx_predict hands its caller, as DIR/mean.npy and
+DIR/var.npy (float64, M entries each; the mean is that of the centred targets the step fits).  The inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes
@@ -438,8 +446,8 @@ def run_single(args):
         lib.gpx_free(h)
 
     # Timed region: only the dominant kernel (128x128-tile GEMM launches, ~106 per step) is bracketed with HIP events
-    # on its stream (level 1; bracketing all ~1100 launches of a step costs ~9 % of the step).  The per-class table is
-    # taken afterwards from ONE extra, untimed step at level 2.  The switch is process wide so gpx_fit is covered.
+    # on its stream (level 1; bracketing all ~1100 launches of a step costs ~9 % of the step).  With --full the per-class table
+    # is taken afterwards from ONE extra, untimed step at level 2.  The switch is process wide so gpx_fit is covered.
     os.environ["GPX_PROFILE"] = os.environ.get("GPX_BENCH_PROFILE", "1")
     for _ in range(args.warmup):
         step(False)
@@ -449,42 +457,48 @@ def run_single(args):
         step(True)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:    # before anything else runs on mean_d / var_d: the last timed step's outputs
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "mean.npy"), mean_d.cpu().numpy())
+        np.save(os.path.join(args.dump_outputs, "var.npy"), var_d.cpu().numpy())
 
     value = (N + M) * args.steps / elapsed
     g_n, g_ms, g_flops = prof[_gpx.K_GEMM]
     table_prof = {k: list(v) for k, v in prof.items()}
-    if os.environ["GPX_PROFILE"] != "2":
+    table_steps = None
+    if os.environ["GPX_PROFILE"] == "2":
+        table_steps = args.steps
+    elif args.full:
         for k in prof:
             prof[k] = [0, 0.0, 0.0]
         os.environ["GPX_PROFILE"] = "2"
         step(True, clock=False)
         torch.cuda.synchronize()
         table_prof, table_steps = prof, 1
-    else:
-        table_steps = args.steps
     # the sections below (propagation, Python classes, likelihood, SPGP, C2 / C4) are timed WITHOUT event bracketing: left at level 2
     # (all ~600 launches of a fit bracketed) the Python-API fit read 28.9 ms where it takes 27.1 (tools/probe_python_overhead.py)
     os.environ["GPX_PROFILE"] = "0"
     achieved = g_flops / (g_ms * 1e-3) / 1e12 if g_ms > 0 else 0.0
-    # known-good references on the same box: (i) the issue rate of v_mfma_f64_16x16x4_f64 itself (gpx_bench_mfma_f64: what `peak`
-    # stands for, re-measured here), (ii) the vendor DGEMM (rocBLAS through torch) on an 8192^3 NT product -- best of 5 after 3
-    # warm-ups (a single cold shot read 34 TFLOP/s in round 3's driver run against 74 warm)
-    probe_tf = ctypes.c_double()
-    mfma_probe = probe_tf.value if lib.gpx_bench_mfma_f64(4096, ctypes.byref(probe_tf)) == 0 else None
-    a_ = torch.randn(8192, 8192, dtype=torch.float64, device=dev)
-    for _ in range(3):
-        c_ = a_ @ a_.T
-    torch.cuda.synchronize()
-    best_ms = 1e30
-    for _ in range(5):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        c_ = a_ @ a_.T
-        e1.record()
+    if args.full:
+        # known-good references on the same box: (i) the issue rate of v_mfma_f64_16x16x4_f64 itself (gpx_bench_mfma_f64: what `peak`
+        # stands for, re-measured here), (ii) the vendor DGEMM (rocBLAS through torch) on an 8192^3 NT product -- best of 5 after 3
+        # warm-ups (a single cold shot once read 34 TFLOP/s against 74 warm)
+        probe_tf = ctypes.c_double()
+        mfma_probe = probe_tf.value if lib.gpx_bench_mfma_f64(4096, ctypes.byref(probe_tf)) == 0 else None
+        a_ = torch.randn(8192, 8192, dtype=torch.float64, device=dev)
+        for _ in range(3):
+            c_ = a_ @ a_.T
         torch.cuda.synchronize()
-        best_ms = min(best_ms, e0.elapsed_time(e1))
-    vendor_tf = 2.0 * 8192 ** 3 / (best_ms * 1e-3) / 1e12
-    del a_, c_
+        best_ms = 1e30
+        for _ in range(5):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            c_ = a_ @ a_.T
+            e1.record()
+            torch.cuda.synchronize()
+            best_ms = min(best_ms, e0.elapsed_time(e1))
+        vendor_tf = 2.0 * 8192 ** 3 / (best_ms * 1e-3) / 1e12
+        del a_, c_
 
     traffic, traffic_src = None, None
     try:   # HBM bytes per launch of the dominant kernel from the committed rocprofv3 --pmc passes (same workload)
@@ -538,13 +552,18 @@ def run_single(args):
             "launches_per_step": g_n / max(1, args.steps),
             "avg_launch_ms": g_ms / max(1, g_n),
             "flops_per_step": g_flops / max(1, args.steps),
-            "mfma_probe_tflops": mfma_probe,           # back-to-back v_mfma_f64_16x16x4_f64 on this box (the denominator, re-measured)
-            "vendor_dgemm_8192_tflops_same_box": vendor_tf,   # best of 5 after 3 warm-ups
         },
-        "kernel_classes_from_untimed_profiling_step": {
-            _gpx.KERNEL_CLASS_NAMES[k]: {"launches": table_prof[k][0] / table_steps, "ms": table_prof[k][1] / table_steps,
-                                         "work": table_prof[k][2] / table_steps} for k in range(NCLS) if table_prof[k][0]},
     }
+    if args.full:
+        out["roofline"]["mfma_probe_tflops"] = mfma_probe                   # back-to-back v_mfma_f64_16x16x4_f64 on this box (the denominator, re-measured)
+        out["roofline"]["vendor_dgemm_8192_tflops_same_box"] = vendor_tf    # best of 5 after 3 warm-ups
+    if table_steps:
+        out["kernel_classes_from_untimed_profiling_step"] = {
+            _gpx.KERNEL_CLASS_NAMES[k]: {"launches": table_prof[k][0] / table_steps, "ms": table_prof[k][1] / table_steps,
+                                         "work": table_prof[k][2] / table_steps} for k in range(NCLS) if table_prof[k][0]}
+    if not args.full:
+        print(json.dumps(out))
+        return
     if not args.no_propagate:
         out["propagate"] = propagate_section(lib, _gpx, vp, xd, td, th, N, d)
     if not args.no_python_api:
@@ -616,13 +635,23 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/mean.npy and DIR/var.npy (float64; one GPU only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also measure and check everything else: MFMA issue-rate and vendor DGEMM probes, "
+                         "the per-kernel-class table, propagation, Python classes, likelihood, SPGP, C2 / C4 / multi-ABI points, "
+                         "the CPU baseline and the parity checks against the oracle (the --no-* options below drop parts of it)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg (and the parity check against it)")
     ap.add_argument("--cpu-budget", type=float, default=240.0, help="seconds the CPU baseline may take (full workload if it fits)")
     ap.add_argument("--no-python-api", action="store_true", help="skip the second figure through the Python classes")
     ap.add_argument("--no-propagate", action="store_true", help="skip the (untimed) propagate_GA section and its parity check against the oracle")
     ap.add_argument("--no-extras", action="store_true", help="skip the (untimed) likelihood (f1), SPGP config-5 (f3), C2 and one-GPU C4 figures")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if args.dump_outputs and (args.gpus > 1 or world > 1 or os.environ.get("GPX_BENCH_SHARDED")):
+        ap.error("--dump-outputs: only the single-GPU path (--gpus 1) writes its outputs")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and not os.environ.get("GPX_BENCH_SHARDED"):
         raise SystemExit(self_launch(sys.argv[1:], args.gpus))    # (imported and called as main(): the module-level launcher did not run)
     rehearsal = bool(os.environ.get("GPX_BENCH_SHARDED"))    # diagnostic: the sharded code path with ONE rank (world size 1)

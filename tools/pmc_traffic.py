@@ -38,7 +38,7 @@ def main():
     f_raw = sum(allk[k]["FETCH_SIZE_KB"] for k in dom) * 1024.0
     w = sum(allk[k]["WRITE_SIZE_KB"] for k in dom) * 1024.0
     out = {
-        "command": "rocprofv3 --pmc FETCH_SIZE (and, separately, --pmc WRITE_SIZE) --output-format csv -- python3 bench.py --steps 1 --warmup 0 --no-cpu --no-propagate --no-extras --no-python-api",
+        "command": "rocprofv3 --pmc FETCH_SIZE (and, separately, --pmc WRITE_SIZE) --output-format csv -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu --no-propagate --no-extras --no-python-api",
         "workload": "C3: N=16384 d=8 M=16384; every fit+estimate_many step the command runs (timed + untimed profiling step)",
         "kernel": "gemm_nt_f64_kernel<4,4,*> + gemm_nt_f64_trap_signal_kernel + gemm_nt_f64_reduce_kernel (128x128 tile launches: the bulk of the flops)",
         "launches": launches,
