@@ -228,7 +228,8 @@ enum {
     GPX_K_GEMM_SMALL = 7,/* the same GEMM kernel in its 64/32-row tile variants (critical-path products) */
     GPX_K_TRSV_RIDE = 8, /* the part of the alpha solve that runs underneath the factorisation's tail (square inverses,
                           * forward substitution of the finished panels): off the critical path, timed under contention */
-    GPX_K_COUNT = 9
+    GPX_K_GEMM_EMU = 9,  /* estimate_many's deep updates as int8 residue products (split + int8 MFMA + rebuild; fp64-equivalent flops) */
+    GPX_K_COUNT = 10
 };
 /* level 0 = off, 1 = bracket only the dominant kernel (GPX_K_GEMM: 128x128-tile launches), 2 = every class.
  * Environment variable GPX_PROFILE=<level> sets the level of handles at creation (covers gpx_fit itself). */
@@ -238,6 +239,13 @@ int gpx_profile_read(gpx_handle *h, int kernel_class, int64_t *launches, double 
 
 /* ---- device micro-benchmarks used to re-verify the roofline denominators on the box ---- */
 int gpx_bench_mfma_f64(int iters, double *tflops);          /* back-to-back v_mfma_f64_16x16x4_f64 */
+/* the int8 residue product of the emulated update alone (rows, cols multiples of 256, K of 128, K < 2^17), random residues,
+ * nmod moduli in one launch: mean time per launch */
+int gpx_bench_emu_i8(int64_t rows, int64_t cols, int64_t K, int nmod, int iters, double *ms);
+/* C[rows, cols] -= A[rows, K] B[cols, K]^T on device buffers (row-major fp64) through the emulated update (Ozaki scheme II on int8
+ * matrix cores; GPX_EMU_MODULI moduli); K a multiple of 128 below 2^17.  Synchronous. */
+int gpx_emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t rows, int64_t cols,
+                        int64_t K);
 int gpx_bench_hbm(int64_t bytes, int iters, double *write_gbs, double *copy_gbs);
 /* mode 0: MFMA f64 only, 1: VALU v_fma_f64 only, 2: half the waves each; `blocks` workgroups of 4 waves.
  * cycles_per_inst from s_memtime, clock_ghz from s_memtime / s_memrealtime (the clock held under load). */

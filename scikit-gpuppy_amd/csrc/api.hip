@@ -750,6 +750,15 @@ static int predict_common(gpx_handle *h, const double *xs, const double *kv, con
         dfree(Zs); if (xq) dfree(xq); if (xqw) dfree(xqw); if (mv) dfree(mv); if (kd) dfree(kd);
         return rc;
     }
+    // the emulated updates' workspace (emu.hip), once per call: sized for the chunk, it serves every shorter one
+    EmuWork ew;
+    if (!few) trsm_emu_need(ew, chunk, &h->tri, 0, h->tri.P);
+    if (ew.a_bytes && (rc = emu_work_alloc(ew))) {
+        dfree(Zs); dfree(xq); dfree(xqw); dfree(mv); dfree(kd);
+        if (part) dfree(part);
+        return rc;
+    }
+    const EmuWork *emu = ew.ra ? &ew : nullptr;
     for (int64_t m0 = 0; m0 < m && rc == 0; m0 += chunk) {
         const int64_t mc = std::min<int64_t>(chunk, m - m0), mp = round_up(mc, TILE);
         hipError_t e = hipSuccess;
@@ -771,7 +780,7 @@ static int predict_common(gpx_handle *h, const double *xs, const double *kv, con
         if (fused && mp >= 3072) {
             GemmReduce red;
             red.y = h->y; red.p2 = part; red.py = part + chunk * nslots; red.nslots = nslots;
-            if ((rc = trsm_right_lt_squares(h->Z, Zs, h->npad, mp, &h->tri, 0, h->tri.P, s, &h->prof, &red))) break;
+            if ((rc = trsm_right_lt_squares(h->Z, Zs, h->npad, mp, &h->tri, 0, h->tri.P, s, &h->prof, &red, emu))) break;
             ProfScope ps(&h->prof, s, GPX_K_REDUCE, 16.0 * (double)mc * (double)nslots);
             if ((rc = launch_predict_finish(red.p2, red.py, nslots, mc, h->v + h->vt, mv, mv + chunk, s, xs ? nullptr : kd))) break;
         } else if (few) {
@@ -781,7 +790,7 @@ static int predict_common(gpx_handle *h, const double *xs, const double *kv, con
             if ((rc = h->tri.solve(h->Z, h->npad, (int)mc, Zs, nullptr, s, &h->prof))) break;
             if ((rc = launch_predict_reduce(Zs, h->npad, mc, h->npad, h->y, h->v + h->vt, mv, mv + chunk, s, &h->prof, xs ? nullptr : kd))) break;
         } else {
-            if ((rc = trsm_right_lt_squares(h->Z, Zs, h->npad, mp, &h->tri, 0, h->tri.P, s, &h->prof))) break;
+            if ((rc = trsm_right_lt_squares(h->Z, Zs, h->npad, mp, &h->tri, 0, h->tri.P, s, &h->prof, nullptr, emu))) break;
             if ((rc = launch_predict_reduce(Zs, h->npad, mc, h->npad, h->y, h->v + h->vt, mv, mv + chunk, s, &h->prof, xs ? nullptr : kd))) break;
         }
         e = hipMemcpyAsync(mean_out + m0, mv, sizeof(double) * mc, hipMemcpyDefault, s);
@@ -790,6 +799,7 @@ static int predict_common(gpx_handle *h, const double *xs, const double *kv, con
         if (e != hipSuccess) { gpx_set_error("predict copy-out failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
     }
     (void)hipStreamSynchronize(s);
+    emu_work_free(ew);
     dfree(Zs);
     dfree(xq);
     dfree(xqw);

@@ -217,8 +217,12 @@ int trsm_right_lt(double *Z, int64_t ldz, int64_t rows, const double *L, int64_t
 struct TriSolver;
 // red (optional; p2 / py zeroed by the caller, y = the vector at column 0, nslots = ldz / 64): every slab's leaf product also leaves the
 // row sums  sum_c Zs_rc^2, sum_c Zs_rc y_c  of its columns in the slots of those columns
+// emu (estimate_many only; a workspace grown by trsm_emu_need for at least these rows): the deep updates go through emu_gemm_nt_sub
+// where emu_enabled(K) holds
+struct EmuWork;
 int trsm_right_lt_squares(double *Z, double *Zs, int64_t ldz, int64_t rows, const TriSolver *ts, int64_t p0, int64_t p1,
-                          hipStream_t s, Profiler *prof, const GemmReduce *red = nullptr);
+                          hipStream_t s, Profiler *prof, const GemmReduce *red = nullptr, const EmuWork *emu = nullptr);
+void trsm_emu_need(EmuWork &w, int64_t rows, const TriSolver *ts, int64_t p0, int64_t p1);
 int launch_slab_reduce(const double *Zs, int64_t ldz, int64_t rows, int64_t width, const double *y, double *p2, double *py, int64_t nslots, int64_t slot,
                        hipStream_t s);
 int launch_predict_finish(const double *p2, const double *py, int64_t nslots, int64_t m, double vplusvt, double *mean, double *var, hipStream_t s,
@@ -238,6 +242,20 @@ int launch_predict_reduce(const double *Z, int64_t ldz, int64_t m, int64_t npad,
                           double *mean, double *var, hipStream_t s, Profiler *prof, const double *kdiag = nullptr);
 int launch_set_identity(double *Z, int64_t ld, int64_t n, hipStream_t s);
 int launch_symmetrize_lower(double *A, int64_t ld, int64_t n, hipStream_t s);
+
+// fp64 product emulated on int8 matrix cores (emu.hip, Ozaki scheme II): C[rows, cols] -= A[rows, K] B[cols, K]^T, row-major;
+// K a multiple of 128 below 2^17.  emu_enabled(K): GPX_EMU_F64 (default 1) and K >= GPX_EMU_MIN_K (default 4096); the path depends on K only.
+// Workspace (int8 residues of A / B tiles, product residues, row scales), owned by the caller: emu_work_need grows it to cover a product's
+// shape, emu_work_alloc takes it from the pool (dalloc), emu_work_free returns it once the work queued with it has finished.
+struct EmuWork { int8_t *ra = nullptr, *rb = nullptr, *rr = nullptr; int *sig = nullptr; int64_t a_bytes = 0, b_bytes = 0, r_bytes = 0, sig_n = 0; };
+void emu_work_need(EmuWork &w, int64_t rows, int64_t cols, int64_t K);
+int emu_work_alloc(EmuWork &w);
+void emu_work_free(EmuWork &w);
+int emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t rows, int64_t cols, int64_t K,
+                    const EmuWork &w, hipStream_t s, Profiler *prof);
+bool emu_enabled(int64_t K);
+int emu_moduli();                        // GPX_EMU_MODULI (default 16, 2 .. 16)
+int emu_scale_bits(int64_t K, int L);    // alpha + beta: the largest s with K 2^s < P / 2
 
 // device selection (api.hip): hipSetDevice to the calling thread's gpx_set_device choice, gfx950 only
 int gpx_require_device();

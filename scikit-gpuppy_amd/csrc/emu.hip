@@ -1,0 +1,434 @@
+// emu.hip -- fp64 products C -= A B^T emulated on the int8 matrix cores (Ozaki scheme II) for gfx950.
+//
+// estimate_many's deep TRSM updates (tsolve.hip, trsm_right_lt_squares) are full rectangular NT products with K = 4096 .. 32768.  fp64 MFMA
+// runs at 78.6 TFLOP/s; v_mfma_i32_32x32x32_i8 retires 2048 int8 ops per clock per SIMD (~5 POPS).  Scheme II:
+//   1. split   : row i of A is scaled by 2^sig_i so that |a_ik 2^sig_i| <= 2^alpha and rounded to the integer a'_ik (exact in fp64, at most
+//                56 bits); likewise row j of B with tau_j and beta.  Every a'_ik is stored as its symmetric residues mod L pairwise coprime
+//                moduli p_l (int8).
+//   2. products: one exact int8 -> int32 GEMM per modulus (|residue| <= 128, so |sum| <= K 2^14 < 2^31 for K < 2^17), reduced mod p_l in
+//                the epilogue and stored as one byte.
+//   3. rebuild : per entry, Garner's mixed-radix digits of the L residues (balanced digits, fp32 arithmetic on integers < 2^17: exact),
+//                then the integer X = sum_i a'_ik b'_jk by an exact 128-bit Horner pass, rounded once to fp64 (two roundings in all:
+//                |fl(X) - X| <= 1 ulp), and C_ij -= X 2^-(sig_i + tau_j).
+// alpha + beta is the largest integer with K 2^(alpha+beta) < P / 2 (P = p_1 .. p_L): the residues then determine X uniquely.  At L = 16
+// (log2 P = 125.2) and K = 8192 that is alpha = 56, beta = 55: every row's largest entries are converted exactly, an entry 2^-e below its
+// row's largest keeps 55 - e bits.  Each output row depends only on its own row of A and on B, whatever the tiling.
+#include <math.h>
+#include <stdlib.h>
+#include <algorithm>
+
+#include "common.h"
+
+#include "gemm_tile.h"
+
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef int v16i __attribute__((ext_vector_type(16)));
+
+constexpr int EMU_MAXL = 16;
+constexpr int EMU_BT = 256;   // int8 block tile: 256 x 256, 2 x 4 waves of 128 x 64 (4 x 2 MFMAs of 32 x 32), two waves per SIMD
+constexpr int EMU_BK = 128;   // k bytes per LDS stage (one 128-byte row per operand row, the fp64 kernel's image geometry)
+
+// pairwise coprime (256 = 2^8, 255 = 3 5 17, 253 = 11 23, 247 = 13 19, the rest prime); the first L are used
+constexpr int EMU_MODULI[EMU_MAXL] = {256, 255, 253, 251, 247, 241, 239, 233, 229, 227, 223, 211, 199, 197, 193, 191};
+
+struct EmuGarner { float c[EMU_MAXL][EMU_MAXL]; };   // c[j][k] = p_j^-1 mod p_k (j < k)
+constexpr EmuGarner emu_garner_table()
+{
+    EmuGarner g{};
+    for (int k = 0; k < EMU_MAXL; ++k)
+        for (int j = 0; j < k; ++j) {
+            const int pk = EMU_MODULI[k], a = EMU_MODULI[j] % pk;
+            int inv = 0;
+            for (int x = 1; x < pk; ++x)
+                if (a * x % pk == 1) { inv = x; break; }
+            g.c[j][k] = (float)inv;
+        }
+    return g;
+}
+static __constant__ const int emu_p[EMU_MAXL] = {256, 255, 253, 251, 247, 241, 239, 233, 229, 227, 223, 211, 199, 197, 193, 191};
+static __constant__ const EmuGarner emu_garner = emu_garner_table();
+
+constexpr int EMU_NONFINITE = 0x7fffffff;   // row scale of a row that holds a NaN or an Inf: its outputs are NaN
+
+// ---- switches (read once per process) -----------------------------------------------------------------------------
+int emu_moduli()
+{
+    static const int v = [] { const char *e = getenv("GPX_EMU_MODULI"); const int l = e ? atoi(e) : EMU_MAXL; return std::min(EMU_MAXL, std::max(2, l)); }();
+    return v;
+}
+bool emu_enabled(int64_t K)
+{
+    static const int on = [] { const char *e = getenv("GPX_EMU_F64"); return e ? atoi(e) : 1; }();
+    static const long min_k = [] { const char *e = getenv("GPX_EMU_MIN_K"); return e ? atol(e) : 4096L; }();
+    return on && K >= min_k && K < (1 << 17) && K % EMU_BK == 0;
+}
+// alpha + beta: the largest integer s with K 2^s < P / 2
+int emu_scale_bits(int64_t K, int L)
+{
+    double log2p = 0.0;
+    for (int l = 0; l < L; ++l) log2p += log2((double)EMU_MODULI[l]);
+    return (int)floor(log2p - 1.0 - log2((double)K) - 1e-9);
+}
+
+// ---- split: one workgroup per row of X [rows, K] (fp64, ldx) -> residue planes res[l][row][K] (int8) and the row's scale exponent ----
+// rows >= rows_real are padding: zero residues.  The integer a' = rint(x 2^sig) (|a'| <= 2^bits) is exact in fp64; its residue mod p is
+// a' - p q with q = rint(a' / p) off by at most one (the fma is exact: the result is a small integer), then made symmetric.
+__global__ __launch_bounds__(256) void emu_split_kernel(const double *__restrict__ X, long ldx, long rows_real, int K, int bits, int L,
+                                                        int8_t *__restrict__ res, long plane, int *__restrict__ sig)
+{
+    const long row = blockIdx.x;
+    const int t = threadIdx.x;
+    __shared__ double red_max[4];
+    __shared__ int red_bad[4];
+    int8_t *out = res + row * (long)K;
+    if (row >= rows_real) {
+        for (int c = 4 * t; c < K; c += 1024)
+            for (int l = 0; l < L; ++l) *reinterpret_cast<int *>(out + l * plane + c) = 0;
+        if (t == 0) sig[row] = 0;
+        return;
+    }
+    const double *x = X + row * ldx;
+    double m = 0.0;
+    int bad = 0;
+    for (int c = 2 * t; c < K; c += 512) {
+        const v2d v = *reinterpret_cast<const v2d *>(x + c);
+        bad |= (int)!isfinite(v.x) | (int)!isfinite(v.y);
+        m = fmax(m, fmax(fabs(v.x), fabs(v.y)));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { m = fmax(m, __shfl_xor(m, o)); bad |= __shfl_xor(bad, o); }
+    if ((t & 63) == 0) { red_max[t >> 6] = m; red_bad[t >> 6] = bad; }
+    __syncthreads();
+    m = fmax(fmax(red_max[0], red_max[1]), fmax(red_max[2], red_max[3]));
+    bad = red_bad[0] | red_bad[1] | red_bad[2] | red_bad[3];
+    // |x| 2^s < 2^bits for the row's largest |x| in [2^e, 2^(e+1)); an all-zero row keeps s = 0 (its residues are 0)
+    const int s = (bad || m == 0.0) ? 0 : bits - 1 - ilogb(m);
+    if (t == 0) sig[row] = bad ? EMU_NONFINITE : s;
+    for (int c = 4 * t; c < K; c += 1024) {
+        const v2d v0 = *reinterpret_cast<const v2d *>(x + c), v1 = *reinterpret_cast<const v2d *>(x + c + 2);
+        double a[4] = {rint(ldexp(v0.x, s)), rint(ldexp(v0.y, s)), rint(ldexp(v1.x, s)), rint(ldexp(v1.y, s))};
+        if (bad) a[0] = a[1] = a[2] = a[3] = 0.0;
+#pragma unroll
+        for (int l = 0; l < EMU_MAXL; ++l) {
+            if (l >= L) continue;
+            const double p = (double)emu_p[l], pinv = 1.0 / p, h = 0.5 * p;
+            unsigned packed = 0;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                double r = fma(-rint(a[e] * pinv), p, a[e]);
+                r = r > h ? r - p : (r < -h ? r + p : r);      // [-p/2, p/2]; 256 wraps to -128 in the byte (same residue)
+                packed |= ((unsigned)(int)r & 0xffu) << (8 * e);
+            }
+            *reinterpret_cast<unsigned *>(out + l * plane + c) = packed;
+        }
+    }
+}
+
+// ---- products: R_l = (A_l B_l^T) mod p_l, int8 in, int32 accumulate, one byte out -----------------------------------------------------
+// One launch covers every modulus: workgroup -> (l, by, bx) in an XCD-aware order (each XCD takes a contiguous chunk of the logical order;
+// inside a modulus groups of 8 tile rows, column-major, so the tiles resident on an XCD share A and B panels through its L2).
+// LDS image, staging and swizzle as gemm_tile.h: per stage [256][128 B] of A then of B, filled by LDS-DMA (16 B per lane, 8 rows per
+// wave-instruction), granule index XOR (row >> 1) & 7 on the source address and on the fragment reads; a 32 x 32 x 32 fragment is one
+// ds_read_b128 per lane (row lane & 31, k-bytes 16 (lane >> 5) .. +15 of a 32-byte slice), conflict-free under that swizzle.
+// A, B: planes of [tm 256][K] and [tn 256][K] bytes (lda = ldb = K); R: planes of [tm 256][ldr] bytes.
+__global__ __launch_bounds__(512, 1) void emu_i8_gemm_kernel(const int8_t *__restrict__ A, const int8_t *__restrict__ B, long sa, long sb, int K,
+                                                             int8_t *__restrict__ R, long ldr, long sr, int tm, int tn)
+{
+    __shared__ __attribute__((aligned(1024))) int8_t smem[2 * 2 * EMU_BT * EMU_BK];   // 128 KiB: two stages of A and B
+    constexpr int STAGE = 2 * EMU_BT * EMU_BK;
+    const int nwg = gridDim.x, orig = blockIdx.x;
+    const int lid = xcd_chunk_start(nwg, orig & 7) + (orig >> 3);
+    const int per = tm * tn, z = lid / per;
+    int rem = lid - z * per;
+    const int g = rem / (8 * tn), first = 8 * g, grows = std::min(8, tm - first);
+    rem -= g * 8 * tn;
+    const int bx = rem / grows, by = first + rem - bx * grows;
+
+    const int t = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
+    const int wr = wave >> 2, wc = wave & 3;
+    const int drow = lane >> 3;
+    const char *Abase = reinterpret_cast<const char *>(A + z * sa + (long)by * EMU_BT * K);
+    const char *Bbase = reinterpret_cast<const char *>(B + z * sb + (long)bx * EMU_BT * K);
+    unsigned off[4];   // instruction u of this wave covers rows 8 (wave + 8 u) .. +7 of either operand's 256-row panel
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int row = 8 * (wave + 8 * u) + drow;
+        off[u] = (unsigned)((long)row * K + 16 * ((lane & 7) ^ ((row >> 1) & 7)));
+    }
+    const unsigned lds_base = (unsigned)(unsigned long)(__attribute__((address_space(3))) int8_t *)smem;
+#define EMU_DMA_ONE(SBASE, VOFF, LDSBYTES) \
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(LDSBYTES), "v"(VOFF), "s"(SBASE) : "memory");
+#define EMU_DMA_STAGE(BUF, KT)                                                                                              \
+    {                                                                                                                       \
+        const char *ak_ = gpx_uniform_ptr(Abase + (long)(KT) * EMU_BK);                                                     \
+        const char *bk_ = gpx_uniform_ptr(Bbase + (long)(KT) * EMU_BK);                                                     \
+        _Pragma("unroll") for (int u_ = 0; u_ < 4; ++u_)                                                                    \
+            EMU_DMA_ONE(ak_, off[u_], __builtin_amdgcn_readfirstlane(lds_base + (unsigned)((BUF) * STAGE + (wave + 8 * u_) * 1024)))  \
+        _Pragma("unroll") for (int u_ = 0; u_ < 4; ++u_)                                                                    \
+            EMU_DMA_ONE(bk_, off[u_], __builtin_amdgcn_readfirstlane(lds_base + (unsigned)((BUF) * STAGE + EMU_BT * EMU_BK + (wave + 8 * u_) * 1024))) \
+    }
+    const int nk = K / EMU_BK;
+    EMU_DMA_STAGE(0, 0)
+    v16i acc[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = (v16i){};
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+
+    const int fr = lane & 31, sw = (fr >> 1) & 7;
+    int koff[4];
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) koff[kk] = 16 * ((2 * kk + (lane >> 5)) ^ sw);
+    const int a_row = (wr * 128 + fr) * EMU_BK, b_row = EMU_BT * EMU_BK + (wc * 64 + fr) * EMU_BK;
+    typedef const __attribute__((address_space(3))) v4i lds_v4i;
+    const __attribute__((address_space(3))) int8_t *lsm = (const __attribute__((address_space(3))) int8_t *)smem;
+    v4i fa[2][4], fb[2][2];
+#define EMU_LOAD_FRAGS(SET, BUFOFF, KK)                                                              \
+    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                 \
+        fa[SET][i_] = *(lds_v4i *)(lsm + (BUFOFF) + a_row + i_ * 32 * EMU_BK + koff[KK]);            \
+    _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_)                                                 \
+        fb[SET][i_] = *(lds_v4i *)(lsm + (BUFOFF) + b_row + i_ * 32 * EMU_BK + koff[KK]);
+#define EMU_MMA(SET)                                                                                 \
+    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                 \
+        _Pragma("unroll") for (int j_ = 0; j_ < 2; ++j_)                                             \
+            acc[i_][j_] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[SET][i_], fb[SET][j_], acc[i_][j_], 0, 0, 0);
+    EMU_LOAD_FRAGS(0, 0, 0)
+#define EMU_KSTEP(CUR_OFF, NXT_OFF, NXT_BUF, KT)                   \
+    {                                                             \
+        const bool has_next_ = (KT) + 1 < nk;                     \
+        if (has_next_) EMU_DMA_STAGE(NXT_BUF, (KT) + 1)           \
+        EMU_LOAD_FRAGS(1, CUR_OFF, 1)                             \
+        EMU_MMA(0)                                                \
+        __builtin_amdgcn_sched_barrier(0);                        \
+        EMU_LOAD_FRAGS(0, CUR_OFF, 2)                             \
+        EMU_MMA(1)                                                \
+        __builtin_amdgcn_sched_barrier(0);                        \
+        EMU_LOAD_FRAGS(1, CUR_OFF, 3)                             \
+        EMU_MMA(0)                                                \
+        __builtin_amdgcn_sched_barrier(0);                        \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          \
+        __syncthreads();                                          \
+        if (has_next_) { EMU_LOAD_FRAGS(0, NXT_OFF, 0) }          \
+        EMU_MMA(1)                                                \
+        __builtin_amdgcn_sched_barrier(0);                        \
+    }
+    for (int kt = 0; kt < nk; kt += 2) {
+        EMU_KSTEP(0, STAGE, 1, kt)
+        if (kt + 1 < nk) EMU_KSTEP(STAGE, 0, 0, kt + 1)
+    }
+#undef EMU_KSTEP
+#undef EMU_LOAD_FRAGS
+#undef EMU_MMA
+#undef EMU_DMA_STAGE
+#undef EMU_DMA_ONE
+
+    // epilogue: accumulator register r of tile (i, j) is row (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column lane & 31; |v| < 2^31 is exact
+    // in fp64 and v / p is never within 1 / (2p) of a half-integer for odd p (256: a tie wraps to the same byte)
+    const double p = (double)emu_p[z], pinv = 1.0 / p;
+    int8_t *Rw = R + z * sr + ((long)by * EMU_BT + wr * 128 + 4 * (lane >> 5)) * ldr + (long)bx * EMU_BT + wc * 64 + fr;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const double v = (double)acc[i][j][r];
+                Rw[(long)(i * 32 + (r & 3) + 8 * (r >> 2)) * ldr + j * 32] = (int8_t)(int)fma(-rint(v * pinv), p, v);
+            }
+}
+
+// ---- rebuild: C_ij -= X_ij 2^-(sig_i + tau_j), four consecutive columns per thread ----------------------------------------------
+__global__ __launch_bounds__(256) void emu_rebuild_kernel(const int8_t *__restrict__ R, long ldr, long sr, int L, const int *__restrict__ sa,
+                                                          const int *__restrict__ sb, double *__restrict__ C, long ldc, long rows, long cols)
+{
+    const long q4 = (cols + 3) >> 2;
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    const long i = idx / q4, j0 = (idx - i * q4) * 4;
+    if (i >= rows) return;
+    unsigned w[EMU_MAXL];
+#pragma unroll
+    for (int l = 0; l < EMU_MAXL; ++l)
+        if (l < L) w[l] = *reinterpret_cast<const unsigned *>(R + l * sr + i * ldr + j0);
+    const int si = sa[i];
+    double *c = C + i * ldc + j0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (j0 + e >= cols) continue;
+        const int tj = sb[j0 + e];
+        if (si == EMU_NONFINITE || tj == EMU_NONFINITE) { c[e] = __builtin_nan(""); continue; }
+        // Garner: X = sum_k v_k p_0 .. p_(k-1), digit 0 in [-128, 127], digit k >= 1 in [-(p_k - 1) / 2, (p_k - 1) / 2]; every
+        // intermediate is an integer below 2^17 in magnitude, so the fp32 arithmetic is exact
+        float v[EMU_MAXL];
+        v[0] = (float)(int8_t)(w[0] >> (8 * e));
+#pragma unroll
+        for (int k = 1; k < EMU_MAXL; ++k) {
+            if (k >= L) continue;
+            const float pk = (float)emu_p[k], pkinv = 1.0f / pk, hk = 0.5f * (pk - 1.0f);
+            float tk = (float)(int8_t)(w[k] >> (8 * e));
+#pragma unroll
+            for (int jj = 0; jj < k; ++jj) {
+                tk = (tk - v[jj]) * emu_garner.c[jj][k];
+                tk = fmaf(-rintf(tk * pkinv), pk, tk);
+            }
+            tk = tk > hk ? tk - pk : (tk < -hk ? tk + pk : tk);
+            v[k] = tk;
+        }
+        __int128 X = (__int128)(int)v[L - 1];
+#pragma unroll
+        for (int k = EMU_MAXL - 2; k >= 0; --k)
+            if (k <= L - 2) X = X * emu_p[k] + (int)v[k];
+        const long hi = (long)(X >> 64);
+        const unsigned long lo = (unsigned long)X;
+        const double xd = (hi == ((long)lo >> 63)) ? (double)(long)lo : fma((double)hi, 0x1p64, (double)lo);
+        c[e] -= ldexp(xd, -(si + tj));
+    }
+}
+
+// ---- workspace -------------------------------------------------------------------------------------------------------------
+// Residues of a row tile of A and a column tile of B and the product residues of their block, each at most 2 GiB: at N = M = 16384
+// (K = 8192) one tile of each; deeper products (K = 32768 at N = 65536) loop over row tiles and, inside, column tiles.  Every bound below
+// grows with rows, so a workspace sized for a predict chunk serves every shorter chunk.
+static int64_t emu_cap(int64_t K, int L) { return std::max<int64_t>(EMU_BT, (((int64_t)1 << 31) / (K * L)) / EMU_BT * EMU_BT); }
+
+void emu_work_need(EmuWork &w, int64_t rows, int64_t cols, int64_t K)
+{
+    const int L = emu_moduli();
+    const int64_t cap = emu_cap(K, L), rt = std::min(round_up(rows, EMU_BT), cap), ct = std::min(round_up(cols, EMU_BT), cap);
+    w.a_bytes = std::max(w.a_bytes, rt * K * L);
+    w.b_bytes = std::max(w.b_bytes, ct * K * L);
+    w.r_bytes = std::max(w.r_bytes, std::min(rt * ct * L, (int64_t)1 << 31));
+    w.sig_n = std::max(w.sig_n, rt + ct);
+}
+
+int emu_work_alloc(EmuWork &w)
+{
+    double *a = nullptr, *b = nullptr, *r = nullptr, *g = nullptr;
+    int rc = 0;
+    if ((rc = dalloc(&a, w.a_bytes / 8)) || (rc = dalloc(&b, w.b_bytes / 8)) || (rc = dalloc(&r, w.r_bytes / 8)) || (rc = dalloc(&g, (w.sig_n + 1) / 2))) {
+        if (a) dfree(a);
+        if (b) dfree(b);
+        if (r) dfree(r);
+        return rc;
+    }
+    w.ra = (int8_t *)a;
+    w.rb = (int8_t *)b;
+    w.rr = (int8_t *)r;
+    w.sig = (int *)g;
+    return 0;
+}
+
+void emu_work_free(EmuWork &w)   // (after the work queued with it has finished)
+{
+    if (w.ra) dfree(w.ra);
+    if (w.rb) dfree(w.rb);
+    if (w.rr) dfree(w.rr);
+    if (w.sig) dfree(w.sig);
+    w = EmuWork();
+}
+
+// ---- C[rows, cols] -= A[rows, K] B[cols, K]^T (row-major, fp64), in a workspace sized by emu_work_need for at least these shapes ----------
+int emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t rows, int64_t cols, int64_t K,
+                    const EmuWork &w, hipStream_t s, Profiler *prof)
+{
+    if (rows <= 0 || cols <= 0) return 0;
+    if (K % EMU_BK || K >= (1 << 17)) { gpx_set_error("emu_gemm_nt_sub: K = %ld out of range", (long)K); return GPX_ERR_BAD_ARG; }
+    const int L = emu_moduli();
+    const int bits = emu_scale_bits(K, L), abits = bits - bits / 2, bbits = bits / 2;
+    const int64_t cap = emu_cap(K, L);
+    const int64_t rt = std::min<int64_t>(round_up(rows, EMU_BT), cap);
+    int64_t ct = std::min<int64_t>(round_up(cols, EMU_BT), cap);
+    while (ct > EMU_BT && rt * ct * L > ((int64_t)1 << 31)) ct -= EMU_BT;
+    if (!w.ra || rt * K * L > w.a_bytes || ct * K * L > w.b_bytes || rt * ct * L > w.r_bytes || rt + ct > w.sig_n) {
+        gpx_set_error("emu_gemm_nt_sub: workspace too small for %ld x %ld x %ld", (long)rows, (long)cols, (long)K);
+        return GPX_ERR_STATE;
+    }
+    ProfScope ps(prof, s, GPX_K_GEMM_EMU, 2.0 * (double)rows * (double)cols * (double)K);
+    int8_t *ra = w.ra, *rb = w.rb, *rr = w.rr;
+    int *sga = w.sig, *sgb = sga + rt;
+    for (int64_t r0 = 0; r0 < rows; r0 += rt) {
+        const int64_t nr = std::min(rt, rows - r0), nrp = round_up(nr, EMU_BT);
+        hipLaunchKernelGGL(emu_split_kernel, dim3((unsigned)nrp), dim3(256), 0, s, A + r0 * lda, (long)lda, (long)nr, (int)K, abits, L, ra,
+                           (long)(nrp * K), sga);
+        for (int64_t c0 = 0; c0 < cols; c0 += ct) {
+            const int64_t nc = std::min(ct, cols - c0), ncp = round_up(nc, EMU_BT);
+            hipLaunchKernelGGL(emu_split_kernel, dim3((unsigned)ncp), dim3(256), 0, s, B + c0 * ldb, (long)ldb, (long)nc, (int)K, bbits, L, rb,
+                               (long)(ncp * K), sgb);
+            const int tm = (int)(nrp / EMU_BT), tn = (int)(ncp / EMU_BT);
+            hipLaunchKernelGGL(emu_i8_gemm_kernel, dim3((unsigned)(tm * tn * L)), dim3(512), 0, s, (const int8_t *)ra, (const int8_t *)rb,
+                               (long)(nrp * K), (long)(ncp * K), (int)K, rr, (long)ncp, (long)(nrp * ncp), tm, tn);
+            const long thr = (long)nr * ((nc + 3) / 4);
+            hipLaunchKernelGGL(emu_rebuild_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, (const int8_t *)rr, (long)ncp,
+                               (long)(nrp * ncp), L, (const int *)sga, (const int *)sgb, C + r0 * ldc + c0, (long)ldc, (long)nr, (long)nc);
+        }
+        GPX_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+// ---- C-ABI: the emulated product on caller device buffers (tests), the int8 product kernel alone on random residues (its rate) -------
+extern "C" int gpx_emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t rows, int64_t cols,
+                                   int64_t K)
+{
+    GPX_TRY(gpx_require_device());
+    if (rows < 0 || cols < 0 || K <= 0 || !A || !B || !C) { gpx_set_error("gpx_emu_gemm_nt_sub: bad arguments"); return GPX_ERR_BAD_ARG; }
+    EmuWork w;
+    emu_work_need(w, rows, cols, K);
+    GPX_TRY(emu_work_alloc(w));
+    int rc = emu_gemm_nt_sub(A, lda, B, ldb, C, ldc, rows, cols, K, w, 0, nullptr);
+    if (hipStreamSynchronize(0) != hipSuccess && rc == 0) { gpx_set_error("gpx_emu_gemm_nt_sub: stream failed"); rc = GPX_ERR_HIP; }
+    emu_work_free(w);
+    return rc;
+}
+
+__global__ void emu_fill_kernel(int8_t *p, long n, unsigned seed)
+{
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        unsigned x = (unsigned)i * 2654435761u ^ seed;
+        x ^= x >> 15; x *= 2246822519u; x ^= x >> 13;
+        p[i] = (int8_t)(x & 0xff);
+    }
+}
+
+extern "C" int gpx_bench_emu_i8(int64_t rows, int64_t cols, int64_t K, int nmod, int iters, double *ms)
+{
+    GPX_TRY(gpx_require_device());
+    if (rows % EMU_BT || cols % EMU_BT || K % EMU_BK || K >= (1 << 17) || nmod < 1 || nmod > EMU_MAXL || iters < 1 || !ms) {
+        gpx_set_error("gpx_bench_emu_i8: bad arguments");
+        return GPX_ERR_BAD_ARG;
+    }
+    double *wa = nullptr, *wb = nullptr, *wr = nullptr;
+    int rc = 0;
+    if ((rc = dalloc(&wa, rows * K * nmod / 8)) || (rc = dalloc(&wb, cols * K * nmod / 8)) || (rc = dalloc(&wr, rows * cols * nmod / 8))) {
+        if (wa) dfree(wa);
+        if (wb) dfree(wb);
+        return rc;
+    }
+    hipLaunchKernelGGL(emu_fill_kernel, dim3(4096), dim3(256), 0, 0, (int8_t *)wa, (long)(rows * K * nmod), 1u);
+    hipLaunchKernelGGL(emu_fill_kernel, dim3(4096), dim3(256), 0, 0, (int8_t *)wb, (long)(cols * K * nmod), 2u);
+    const int tm = (int)(rows / EMU_BT), tn = (int)(cols / EMU_BT);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    float t = 0.0f;
+    hipError_t e = hipEventCreate(&e0);
+    if (e == hipSuccess) e = hipEventCreate(&e1);
+    for (int it = -1; it < iters && e == hipSuccess; ++it) {   // it = -1: warm-up
+        if (it == 0) e = hipEventRecord(e0, 0);
+        hipLaunchKernelGGL(emu_i8_gemm_kernel, dim3((unsigned)(tm * tn * nmod)), dim3(512), 0, 0, (const int8_t *)wa, (const int8_t *)wb,
+                           (long)(rows * K), (long)(cols * K), (int)K, (int8_t *)wr, (long)cols, (long)(rows * cols), tm, tn);
+        if (e == hipSuccess) e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(e1, 0);
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    if (e == hipSuccess) e = hipEventElapsedTime(&t, e0, e1);
+    if (e != hipSuccess) { gpx_set_error("gpx_bench_emu_i8: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; }
+    *ms = t / iters;
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    (void)hipDeviceSynchronize();
+    dfree(wa);
+    dfree(wb);
+    dfree(wr);
+    return rc;
+}

@@ -469,7 +469,7 @@ int launch_predict_finish(const double *p2, const double *py, int64_t nslots, in
 }
 
 int trsm_right_lt_squares(double *Z, double *Zs, int64_t ldz, int64_t rows, const TriSolver *ts, int64_t p0, int64_t p1, hipStream_t s,
-                          Profiler *prof, const GemmReduce *red)
+                          Profiler *prof, const GemmReduce *red, const EmuWork *emu)
 {
     const int64_t np = p1 - p0;
     if (np <= 0 || rows <= 0) return 0;
@@ -491,15 +491,33 @@ int trsm_right_lt_squares(double *Z, double *Zs, int64_t ldz, int64_t rows, cons
     int64_t h = 1;
     while (h * 2 < np) h *= 2;
     const int64_t pm = p0 + h;
-    GPX_TRY(trsm_right_lt_squares(Z, Zs, ldz, rows, ts, p0, pm, s, prof, red));
+    GPX_TRY(trsm_right_lt_squares(Z, Zs, ldz, rows, ts, p0, pm, s, prof, red, emu));
     // Z[:, pm..p1) -= Zs[:, p0..pm) L[pm..p1, p0..pm)^T
     const int64_t c0 = p0 * PB, cm = pm * PB, c1 = std::min<int64_t>(p1 * PB, ts->npad);
+    // estimate_many: the deep updates (K >= GPX_EMU_MIN_K) on the int8 matrix cores (emu.hip); the choice depends on K alone, so every output
+    // row is computed the same way whatever the number of queries, the chunk or the rank
+    if (emu && emu_enabled(cm - c0)) {
+        GPX_TRY(emu_gemm_nt_sub(Zs + c0, ldz, ts->L + cm * ts->ld + c0, ts->ld, Z + cm, ldz, rows, c1 - cm, cm - c0, *emu, s, prof));
+        return trsm_right_lt_squares(Z, Zs, ldz, rows, ts, pm, p1, s, prof, red, emu);
+    }
     // (an update that would fill fewer than 448 of the chip's 512 places with 128 x 128 tiles -- a few thousand queries, the short updates at
     // the bottom of the recursion -- runs on 64 x 64 tiles instead)
     const double utiles = (double)(rows / TILE) * (double)((c1 - cm) / TILE);
     GPX_TRY(launch_gemm_nt(Zs + c0, ldz, ts->L + cm * ts->ld + c0, ts->ld, Z + cm, ldz, rows, c1 - cm, cm - c0, -1.0, 1.0, 0, s, prof, 0, 0,
                            utiles >= 192.0 && utiles < 448.0 ? 1 : 0));
-    return trsm_right_lt_squares(Z, Zs, ldz, rows, ts, pm, p1, s, prof, red);
+    return trsm_right_lt_squares(Z, Zs, ldz, rows, ts, pm, p1, s, prof, red, emu);
+}
+
+// the workspace the emulated updates of trsm_right_lt_squares(rows, p0, p1) need (the same recursion, nothing queued)
+void trsm_emu_need(EmuWork &w, int64_t rows, const TriSolver *ts, int64_t p0, int64_t p1)
+{
+    if (p1 - p0 <= 1 || rows <= 0) return;
+    int64_t h = 1;
+    while (h * 2 < p1 - p0) h *= 2;
+    const int64_t pm = p0 + h, c0 = p0 * PB, cm = pm * PB, c1 = std::min<int64_t>(p1 * PB, ts->npad);
+    trsm_emu_need(w, rows, ts, p0, pm);
+    if (emu_enabled(cm - c0)) emu_work_need(w, rows, c1 - cm, cm - c0);
+    trsm_emu_need(w, rows, ts, pm, p1);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -14,9 +14,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GPX_LIB", os.path.join(_HERE, "libgpx.so"))   # GPX_LIB: diagnostic builds only
 
 GPX_ERR_BAD_ARG, GPX_ERR_HIP, GPX_ERR_NO_DEVICE, GPX_ERR_STATE = -1, -2, -3, -4
-K_GRAM, K_GEMM, K_POTRF_LEAF, K_TRSV, K_REDUCE, K_QUAD, K_EXACT, K_GEMM_SMALL, K_TRSV_RIDE = range(9)
+K_GRAM, K_GEMM, K_POTRF_LEAF, K_TRSV, K_REDUCE, K_QUAD, K_EXACT, K_GEMM_SMALL, K_TRSV_RIDE, K_GEMM_EMU = range(10)
 KERNEL_CLASS_NAMES = ["gram", "gemm_f64_mfma", "potrf_leaf", "trsv", "predict_reduce", "approx_quad", "exact_sum",
-                      "gemm_f64_mfma_small_tiles", "trsv_under_factorisation"]
+                      "gemm_f64_mfma_small_tiles", "trsv_under_factorisation", "gemm_f64_emulated_int8"]
 
 if not os.path.exists(LIB_PATH):
     raise ImportError(
@@ -82,6 +82,8 @@ SIGNATURES = {
     "gpx_profile_reset": (_int, [_hp]),
     "gpx_profile_read": (_int, [_hp, _int, ctypes.POINTER(_i64), ctypes.POINTER(_dbl), ctypes.POINTER(_dbl)]),
     "gpx_bench_mfma_f64": (_int, [_int, ctypes.POINTER(_dbl)]),
+    "gpx_bench_emu_i8": (_int, [_i64, _i64, _i64, _int, _int, ctypes.POINTER(_dbl)]),
+    "gpx_emu_gemm_nt_sub": (_int, [_dp, _i64, _dp, _i64, _dp, _i64, _i64, _i64, _i64]),
     "gpx_bench_hbm": (_int, [_i64, _int, ctypes.POINTER(_dbl), ctypes.POINTER(_dbl)]),
     "gpx_bench_fp64_pipes": (_int, [_int, _int, _int] + [ctypes.POINTER(_dbl)] * 3),
     "gpx_dev_gram": (_int, [_dp, _i64, _dp, _i64, _int, _dp, _dbl, _int, _int, _dp, _i64, _i64, _i64, ctypes.c_void_p]),
