@@ -132,6 +132,16 @@ int gpx_cjh(gpx_handle *h, const double *u, double *C, double *J, double *H);
 int gpx_propagate_approx(gpx_handle *h, const double *u, const double *Sigma,
                          double *mean, double *var, double *sigma2, double *rest);
 
+/* The same for b inputs in ONE call (there is no reference counterpart: it replaces a caller's loop over propagate_GA,
+ * skgpuppy/UncertaintyPropagation.py:490-523, each turn of which runs :397-481).  U [b, d]; Sigma [b, d, d], or ONE [d, d] matrix
+ * for every input when sigma_shared != 0.  Input i's vectors C, tr = tracedot(H, Sigma_i), J_1..J_d are d + 2 right-hand sides of the
+ * many-right-hand-side triangular solver of gpx_predict (z_v = L^-1 v; beta.v = z_v.y, v.Kinv v = |z_v|^2, tr.Kinv C = z_tr.z_C):
+ * K^-1 is never built and the cache of the single-input calls is left alone.  mean [b] (WITHOUT meant) and var [b] are required,
+ * sigma2 [b] and rest [b] may be NULL; host or device pointers.  An input's result does not depend on its place in the batch.
+ * b = 0 is a no-op. */
+int gpx_propagate_approx_many(gpx_handle *h, const double *U, const double *Sigma, int sigma_shared, int64_t b,
+                              double *mean, double *var, double *sigma2, double *rest);
+
 /* Row-sharded form for the multi-GPU host (last row): the 4 + 2 d sums behind gpx_propagate_approx restricted to
  * rows [row0, row1) of K^-1 (row0 a multiple of GPX_TILE, row1 a multiple of GPX_TILE or n).  partial_out [4 + 2 d]:
  * beta.C, beta.tr, C.KinvC, KinvC.tr, then per k: J_k.KinvJ_k, beta.J_k.  The ranks add their partials (ONE all-reduce of

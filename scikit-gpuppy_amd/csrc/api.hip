@@ -30,6 +30,11 @@ int launch_trace(const double *x, int64_t n, int64_t npad, int d, const double *
                  const double *Sigma_dev, const double *cplain, double *tr, hipStream_t s);
 int launch_cjh(const double *x, int64_t n, int d, const double *u_dev, const double *w_dev, double v, double vt, double *C,
                double *J, double *H, hipStream_t s);
+int launch_approx_build_many(const double *x, int64_t n, int64_t npad, int d, const double *U_dev, const double *Sigma_dev,
+                             int64_t sigma_stride, int64_t nb, int64_t rows_pad, const double *w_dev, double v, double vt, double *Z,
+                             hipStream_t s, Profiler *prof);
+int launch_approx_reduce_many(const double *Zs, int64_t npad, int d, const double *y, const double *Sigma_dev, int64_t sigma_stride,
+                              int64_t nb, double vplusvt, double *out, int64_t ldo, hipStream_t s, Profiler *prof);
 int launch_exact_build(const double *x, int64_t n, int64_t npad, int d, const double *u_dev, const double *w_dev,
                        const double *Ls_dev, const double *dinv_diag_dev, double v, double vt, double nc1, double *aT,
                        double *bT, double *e, double *F, double *lm, hipStream_t s);
@@ -726,39 +731,76 @@ extern "C" int gpx_logdet(gpx_handle *h, double *logdet)
 }
 
 // ---- predict -----------------------------------------------------------------------------------
+// The many-right-hand-side solve behind gpx_predict / gpx_predict_kv and gpx_propagate_approx_many: rows of h->Z (leading dimension
+// npad, zero padded to the 128-row tile) -> Zs = Z L^-T, in chunks of `chunk` rows.  begin sizes the chunk and takes Z, Zs and the
+// emulated updates' workspace once per call; run solves one chunk; end returns the buffers once the stream is idle.
+struct RowSolve {
+    int64_t chunk = 0;
+    bool few = false;       // a handful of rows: the few-right-hand-side solver (one sweep over the factor's triangle)
+    double *Zs = nullptr;   // [chunk, npad]
+    EmuWork ew;
+    const EmuWork *emu = nullptr;
+};
+
+static int row_solve_begin(gpx_handle *h, int64_t m, RowSolve &rs)
+{
+    int64_t cap = ((int64_t)8 << 30) / (h->npad * (int64_t)sizeof(double));   // rows per 8 GB buffer (two of them: Z and Zs)
+    cap = std::max<int64_t>(TILE, cap / TILE * TILE);
+    cap = std::min<int64_t>(cap, 32768);
+    rs.chunk = std::min<int64_t>(round_up(m, TILE), cap);
+    GPX_TRY(ensure_Z(h, rs.chunk));
+    // the triangular solve runs out of place against the inverted diagonal squares (tsolve.hip): second slab-major buffer
+    GPX_TRY(dalloc(&rs.Zs, rs.chunk * h->npad));
+    rs.few = m <= 32 && h->tri.ready() && h->tri.P >= 2;
+    // the emulated updates' workspace (emu.hip), once per call: sized for the chunk, it serves every shorter one
+    if (!rs.few) trsm_emu_need(rs.ew, rs.chunk, &h->tri, 0, h->tri.P);
+    if (rs.ew.a_bytes) {
+        const int rc = emu_work_alloc(rs.ew);
+        if (rc) { dfree(rs.Zs); rs.Zs = nullptr; return rc; }
+    }
+    rs.emu = rs.ew.ra ? &rs.ew : nullptr;
+    return 0;
+}
+
+// Zs[0 : mp) <- Z[0 : mp) L^-T (mc real rows, mp = mc rounded up to the tile); red: the fused row sums of tsolve.hip (many rows only)
+static int row_solve_run(gpx_handle *h, const RowSolve &rs, int64_t mc, int64_t mp, const GemmReduce *red)
+{
+    // a handful of queries (estimate(x_star), plots): the solver for a few right-hand sides -- one forward sweep over the factor's
+    // triangle (HBM-bound, ~0.5 ms at N = 16384) instead of the many-right-hand-side recursion on one 128-row tile (its products
+    // would be 128 x K strips with K up to N/2: 2.5-3 ms)
+    if (!red && rs.few) return h->tri.solve(h->Z, h->npad, (int)mc, rs.Zs, nullptr, h->stream, &h->prof);
+    return trsm_right_lt_squares(h->Z, rs.Zs, h->npad, mp, &h->tri, 0, h->tri.P, h->stream, &h->prof, red, rs.emu);
+}
+
+static void row_solve_end(gpx_handle *h, RowSolve &rs)
+{
+    (void)hipStreamSynchronize(h->stream);
+    emu_work_free(rs.ew);
+    if (rs.Zs) dfree(rs.Zs);
+    rs.Zs = nullptr;
+}
+
 // xs != nullptr: the cross-covariance rows come from the Gram kernel (gpx_predict); otherwise kv [m, n] is the caller's
 // (gpx_predict_kv) and kdiag [m] the prior variance of each query (the diagonal of cov_matrix(x_star), GaussianProcess.py:75)
 static int predict_common(gpx_handle *h, const double *xs, const double *kv, const double *kdiag, int64_t m, double *mean_out, double *var_out)
 {
     hipStream_t s = h->stream;
     const int d = h->d;
-    int64_t cap = ((int64_t)8 << 30) / (h->npad * (int64_t)sizeof(double));   // rows per 8 GB buffer (two of them: Z and Zs)
-    cap = std::max<int64_t>(TILE, cap / TILE * TILE);
-    cap = std::min<int64_t>(cap, 32768);
-    const int64_t chunk = std::min<int64_t>(round_up(m, TILE), cap);
-    GPX_TRY(ensure_Z(h, chunk));
-    // the triangular solve runs out of place against the inverted diagonal squares (tsolve.hip): second slab-major buffer
-    double *xq = nullptr, *xqw = nullptr, *mv = nullptr, *Zs = nullptr, *kd = nullptr, *part = nullptr;
-    GPX_TRY(dalloc(&Zs, chunk * h->npad));
+    RowSolve rs;
+    GPX_TRY(row_solve_begin(h, m, rs));
+    const int64_t chunk = rs.chunk;
+    double *xq = nullptr, *xqw = nullptr, *mv = nullptr, *kd = nullptr, *part = nullptr;
     int rc = 0;
     // the row sums |z|^2 and z.y ride in the epilogue of each slab's last product (tsolve.hip): per row one partial pair per 64 columns
     const int64_t nslots = h->npad / 64;
     const bool fused = chunk >= 3072;
-    const bool few = m <= 32 && h->tri.ready() && h->tri.P >= 2;
     if ((rc = dalloc(&xq, chunk * std::max(d, 1))) || (rc = dalloc(&xqw, chunk * std::max(d, 1))) || (rc = dalloc(&mv, 2 * chunk)) || (rc = dalloc(&kd, chunk)) ||
         (fused && (rc = dalloc(&part, 2 * chunk * nslots)))) {
-        dfree(Zs); if (xq) dfree(xq); if (xqw) dfree(xqw); if (mv) dfree(mv); if (kd) dfree(kd);
+        row_solve_end(h, rs);
+        if (xq) dfree(xq); if (xqw) dfree(xqw); if (mv) dfree(mv); if (kd) dfree(kd);
         return rc;
     }
-    // the emulated updates' workspace (emu.hip), once per call: sized for the chunk, it serves every shorter one
-    EmuWork ew;
-    if (!few) trsm_emu_need(ew, chunk, &h->tri, 0, h->tri.P);
-    if (ew.a_bytes && (rc = emu_work_alloc(ew))) {
-        dfree(Zs); dfree(xq); dfree(xqw); dfree(mv); dfree(kd);
-        if (part) dfree(part);
-        return rc;
-    }
-    const EmuWork *emu = ew.ra ? &ew : nullptr;
+    double *Zs = rs.Zs;
     for (int64_t m0 = 0; m0 < m && rc == 0; m0 += chunk) {
         const int64_t mc = std::min<int64_t>(chunk, m - m0), mp = round_up(mc, TILE);
         hipError_t e = hipSuccess;
@@ -780,17 +822,11 @@ static int predict_common(gpx_handle *h, const double *xs, const double *kv, con
         if (fused && mp >= 3072) {
             GemmReduce red;
             red.y = h->y; red.p2 = part; red.py = part + chunk * nslots; red.nslots = nslots;
-            if ((rc = trsm_right_lt_squares(h->Z, Zs, h->npad, mp, &h->tri, 0, h->tri.P, s, &h->prof, &red, emu))) break;
+            if ((rc = row_solve_run(h, rs, mc, mp, &red))) break;
             ProfScope ps(&h->prof, s, GPX_K_REDUCE, 16.0 * (double)mc * (double)nslots);
             if ((rc = launch_predict_finish(red.p2, red.py, nslots, mc, h->v + h->vt, mv, mv + chunk, s, xs ? nullptr : kd))) break;
-        } else if (few) {
-            // a handful of queries (estimate(x_star), plots): the solver for a few right-hand sides -- one forward sweep over the factor's
-            // triangle (HBM-bound, ~0.5 ms at N = 16384) instead of the many-right-hand-side recursion on one 128-row tile (its products
-            // would be 128 x K strips with K up to N/2: 2.5-3 ms)
-            if ((rc = h->tri.solve(h->Z, h->npad, (int)mc, Zs, nullptr, s, &h->prof))) break;
-            if ((rc = launch_predict_reduce(Zs, h->npad, mc, h->npad, h->y, h->v + h->vt, mv, mv + chunk, s, &h->prof, xs ? nullptr : kd))) break;
         } else {
-            if ((rc = trsm_right_lt_squares(h->Z, Zs, h->npad, mp, &h->tri, 0, h->tri.P, s, &h->prof, nullptr, emu))) break;
+            if ((rc = row_solve_run(h, rs, mc, mp, nullptr))) break;
             if ((rc = launch_predict_reduce(Zs, h->npad, mc, h->npad, h->y, h->v + h->vt, mv, mv + chunk, s, &h->prof, xs ? nullptr : kd))) break;
         }
         e = hipMemcpyAsync(mean_out + m0, mv, sizeof(double) * mc, hipMemcpyDefault, s);
@@ -798,9 +834,7 @@ static int predict_common(gpx_handle *h, const double *xs, const double *kv, con
         if (e == hipSuccess) e = hipStreamSynchronize(s);
         if (e != hipSuccess) { gpx_set_error("predict copy-out failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
     }
-    (void)hipStreamSynchronize(s);
-    emu_work_free(ew);
-    dfree(Zs);
+    row_solve_end(h, rs);
     dfree(xq);
     dfree(xqw);
     dfree(mv);
@@ -1144,6 +1178,57 @@ extern "C" int gpx_propagate_approx(gpx_handle *h, const double *u, const double
     if (rest) *rest = var2 + var3;
     if (var) *var = s2 + var2 + var3;
     return 0;
+}
+
+// Batched Approx: b inputs as b (d + 2) right-hand sides [C, tr, J_1..J_d] of the many-right-hand-side solver that serves
+// gpx_predict.  With K = L L^T, y = L^-1 t and z_v = L^-1 v every sum of gpx_propagate_approx is a row product of the solved block:
+// beta.v = z_v.y, v.Kinv v = |z_v|^2, tr.Kinv C = z_tr.z_C.  No K^-1, no use of the handle's single-u cache, one synchronisation
+// per chunk; an input never straddles two chunks.
+extern "C" int gpx_propagate_approx_many(gpx_handle *h, const double *U, const double *Sigma, int sigma_shared, int64_t b,
+                                         double *mean, double *var, double *sigma2, double *rest)
+{
+    CHECK_H(h);
+    NEED_KERNEL(h, "gpx_propagate_approx_many");
+    if (b < 0 || (b > 0 && (!U || !Sigma || !mean || !var))) { gpx_set_error("gpx_propagate_approx_many: bad arguments"); return GPX_ERR_BAD_ARG; }
+    if (b == 0) return 0;
+    hipStream_t s = h->stream;
+    const int d = h->d, nrow = d + 2;
+    RowSolve rs;
+    GPX_TRY(row_solve_begin(h, b * nrow, rs));
+    const int64_t bchunk = rs.chunk / nrow;           // inputs per chunk (chunk >= 128 > d + 2)
+    const int64_t nsig = sigma_shared ? 1 : bchunk;
+    double *ud = nullptr, *sd = nullptr, *od = nullptr;
+    int rc = 0;
+    if ((rc = dalloc(&ud, bchunk * d)) || (rc = dalloc(&sd, nsig * d * d)) || (rc = dalloc(&od, 4 * bchunk))) {
+        row_solve_end(h, rs);
+        if (ud) dfree(ud);
+        if (sd) dfree(sd);
+        return rc;
+    }
+    hipError_t e = hipSuccess;
+    if (sigma_shared) e = hipMemcpyAsync(sd, Sigma, sizeof(double) * d * d, hipMemcpyDefault, s);
+    if (e != hipSuccess) { gpx_set_error("copy Sigma failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; }
+    const int64_t sstride = sigma_shared ? 0 : (int64_t)d * d;
+    for (int64_t b0 = 0; b0 < b && rc == 0; b0 += bchunk) {
+        const int64_t bc = std::min<int64_t>(bchunk, b - b0), mc = bc * nrow, mp = round_up(mc, TILE);
+        e = hipMemcpyAsync(ud, U + b0 * d, sizeof(double) * bc * d, hipMemcpyDefault, s);
+        if (e == hipSuccess && !sigma_shared) e = hipMemcpyAsync(sd, Sigma + b0 * d * d, sizeof(double) * bc * d * d, hipMemcpyDefault, s);
+        if (e != hipSuccess) { gpx_set_error("copy U / Sigma failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
+        if ((rc = launch_approx_build_many(h->x, h->n, h->npad, d, ud, sd, sstride, bc, mp, h->wdev, h->v, h->vt, h->Z, s, &h->prof))) break;
+        if ((rc = row_solve_run(h, rs, mc, mp, nullptr))) break;
+        if ((rc = launch_approx_reduce_many(rs.Zs, h->npad, d, h->y, sd, sstride, bc, h->v + h->vt, od, bchunk, s, &h->prof))) break;
+        e = hipMemcpyAsync(mean + b0, od, sizeof(double) * bc, hipMemcpyDefault, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(var + b0, od + bchunk, sizeof(double) * bc, hipMemcpyDefault, s);
+        if (e == hipSuccess && sigma2) e = hipMemcpyAsync(sigma2 + b0, od + 2 * bchunk, sizeof(double) * bc, hipMemcpyDefault, s);
+        if (e == hipSuccess && rest) e = hipMemcpyAsync(rest + b0, od + 3 * bchunk, sizeof(double) * bc, hipMemcpyDefault, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { gpx_set_error("propagate copy-out failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
+    }
+    row_solve_end(h, rs);
+    dfree(ud);
+    dfree(sd);
+    dfree(od);
+    return rc;
 }
 
 // Row-sharded form of the Approx propagation (last row): the 4 + 2 d sums of gpx_propagate_approx restricted to

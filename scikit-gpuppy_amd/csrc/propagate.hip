@@ -123,6 +123,215 @@ int launch_dot_pairs(const std::vector<std::pair<const double *, const double *>
 }
 
 // ---------------------------------------------------------------------------------------------
+// Batched Approx (gpx_propagate_approx_many): the d + 2 vectors of MANY inputs as the rows of a right-hand-side block for
+// the many-right-hand-side triangular solver.  Row b (d + 2) + r of Z (leading dimension npad):
+//   r = 0: C_i (+vt iff x_i == u_b elementwise)   r = 1: tr_i = tracedot(H_i, Sigma_b)   r = 2 + k: J_ik
+// A workgroup owns 128 columns (a lane two adjacent ones: 16-byte stores, 1 KB per wave and row) and AB_INPUTS inputs, four per
+// wave; the x tile sits in LDS k-major as in gram_kernel, and the input's u, w, Sigma are wave-uniform: they come through the
+// scalar cache (loads only).  One exp per (input, column).  DR > 0: d <= DR and the scaled differences w_k (x_ik - u_k) stay
+// in registers; DR = 0: any d, they are recomputed from the LDS tile.
+// ---------------------------------------------------------------------------------------------
+constexpr int AB_COLS = 128;
+constexpr int AB_INPUTS = 16;
+
+template <int DR>
+__global__ __launch_bounds__(256) void approx_build_many_kernel(const double *__restrict__ x, long n, long npad, int d,
+                                                               const double *__restrict__ U, const double *__restrict__ Sigma,
+                                                               long sigma_stride, long nb, const double *__restrict__ w, double v,
+                                                               double vt, double *__restrict__ Z)
+{
+    extern __shared__ __attribute__((aligned(16))) double ab_smem[];
+    double *x_s = ab_smem;   // [d][128] raw inputs of the tile's columns, k-major
+    const int t = threadIdx.x;
+    const long col0 = (long)blockIdx.x * AB_COLS;
+    for (int e = t; e < AB_COLS * d; e += 256) {
+        const int c = e & (AB_COLS - 1), k = e >> 7;
+        const long gc = col0 + c;
+        x_s[k * AB_COLS + c] = (gc < n) ? x[gc * d + k] : 0.0;
+    }
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
+    const long c = col0 + 2 * lane;
+    const bool in0 = c < n, in1 = c + 1 < n;
+    const int nrow = d + 2;
+    for (int j = 0; j < AB_INPUTS / 4; ++j) {
+        const long b = (long)blockIdx.y * AB_INPUTS + 4 * j + wave;   // wave-uniform
+        if (b >= nb) break;
+        const double *u = U + b * d, *S = Sigma + b * sigma_stride;
+        double *zrow = Z + b * nrow * npad + c;
+        double wd0[DR > 0 ? DR : 1], wd1[DR > 0 ? DR : 1];
+        double q0 = 0.0, q1 = 0.0;
+        bool same0 = true, same1 = true;
+        if constexpr (DR > 0) {
+#pragma unroll
+            for (int k = 0; k < DR; ++k) {
+                wd0[k] = 0.0; wd1[k] = 0.0;
+                if (k < d) {
+                    const v2d xv = *reinterpret_cast<const v2d *>(&x_s[k * AB_COLS + 2 * lane]);
+                    const double uk = u[k], wk = w[k];
+                    const double d0 = xv.x - uk, d1 = xv.y - uk;
+                    same0 = same0 && (xv.x == uk);
+                    same1 = same1 && (xv.y == uk);
+                    wd0[k] = wk * d0; wd1[k] = wk * d1;
+                    q0 = fma(wd0[k], d0, q0);
+                    q1 = fma(wd1[k], d1, q1);
+                }
+            }
+        } else {
+            for (int k = 0; k < d; ++k) {
+                const v2d xv = *reinterpret_cast<const v2d *>(&x_s[k * AB_COLS + 2 * lane]);
+                const double uk = u[k], wk = w[k];
+                const double d0 = xv.x - uk, d1 = xv.y - uk;
+                same0 = same0 && (xv.x == uk);
+                same1 = same1 && (xv.y == uk);
+                q0 = fma(wk * d0, d0, q0);
+                q1 = fma(wk * d1, d1, q1);
+            }
+        }
+        const double c0 = in0 ? v * exp(-0.5 * q0) : 0.0, c1 = in1 ? v * exp(-0.5 * q1) : 0.0;
+        v2d o;
+        o.x = (in0 && same0) ? c0 + vt : c0;
+        o.y = (in1 && same1) ? c1 + vt : c1;
+        *reinterpret_cast<v2d *>(zrow) = o;
+        // tr = c ( (w delta)^T Sigma (w delta) - sum_k w_k Sigma_kk ), full Sigma (trace_kernel) ; J_k = -w_k delta_k c
+        double s0 = 0.0, s1 = 0.0, wdiag = 0.0;
+        if constexpr (DR > 0) {
+#pragma unroll
+            for (int a = 0; a < DR; ++a) {
+                if (a < d) {
+                    double r0 = 0.0, r1 = 0.0;
+#pragma unroll
+                    for (int e = 0; e < DR; ++e)
+                        if (e < d) {
+                            const double sg = S[a * d + e];
+                            r0 = fma(sg, wd0[e], r0);
+                            r1 = fma(sg, wd1[e], r1);
+                        }
+                    s0 = fma(wd0[a], r0, s0);
+                    s1 = fma(wd1[a], r1, s1);
+                    wdiag = fma(w[a], S[a * d + a], wdiag);
+                    v2d jk;
+                    jk.x = -wd0[a] * c0; jk.y = -wd1[a] * c1;
+                    *reinterpret_cast<v2d *>(zrow + (long)(2 + a) * npad) = jk;
+                }
+            }
+        } else {
+            for (int a = 0; a < d; ++a) {
+                double r0 = 0.0, r1 = 0.0;
+                for (int e = 0; e < d; ++e) {
+                    const v2d xv = *reinterpret_cast<const v2d *>(&x_s[e * AB_COLS + 2 * lane]);
+                    const double sg = S[a * d + e], ue = u[e], we = w[e];
+                    r0 = fma(sg, we * (xv.x - ue), r0);
+                    r1 = fma(sg, we * (xv.y - ue), r1);
+                }
+                const v2d xa = *reinterpret_cast<const v2d *>(&x_s[a * AB_COLS + 2 * lane]);
+                const double a0 = w[a] * (xa.x - u[a]), a1 = w[a] * (xa.y - u[a]);
+                s0 = fma(a0, r0, s0);
+                s1 = fma(a1, r1, s1);
+                wdiag = fma(w[a], S[a * d + a], wdiag);
+                v2d jk;
+                jk.x = -a0 * c0; jk.y = -a1 * c1;
+                *reinterpret_cast<v2d *>(zrow + (long)(2 + a) * npad) = jk;
+            }
+        }
+        o.x = c0 * (s0 - wdiag);
+        o.y = c1 * (s1 - wdiag);
+        *reinterpret_cast<v2d *>(zrow + npad) = o;
+    }
+}
+
+// Z [rows_pad, npad]: rows [0, nb (d + 2)) written by the kernel (every column, zeros from n on), the rest of the last 128-row tile cleared
+int launch_approx_build_many(const double *x, int64_t n, int64_t npad, int d, const double *U_dev, const double *Sigma_dev,
+                             int64_t sigma_stride, int64_t nb, int64_t rows_pad, const double *w_dev, double v, double vt, double *Z,
+                             hipStream_t s, Profiler *prof)
+{
+    if (nb <= 0) return 0;
+    const int64_t rows = nb * (d + 2);
+    if (npad % AB_COLS || rows > rows_pad) { gpx_set_error("approx_build_many: bad block shape"); return GPX_ERR_BAD_ARG; }
+    ProfScope ps(prof, s, GPX_K_GRAM, 8.0 * (double)rows_pad * (double)npad);
+    if (rows_pad > rows) GPX_HIP(hipMemsetAsync(Z + rows * npad, 0, sizeof(double) * (rows_pad - rows) * npad, s));
+    const dim3 grid((unsigned)(npad / AB_COLS), (unsigned)((nb + AB_INPUTS - 1) / AB_INPUTS));
+    const size_t lds = sizeof(double) * AB_COLS * d;
+    if (d <= 8)
+        hipLaunchKernelGGL(approx_build_many_kernel<8>, grid, dim3(256), lds, s, x, (long)n, (long)npad, d, U_dev, Sigma_dev,
+                           (long)sigma_stride, (long)nb, w_dev, v, vt, Z);
+    else
+        hipLaunchKernelGGL(approx_build_many_kernel<0>, grid, dim3(256), lds, s, x, (long)n, (long)npad, d, U_dev, Sigma_dev,
+                           (long)sigma_stride, (long)nb, w_dev, v, vt, Z);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// One pass over the solved block Zs (row b (d + 2) + r = L^-1 of the vector above), one workgroup per input: per row |z_r|^2 and
+// z_r . y, for rows 0 and 1 also z_C . z_tr, then the four outputs (UncertaintyPropagation.py:397-481 with K^-1 = L^-T L^-1):
+//   mean = z_C.y + 1/2 z_tr.y   sigma2 = (v + vt) - |z_C|^2   rest = -sum_k Sigma_kk (|z_Jk|^2 - (z_Jk.y)^2) - z_C.z_tr
+// No atomics; thread -> column, wave -> LDS slot and the final sum are fixed, so an input's result does not depend on its
+// place in the batch.  out: [4][ldo] = mean | var | sigma2 | rest.
+__global__ __launch_bounds__(256) void approx_reduce_many_kernel(const double *__restrict__ Zs, long npad, int d,
+                                                                const double *__restrict__ y, const double *__restrict__ Sigma,
+                                                                long sigma_stride, double vplusvt, double *__restrict__ out, long ldo)
+{
+    __shared__ double part[(GPX_MAX_D + 2) * 2 + 1][4];
+    const long b = blockIdx.x;
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const double *z0 = Zs + b * (d + 2) * npad, *z1 = z0 + npad;
+    {
+        double q0 = 0.0, y0 = 0.0, q1 = 0.0, y1 = 0.0, x01 = 0.0;
+        for (long c = 2 * t; c < npad; c += 512) {
+            const v2d a = *reinterpret_cast<const v2d *>(z0 + c), e = *reinterpret_cast<const v2d *>(z1 + c);
+            const v2d yy = *reinterpret_cast<const v2d *>(y + c);
+            q0 = fma(a.x, a.x, q0); q0 = fma(a.y, a.y, q0);
+            y0 = fma(a.x, yy.x, y0); y0 = fma(a.y, yy.y, y0);
+            q1 = fma(e.x, e.x, q1); q1 = fma(e.y, e.y, q1);
+            y1 = fma(e.x, yy.x, y1); y1 = fma(e.y, yy.y, y1);
+            x01 = fma(a.x, e.x, x01); x01 = fma(a.y, e.y, x01);
+        }
+        q0 = wave_sum_p(q0); y0 = wave_sum_p(y0); q1 = wave_sum_p(q1); y1 = wave_sum_p(y1); x01 = wave_sum_p(x01);
+        if (lane == 0) { part[0][wave] = q0; part[1][wave] = y0; part[2][wave] = q1; part[3][wave] = y1; part[2 * (d + 2)][wave] = x01; }
+    }
+    for (int r = 2; r < d + 2; ++r) {
+        const double *zr = z0 + (long)r * npad;
+        double q = 0.0, sy = 0.0;
+        for (long c = 2 * t; c < npad; c += 512) {
+            const v2d a = *reinterpret_cast<const v2d *>(zr + c);
+            const v2d yy = *reinterpret_cast<const v2d *>(y + c);
+            q = fma(a.x, a.x, q); q = fma(a.y, a.y, q);
+            sy = fma(a.x, yy.x, sy); sy = fma(a.y, yy.y, sy);
+        }
+        q = wave_sum_p(q); sy = wave_sum_p(sy);
+        if (lane == 0) { part[2 * r][wave] = q; part[2 * r + 1][wave] = sy; }
+    }
+    __syncthreads();
+    if (t == 0) {
+        auto tot = [&](int i) { return (part[i][0] + part[i][1]) + (part[i][2] + part[i][3]); };
+        const double *S = Sigma + b * sigma_stride;
+        const double mean = tot(1) + 0.5 * tot(3);
+        const double s2 = vplusvt - tot(0);
+        double var2 = 0.0;
+        for (int k = 0; k < d; ++k) {
+            const double zy = tot(2 * (k + 2) + 1);
+            var2 += S[k * d + k] * (tot(2 * (k + 2)) - zy * zy);
+        }
+        const double rest = -var2 - tot(2 * (d + 2));
+        out[b] = mean;
+        out[ldo + b] = s2 + rest;
+        out[2 * ldo + b] = s2;
+        out[3 * ldo + b] = rest;
+    }
+}
+
+int launch_approx_reduce_many(const double *Zs, int64_t npad, int d, const double *y, const double *Sigma_dev, int64_t sigma_stride,
+                              int64_t nb, double vplusvt, double *out, int64_t ldo, hipStream_t s, Profiler *prof)
+{
+    if (nb <= 0) return 0;
+    ProfScope ps(prof, s, GPX_K_REDUCE, 8.0 * (double)nb * (double)(d + 2) * (double)npad);
+    hipLaunchKernelGGL(approx_reduce_many_kernel, dim3((unsigned)nb), dim3(256), 0, s, Zs, (long)npad, d, y, Sigma_dev,
+                       (long)sigma_stride, vplusvt, out, (long)ldo);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // KV[c][i] = sum_j Kinv[i][j] V[c][j] for c < nc: the ONE pass over Kinv that feeds every quadratic form of
 // the Approx propagation (loops K2..K6 of the reference, UncertaintyPropagation2.pyx:221-257,340-380, each of
 // which re-reads the whole N x N matrix serially).  HBM-bound: 8 N^2 bytes.

@@ -146,6 +146,47 @@ class UncertaintyPropagationApprox(UncertaintyPropagationGA):
         mean, var, _s2, _rest = self._parts(u, Sigma_x)
         return np.float64(mean + self.gp._get_mean_t()), np.float64(var)
 
+    # ---- many inputs in one call (no reference counterpart: what a caller's loop over propagate_GA computes) ----
+    def _many_args(self, U, Sigma_x):
+        d = self.gp.d
+        UU = _gpx.f64(U)
+        S = _gpx.f64(Sigma_x)
+        if UU.ndim != 2 or UU.shape[1] != d:
+            raise ValueError("U must be (B, %d), got %s" % (d, UU.shape))
+        if S.shape != (d, d) and S.shape != (len(UU), d, d):
+            raise ValueError("Sigma_x must be (%d, %d) or (%d, %d, %d), got %s" % (d, d, len(UU), d, d, S.shape))
+        return UU, S
+
+    def _parts_many(self, U, Sigma_x):
+        """(mean without meant, variance, sigma2, rest), each [B].  Built-in kernel: ONE gpx_propagate_approx_many call -- every
+        input's C, tr, J_1..J_d are d + 2 rows of the many-right-hand-side solve behind estimate_many; K^-1 is not built and the
+        single-input caches (self.u, C_ux, ...) are not touched.  Generic route (any other Covariance, SPGP): a loop over the
+        single-input path on a fresh instance -- correct, not accelerated."""
+        UU, S = self._many_args(U, Sigma_x)
+        B = len(UU)
+        shared = S.ndim == 2
+        out = [np.empty(B) for _ in range(4)]
+        if self._generic():
+            one = type(self)(self.gp)
+            for i in range(B):
+                parts = one._parts(UU[i], S if shared else S[i])
+                for o, p in zip(out, parts):
+                    o[i] = p
+            return out
+        st = _gpx.lib.gpx_propagate_approx_many(self.gp._dev().handle, _gpx.ptr(UU), _gpx.ptr(S), int(shared), B,
+                                                *[_gpx.ptr(o) for o in out])
+        _gpx.check(st, "gpx_propagate_approx_many")
+        return out
+
+    def propagate_mean_many(self, U, Sigma_x):
+        """propagate_mean for the rows of U (B, d); Sigma_x (d, d) for all of them or (B, d, d): means [B] WITHOUT meant"""
+        return self._parts_many(U, Sigma_x)[0]
+
+    def propagate_GA_many(self, U, Sigma_x):
+        """propagate_GA for the rows of U (B, d); Sigma_x (d, d) for all of them or (B, d, d): (means [B] with meant, variances [B])"""
+        mean, var, _s2, _rest = self._parts_many(U, Sigma_x)
+        return mean + self.gp._get_mean_t(), var
+
     # The three quadratic-form helpers of the reference (UncertaintyPropagation.py:412-488 / UncertaintyPropagation2.pyx:221-299)
     # take explicit Kinv / x / beta / C_ux / J_ux / H_ux arrays.  Called the way the reference itself calls them -- with the fitted
     # GP's own Kinv and the caches of the last propagation (or with nothing) -- the sums come from the device cache of `u`.  Any
