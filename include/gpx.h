@@ -253,7 +253,10 @@ int gpx_bench_mfma_f64(int iters, double *tflops);          /* back-to-back v_mf
  * nmod moduli in one launch: mean time per launch */
 int gpx_bench_emu_i8(int64_t rows, int64_t cols, int64_t K, int nmod, int iters, double *ms);
 /* C[rows, cols] -= A[rows, K] B[cols, K]^T on device buffers (row-major fp64) through the emulated update (Ozaki scheme II on int8
- * matrix cores; GPX_EMU_MODULI moduli); K a multiple of 128 below 2^17.  Synchronous. */
+ * matrix cores; GPX_EMU_MODULI moduli).  A, B and C may be windows of larger matrices.  Synchronous.
+ * GPX_ERR_BAD_ARG, with text in gpx_last_error() and before anything is allocated, queued or written, unless: K is a multiple of 128
+ * below 2^17; lda >= K, ldb >= K, ldc >= cols; lda and ldb are even and A and B 16-byte aligned (the rows are read in pairs of
+ * doubles; C needs no more than its natural 8 bytes and ldc may be odd).  rows = 0 or cols = 0 is a valid empty product. */
 int gpx_emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t rows, int64_t cols,
                         int64_t K);
 int gpx_bench_hbm(int64_t bytes, int iters, double *write_gbs, double *copy_gbs);

@@ -14,6 +14,7 @@
 // (log2 P = 125.2) and K = 8192 that is alpha = 56, beta = 55: every row's largest entries are converted exactly, an entry 2^-e below its
 // row's largest keeps 55 - e bits.  Each output row depends only on its own row of A and on B, whatever the tiling.
 #include <math.h>
+#include <stdint.h>
 #include <stdlib.h>
 #include <algorithm>
 
@@ -329,6 +330,29 @@ void emu_work_free(EmuWork &w)   // (after the work queued with it has finished)
     w = EmuWork();
 }
 
+// What the kernels take for granted of a caller outside the library (gpx_emu_gemm_nt_sub; tsolve.hip passes slabs of 128-padded matrices at
+// offsets that are multiples of 1024), checked on the host before anything is allocated or queued: K a multiple of 128 below 2^17 (the
+// int8 k-stage; K 2^14 < 2^31 in the int32 accumulators), leading dimensions that hold a row (lda, ldb >= K, ldc >= cols), and rows of
+// A and B that start on 16 bytes (base pointers 16-byte aligned, lda and ldb even): emu_split_kernel reads pairs of doubles.
+static int emu_check_args(const double *A, int64_t lda, const double *B, int64_t ldb, int64_t ldc, int64_t cols, int64_t K)
+{
+    if (K <= 0 || K % EMU_BK || K >= (1 << 17)) {
+        gpx_set_error("emu_gemm_nt_sub: K = %ld is not a multiple of %d in [%d, 2^17)", (long)K, EMU_BK, EMU_BK);
+        return GPX_ERR_BAD_ARG;
+    }
+    if (lda < K || ldb < K || ldc < cols) {
+        gpx_set_error("emu_gemm_nt_sub: leading dimension shorter than a row (lda %ld, ldb %ld < K %ld, or ldc %ld < cols %ld)", (long)lda, (long)ldb,
+                      (long)K, (long)ldc, (long)cols);
+        return GPX_ERR_BAD_ARG;
+    }
+    if ((lda | ldb) & 1 || ((uintptr_t)A | (uintptr_t)B) & 15) {
+        gpx_set_error("emu_gemm_nt_sub: A and B must be 16-byte aligned with even lda, ldb (lda %ld, ldb %ld, A %p, B %p)", (long)lda, (long)ldb,
+                      (const void *)A, (const void *)B);
+        return GPX_ERR_BAD_ARG;
+    }
+    return 0;
+}
+
 // ---- C[rows, cols] -= A[rows, K] B[cols, K]^T (row-major, fp64), in a workspace sized by emu_work_need for at least these shapes ----------
 int emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t rows, int64_t cols, int64_t K,
                     const EmuWork &w, hipStream_t s, Profiler *prof)
@@ -373,7 +397,9 @@ extern "C" int gpx_emu_gemm_nt_sub(const double *A, int64_t lda, const double *B
                                    int64_t K)
 {
     GPX_TRY(gpx_require_device());
-    if (rows < 0 || cols < 0 || K <= 0 || !A || !B || !C) { gpx_set_error("gpx_emu_gemm_nt_sub: bad arguments"); return GPX_ERR_BAD_ARG; }
+    if (rows < 0 || cols < 0 || !A || !B || !C) { gpx_set_error("gpx_emu_gemm_nt_sub: bad arguments"); return GPX_ERR_BAD_ARG; }
+    GPX_TRY(emu_check_args(A, lda, B, ldb, ldc, cols, K));   // before the workspace is sized and allocated
+    if (rows == 0 || cols == 0) return 0;
     EmuWork w;
     emu_work_need(w, rows, cols, K);
     GPX_TRY(emu_work_alloc(w));

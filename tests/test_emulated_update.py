@@ -15,61 +15,9 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+from _emu_model import MODULI, emulated_product, garner, scale_bits, split_row
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MODULI = [256, 255, 253, 251, 247, 241, 239, 233, 229, 227, 223, 211, 199, 197, 193, 191]
-
-
-def scale_bits(K, L):
-    """alpha + beta as emu.hip computes it: the largest s with K 2^s < P / 2."""
-    return math.floor(sum(math.log2(p) for p in MODULI[:L]) - 1.0 - math.log2(K) - 1e-9)
-
-
-def balanced(r, p):
-    r %= p
-    if p == 256:
-        return r - 256 if r >= 128 else r
-    return r - p if r > (p - 1) // 2 else r
-
-
-def split_row(x, bits):
-    """(integers a', exponent s): a' = rint(x 2^s) with the row's largest |x| in [2^(bits-1), 2^bits) after scaling."""
-    m = max(abs(v) for v in x)
-    if m == 0.0:
-        return [0] * len(x), 0
-    s = bits - 1 - (math.frexp(m)[1] - 1)
-    return [int(round(math.ldexp(v, s))) for v in x], s
-
-
-def garner(res, L):
-    """balanced mixed-radix digits of the residues -> the integer in [-P/2, P/2) (what emu_rebuild_kernel evaluates)."""
-    v = [balanced(res[0], MODULI[0])]
-    for k in range(1, L):
-        pk, t = MODULI[k], res[k]
-        for j in range(k):
-            t = (t - v[j]) * pow(MODULI[j], -1, pk)
-        v.append(balanced(t, pk))
-    x = 0
-    for k in range(L - 1, -1, -1):
-        x = x * MODULI[k] + v[k]
-    return x
-
-
-def emulated_product(A, B, L=16):
-    K = len(A[0])
-    bits = scale_bits(K, L)
-    ab, bb = bits - bits // 2, bits // 2
-    sa = [split_row(r, ab) for r in A]
-    sb = [split_row(r, bb) for r in B]
-    out = []
-    for ai, si in sa:
-        row = []
-        for bj, tj in sb:
-            res = [sum(balanced(a, p) * balanced(b, p) for a, b in zip(ai, bj)) for p in MODULI[:L]]
-            X = garner([balanced(r, p) for r, p in zip(res, MODULI[:L])], L)
-            assert X == sum(a * b for a, b in zip(ai, bj))             # the residues determine the integer product
-            row.append(Fraction(X) / Fraction(2) ** (si + tj))
-        out.append(row)
-    return out
 
 
 def test_moduli_pairwise_coprime():
@@ -81,11 +29,11 @@ def test_moduli_pairwise_coprime():
 
 def test_bit_budget_every_k():
     P = math.prod(MODULI)
-    for L in (8, 12, 16):
+    for L in range(2, 17):                                              # every count of moduli emu_moduli() accepts
         PL = math.prod(MODULI[:L])
         for K in range(128, 1 << 17, 128):
             s = scale_bits(K, L)
-            assert K * 2 ** s < PL // 2 <= K * 2 ** (s + 1)                # largest such s
+            assert K * Fraction(2) ** s < PL // 2 <= K * Fraction(2) ** (s + 1)   # largest such s (negative for few moduli and deep K)
             assert K * 128 * 128 < 2 ** 31                              # int32 accumulation of int8 residues is exact
     assert scale_bits(8192, 16) == 111 and (111 - 111 // 2, 111 // 2) == (56, 55)
     assert P.bit_length() == 126
