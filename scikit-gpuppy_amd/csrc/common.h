@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <algorithm>
 #include <functional>
 #include <string>
 #include <vector>
@@ -137,7 +138,7 @@ struct gpx_handle {
     double *alpha = nullptr;    // [npad] K^-1 t
     TriSolver tri;              // few-right-hand-side solves against L (alpha, the propagation right after a fit)
     double *Kinv = nullptr;     // [npad, npad] lazily materialised
-    double *KinvRows = nullptr; // [kr1 - kr0, npad]: a row panel of K^-1 alone (the row-sharded propagation; api.hip, ensure_kinv_rows)
+    double *KinvRows = nullptr; // [kr1 - kr0, npad]: a row panel of K^-1 alone (the row-sharded propagation; predict.hip, ensure_kinv_rows)
     int64_t kr0 = 0, kr1 = 0;
     int *info_dev = nullptr;    // [0] potrf info (1-based failing column, 0 = ok)
     double logdet = 0;
@@ -147,8 +148,7 @@ struct gpx_handle {
     double *Z = nullptr;        // predict / inverse workspace [zrows, npad]
     int64_t zrows = 0;
     double *small = nullptr;    // small device scratch (reductions, propagate vectors)
-    double *hstage = nullptr;   // pinned host staging block of the propagation calls (api.hip, pinned_acquire)
-    int64_t small_elems = 0;
+    double *hstage = nullptr;   // pinned host staging block of the propagation calls (runtime.hip, pinned_acquire)
 
     // propagate cache (keyed on u)
     int approx_solves = 0;      // new-u propagations served by triangular solves so far (K^-1 is built after a few)
@@ -243,30 +243,121 @@ int launch_predict_reduce(const double *Z, int64_t ldz, int64_t m, int64_t npad,
 int launch_set_identity(double *Z, int64_t ld, int64_t n, hipStream_t s);
 int launch_symmetrize_lower(double *A, int64_t ld, int64_t n, hipStream_t s);
 
+// device selection (runtime.hip): hipSetDevice to the calling thread's gpx_set_device choice, gfx950 only
+int gpx_require_device();
+int gpx_thread_device();   // the calling host thread's gpx_set_device choice
+
+// caching device allocator, stream cache and pinned staging blocks (runtime.hip)
+int dalloc(double **p, int64_t elems);
+void dfree(void *p);   // the caller guarantees that no kernel still uses p
+hipStream_t stream_acquire(int high_priority);
+void stream_release(hipStream_t s, int high_priority);
+double *pinned_acquire();
+void pinned_release(double *p);
+
+// The pool blocks a call takes for its own duration.  They go back to the pool in the destructor, after ONE synchronisation of
+// the stream the call queues on: no kernel still uses a block when it returns to the pool, on whichever path the call ends.
+// (An owner that holds nothing has nothing to wait for.)
+struct Scratch {
+    hipStream_t s;
+    std::vector<void *> blocks;
+    explicit Scratch(hipStream_t s_) : s(s_) {}
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    ~Scratch()
+    {
+        if (blocks.empty()) return;
+        (void)hipStreamSynchronize(s);
+        for (void *p : blocks) dfree(p);
+    }
+    // *p <- count elements of T (double, or the int status words and int8_t residues that share the pool of doubles)
+    template <class T> int take(T **p, int64_t count)
+    {
+        double *q = nullptr;
+        *p = nullptr;
+        GPX_TRY(dalloc(&q, (count * (int64_t)sizeof(T) + 7) / 8));
+        blocks.push_back(q);
+        *p = reinterpret_cast<T *>(q);
+        return 0;
+    }
+    // a block that outlives the call (committed to a handle on success) leaves the scope
+    double *release(double *p) { blocks.erase(std::find(blocks.begin(), blocks.end(), (void *)p)); return p; }
+};
+
 // fp64 product emulated on int8 matrix cores (emu.hip, Ozaki scheme II): C[rows, cols] -= A[rows, K] B[cols, K]^T, row-major;
 // K a multiple of 128 below 2^17.  emu_enabled(K): GPX_EMU_F64 (default 1) and K >= GPX_EMU_MIN_K (default 4096); the path depends on K only.
-// Workspace (int8 residues of A / B tiles, product residues, row scales), owned by the caller: emu_work_need grows it to cover a product's
-// shape, emu_work_alloc takes it from the pool (dalloc), emu_work_free returns it once the work queued with it has finished.
+// Workspace (int8 residues of A / B tiles, product residues, row scales): emu_work_need grows it to cover a product's shape,
+// emu_work_alloc takes it into the caller's Scratch.
 struct EmuWork { int8_t *ra = nullptr, *rb = nullptr, *rr = nullptr; int *sig = nullptr; int64_t a_bytes = 0, b_bytes = 0, r_bytes = 0, sig_n = 0; };
 void emu_work_need(EmuWork &w, int64_t rows, int64_t cols, int64_t K);
-int emu_work_alloc(EmuWork &w);
-void emu_work_free(EmuWork &w);
+int emu_work_alloc(EmuWork &w, Scratch &sc);
 int emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t rows, int64_t cols, int64_t K,
                     const EmuWork &w, hipStream_t s, Profiler *prof);
 bool emu_enabled(int64_t K);
 int emu_moduli();                        // GPX_EMU_MODULI (default 16, 2 .. 16)
 int emu_scale_bits(int64_t K, int L);    // alpha + beta: the largest s with K 2^s < P / 2
 
-// device selection (api.hip): hipSetDevice to the calling thread's gpx_set_device choice, gfx950 only
-int gpx_require_device();
-
-// caching device allocator and stream cache (api.hip)
-int dalloc(double **p, int64_t elems);
-void dfree(void *p);
-int gpx_thread_device();   // the calling host thread's gpx_set_device choice (api.hip)
-hipStream_t stream_acquire(int high_priority);
-void stream_release(hipStream_t s, int high_priority);
-
-// propagate.hip
+// ---- launchers of propagate.hip ----------------------------------------------------------------
+int launch_nll_grad(const double *Kinv, int64_t ld, int64_t n, int64_t npad, int d, const double *alpha, const double *xw,
+                    double v, double *partial, double *out_dev, int *dmax_used, hipStream_t s, Profiler *prof);
+int launch_kinv_pass(const double *Kinv, int64_t ld, int64_t npad, int nc, const double *V, double *KV, hipStream_t s,
+                     Profiler *prof, int64_t nrows = 0);
 int launch_dot_pairs(const std::vector<std::pair<const double *, const double *>> &pr, long n, double *out_dev, hipStream_t s);
-int propagate_build_V(gpx_handle *h, const double *u_host);
+int launch_exact_sum(const double *Kinv, int64_t ld, int64_t npad, int d, const double *beta, const double *aT,
+                     const double *bT, const double *e, const double *F, double *partial, double *out_dev, hipStream_t s,
+                     Profiler *prof, int64_t row0 = 0, int64_t row1 = 0);
+int launch_approx_build(const double *x, int64_t n, int64_t npad, int d, const double *u_dev, const double *w_dev, double v,
+                        double vt, double *VM, double *AUX, double *cplain, hipStream_t s);
+int launch_trace(const double *x, int64_t n, int64_t npad, int d, const double *u_dev, const double *w_dev,
+                 const double *Sigma_dev, const double *cplain, double *tr, hipStream_t s);
+int launch_cjh(const double *x, int64_t n, int d, const double *u_dev, const double *w_dev, double v, double vt, double *C,
+               double *J, double *H, hipStream_t s);
+int launch_approx_build_many(const double *x, int64_t n, int64_t npad, int d, const double *U_dev, const double *Sigma_dev,
+                             int64_t sigma_stride, int64_t nb, int64_t rows_pad, const double *w_dev, double v, double vt, double *Z,
+                             hipStream_t s, Profiler *prof);
+int launch_approx_reduce_many(const double *Zs, int64_t npad, int d, const double *y, const double *Sigma_dev, int64_t sigma_stride,
+                              int64_t nb, double vplusvt, double *out, int64_t ldo, hipStream_t s, Profiler *prof);
+int launch_exact_build(const double *x, int64_t n, int64_t npad, int d, const double *u_dev, const double *w_dev,
+                       const double *Ls_dev, const double *dinv_diag_dev, double v, double vt, double nc1, double *aT,
+                       double *bT, double *e, double *F, double *lm, hipStream_t s);
+int launch_exact_build_generic(const double *x, int64_t n, int64_t npad, int d, const double *u_dev, const double *Ls_dev,
+                               const double *dinv_diag_dev, const double *C_dev, double nc1, double *aT, double *bT, double *e, double *F,
+                               double *lm, hipStream_t s);
+
+// ---- host orchestration shared by fit.hip, predict.hip and propagate_api.hip ---------------------
+// (helpers, not interface: they stay out of the library's dynamic symbol table)
+#pragma GCC visibility push(hidden)
+#define CHECK_H(h)                                                  \
+    do {                                                            \
+        if (!(h)) { gpx_set_error("null handle"); return GPX_ERR_BAD_ARG; } \
+        GPX_HIP(hipSetDevice((h)->device));                         \
+    } while (0)
+// entry points that evaluate the GaussianCovariance kernel need the handle's inputs and theta: not a gpx_fit_matrix handle
+#define NEED_KERNEL(h, what)                                                                                             \
+    do {                                                                                                                 \
+        if ((h)->d == 0) { gpx_set_error(what ": the handle was built from a supplied matrix (gpx_fit_matrix): no inputs / theta to evaluate the kernel on"); return GPX_ERR_STATE; } \
+    } while (0)
+
+int fetch_small(double *dst, const double *src, size_t n);   // a few doubles from a caller's pointer (host or device) into host memory (runtime.hip)
+int ensure_Z(gpx_handle *h, int64_t rows);
+int ensure_kinv(gpx_handle *h);
+int ensure_kinv_rows(gpx_handle *h, int64_t row0, int64_t row1, const double **base);
+int check_row_range(const gpx_handle *h, int64_t row0, int64_t row1, const char *what);   // of the row-sharded entry points (predict.hip)
+
+// The many-right-hand-side solve behind gpx_predict / gpx_predict_kv and gpx_propagate_approx_many (predict.hip): rows of h->Z (leading
+// dimension npad, zero padded to the 128-row tile) -> Zs = Z L^-T, in chunks of `chunk` rows.  begin sizes the chunk and takes Z, Zs and
+// the emulated updates' workspace once per call; run solves one chunk; the buffers (and whatever else the caller takes from sc) go back
+// with the RowSolve.
+struct RowSolve {
+    Scratch sc;
+    int64_t chunk = 0;
+    bool few = false;       // a handful of rows: the few-right-hand-side solver (one sweep over the factor's triangle)
+    double *Zs = nullptr;   // [chunk, npad]
+    EmuWork ew;
+    const EmuWork *emu = nullptr;
+    explicit RowSolve(hipStream_t s) : sc(s) {}
+};
+int row_solve_begin(gpx_handle *h, int64_t m, RowSolve &rs);
+// Zs[0 : mp) <- Z[0 : mp) L^-T (mc real rows, mp = mc rounded up to the tile); red: the fused row sums of tsolve.hip (many rows only)
+int row_solve_run(gpx_handle *h, const RowSolve &rs, int64_t mc, int64_t mp, const GemmReduce *red);
+#pragma GCC visibility pop

@@ -23,7 +23,7 @@
 // producers store tiles write-through (sc1), every storing wave drains its stores, the workgroup meets, ONE lane bumps the counter
 // with an agent-scope atomic; consumers poll relaxed from one wave, then ONE agent-scope acquire (L1 invalidate), workgroup barrier,
 // plain loads / LDS-DMA.  Every spin is bounded: an expired wait sets the ABORT word (all workgroups leave) and the factorisation's
-// STALL word (the host then repeats the fit on the launch-per-step schedule; api.hip).
+// STALL word (the host then repeats the fit on the launch-per-step schedule; fit.hip).
 //
 // Dependencies are counters, all relative to the first tile column c0 = 8 pbase the kernel owns:
 //   ver[i][j]   eighth-tile updates applied to tile (i, j) by the panels before its own: BULK adds 8, either part of an SQ slab 1 -> 8 q

@@ -304,30 +304,12 @@ void emu_work_need(EmuWork &w, int64_t rows, int64_t cols, int64_t K)
     w.sig_n = std::max(w.sig_n, rt + ct);
 }
 
-int emu_work_alloc(EmuWork &w)
+int emu_work_alloc(EmuWork &w, Scratch &sc)
 {
-    double *a = nullptr, *b = nullptr, *r = nullptr, *g = nullptr;
-    int rc = 0;
-    if ((rc = dalloc(&a, w.a_bytes / 8)) || (rc = dalloc(&b, w.b_bytes / 8)) || (rc = dalloc(&r, w.r_bytes / 8)) || (rc = dalloc(&g, (w.sig_n + 1) / 2))) {
-        if (a) dfree(a);
-        if (b) dfree(b);
-        if (r) dfree(r);
-        return rc;
-    }
-    w.ra = (int8_t *)a;
-    w.rb = (int8_t *)b;
-    w.rr = (int8_t *)r;
-    w.sig = (int *)g;
-    return 0;
-}
-
-void emu_work_free(EmuWork &w)   // (after the work queued with it has finished)
-{
-    if (w.ra) dfree(w.ra);
-    if (w.rb) dfree(w.rb);
-    if (w.rr) dfree(w.rr);
-    if (w.sig) dfree(w.sig);
-    w = EmuWork();
+    GPX_TRY(sc.take(&w.ra, w.a_bytes));
+    GPX_TRY(sc.take(&w.rb, w.b_bytes));
+    GPX_TRY(sc.take(&w.rr, w.r_bytes));
+    return sc.take(&w.sig, w.sig_n);
 }
 
 // What the kernels take for granted of a caller outside the library (gpx_emu_gemm_nt_sub; tsolve.hip passes slabs of 128-padded matrices at
@@ -400,12 +382,12 @@ extern "C" int gpx_emu_gemm_nt_sub(const double *A, int64_t lda, const double *B
     if (rows < 0 || cols < 0 || !A || !B || !C) { gpx_set_error("gpx_emu_gemm_nt_sub: bad arguments"); return GPX_ERR_BAD_ARG; }
     GPX_TRY(emu_check_args(A, lda, B, ldb, ldc, cols, K));   // before the workspace is sized and allocated
     if (rows == 0 || cols == 0) return 0;
+    Scratch sc(0);
     EmuWork w;
     emu_work_need(w, rows, cols, K);
-    GPX_TRY(emu_work_alloc(w));
+    GPX_TRY(emu_work_alloc(w, sc));
     int rc = emu_gemm_nt_sub(A, lda, B, ldb, C, ldc, rows, cols, K, w, 0, nullptr);
     if (hipStreamSynchronize(0) != hipSuccess && rc == 0) { gpx_set_error("gpx_emu_gemm_nt_sub: stream failed"); rc = GPX_ERR_HIP; }
-    emu_work_free(w);
     return rc;
 }
 
@@ -425,15 +407,14 @@ extern "C" int gpx_bench_emu_i8(int64_t rows, int64_t cols, int64_t K, int nmod,
         gpx_set_error("gpx_bench_emu_i8: bad arguments");
         return GPX_ERR_BAD_ARG;
     }
-    double *wa = nullptr, *wb = nullptr, *wr = nullptr;
+    Scratch sc(0);
+    int8_t *wa = nullptr, *wb = nullptr, *wr = nullptr;
     int rc = 0;
-    if ((rc = dalloc(&wa, rows * K * nmod / 8)) || (rc = dalloc(&wb, cols * K * nmod / 8)) || (rc = dalloc(&wr, rows * cols * nmod / 8))) {
-        if (wa) dfree(wa);
-        if (wb) dfree(wb);
-        return rc;
-    }
-    hipLaunchKernelGGL(emu_fill_kernel, dim3(4096), dim3(256), 0, 0, (int8_t *)wa, (long)(rows * K * nmod), 1u);
-    hipLaunchKernelGGL(emu_fill_kernel, dim3(4096), dim3(256), 0, 0, (int8_t *)wb, (long)(cols * K * nmod), 2u);
+    GPX_TRY(sc.take(&wa, rows * K * nmod));
+    GPX_TRY(sc.take(&wb, cols * K * nmod));
+    GPX_TRY(sc.take(&wr, rows * cols * nmod));
+    hipLaunchKernelGGL(emu_fill_kernel, dim3(4096), dim3(256), 0, 0, wa, (long)(rows * K * nmod), 1u);
+    hipLaunchKernelGGL(emu_fill_kernel, dim3(4096), dim3(256), 0, 0, wb, (long)(cols * K * nmod), 2u);
     const int tm = (int)(rows / EMU_BT), tn = (int)(cols / EMU_BT);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     float t = 0.0f;
@@ -442,7 +423,7 @@ extern "C" int gpx_bench_emu_i8(int64_t rows, int64_t cols, int64_t K, int nmod,
     for (int it = -1; it < iters && e == hipSuccess; ++it) {   // it = -1: warm-up
         if (it == 0) e = hipEventRecord(e0, 0);
         hipLaunchKernelGGL(emu_i8_gemm_kernel, dim3((unsigned)(tm * tn * nmod)), dim3(512), 0, 0, (const int8_t *)wa, (const int8_t *)wb,
-                           (long)(rows * K), (long)(cols * K), (int)K, (int8_t *)wr, (long)cols, (long)(rows * cols), tm, tn);
+                           (long)(rows * K), (long)(cols * K), (int)K, wr, (long)cols, (long)(rows * cols), tm, tn);
         if (e == hipSuccess) e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipEventRecord(e1, 0);
@@ -453,8 +434,5 @@ extern "C" int gpx_bench_emu_i8(int64_t rows, int64_t cols, int64_t K, int nmod,
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     (void)hipDeviceSynchronize();
-    dfree(wa);
-    dfree(wb);
-    dfree(wr);
     return rc;
 }

@@ -1,0 +1,253 @@
+// predict.hip -- the C-ABI of libgpx (include/gpx.h), part 2: everything that solves against the factor after a fit -- the
+// many-row solve behind estimate_many, the few-vector solves, K^-1 and its row panels.
+#include <algorithm>
+#include <initializer_list>
+
+#include "common.h"
+
+int ensure_Z(gpx_handle *h, int64_t rows)
+{
+    if (h->zrows >= rows && h->Z) return 0;
+    if (h->Z) { dfree(h->Z); h->Z = nullptr; h->zrows = 0; }
+    GPX_TRY(dalloc(&h->Z, rows * h->npad));
+    h->zrows = rows;
+    return 0;
+}
+
+// ---- predict (RowSolve: common.h) ----------------------------------------------------------------
+int row_solve_begin(gpx_handle *h, int64_t m, RowSolve &rs)
+{
+    int64_t cap = ((int64_t)8 << 30) / (h->npad * (int64_t)sizeof(double));   // rows per 8 GB buffer (two of them: Z and Zs)
+    cap = std::max<int64_t>(TILE, cap / TILE * TILE);
+    cap = std::min<int64_t>(cap, 32768);
+    rs.chunk = std::min<int64_t>(round_up(m, TILE), cap);
+    GPX_TRY(ensure_Z(h, rs.chunk));
+    // the triangular solve runs out of place against the inverted diagonal squares (tsolve.hip): second slab-major buffer
+    GPX_TRY(rs.sc.take(&rs.Zs, rs.chunk * h->npad));
+    rs.few = m <= 32 && h->tri.ready() && h->tri.P >= 2;
+    // the emulated updates' workspace (emu.hip), once per call: sized for the chunk, it serves every shorter one
+    if (!rs.few) trsm_emu_need(rs.ew, rs.chunk, &h->tri, 0, h->tri.P);
+    if (rs.ew.a_bytes) GPX_TRY(emu_work_alloc(rs.ew, rs.sc));
+    rs.emu = rs.ew.ra ? &rs.ew : nullptr;
+    return 0;
+}
+
+int row_solve_run(gpx_handle *h, const RowSolve &rs, int64_t mc, int64_t mp, const GemmReduce *red)
+{
+    // a handful of queries (estimate(x_star), plots): the solver for a few right-hand sides -- one forward sweep over the factor's
+    // triangle (HBM-bound, ~0.5 ms at N = 16384) instead of the many-right-hand-side recursion on one 128-row tile (its products
+    // would be 128 x K strips with K up to N/2: 2.5-3 ms)
+    if (!red && rs.few) return h->tri.solve(h->Z, h->npad, (int)mc, rs.Zs, nullptr, h->stream, &h->prof);
+    return trsm_right_lt_squares(h->Z, rs.Zs, h->npad, mp, &h->tri, 0, h->tri.P, h->stream, &h->prof, red, rs.emu);
+}
+
+// xs != nullptr: the cross-covariance rows come from the Gram kernel (gpx_predict); otherwise kv [m, n] is the caller's
+// (gpx_predict_kv) and kdiag [m] the prior variance of each query (the diagonal of cov_matrix(x_star), GaussianProcess.py:75)
+static int predict_common(gpx_handle *h, const double *xs, const double *kv, const double *kdiag, int64_t m, double *mean_out, double *var_out)
+{
+    hipStream_t s = h->stream;
+    const int d = h->d;
+    RowSolve rs(s);
+    GPX_TRY(row_solve_begin(h, m, rs));
+    const int64_t chunk = rs.chunk;
+    double *xq = nullptr, *xqw = nullptr, *mv = nullptr, *kd = nullptr, *part = nullptr;
+    int rc = 0;
+    // the row sums |z|^2 and z.y ride in the epilogue of each slab's last product (tsolve.hip): per row one partial pair per 64 columns
+    const int64_t nslots = h->npad / 64;
+    const bool fused = chunk >= 3072;
+    GPX_TRY(rs.sc.take(&xq, chunk * std::max(d, 1)));
+    GPX_TRY(rs.sc.take(&xqw, chunk * std::max(d, 1)));
+    GPX_TRY(rs.sc.take(&mv, 2 * chunk));
+    GPX_TRY(rs.sc.take(&kd, chunk));
+    if (fused) GPX_TRY(rs.sc.take(&part, 2 * chunk * nslots));
+    double *Zs = rs.Zs;
+    for (int64_t m0 = 0; m0 < m && rc == 0; m0 += chunk) {
+        const int64_t mc = std::min<int64_t>(chunk, m - m0), mp = round_up(mc, TILE);
+        hipError_t e = hipSuccess;
+        if (xs) {
+            e = hipMemcpyAsync(xq, xs + m0 * d, sizeof(double) * mc * d, hipMemcpyDefault, s);
+            if (e != hipSuccess) { gpx_set_error("copy xs failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
+            if ((rc = launch_scale_rows(xq, mc, mp, d, h->sw, xqw, s))) break;
+            // kv = cross-covariance (no vt), zero padded: rows >= mc and columns >= n are 0
+            if ((rc = launch_gram(xqw, mc, h->xs_w, h->n, d, h->v, 0.0, 0, 1, h->Z, h->npad, mp, h->npad, s, &h->prof))) break;
+        } else {
+            // the operator's own cross-covariance rows, zero padded to the tile grid
+            e = hipMemsetAsync(h->Z, 0, sizeof(double) * mp * h->npad, s);
+            if (e == hipSuccess) e = hipMemcpy2DAsync(h->Z, sizeof(double) * h->npad, kv + m0 * h->n, sizeof(double) * h->n, sizeof(double) * h->n, mc, hipMemcpyDefault, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(kd, kdiag + m0, sizeof(double) * mc, hipMemcpyDefault, s);
+            if (e != hipSuccess) { gpx_set_error("copy kv / kdiag failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
+        }
+        // Z <- kv L^-T  : row m of Z is (L^-1 kv_m)^T
+        // var = k_mm - |z|^2 (k_mm = v + vt for the built-in kernel: k includes vt, GaussianProcess.py:75,78) ; mean = z . y
+        if (fused && mp >= 3072) {
+            GemmReduce red;
+            red.y = h->y; red.p2 = part; red.py = part + chunk * nslots; red.nslots = nslots;
+            if ((rc = row_solve_run(h, rs, mc, mp, &red))) break;
+            ProfScope ps(&h->prof, s, GPX_K_REDUCE, 16.0 * (double)mc * (double)nslots);
+            if ((rc = launch_predict_finish(red.p2, red.py, nslots, mc, h->v + h->vt, mv, mv + chunk, s, xs ? nullptr : kd))) break;
+        } else {
+            if ((rc = row_solve_run(h, rs, mc, mp, nullptr))) break;
+            if ((rc = launch_predict_reduce(Zs, h->npad, mc, h->npad, h->y, h->v + h->vt, mv, mv + chunk, s, &h->prof, xs ? nullptr : kd))) break;
+        }
+        e = hipMemcpyAsync(mean_out + m0, mv, sizeof(double) * mc, hipMemcpyDefault, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(var_out + m0, mv + chunk, sizeof(double) * mc, hipMemcpyDefault, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { gpx_set_error("predict copy-out failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
+    }
+    return rc;
+}
+
+extern "C" int gpx_predict(gpx_handle *h, const double *xs, int64_t m, double *mean_out, double *var_out)
+{
+    CHECK_H(h);
+    NEED_KERNEL(h, "gpx_predict");
+    if (m < 0 || (m > 0 && (!xs || !mean_out || !var_out))) { gpx_set_error("gpx_predict: bad arguments"); return GPX_ERR_BAD_ARG; }
+    if (m == 0) return 0;
+    return predict_common(h, xs, nullptr, nullptr, m, mean_out, var_out);
+}
+
+// estimate_many for ANY operator (skgpuppy/GaussianProcess.py:68-80): kv = cov.cov_matrix_ij(x_star, x) [m, n] and
+// kdiag = diag(cov.cov_matrix(x_star)) [m] come from the caller; mean_out = kv alpha (WITHOUT meant), var_out = kdiag - |L^-1 kv^T|^2.
+// Works on every handle (gpx_fit and gpx_fit_matrix).
+extern "C" int gpx_predict_kv(gpx_handle *h, const double *kv, int64_t m, const double *kdiag, double *mean_out, double *var_out)
+{
+    CHECK_H(h);
+    if (m < 0 || (m > 0 && (!kv || !kdiag || !mean_out || !var_out))) { gpx_set_error("gpx_predict_kv: bad arguments"); return GPX_ERR_BAD_ARG; }
+    if (m == 0) return 0;
+    return predict_common(h, nullptr, kv, kdiag, m, mean_out, var_out);
+}
+
+// ---- a few vectors against the factor ----------------------------------------------------------------
+// The block loop of gpx_solve / gpx_chol_mul: the rows of in [nrhs, n], 32 at a time and zero padded to npad, into b; run(nc) queues
+// the solver call on that block; every (device block [32, npad], caller's [nrhs, n] or null) pair of outs is then copied out.
+template <class Run>
+static int row_blocks(gpx_handle *h, const double *in, int nrhs, double *b, Run run, std::initializer_list<std::pair<const double *, double *>> outs)
+{
+    hipStream_t s = h->stream;
+    const size_t rn = sizeof(double) * h->n, rp = sizeof(double) * h->npad;
+    for (int c0 = 0; c0 < nrhs; c0 += 32) {
+        const int nc = std::min(32, nrhs - c0);
+        GPX_HIP(hipMemsetAsync(b, 0, 32 * rp, s));
+        GPX_HIP(hipMemcpy2DAsync(b, rp, in + (int64_t)c0 * h->n, rn, rn, nc, hipMemcpyDefault, s));
+        GPX_TRY(run(nc));
+        for (const auto &o : outs)
+            if (o.second) GPX_HIP(hipMemcpy2DAsync(o.second + (int64_t)c0 * h->n, rn, o.first, rp, rn, nc, hipMemcpyDefault, s));
+    }
+    GPX_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+// K^-1 B (and L^-1 B) for a few right-hand sides without K^-1: two sweeps over the triangle of L per 32 right-hand sides
+extern "C" int gpx_solve(gpx_handle *h, const double *B, int nrhs, double *Linv_B_out, double *Kinv_B_out)
+{
+    CHECK_H(h);
+    if (!B || nrhs < 1 || (!Linv_B_out && !Kinv_B_out)) { gpx_set_error("gpx_solve: bad arguments (nrhs=%d)", nrhs); return GPX_ERR_BAD_ARG; }
+    Scratch sc(h->stream);
+    double *b = nullptr;   // [3][32][npad]: zero-padded right-hand sides, L^-1 B, K^-1 B
+    GPX_TRY(sc.take(&b, 3 * 32 * h->npad));
+    double *y = b + 32 * h->npad, *a = y + 32 * h->npad;
+    return row_blocks(h, B, nrhs, b, [&](int nc) { return h->tri.solve(b, h->npad, nc, Linv_B_out ? y : nullptr, Kinv_B_out ? a : nullptr, h->stream, &h->prof); },
+                      {{y, Linv_B_out}, {a, Kinv_B_out}});
+}
+
+// L Z for a few vectors (rows of Z): a draw t = L z ~ N(0, K) for every standard-normal row z
+extern "C" int gpx_chol_mul(gpx_handle *h, const double *Z, int nrhs, double *out)
+{
+    CHECK_H(h);
+    if (!Z || !out || nrhs < 1) { gpx_set_error("gpx_chol_mul: bad arguments (nrhs=%d)", nrhs); return GPX_ERR_BAD_ARG; }
+    Scratch sc(h->stream);
+    double *b = nullptr;   // [2][32][npad]
+    GPX_TRY(sc.take(&b, 2 * 32 * h->npad));
+    double *o = b + 32 * h->npad;
+    return row_blocks(h, Z, nrhs, b, [&](int nc) { return h->tri.mul_lower(b, h->npad, nc, o, h->stream); }, {{o, out}});
+}
+
+// ---- K^-1 and its row panels ---------------------------------------------------------------------------
+int ensure_kinv(gpx_handle *h)
+{
+    if (h->Kinv) return 0;
+    hipStream_t s = h->stream;
+    GPX_TRY(ensure_Z(h, h->npad));
+    Scratch sc(s);
+    double *K = nullptr;
+    GPX_TRY(sc.take(&K, h->npad * h->npad));
+    // Z = L^-T (upper triangular, structured recursion) ; Kinv = Z Z^T = L^-T L^-1 (lower strips, then mirrored)
+    // (handles without a prepared solver: the 128-column leaves of chol.hip)
+    GPX_TRY(h->tri.ready() ? build_kinv_from_solver(&h->tri, h->Z, K, s, &h->prof)
+                           : build_kinv_from_factor(h->L, h->npad, h->nblk, h->Dinv, h->Z, K, s, &h->prof));
+    const hipError_t e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { gpx_set_error("Kinv build failed: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
+    h->Kinv = sc.release(K);
+    return 0;
+}
+
+// Rows [row0, row1) (multiples of 128, row1 <= npad) of K^-1 for the row-sharded propagation: the whole matrix if it exists or if the
+// range is all of it, otherwise a row PANEL built alone (TriSolver::kinv_rows: 2 m N^2 flop, three m x N buffers) and kept until another
+// range is asked for.  Returns in *base a pointer that is indexed with ABSOLUTE row numbers (base + i * npad is row i).
+int ensure_kinv_rows(gpx_handle *h, int64_t row0, int64_t row1, const double **base)
+{
+    const int64_t np = h->npad;
+    // a panel that does not contain the range is replaced by one over the hull of both (a rank's Approx and Exact shards differ: equal
+    // rows against equal area of the triangle); a hull of three quarters of the rows or more is not worth a panel
+    if (h->KinvRows && !(h->kr0 <= row0 && row1 <= h->kr1)) { row0 = std::min(row0, h->kr0); row1 = std::max(row1, h->kr1); }
+    if (!h->Kinv && 4 * (row1 - row0) < 3 * np && h->tri.ready() && row1 > row0) {
+        if (!(h->KinvRows && h->kr0 <= row0 && row1 <= h->kr1)) {
+            hipStream_t s = h->stream;
+            if (h->KinvRows) { GPX_HIP(hipStreamSynchronize(s)); dfree(h->KinvRows); h->KinvRows = nullptr; }
+            const int64_t m = row1 - row0;
+            Scratch sc(s);
+            double *X = nullptr, *Zb = nullptr, *Yb = nullptr, *Tb = nullptr;
+            GPX_TRY(sc.take(&X, m * np));
+            GPX_TRY(sc.take(&Zb, m * np));
+            GPX_TRY(sc.take(&Yb, m * np));
+            GPX_TRY(sc.take(&Tb, (int64_t)CHOL_PANEL_COLS * np));
+            GPX_TRY(h->tri.kinv_rows(row0, row1, X, Zb, Yb, Tb, s, &h->prof));
+            const hipError_t e = hipStreamSynchronize(s);
+            if (e != hipSuccess) { gpx_set_error("K^-1 row panel failed: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
+            h->KinvRows = sc.release(X); h->kr0 = row0; h->kr1 = row1;
+        }
+        *base = reinterpret_cast<const double *>(reinterpret_cast<uintptr_t>(h->KinvRows) - (uintptr_t)(sizeof(double) * (size_t)(h->kr0 * np)));
+        return 0;
+    }
+    if (h->KinvRows && !h->Kinv) { GPX_HIP(hipStreamSynchronize(h->stream)); dfree(h->KinvRows); h->KinvRows = nullptr; h->kr0 = h->kr1 = 0; }
+    GPX_TRY(ensure_kinv(h));
+    *base = h->Kinv;
+    return 0;
+}
+
+// a row range of the sharded entry points: 0 <= row0 <= row1 <= n, each end a multiple of 128 or n
+int check_row_range(const gpx_handle *h, int64_t row0, int64_t row1, const char *what)
+{
+    if (row0 < 0 || row1 < row0 || row1 > h->n || (row0 % TILE && row0 != h->n) || (row1 % TILE && row1 != h->n)) {
+        gpx_set_error("%s: bad arguments (rows [%ld, %ld) of %ld)", what, (long)row0, (long)row1, (long)h->n);
+        return GPX_ERR_BAD_ARG;
+    }
+    return 0;
+}
+
+// test / tool access: rows [row0, row1) of K^-1 (multiples of 128 or n) -> out [row1 - row0, n] (host or device), built as the
+// row-sharded propagation builds them
+extern "C" int gpx_kinv_rows(gpx_handle *h, int64_t row0, int64_t row1, double *out)
+{
+    CHECK_H(h);
+    // (an empty range is an error here alone; with it excluded, row0 == n cannot pass and the shared test is the test of old)
+    if (!out || row1 <= row0) { gpx_set_error("gpx_kinv_rows: bad arguments (rows [%ld, %ld) of %ld)", (long)row0, (long)row1, (long)h->n); return GPX_ERR_BAD_ARG; }
+    GPX_TRY(check_row_range(h, row0, row1, "gpx_kinv_rows"));
+    const double *base = nullptr;
+    GPX_TRY(ensure_kinv_rows(h, row0, round_up(row1, TILE), &base));
+    GPX_HIP(hipMemcpy2DAsync(out, sizeof(double) * h->n, base + row0 * h->npad, sizeof(double) * h->npad, sizeof(double) * h->n, (size_t)(row1 - row0),
+                             hipMemcpyDefault, h->stream));
+    GPX_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+extern "C" int gpx_kinv(gpx_handle *h, double *Kinv_out)
+{
+    CHECK_H(h);
+    if (!Kinv_out) { gpx_set_error("null argument"); return GPX_ERR_BAD_ARG; }
+    GPX_TRY(ensure_kinv(h));
+    GPX_HIP(hipMemcpy2DAsync(Kinv_out, sizeof(double) * h->n, h->Kinv, sizeof(double) * h->npad, sizeof(double) * h->n, h->n,
+                             hipMemcpyDefault, h->stream));
+    GPX_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+}

@@ -1,0 +1,597 @@
+// propagate_api.hip -- the C-ABI of libgpx (include/gpx.h), part 3: the uncertainty-propagation entry points (Approx, Exact, their
+// sharded and supplied-matrix forms); the kernels they launch live in propagate.hip.
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <new>
+
+#include "common.h"
+
+// ---- propagation -----------------------------------------------------------------------------------
+// layout of h->V: [128][npad] rows 0 = C, 1..d = J_k (rest zero, so the block is one GEMM row tile)
+// layout of h->KV: [128][npad] = V Kinv ; followed by AUX [(d+1)][npad] (row 0 tr, rows 1..d H_kk),
+//                  cplain[npad], udev[GPX_MAX_D], Sigma[GPX_MAX_D^2], out[256]
+static inline double *aux_ptr(gpx_handle *h) { return h->KV + (int64_t)TILE * h->npad; }
+static inline double *cplain_ptr(gpx_handle *h) { return aux_ptr(h) + (int64_t)(h->d + 1) * h->npad; }
+static inline double *udev_ptr(gpx_handle *h) { return cplain_ptr(h) + h->npad; }
+static inline double *sigma_ptr(gpx_handle *h) { return udev_ptr(h) + GPX_MAX_D; }
+static inline double *out_ptr(gpx_handle *h) { return sigma_ptr(h) + GPX_MAX_D * GPX_MAX_D; }
+
+static int ensure_prop_buffers(gpx_handle *h)
+{
+    if (h->V) return 0;
+    // both buffers are committed to the handle only when both allocations and the clear have been issued
+    Scratch sc(h->stream);
+    double *V = nullptr, *KV = nullptr;
+    GPX_TRY(sc.take(&V, (int64_t)TILE * h->npad));
+    GPX_TRY(sc.take(&KV, (int64_t)TILE * h->npad + (int64_t)(h->d + 2) * h->npad + GPX_MAX_D + GPX_MAX_D * GPX_MAX_D + 256));
+    if (hipMemsetAsync(V, 0, sizeof(double) * TILE * h->npad, h->stream) != hipSuccess) { gpx_set_error("hipMemsetAsync(V) failed"); return GPX_ERR_HIP; }
+    h->V = sc.release(V);
+    h->KV = sc.release(KV);
+    return 0;
+}
+
+// how many new-u propagations are answered by the two streaming triangular solves before K^-1 is materialised
+// (49 ms once at N = 16384, then one pass over it per new u): a single propagate_GA after a fit never pays for
+// K^-1, an inverse-propagation loop switches over after a while
+static int approx_solve_limit()
+{
+    static const int v = getenv("GPX_APPROX_SOLVE_CALLS") ? atoi(getenv("GPX_APPROX_SOLVE_CALLS")) : 24;
+    return v;
+}
+
+// u and Sigma (the caller's pointers, host or device; Sigma may be null) into the handle's pinned block and on to udev_ptr / sigma_ptr:
+// hstage [0, 64) u | [64, 64 + 4096) Sigma | [4160, ..) results.  The block is pinned, so the uploads are asynchronous: no entry
+// point synchronises for its arguments.
+static inline double *staged_sigma(gpx_handle *h) { return h->hstage + 64; }
+static inline double *staged_out(gpx_handle *h) { return h->hstage + 64 + GPX_MAX_D * GPX_MAX_D; }
+static int stage_u_sigma(gpx_handle *h, const double *u, const double *Sigma)
+{
+    const int d = h->d;
+    GPX_TRY(ensure_prop_buffers(h));
+    if (!h->hstage && !(h->hstage = pinned_acquire())) { gpx_set_error("hipHostMalloc (staging block) failed"); return GPX_ERR_HIP; }
+    double *uh = h->hstage, *Sh = staged_sigma(h);
+    GPX_TRY(fetch_small(uh, u, d));
+    GPX_HIP(hipMemcpyAsync(udev_ptr(h), uh, sizeof(double) * d, hipMemcpyHostToDevice, h->stream));
+    if (!Sigma) return 0;
+    GPX_TRY(fetch_small(Sh, Sigma, (size_t)d * d));
+    GPX_HIP(hipMemcpyAsync(sigma_ptr(h), Sh, sizeof(double) * d * d, hipMemcpyHostToDevice, h->stream));
+    return 0;
+}
+
+// V, AUX and KV for the staged u (stage_u_sigma), unless they already belong to it
+static int prepare_u(gpx_handle *h)
+{
+    const bool by_solves = !h->Kinv && h->approx_solves < approx_solve_limit();
+    if (!by_solves) GPX_TRY(ensure_kinv(h));
+    const double *uh = h->hstage;
+    if (h->have_u && memcmp(uh, h->u, sizeof(double) * h->d) == 0) return 0;
+    hipStream_t s = h->stream;
+    h->have_u = false;
+    GPX_TRY(launch_approx_build(h->x, h->n, h->npad, h->d, udev_ptr(h), h->wdev, h->v, h->vt, h->V, aux_ptr(h), cplain_ptr(h), s));
+    if (by_solves) {
+        // KV = V K^-1 row by row: K^-1 v = L^-T (L^-1 v) as two sweeps of the few-right-hand-side triangular solver
+        // (tsolve.hip) that read the triangle of L once each -- no K^-1, no transposed copy of the factor
+        const int nrhs = h->d + 1;
+        for (int c0 = 0; c0 < nrhs; c0 += 32)
+            GPX_TRY(h->tri.solve(h->V + (int64_t)c0 * h->npad, h->npad, std::min(32, nrhs - c0), nullptr, h->KV + (int64_t)c0 * h->npad, s, &h->prof));
+        ++h->approx_solves;
+    } else {
+        // KV = V Kinv^T (= V Kinv): rows 0..d are Kinv C, Kinv J_k -- the ONE pass over Kinv shared by K2..K6
+        GPX_TRY(launch_kinv_pass(h->Kinv, h->npad, h->npad, h->d + 1, h->V, h->KV, s, &h->prof));
+    }
+    memcpy(h->u, uh, sizeof(double) * h->d);
+    h->have_u = true;
+    return 0;
+}
+
+extern "C" int gpx_cjh(gpx_handle *h, const double *u, double *C, double *J, double *H)
+{
+    CHECK_H(h);
+    NEED_KERNEL(h, "gpx_cjh");
+    if (!u) { gpx_set_error("null u"); return GPX_ERR_BAD_ARG; }
+    const int64_t n = h->n;
+    const int d = h->d;
+    hipStream_t s = h->stream;
+    Scratch sc(s);
+    double *ud = nullptr, *buf = nullptr;
+    GPX_TRY(sc.take(&ud, d));
+    GPX_TRY(sc.take(&buf, n * (1 + d + (int64_t)d * d)));
+    GPX_HIP(hipMemcpy(ud, u, sizeof(double) * d, hipMemcpyDefault));
+    double *Cd = buf, *Jd = buf + n, *Hd = Jd + n * d;
+    GPX_TRY(launch_cjh(h->x, n, d, ud, h->wdev, h->v, h->vt, C ? Cd : nullptr, J ? Jd : nullptr, H ? Hd : nullptr, s));
+    if (C) GPX_HIP(hipMemcpyAsync(C, Cd, sizeof(double) * n, hipMemcpyDefault, s));
+    if (J) GPX_HIP(hipMemcpyAsync(J, Jd, sizeof(double) * n * d, hipMemcpyDefault, s));
+    if (H) GPX_HIP(hipMemcpyAsync(H, Hd, sizeof(double) * n * d * d, hipMemcpyDefault, s));
+    GPX_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+// The dot pairs of the Approx sums that the vectors k0 <= k < k1 of [C, J_1 .. J_d] carry, over the rows from row0 on.  In the order of
+// the whole list -- 0 beta.C  1 beta.tr  2 C.KinvC  3 KinvC.tr (vector 0), then per k >= 1: J_k.KinvJ_k , beta.J_k -- a range of vectors
+// is a run of consecutive slots: *slot0 (optional) is the slot of the first pair returned.
+typedef std::vector<std::pair<const double *, const double *>> DotPairs;
+static DotPairs approx_pairs(gpx_handle *h, int64_t row0, int k0, int k1, int *slot0 = nullptr)
+{
+    DotPairs pr;
+    const double *al = h->alpha + row0, *tr = aux_ptr(h) + row0;
+    if (slot0) *slot0 = k0 == 0 ? 0 : 2 + 2 * k0;
+    for (int k = k0; k < k1; ++k) {
+        const double *v = h->V + (int64_t)k * h->npad + row0, *kv = h->KV + (int64_t)k * h->npad + row0;
+        if (k == 0) {
+            pr.push_back({al, v});
+            pr.push_back({al, tr});
+            pr.push_back({v, kv});
+            pr.push_back({kv, tr});
+        } else {
+            pr.push_back({v, kv});
+            pr.push_back({al, v});
+        }
+    }
+    return pr;
+}
+
+extern "C" int gpx_propagate_approx(gpx_handle *h, const double *u, const double *Sigma, double *mean, double *var,
+                                    double *sigma2, double *rest)
+{
+    CHECK_H(h);
+    NEED_KERNEL(h, "gpx_propagate_approx");
+    if (!u || !Sigma) { gpx_set_error("null u / Sigma"); return GPX_ERR_BAD_ARG; }
+    const int d = h->d;
+    const int64_t np = h->npad;
+    hipStream_t s = h->stream;
+    GPX_TRY(stage_u_sigma(h, u, Sigma));
+    GPX_TRY(prepare_u(h));
+    const double *Sh = staged_sigma(h);
+    double *o = staged_out(h);
+    GPX_TRY(launch_trace(h->x, h->n, np, d, udev_ptr(h), h->wdev, sigma_ptr(h), cplain_ptr(h), aux_ptr(h), s));
+    const DotPairs pr = approx_pairs(h, 0, 0, d + 1);
+    GPX_TRY(launch_dot_pairs(pr, np, out_ptr(h), s));
+    GPX_HIP(hipMemcpyAsync(o, out_ptr(h), sizeof(double) * pr.size(), hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipStreamSynchronize(s));                         // the call's one synchronisation
+    const double mu = o[0] + 0.5 * o[1];                      // UncertaintyPropagation.py:397-408
+    const double s2 = (h->v + h->vt) - o[2];                  // :412-433  (C(u,u) = v + vt)
+    double var2 = 0.0;                                        // :435-460
+    for (int k = 0; k < d; ++k) var2 += Sh[k * d + k] * (o[4 + 2 * k] - o[5 + 2 * k] * o[5 + 2 * k]);
+    var2 = -var2;
+    const double var3 = -o[3];                                // :464-479 with Kinv symmetric
+    if (mean) *mean = mu;
+    if (sigma2) *sigma2 = s2;
+    if (rest) *rest = var2 + var3;
+    if (var) *var = s2 + var2 + var3;
+    return 0;
+}
+
+// Batched Approx: b inputs as b (d + 2) right-hand sides [C, tr, J_1..J_d] of the many-right-hand-side solver that serves
+// gpx_predict.  With K = L L^T, y = L^-1 t and z_v = L^-1 v every sum of gpx_propagate_approx is a row product of the solved block:
+// beta.v = z_v.y, v.Kinv v = |z_v|^2, tr.Kinv C = z_tr.z_C.  No K^-1, no use of the handle's single-u cache, one synchronisation
+// per chunk; an input never straddles two chunks.
+extern "C" int gpx_propagate_approx_many(gpx_handle *h, const double *U, const double *Sigma, int sigma_shared, int64_t b,
+                                         double *mean, double *var, double *sigma2, double *rest)
+{
+    CHECK_H(h);
+    NEED_KERNEL(h, "gpx_propagate_approx_many");
+    if (b < 0 || (b > 0 && (!U || !Sigma || !mean || !var))) { gpx_set_error("gpx_propagate_approx_many: bad arguments"); return GPX_ERR_BAD_ARG; }
+    if (b == 0) return 0;
+    hipStream_t s = h->stream;
+    const int d = h->d, nrow = d + 2;
+    RowSolve rs(s);
+    GPX_TRY(row_solve_begin(h, b * nrow, rs));
+    const int64_t bchunk = rs.chunk / nrow;           // inputs per chunk (chunk >= 128 > d + 2)
+    const int64_t nsig = sigma_shared ? 1 : bchunk;
+    double *ud = nullptr, *sd = nullptr, *od = nullptr;
+    int rc = 0;
+    GPX_TRY(rs.sc.take(&ud, bchunk * d));
+    GPX_TRY(rs.sc.take(&sd, nsig * d * d));
+    GPX_TRY(rs.sc.take(&od, 4 * bchunk));
+    hipError_t e = hipSuccess;
+    if (sigma_shared) e = hipMemcpyAsync(sd, Sigma, sizeof(double) * d * d, hipMemcpyDefault, s);
+    if (e != hipSuccess) { gpx_set_error("copy Sigma failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; }
+    const int64_t sstride = sigma_shared ? 0 : (int64_t)d * d;
+    for (int64_t b0 = 0; b0 < b && rc == 0; b0 += bchunk) {
+        const int64_t bc = std::min<int64_t>(bchunk, b - b0), mc = bc * nrow, mp = round_up(mc, TILE);
+        e = hipMemcpyAsync(ud, U + b0 * d, sizeof(double) * bc * d, hipMemcpyDefault, s);
+        if (e == hipSuccess && !sigma_shared) e = hipMemcpyAsync(sd, Sigma + b0 * d * d, sizeof(double) * bc * d * d, hipMemcpyDefault, s);
+        if (e != hipSuccess) { gpx_set_error("copy U / Sigma failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
+        if ((rc = launch_approx_build_many(h->x, h->n, h->npad, d, ud, sd, sstride, bc, mp, h->wdev, h->v, h->vt, h->Z, s, &h->prof))) break;
+        if ((rc = row_solve_run(h, rs, mc, mp, nullptr))) break;
+        if ((rc = launch_approx_reduce_many(rs.Zs, h->npad, d, h->y, sd, sstride, bc, h->v + h->vt, od, bchunk, s, &h->prof))) break;
+        e = hipMemcpyAsync(mean + b0, od, sizeof(double) * bc, hipMemcpyDefault, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(var + b0, od + bchunk, sizeof(double) * bc, hipMemcpyDefault, s);
+        if (e == hipSuccess && sigma2) e = hipMemcpyAsync(sigma2 + b0, od + 2 * bchunk, sizeof(double) * bc, hipMemcpyDefault, s);
+        if (e == hipSuccess && rest) e = hipMemcpyAsync(rest + b0, od + 3 * bchunk, sizeof(double) * bc, hipMemcpyDefault, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { gpx_set_error("propagate copy-out failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
+    }
+    return rc;
+}
+
+// Row-sharded form of the Approx propagation (last row): the 4 + 2 d sums of gpx_propagate_approx restricted to
+// the rows [row0, row1) of K^-1 -- (K^-1 v)_i needs row i of K^-1 only, and every quadratic form is a sum over i.  The
+// caller adds the partials of all row panels (one all-reduce of 4 + 2 d doubles across the ranks) and finishes with
+// skgpuppy_amd.distributed.combine_approx_partials.  partial_out: 0 beta.C  1 beta.tr  2 C.KinvC  3 KinvC.tr, then per k:
+// J_k.KinvJ_k, beta.J_k.  row0 must be a multiple of 128; row1 a multiple of 128 or n.
+extern "C" int gpx_propagate_approx_rows(gpx_handle *h, const double *u, const double *Sigma, int64_t row0, int64_t row1,
+                                         double *partial_out)
+{
+    CHECK_H(h);
+    NEED_KERNEL(h, "gpx_propagate_approx_rows");
+    if (!u || !Sigma || !partial_out) { gpx_set_error("gpx_propagate_approx_rows: null argument"); return GPX_ERR_BAD_ARG; }
+    GPX_TRY(check_row_range(h, row0, row1, "gpx_propagate_approx_rows"));
+    const int d = h->d;
+    const int64_t np = h->npad;
+    hipStream_t s = h->stream;
+    const double *kbase = nullptr;
+    if (row1 > row0) GPX_TRY(ensure_kinv_rows(h, row0, round_up(row1, TILE), &kbase));
+    h->have_u = false;   // KV is about to hold a row panel only
+    GPX_TRY(stage_u_sigma(h, u, Sigma));
+    GPX_TRY(launch_approx_build(h->x, h->n, np, d, udev_ptr(h), h->wdev, h->v, h->vt, h->V, aux_ptr(h), cplain_ptr(h), s));
+    double *tr = aux_ptr(h);
+    GPX_TRY(launch_trace(h->x, h->n, np, d, udev_ptr(h), h->wdev, sigma_ptr(h), cplain_ptr(h), tr, s));
+    const int64_t r1p = round_up(row1, TILE), len = row1 > row0 ? r1p - row0 : 0;   // rows past n are padding: V and tr are zero there
+    const int npair = 4 + 2 * d;
+    if (len > 0) {
+        GPX_TRY(launch_kinv_pass(kbase + row0 * np, np, np, d + 1, h->V, h->KV + row0, s, &h->prof, len));
+        GPX_TRY(launch_dot_pairs(approx_pairs(h, row0, 0, d + 1), len, out_ptr(h), s));
+    } else GPX_HIP(hipMemsetAsync(out_ptr(h), 0, sizeof(double) * npair, s));
+    double o[4 + 2 * GPX_MAX_D];
+    GPX_HIP(hipMemcpyAsync(o, out_ptr(h), sizeof(double) * npair, hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipStreamSynchronize(s));
+    GPX_HIP(hipMemcpy(partial_out, o, sizeof(double) * npair, hipMemcpyDefault));
+    return 0;
+}
+
+// Right-hand-side-sharded form of the Approx propagation for the multi-GPU host: the share of the 4 + 2 d sums (same order as
+// gpx_propagate_approx_rows) that the vectors k0 <= k < k1 of [C, J_1 .. J_d] contribute -- vector 0 carries beta.C, beta.tr,
+// C.KinvC, KinvC.tr; vector k >= 1 carries J_k.KinvJ_k and beta.J_k -- with K^-1 v through the two-sweep triangular solver on the
+// rank's copy of the factor.  No K^-1 is ever materialised (34 GB per rank at N = 65536); the other entries come back zero, the
+// ranks add their vectors in one all-reduce.  (The sweeps are bound by the bytes of the factor, not by the number of vectors:
+// the split saves memory, not time.)
+extern "C" int gpx_propagate_approx_rhs(gpx_handle *h, const double *u, const double *Sigma, int k0, int k1, double *partial_out)
+{
+    CHECK_H(h);
+    NEED_KERNEL(h, "gpx_propagate_approx_rhs");
+    if (!u || !Sigma || !partial_out || k0 < 0 || k1 < k0 || k1 > h->d + 1) {
+        gpx_set_error("gpx_propagate_approx_rhs: bad arguments (vectors [%d, %d) of %d)", k0, k1, h->d + 1);
+        return GPX_ERR_BAD_ARG;
+    }
+    const int d = h->d;
+    const int64_t np = h->npad;
+    hipStream_t s = h->stream;
+    h->have_u = false;   // KV is about to hold some rows only
+    GPX_TRY(stage_u_sigma(h, u, Sigma));
+    const int npair = 4 + 2 * d;
+    double o[4 + 2 * GPX_MAX_D];
+    for (int i = 0; i < npair; ++i) o[i] = 0.0;
+    if (k1 > k0) {
+        GPX_TRY(launch_approx_build(h->x, h->n, np, d, udev_ptr(h), h->wdev, h->v, h->vt, h->V, aux_ptr(h), cplain_ptr(h), s));
+        double *tr = aux_ptr(h);
+        GPX_TRY(launch_trace(h->x, h->n, np, d, udev_ptr(h), h->wdev, sigma_ptr(h), cplain_ptr(h), tr, s));
+        for (int c0 = k0; c0 < k1; c0 += 32)
+            GPX_TRY(h->tri.solve(h->V + (int64_t)c0 * np, np, std::min(32, k1 - c0), nullptr, h->KV + (int64_t)c0 * np, s, &h->prof));
+        int slot0 = 0;
+        const DotPairs pr = approx_pairs(h, 0, k0, k1, &slot0);
+        GPX_TRY(launch_dot_pairs(pr, np, out_ptr(h), s));
+        double tmp[4 + 2 * GPX_MAX_D];
+        GPX_HIP(hipMemcpyAsync(tmp, out_ptr(h), sizeof(double) * pr.size(), hipMemcpyDeviceToHost, s));
+        GPX_HIP(hipStreamSynchronize(s));
+        for (size_t i = 0; i < pr.size(); ++i) o[slot0 + i] = tmp[i];
+    }
+    GPX_HIP(hipMemcpy(partial_out, o, sizeof(double) * npair, hipMemcpyDefault));
+    return 0;
+}
+
+extern "C" int gpx_propagate_dvh(gpx_handle *h, const double *u, double *dvh_out)
+{
+    CHECK_H(h);
+    NEED_KERNEL(h, "gpx_propagate_dvh");
+    if (!u || !dvh_out) { gpx_set_error("null argument"); return GPX_ERR_BAD_ARG; }
+    const int d = h->d;
+    const int64_t np = h->npad;
+    hipStream_t s = h->stream;
+    GPX_TRY(stage_u_sigma(h, u, nullptr));
+    GPX_TRY(prepare_u(h));
+    DotPairs pr;
+    for (int k = 0; k < d; ++k) {
+        pr.push_back({h->V + (int64_t)(k + 1) * np, h->KV + (int64_t)(k + 1) * np});   // J_k Kinv J_k
+        pr.push_back({h->alpha, h->V + (int64_t)(k + 1) * np});                        // beta . J_k
+        pr.push_back({h->KV, aux_ptr(h) + (int64_t)(k + 1) * np});                     // (Kinv C) . H_kk
+    }
+    GPX_TRY(launch_dot_pairs(pr, np, out_ptr(h), s));
+    double o[3 * GPX_MAX_D];
+    GPX_HIP(hipMemcpyAsync(o, out_ptr(h), sizeof(double) * pr.size(), hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipStreamSynchronize(s));
+    double res[GPX_MAX_D];
+    for (int k = 0; k < d; ++k) {
+        const double v2 = -(o[3 * k] - o[3 * k + 1] * o[3 * k + 1]);   // UncertaintyPropagation.py:593-607
+        const double v3 = -o[3 * k + 2];                               // :614-627
+        res[k] = v2 + v3;
+    }
+    GPX_HIP(hipMemcpy(dvh_out, res, sizeof(double) * d, hipMemcpyDefault));
+    return 0;
+}
+
+// small dense inverse (Gauss-Jordan, partial pivoting) for (W/2 + Sigma), d <= 64
+static int small_inverse(const double *A, int d, double *inv)
+{
+    std::vector<double> M((size_t)d * 2 * d);
+    for (int i = 0; i < d; ++i)
+        for (int j = 0; j < d; ++j) { M[(size_t)i * 2 * d + j] = A[i * d + j]; M[(size_t)i * 2 * d + d + j] = (i == j); }
+    for (int c = 0; c < d; ++c) {
+        int p = c;
+        for (int r = c + 1; r < d; ++r)
+            if (fabs(M[(size_t)r * 2 * d + c]) > fabs(M[(size_t)p * 2 * d + c])) p = r;
+        if (M[(size_t)p * 2 * d + c] == 0.0) return -1;
+        if (p != c)
+            for (int j = 0; j < 2 * d; ++j) std::swap(M[(size_t)p * 2 * d + j], M[(size_t)c * 2 * d + j]);
+        const double piv = M[(size_t)c * 2 * d + c];
+        for (int j = 0; j < 2 * d; ++j) M[(size_t)c * 2 * d + j] /= piv;
+        for (int r = 0; r < d; ++r)
+            if (r != c) {
+                const double f = M[(size_t)r * 2 * d + c];
+                if (f != 0.0)
+                    for (int j = 0; j < 2 * d; ++j) M[(size_t)r * 2 * d + j] -= f * M[(size_t)c * 2 * d + j];
+            }
+    }
+    for (int i = 0; i < d; ++i)
+        for (int j = 0; j < d; ++j) inv[i * d + j] = M[(size_t)i * 2 * d + d + j];
+    return 0;
+}
+
+// Girard's constants of the Exact moments (UncertaintyPropagation.py:247-257, :292-303; Winv of the reference holds w): the diagonal dd,
+// the normalisers nc1 / nc2 and Ls = the symmetric part of Lambda = 2 W - (Sigma + W^-1 / 2)^-1
+struct ExactConstants { std::vector<double> Ls, dd; double nc1 = 1.0, nc2 = 1.0; };
+static int exact_constants(const double *w, const double *Sigma, int d, ExactConstants &c)
+{
+    std::vector<double> A((size_t)d * d), Ai((size_t)d * d);
+    c.Ls.resize((size_t)d * d);
+    c.dd.resize(d);
+    double nc1 = 1.0, nc2 = 1.0;
+    for (int k = 0; k < d; ++k) {
+        const double wk = w[k], sk = Sigma[k * d + k];
+        c.dd[k] = wk - wk / (1.0 + wk * sk);
+        nc1 *= (1.0 + wk * sk);
+        nc2 *= (2.0 * wk * sk + 1.0);
+    }
+    c.nc1 = 1.0 / sqrt(nc1);
+    c.nc2 = 1.0 / sqrt(nc2);
+    for (int i = 0; i < d; ++i)
+        for (int j = 0; j < d; ++j) A[(size_t)i * d + j] = Sigma[i * d + j] + (i == j ? 0.5 / w[i] : 0.0);
+    if (small_inverse(A.data(), d, Ai.data())) { gpx_set_error("W/2 + Sigma is singular"); return GPX_ERR_BAD_ARG; }
+    for (int i = 0; i < d; ++i)
+        for (int j = 0; j < d; ++j) {
+            const double lij = (i == j ? 2.0 * w[i] : 0.0) - Ai[(size_t)i * d + j];
+            const double lji = (i == j ? 2.0 * w[i] : 0.0) - Ai[(size_t)j * d + i];
+            c.Ls[(size_t)i * d + j] = 0.5 * (lij + lji);     // only the symmetric part enters z^T Lambda^-1 z
+        }
+    return 0;
+}
+
+// row0 / row1 (row1 > 0): only the rows [row0, row1) of the sums; then *mean / *var receive the PARTIAL sums  sum_i beta_i l_i
+// and  sum_{i in rows, j <= i} w_ij (Kinv_ij - beta_i beta_j) L_ij / nc2,  and *nc2_out the normaliser
+static int exact_common(gpx_handle *h, const double *u, const double *Sigma, bool want_var, double *mean, double *var,
+                        int64_t row0 = 0, int64_t row1 = 0, double *nc2_out = nullptr)
+{
+    const int d = h->d;
+    const int64_t np = h->npad;
+    hipStream_t s = h->stream;
+    const double *kbase = nullptr;
+    if (want_var) {
+        if (row1 > 0) GPX_TRY(ensure_kinv_rows(h, row0, round_up(row1, TILE), &kbase));   // a rank's row panel (gpx_propagate_exact_rows)
+        else { GPX_TRY(ensure_kinv(h)); kbase = h->Kinv; }
+    }
+    GPX_TRY(stage_u_sigma(h, u, Sigma));
+    ExactConstants c;
+    GPX_TRY(exact_constants(h->w, staged_sigma(h), d, c));
+    const double nc2 = c.nc2;
+    // device scratch: aT[d][np], bT[d][np], e, F, lm, partial[np/16], consts
+    Scratch sc(s);
+    double *buf = nullptr;
+    GPX_TRY(sc.take(&buf, (2 * (int64_t)d + 4) * np + (int64_t)d * d + d + 8));
+    double *aT = buf, *bT = aT + (int64_t)d * np, *e = bT + (int64_t)d * np, *F = e + np, *lm = F + np, *partial = lm + np;
+    double *Lsd = partial + np, *ddd = Lsd + (int64_t)d * d, *outd = ddd + d;
+    GPX_HIP(hipMemcpyAsync(Lsd, c.Ls.data(), sizeof(double) * d * d, hipMemcpyHostToDevice, s));
+    GPX_HIP(hipMemcpyAsync(ddd, c.dd.data(), sizeof(double) * d, hipMemcpyHostToDevice, s));
+    GPX_TRY(launch_exact_build(h->x, h->n, np, d, udev_ptr(h), h->wdev, Lsd, ddd, h->v, h->vt, c.nc1, aT, bT, e, F, lm, s));
+    const bool ranged = row1 > 0;
+    const int64_t r0 = ranged ? row0 : 0, r1 = ranged ? round_up(row1, TILE) : np;   // rows past n are padding (l, F are zero there)
+    if (r1 > r0) GPX_TRY(launch_dot_pairs({{h->alpha + r0, lm + r0}}, r1 - r0, outd, s));
+    else GPX_HIP(hipMemsetAsync(outd, 0, sizeof(double) * 2, s));
+    if (want_var) GPX_TRY(launch_exact_sum(kbase, np, np, d, h->alpha, aT, bT, e, F, partial, outd + 1, s, &h->prof, r0, ranged ? r1 : 0));
+    double o[2] = {0, 0};
+    GPX_HIP(hipMemcpyAsync(o, outd, sizeof(double) * 2, hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipStreamSynchronize(s));
+    const double mu = o[0];
+    if (nc2_out) *nc2_out = nc2;
+    if (ranged) {   // partial sums: the caller adds them over the row panels and finishes
+        if (mean) *mean = o[0];
+        if (var) *var = o[1];
+        return 0;
+    }
+    if (mean) *mean = mu;
+    if (want_var && var) *var = (h->v + h->vt) - nc2 * o[1] - mu * mu;   // UncertaintyPropagation.py:377
+    return 0;
+}
+
+// Row-sharded Exact propagation for the multi-GPU host: partial_out = [ sum_{i in rows} beta_i l_i ,
+// sum_{i in rows, j <= i} w_ij (Kinv_ij - beta_i beta_j) L_ij / nc2 , nc2 ].  After adding the first two over the row panels:
+// mean = p0 (+ meant), var = v + vt - nc2 p1 - p0^2  (UncertaintyPropagation.py:377).  The j <= i triangle makes row i cost
+// i + 1 pairs: shard by equal AREA (skgpuppy_amd.distributed.row_shards(..., triangular=True)).
+extern "C" int gpx_propagate_exact_rows(gpx_handle *h, const double *u, const double *Sigma, int64_t row0, int64_t row1,
+                                        double *partial_out)
+{
+    CHECK_H(h);
+    NEED_KERNEL(h, "gpx_propagate_exact_rows");
+    if (!u || !Sigma || !partial_out) { gpx_set_error("gpx_propagate_exact_rows: null argument"); return GPX_ERR_BAD_ARG; }
+    GPX_TRY(check_row_range(h, row0, row1, "gpx_propagate_exact_rows"));
+    double p[3] = {0.0, 0.0, 0.0};
+    if (row1 > row0) GPX_TRY(exact_common(h, u, Sigma, true, &p[0], &p[1], row0, row1, &p[2]));
+    else GPX_TRY(exact_common(h, u, Sigma, false, nullptr, nullptr, 0, 0, &p[2]));   // empty panel: the normaliser only
+    if (row1 <= row0) { p[0] = 0.0; p[1] = 0.0; }
+    GPX_HIP(hipMemcpy(partial_out, p, sizeof(double) * 3, hipMemcpyDefault));
+    return 0;
+}
+
+extern "C" int gpx_propagate_exact(gpx_handle *h, const double *u, const double *Sigma, double *mean, double *var)
+{
+    CHECK_H(h);
+    NEED_KERNEL(h, "gpx_propagate_exact");
+    if (!u || !Sigma) { gpx_set_error("null u / Sigma"); return GPX_ERR_BAD_ARG; }
+    return exact_common(h, u, Sigma, true, mean, var);
+}
+
+extern "C" int gpx_exact_mean(gpx_handle *h, const double *u, const double *Sigma, double *mean)
+{
+    CHECK_H(h);
+    NEED_KERNEL(h, "gpx_exact_mean");
+    if (!u || !Sigma || !mean) { gpx_set_error("null argument"); return GPX_ERR_BAD_ARG; }
+    return exact_common(h, u, Sigma, false, mean, nullptr);
+}
+
+// ---- a14 for ANY operator.  The reference's UncertaintyPropagationExact talks to the GP only through _get_beta, _get_W_inv,
+// _inv_cov_matrix, _covariance and x (skgpuppy/UncertaintyPropagation.py:269-290, :323-379): with a Covariance subclass of its own
+// cov_matrix_ij / __call__ it runs and returns numbers -- Girard's correction factors built from theta[2:2+d], applied to the
+// operator's own C(u, x_i).  Here: C_ux [n] and cuu = cov(u, u) from the caller (the operator's scalar kernel on the host, N calls as in
+// the reference), x [n, d] and w [d] (the diagonal of _get_W_inv) handle-free, K^-1 and beta from the handle (gpx_fit_matrix or
+// gpx_fit) -- or, with h == NULL, explicit Kinv [n, n] and beta [n] (the reference's Kinv attribute, e.g. of an SPGP model); the
+// N and N^2 sums run in the kernels of the built-in path.  mean WITHOUT meant.
+// lower triangle <- mean of both triangles, padding (rows / columns >= n of the [np, ld] buffer) <- 0, in place: row i's workgroup
+// reads A[j][i], j < i, which no other workgroup writes (those write columns below THEIR row index only)
+__global__ __launch_bounds__(256) void mean_lower_pad_kernel(double *A, long ld, long n, long np)
+{
+    const long i = blockIdx.x;
+    if (i >= n) {
+        for (long j = threadIdx.x; j < np; j += 256) A[i * ld + j] = 0.0;
+        return;
+    }
+    for (long j = threadIdx.x; j < i; j += 256) A[i * ld + j] = 0.5 * (A[i * ld + j] + A[j * ld + i]);
+    for (long j = n + threadIdx.x; j < np; j += 256) A[i * ld + j] = 0.0;
+}
+
+// An explicit K^-1 / beta kept on the device across calls (gpx_kinv_model_*): uploaded, padded to the tile grid and symmetrised ONCE.
+// Uncertainty propagation is typically called many times on one model; without this every call of the h == NULL form moved N^2 doubles
+// over PCIe again.
+struct gpx_kinv_model {
+    int device = 0;
+    int64_t n = 0, np = 0;
+    double *Kp = nullptr;     // [np, np]: lower triangle = mean of both triangles of the supplied matrix, zero padding
+    double *bpad = nullptr;   // [np]: beta, zero padded
+};
+
+// device copies of an explicit K^-1 (optional) and beta, queued on the stream of the caller's scratch
+static int upload_explicit(const double *Kinv, const double *beta, int64_t n, int64_t np, bool want_kinv, Scratch &sc, double **Kp, double **bpad)
+{
+    hipStream_t s = sc.s;
+    *Kp = nullptr;
+    GPX_TRY(sc.take(bpad, np));
+    GPX_HIP(hipMemsetAsync(*bpad, 0, sizeof(double) * np, s));
+    GPX_HIP(hipMemcpyAsync(*bpad, beta, sizeof(double) * n, hipMemcpyDefault, s));
+    if (want_kinv) {
+        // K^-1 goes row by row straight into ONE buffer padded to the tile grid (the padding never enters: F = 0 there).  The pair kernel
+        // visits j <= i only (weight 2) where the reference sums both triangles: the lower triangle of a supplied K^-1 becomes the mean of
+        // both (a Woodbury-built inverse is symmetric to rounding only).
+        GPX_TRY(sc.take(Kp, np * np));
+        GPX_HIP(hipMemcpy2DAsync(*Kp, sizeof(double) * np, Kinv, sizeof(double) * n, sizeof(double) * n, n, hipMemcpyDefault, s));
+        hipLaunchKernelGGL(mean_lower_pad_kernel, dim3((unsigned)np), dim3(256), 0, s, *Kp, (long)np, (long)n, (long)np);
+        GPX_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+// Girard's exact moments from device-resident K^-1 (kbase [np, np], null: mean only) and beta (bdev [np]); everything else from the caller
+static int exact_matrix_core(hipStream_t s, Profiler *prof, const double *kbase, const double *bdev, const double *x, int64_t n, int d, const double *w,
+                             const double *C_ux, const double *u, const double *Sigma, double cuu, double *mean, double *var)
+{
+    for (int k = 0; k < d; ++k)
+        if (!(w[k] > 0.0) || !isfinite(w[k])) { gpx_set_error("gpx_propagate_exact_matrix: w[%d]=%g", k, w[k]); return GPX_ERR_BAD_ARG; }
+    const int64_t np = round_up(n, TILE);
+    const bool want_var = var != nullptr && kbase != nullptr;
+    ExactConstants c;
+    GPX_TRY(exact_constants(w, Sigma, d, c));
+    Scratch sc(s);
+    double *buf = nullptr;
+    GPX_TRY(sc.take(&buf, (2 * (int64_t)d + 6) * np + n * (int64_t)d + (int64_t)d * d + 2 * d + 8));
+    double *aT = buf, *bT = aT + (int64_t)d * np, *e = bT + (int64_t)d * np, *F = e + np, *lm = F + np, *partial = lm + np;
+    double *Cd = partial + np, *xd = Cd + np, *Lsd = xd + n * (int64_t)d, *ddd = Lsd + (int64_t)d * d, *ud = ddd + d, *outd = ud + d;
+    double o[2] = {0, 0};
+    GPX_HIP(hipMemcpyAsync(Lsd, c.Ls.data(), sizeof(double) * d * d, hipMemcpyHostToDevice, s));
+    GPX_HIP(hipMemcpyAsync(ddd, c.dd.data(), sizeof(double) * d, hipMemcpyHostToDevice, s));
+    GPX_HIP(hipMemcpyAsync(ud, u, sizeof(double) * d, hipMemcpyDefault, s));
+    GPX_HIP(hipMemcpyAsync(xd, x, sizeof(double) * n * d, hipMemcpyDefault, s));
+    GPX_HIP(hipMemcpyAsync(Cd, C_ux, sizeof(double) * n, hipMemcpyDefault, s));
+    GPX_TRY(launch_exact_build_generic(xd, n, np, d, ud, Lsd, ddd, Cd, c.nc1, aT, bT, e, F, lm, s));
+    GPX_TRY(launch_dot_pairs({{bdev, lm}}, np, outd, s));
+    if (want_var) GPX_TRY(launch_exact_sum(kbase, np, np, d, bdev, aT, bT, e, F, partial, outd + 1, s, prof));
+    GPX_HIP(hipMemcpyAsync(o, outd, sizeof(double) * (want_var ? 2 : 1), hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipStreamSynchronize(s));
+    if (mean) *mean = o[0];
+    if (var) *var = cuu - c.nc2 * o[1] - o[0] * o[0];   // UncertaintyPropagation.py:377
+    return 0;
+}
+
+extern "C" int gpx_propagate_exact_matrix(gpx_handle *h, const double *Kinv, const double *beta, const double *x, int64_t n, int d,
+                                          const double *w, const double *C_ux, const double *u, const double *Sigma, double cuu,
+                                          double *mean, double *var)
+{
+    GPX_TRY(gpx_require_device());
+    if (h) GPX_HIP(hipSetDevice(h->device));
+    if (!x || !w || !C_ux || !u || !Sigma || n < 1 || d < 1 || d > GPX_MAX_D || (!h && (!beta || (var && !Kinv))) || (h && h->n != n)) {
+        gpx_set_error("gpx_propagate_exact_matrix: bad arguments (n=%ld d=%d%s)", (long)n, d, (h && h->n != n) ? ": the handle holds another n" : "");
+        return GPX_ERR_BAD_ARG;
+    }
+    const bool want_var = var != nullptr;   // the mean is beta . l alone: no K^-1 (46 ms to build at C3), no N^2 pass
+    if (h) {
+        if (want_var) GPX_TRY(ensure_kinv(h));
+        return exact_matrix_core(h->stream, &h->prof, want_var ? h->Kinv : nullptr, h->alpha, x, n, d, w, C_ux, u, Sigma, cuu, mean, var);
+    }
+    // explicit K^-1 / beta, one call: upload, use, free (many calls on one model: gpx_kinv_model_create + gpx_propagate_exact_model)
+    const int64_t np = round_up(n, TILE);
+    Scratch sc(nullptr);
+    double *Kp = nullptr, *bpad = nullptr;
+    GPX_TRY(upload_explicit(Kinv, beta, n, np, want_var, sc, &Kp, &bpad));
+    return exact_matrix_core(nullptr, nullptr, Kp, bpad, x, n, d, w, C_ux, u, Sigma, cuu, mean, var);
+}
+
+extern "C" int gpx_kinv_model_create(const double *Kinv, const double *beta, int64_t n, gpx_kinv_model **out)
+{
+    if (out) *out = nullptr;
+    GPX_TRY(gpx_require_device());
+    if (!Kinv || !beta || !out || n < 1) { gpx_set_error("gpx_kinv_model_create: bad arguments"); return GPX_ERR_BAD_ARG; }
+    int dev = 0;
+    GPX_HIP(hipGetDevice(&dev));
+    const int64_t np = round_up(n, TILE);
+    Scratch sc(nullptr);
+    double *Kp = nullptr, *bpad = nullptr;
+    GPX_TRY(upload_explicit(Kinv, beta, n, np, true, sc, &Kp, &bpad));
+    const hipError_t e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) { gpx_set_error("gpx_kinv_model_create: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
+    gpx_kinv_model *m = new (std::nothrow) gpx_kinv_model();
+    if (!m) { gpx_set_error("out of host memory"); return GPX_ERR_HIP; }
+    m->device = dev;
+    m->n = n;
+    m->np = np;
+    m->Kp = sc.release(Kp);
+    m->bpad = sc.release(bpad);
+    *out = m;
+    return 0;
+}
+
+extern "C" void gpx_kinv_model_free(gpx_kinv_model *m)
+{
+    if (!m) return;
+    (void)hipSetDevice(m->device);
+    (void)hipDeviceSynchronize();
+    dfree(m->Kp);
+    dfree(m->bpad);
+    delete m;
+}
+
+extern "C" int gpx_propagate_exact_model(gpx_kinv_model *m, const double *x, int d, const double *w, const double *C_ux, const double *u,
+                                         const double *Sigma, double cuu, double *mean, double *var)
+{
+    if (!m || !x || !w || !C_ux || !u || !Sigma || d < 1 || d > GPX_MAX_D) { gpx_set_error("gpx_propagate_exact_model: bad arguments"); return GPX_ERR_BAD_ARG; }
+    GPX_HIP(hipSetDevice(m->device));
+    return exact_matrix_core(nullptr, nullptr, m->Kp, m->bpad, x, m->n, d, w, C_ux, u, Sigma, cuu, mean, var);
+}

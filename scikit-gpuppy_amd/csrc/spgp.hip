@@ -367,33 +367,28 @@ extern "C" int gpx_spgp_predict(gpx_spgp *h, const double *xs, int64_t ms, doubl
     const int64_t mp = h->mpad;
     const int64_t chunk = std::min<int64_t>(round_up(ms, TILE), 65536);
     double *xq = nullptr, *xqw = nullptr, *Ka = nullptr, *Kb = nullptr, *Kc = nullptr, *o = nullptr;
-    auto body = [&]() -> int {
-        GPX_TRY(dalloc(&xq, chunk * d)); GPX_TRY(dalloc(&xqw, chunk * d)); GPX_TRY(dalloc(&Ka, chunk * mp)); GPX_TRY(dalloc(&Kb, chunk * mp));
-        GPX_TRY(dalloc(&Kc, chunk * mp));
-        GPX_TRY(dalloc(&o, 5 * chunk));
-        double *mean = o, *unused = o + chunk, *va = o + 2 * chunk, *vb = o + 3 * chunk, *var = o + 4 * chunk;
-        for (int64_t q0 = 0; q0 < ms; q0 += chunk) {
-            const int64_t qc = std::min<int64_t>(chunk, ms - q0), qp = round_up(qc, TILE);
-            GPX_HIP(hipMemcpyAsync(xq, xs + q0 * d, sizeof(double) * qc * d, hipMemcpyDefault, s));
-            GPX_TRY(launch_scale_rows(xq, qc, qp, d, h->sw, xqw, s));
-            GPX_TRY(launch_gram(xqw, qc, h->xbw, h->m, d, h->v, 0.0, 0, 1, Ka, mp, qp, mp, s, nullptr));   // K_*M
-            GPX_TRY(launch_predict_reduce(Ka, mp, qc, mp, h->beta, 0.0, mean, unused, s, nullptr));       // K_*M beta
-            // K_*M L^-T for both factors: one product each with the explicit inverse (zero triangle skipped)
-            GPX_TRY(launch_gemm_nt(Ka, mp, h->LinvM, mp, Kb, mp, qp, mp, mp, 1.0, 0.0, 0, s, nullptr, 0, GEMM_TRI_B_LOWER));
-            GPX_TRY(launch_gemm_nt(Ka, mp, h->LinvB, mp, Kc, mp, qp, mp, mp, 1.0, 0.0, 0, s, nullptr, 0, GEMM_TRI_B_LOWER));
-            GPX_TRY(launch_predict_reduce(Kb, mp, qc, mp, h->mzero, h->v + h->vt, unused, va, s, nullptr));   // v + vt - |K_*M L_M^-T|^2
-            GPX_TRY(launch_predict_reduce(Kc, mp, qc, mp, h->mzero, 0.0, unused, vb, s, nullptr));            //        - |K_*M L_B^-T|^2
-            GPX_TRY(vec_op(VEC_SUB, qc, qc, 0.0, va, vb, var, nullptr, s));
-            GPX_HIP(hipMemcpyAsync(mean_out + q0, mean, sizeof(double) * qc, hipMemcpyDefault, s));
-            GPX_HIP(hipMemcpyAsync(var_out + q0, var, sizeof(double) * qc, hipMemcpyDefault, s));
-            GPX_HIP(hipStreamSynchronize(s));
-        }
-        return 0;
-    };
-    const int rc = body();
-    (void)hipStreamSynchronize(s);
-    dfree(xq); dfree(xqw); dfree(Ka); dfree(Kb); dfree(Kc); dfree(o);
-    return rc;
+    Scratch sc(s);
+    GPX_TRY(sc.take(&xq, chunk * d)); GPX_TRY(sc.take(&xqw, chunk * d)); GPX_TRY(sc.take(&Ka, chunk * mp)); GPX_TRY(sc.take(&Kb, chunk * mp));
+    GPX_TRY(sc.take(&Kc, chunk * mp));
+    GPX_TRY(sc.take(&o, 5 * chunk));
+    double *mean = o, *unused = o + chunk, *va = o + 2 * chunk, *vb = o + 3 * chunk, *var = o + 4 * chunk;
+    for (int64_t q0 = 0; q0 < ms; q0 += chunk) {
+        const int64_t qc = std::min<int64_t>(chunk, ms - q0), qp = round_up(qc, TILE);
+        GPX_HIP(hipMemcpyAsync(xq, xs + q0 * d, sizeof(double) * qc * d, hipMemcpyDefault, s));
+        GPX_TRY(launch_scale_rows(xq, qc, qp, d, h->sw, xqw, s));
+        GPX_TRY(launch_gram(xqw, qc, h->xbw, h->m, d, h->v, 0.0, 0, 1, Ka, mp, qp, mp, s, nullptr));   // K_*M
+        GPX_TRY(launch_predict_reduce(Ka, mp, qc, mp, h->beta, 0.0, mean, unused, s, nullptr));       // K_*M beta
+        // K_*M L^-T for both factors: one product each with the explicit inverse (zero triangle skipped)
+        GPX_TRY(launch_gemm_nt(Ka, mp, h->LinvM, mp, Kb, mp, qp, mp, mp, 1.0, 0.0, 0, s, nullptr, 0, GEMM_TRI_B_LOWER));
+        GPX_TRY(launch_gemm_nt(Ka, mp, h->LinvB, mp, Kc, mp, qp, mp, mp, 1.0, 0.0, 0, s, nullptr, 0, GEMM_TRI_B_LOWER));
+        GPX_TRY(launch_predict_reduce(Kb, mp, qc, mp, h->mzero, h->v + h->vt, unused, va, s, nullptr));   // v + vt - |K_*M L_M^-T|^2
+        GPX_TRY(launch_predict_reduce(Kc, mp, qc, mp, h->mzero, 0.0, unused, vb, s, nullptr));            //        - |K_*M L_B^-T|^2
+        GPX_TRY(vec_op(VEC_SUB, qc, qc, 0.0, va, vb, var, nullptr, s));
+        GPX_HIP(hipMemcpyAsync(mean_out + q0, mean, sizeof(double) * qc, hipMemcpyDefault, s));
+        GPX_HIP(hipMemcpyAsync(var_out + q0, var, sizeof(double) * qc, hipMemcpyDefault, s));
+        GPX_HIP(hipStreamSynchronize(s));
+    }
+    return 0;
 }
 
 // Snelson's O(N M^2) negative log likelihood (Covariance.py:981-1019); jitter delta = 1e-6 on K_M as there (:995-998)
@@ -413,30 +408,25 @@ static int spgp_snelson_prepare(gpx_spgp *h)
     if (!h->sngam) GPX_TRY(dalloc(&h->sngam, np));
     double *L = nullptr, *Dinv = nullptr, *diag = nullptr;
     int info = 0;
-    auto body = [&]() -> int {
-        GPX_TRY(dalloc(&L, mp * mp)); GPX_TRY(dalloc(&Dinv, tt)); GPX_TRY(dalloc(&diag, mp));
-        GPX_TRY(spgp_chol_km(h, 1e-6, L, Dinv, diag, &info));                                       // L = chol(K_M + delta I)
-        if (info > 0) { gpx_set_error("K_M + 1e-6 I is not positive definite (leading minor %d)", info); return info; }
-        GPX_TRY(spgp_solve_into_z(h, L, Dinv, nullptr, h->scrA));                                   // Z = V^T,  V = L^-1 K_MN ; scrA = inv(L)^T
-        GPX_TRY(launch_predict_reduce(h->Z, mp, np, mp, h->mzero, h->v + h->vt, h->va, h->sngam, s, nullptr));   // gamma = v + vt - sum V^2
-        GPX_TRY(vec_op(VEC_SNELSON_EP, n, np, h->vt, h->sngam, nullptr, h->va, h->vc, s));          // va = 1/sqrt(ep), vc = log ep
-        GPX_TRY(vec_op(VEC_MUL, n, np, 0.0, h->t, h->va, h->vb, nullptr, s));                       // vb = y / sqrt(ep)
-        GPX_TRY(spgp_transpose(h, h->Z, h->va, h->Wt));                                             // Wt = V / sqrt(ep)  [M, N]
-        GPX_TRY(launch_set_identity(h->snA, mp, mp, s));
-        GPX_TRY(spgp_wtw(h, h->Wt, h->snA, h->vt));                                                 // A = vt I + V D^-1 V^T
-        GPX_HIP(hipMemsetAsync(h->info, 0, sizeof(int), s));
-        GPX_TRY(chol_factor(h->snA, mp, h->mblk, h->snDinvA, h->sndiagA, h->info, s, nullptr, nullptr, nullptr));
-        GPX_HIP(hipMemcpyAsync(&info, h->info, sizeof(int), hipMemcpyDeviceToHost, s));
-        GPX_TRY(launch_predict_reduce(h->Wt, np, mp, np, h->vb, 0.0, h->ma, h->mb, s, nullptr));    // ma = V D^-1 y
-        GPX_HIP(hipStreamSynchronize(s));
-        if (info > 0) { gpx_set_error("vt I + V V^T is not positive definite (leading minor %d)", info); return info; }
-        return 0;
-    };
-    const int rc = body();
-    (void)hipStreamSynchronize(s);
-    dfree(L); dfree(Dinv); dfree(diag);
-    if (rc == 0) h->sn_valid = h->sn_z = true;
-    return rc;
+    Scratch sc(s);
+    GPX_TRY(sc.take(&L, mp * mp)); GPX_TRY(sc.take(&Dinv, tt)); GPX_TRY(sc.take(&diag, mp));
+    GPX_TRY(spgp_chol_km(h, 1e-6, L, Dinv, diag, &info));                                       // L = chol(K_M + delta I)
+    if (info > 0) { gpx_set_error("K_M + 1e-6 I is not positive definite (leading minor %d)", info); return info; }
+    GPX_TRY(spgp_solve_into_z(h, L, Dinv, nullptr, h->scrA));                                   // Z = V^T,  V = L^-1 K_MN ; scrA = inv(L)^T
+    GPX_TRY(launch_predict_reduce(h->Z, mp, np, mp, h->mzero, h->v + h->vt, h->va, h->sngam, s, nullptr));   // gamma = v + vt - sum V^2
+    GPX_TRY(vec_op(VEC_SNELSON_EP, n, np, h->vt, h->sngam, nullptr, h->va, h->vc, s));          // va = 1/sqrt(ep), vc = log ep
+    GPX_TRY(vec_op(VEC_MUL, n, np, 0.0, h->t, h->va, h->vb, nullptr, s));                       // vb = y / sqrt(ep)
+    GPX_TRY(spgp_transpose(h, h->Z, h->va, h->Wt));                                             // Wt = V / sqrt(ep)  [M, N]
+    GPX_TRY(launch_set_identity(h->snA, mp, mp, s));
+    GPX_TRY(spgp_wtw(h, h->Wt, h->snA, h->vt));                                                 // A = vt I + V D^-1 V^T
+    GPX_HIP(hipMemsetAsync(h->info, 0, sizeof(int), s));
+    GPX_TRY(chol_factor(h->snA, mp, h->mblk, h->snDinvA, h->sndiagA, h->info, s, nullptr, nullptr, nullptr));
+    GPX_HIP(hipMemcpyAsync(&info, h->info, sizeof(int), hipMemcpyDeviceToHost, s));
+    GPX_TRY(launch_predict_reduce(h->Wt, np, mp, np, h->vb, 0.0, h->ma, h->mb, s, nullptr));    // ma = V D^-1 y
+    GPX_HIP(hipStreamSynchronize(s));
+    if (info > 0) { gpx_set_error("vt I + V V^T is not positive definite (leading minor %d)", info); return info; }
+    h->sn_valid = h->sn_z = true;
+    return 0;
 }
 
 extern "C" int gpx_spgp_nll(gpx_spgp *h, double *nll_out)
@@ -624,59 +614,53 @@ extern "C" int gpx_spgp_nll_grad(gpx_spgp *h, double *grad_out)
     double *mats = nullptr, *W2 = nullptr, *vecs = nullptr, *part = nullptr, *small = nullptr, *Tbuf = nullptr;
     std::vector<double> PE((size_t)mp * W), PF((size_t)mp * W), xbw((size_t)mp * d);
     double sg = 0.0;
-    auto body = [&]() -> int {
-        // M x M: Ainv, Scr (L^-T), Qb, Y, Qbar, Qk
-        GPX_TRY(dalloc(&mats, 6 * mm));
-        double *Ainv = mats, *Scr = Ainv + mm, *Qb = Scr + mm, *Y = Qb + mm, *Qbar = Y + mm, *Qk = Qbar + mm;
-        GPX_TRY(dalloc(&W2, mp * np));
-        GPX_TRY(dalloc(&vecs, 2 * np + 2 * mp));
-        double *gv = vecs, *gpos = gv + np;
-        double *betaA = gpos + np, *mj = betaA + mp;
-        GPX_TRY(dalloc(&part, (int64_t)std::max(nbE, nbF) * mp * W));
-        GPX_TRY(dalloc(&small, 2 * mp * W + 8));
-        double *PEd = small, *PFd = PEd + mp * W, *sgd = PFd + mp * W;
-        GPX_TRY(dalloc(&Tbuf, np * mp));
-        double *T = Tbuf;                                                                           // [np, mp] (Wt = V D^-1/2 stays: the second operand of Qb's product)
+    Scratch sc(s);
+    // M x M: Ainv, Scr (L^-T), Qb, Y, Qbar, Qk
+    GPX_TRY(sc.take(&mats, 6 * mm));
+    double *Ainv = mats, *Scr = Ainv + mm, *Qb = Scr + mm, *Y = Qb + mm, *Qbar = Y + mm, *Qk = Qbar + mm;
+    GPX_TRY(sc.take(&W2, mp * np));
+    GPX_TRY(sc.take(&vecs, 2 * np + 2 * mp));
+    double *gv = vecs, *gpos = gv + np;
+    double *betaA = gpos + np, *mj = betaA + mp;
+    GPX_TRY(sc.take(&part, (int64_t)std::max(nbE, nbF) * mp * W));
+    GPX_TRY(sc.take(&small, 2 * mp * W + 8));
+    double *PEd = small, *PFd = PEd + mp * W, *sgd = PFd + mp * W;
+    GPX_TRY(sc.take(&Tbuf, np * mp));
+    double *T = Tbuf;                                                                           // [np, mp] (Wt = V D^-1/2 stays: the second operand of Qb's product)
 
-        // the likelihood's own N m^2 work (factor of K_M, V, gamma, Wt, A and its factor, V D^-1 y): done by a gpx_spgp_nll on this handle
-        // just before (an L-BFGS step), or now
-        if (!(h->sn_valid && h->sn_z)) GPX_TRY(spgp_snelson_prepare(h));
-        h->sn_z = false;                                                                            // (Z is overwritten below; what a likelihood needs stays)
-        double *A = h->snA, *DinvA = h->snDinvA, *gam = h->sngam, *isq = h->va, *ma = h->ma;
-        double *LinvT = h->scrA;                                                                    // inv(L)^T, explicit and upper triangular
-        GPX_TRY(build_kinv_from_factor(A, mp, h->mblk, DinvA, Scr, Ainv, s, nullptr));              // A^-1
-        GPX_TRY(launch_predict_reduce(Ainv, mp, mp, mp, ma, 0.0, betaA, mj, s, nullptr));           // betaA = A^-1 V D^-1 y
-        GPX_TRY(launch_gemm_nt(h->Z, mp, Ainv, mp, T, mp, np, mp, mp, 1.0, 0.0, 0, s, nullptr));    // T = Zt A^-1
-        hipLaunchKernelGGL(spgp_vbar_kernel, dim3((unsigned)((np + 3) / 4)), dim3(256), 0, s, T, (const double *)h->Z, (long)mp, (long)mp, (long)n,
-                           (long)np, (const double *)gam, (const double *)h->t, (const double *)betaA, h->vt, gv);   // T = Vbar^T
-        // Qb = V diag(g) V^T - (I - vt A^-1 - betaA betaA^T) / 2 ; g has both signs, so it cannot be split as sqrt(g) sqrt(g) over the two
-        // sides of ONE symmetric rank-N update -- but it can be split as (g sqrt(ep)) (1 / sqrt(ep)): the second operand is then Wt = V D^-1/2,
-        // which the fit's own product left in place.  One transposing pass and one lower-only N m^2 product instead of two of each (rounds 2-4:
-        // two updates with sqrt(g+) and sqrt(g-), each over all N rows).
-        GPX_TRY(vec_op(VEC_DIV, n, np, 0.0, gv, isq, gpos, nullptr, s));
-        GPX_TRY(spgp_transpose(h, h->Z, gpos, W2));
-        GPX_TRY(spgp_wtw(h, W2, Qb, 0.0, 1.0, h->Wt));
-        GPX_TRY(launch_symmetrize_lower(Qb, mp, mp, s));
-        hipLaunchKernelGGL(spgp_qb_fix_kernel, dim3((unsigned)mp), dim3(256), 0, s, Qb, (const double *)Ainv, (const double *)betaA, (long)mp, h->vt);
-        GPX_TRY(launch_gemm_nt(T, mp, LinvT, mp, h->Z, mp, np, mp, mp, 1.0, 0.0, 0, s, nullptr, 0, GEMM_TRI_B_UPPER));   // Z = Kbar^T = Vbar^T L^-1 (L^-T upper: half the contraction)
-        GPX_TRY(launch_gemm_nt(LinvT, mp, Qb, mp, Y, mp, mp, mp, mp, 1.0, 0.0, 0, s, nullptr));     // Y = L^-T Qb   (Qb symmetric)
-        GPX_TRY(launch_gemm_nt(Y, mp, LinvT, mp, Qbar, mp, mp, mp, mp, 1.0, 0.0, 0, s, nullptr));   // Qbar = L^-T Qb L^-1
-        GPX_TRY(launch_gram(h->xbw, m, h->xbw, m, d, h->v, 0.0, 0, 1, Qk, mp, mp, mp, s, nullptr)); // K_M (no jitter), zero padded
-        GPX_TRY(spgp_epass(h, h->Z, h->Knm, np, h->xw, part, PEd));
-        GPX_TRY(spgp_epass(h, Qbar, Qk, mp, h->xbw, part, PFd));
-        hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, s, (const double *)gv, (long)np, sgd);
-        GPX_HIP(hipGetLastError());
-        GPX_HIP(hipMemcpyAsync(PE.data(), PEd, sizeof(double) * mp * W, hipMemcpyDeviceToHost, s));
-        GPX_HIP(hipMemcpyAsync(PF.data(), PFd, sizeof(double) * mp * W, hipMemcpyDeviceToHost, s));
-        GPX_HIP(hipMemcpyAsync(xbw.data(), h->xbw, sizeof(double) * mp * d, hipMemcpyDeviceToHost, s));
-        GPX_HIP(hipMemcpyAsync(&sg, sgd, sizeof(double), hipMemcpyDeviceToHost, s));
-        GPX_HIP(hipStreamSynchronize(s));
-        return 0;
-    };
-    const int rc = body();
-    (void)hipStreamSynchronize(s);
-    dfree(mats); dfree(W2); dfree(vecs); dfree(part); dfree(small); dfree(Tbuf);
-    if (rc) return rc;
+    // the likelihood's own N m^2 work (factor of K_M, V, gamma, Wt, A and its factor, V D^-1 y): done by a gpx_spgp_nll on this handle
+    // just before (an L-BFGS step), or now
+    if (!(h->sn_valid && h->sn_z)) GPX_TRY(spgp_snelson_prepare(h));
+    h->sn_z = false;                                                                            // (Z is overwritten below; what a likelihood needs stays)
+    double *A = h->snA, *DinvA = h->snDinvA, *gam = h->sngam, *isq = h->va, *ma = h->ma;
+    double *LinvT = h->scrA;                                                                    // inv(L)^T, explicit and upper triangular
+    GPX_TRY(build_kinv_from_factor(A, mp, h->mblk, DinvA, Scr, Ainv, s, nullptr));              // A^-1
+    GPX_TRY(launch_predict_reduce(Ainv, mp, mp, mp, ma, 0.0, betaA, mj, s, nullptr));           // betaA = A^-1 V D^-1 y
+    GPX_TRY(launch_gemm_nt(h->Z, mp, Ainv, mp, T, mp, np, mp, mp, 1.0, 0.0, 0, s, nullptr));    // T = Zt A^-1
+    hipLaunchKernelGGL(spgp_vbar_kernel, dim3((unsigned)((np + 3) / 4)), dim3(256), 0, s, T, (const double *)h->Z, (long)mp, (long)mp, (long)n,
+                       (long)np, (const double *)gam, (const double *)h->t, (const double *)betaA, h->vt, gv);   // T = Vbar^T
+    // Qb = V diag(g) V^T - (I - vt A^-1 - betaA betaA^T) / 2 ; g has both signs, so it cannot be split as sqrt(g) sqrt(g) over the two
+    // sides of ONE symmetric rank-N update -- but it can be split as (g sqrt(ep)) (1 / sqrt(ep)): the second operand is then Wt = V D^-1/2,
+    // which the fit's own product left in place.  One transposing pass and one lower-only N m^2 product instead of two of each (rounds 2-4:
+    // two updates with sqrt(g+) and sqrt(g-), each over all N rows).
+    GPX_TRY(vec_op(VEC_DIV, n, np, 0.0, gv, isq, gpos, nullptr, s));
+    GPX_TRY(spgp_transpose(h, h->Z, gpos, W2));
+    GPX_TRY(spgp_wtw(h, W2, Qb, 0.0, 1.0, h->Wt));
+    GPX_TRY(launch_symmetrize_lower(Qb, mp, mp, s));
+    hipLaunchKernelGGL(spgp_qb_fix_kernel, dim3((unsigned)mp), dim3(256), 0, s, Qb, (const double *)Ainv, (const double *)betaA, (long)mp, h->vt);
+    GPX_TRY(launch_gemm_nt(T, mp, LinvT, mp, h->Z, mp, np, mp, mp, 1.0, 0.0, 0, s, nullptr, 0, GEMM_TRI_B_UPPER));   // Z = Kbar^T = Vbar^T L^-1 (L^-T upper: half the contraction)
+    GPX_TRY(launch_gemm_nt(LinvT, mp, Qb, mp, Y, mp, mp, mp, mp, 1.0, 0.0, 0, s, nullptr));     // Y = L^-T Qb   (Qb symmetric)
+    GPX_TRY(launch_gemm_nt(Y, mp, LinvT, mp, Qbar, mp, mp, mp, mp, 1.0, 0.0, 0, s, nullptr));   // Qbar = L^-T Qb L^-1
+    GPX_TRY(launch_gram(h->xbw, m, h->xbw, m, d, h->v, 0.0, 0, 1, Qk, mp, mp, mp, s, nullptr)); // K_M (no jitter), zero padded
+    GPX_TRY(spgp_epass(h, h->Z, h->Knm, np, h->xw, part, PEd));
+    GPX_TRY(spgp_epass(h, Qbar, Qk, mp, h->xbw, part, PFd));
+    hipLaunchKernelGGL(sum_kernel, dim3(1), dim3(256), 0, s, (const double *)gv, (long)np, sgd);
+    GPX_HIP(hipGetLastError());
+    GPX_HIP(hipMemcpyAsync(PE.data(), PEd, sizeof(double) * mp * W, hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipMemcpyAsync(PF.data(), PFd, sizeof(double) * mp * W, hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipMemcpyAsync(xbw.data(), h->xbw, sizeof(double) * mp * d, hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipMemcpyAsync(&sg, sgd, sizeof(double), hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipStreamSynchronize(s));
     // assemble (coordinates scaled by sqrt(w): (xb - x)^2 w = (xbw - xw)^2)
     std::vector<double> g((size_t)(2 + d + m * d));
     double sE = 0.0, sF = 0.0;
@@ -711,29 +695,24 @@ extern "C" int gpx_spgp_dense(gpx_spgp *h, int which, double *out)
     hipStream_t s = h->stream;
     const int64_t np = h->npad, mp = h->mpad, n = h->n;
     double *C = nullptr;
-    auto body = [&]() -> int {
-        GPX_TRY(dalloc(&C, np * np));
-        const dim3 dg((unsigned)((n + 255) / 256));
-        if (which == 0) {
-            GPX_TRY(spgp_solve_into_z(h, h->LM, h->DinvM));
-            GPX_TRY(launch_gemm_nt(h->Z, mp, h->Z, mp, C, np, np, np, mp, 1.0, 0.0, 0, s, nullptr));      // Q_N = Z Z^T
-            hipLaunchKernelGGL(add_diag_kernel, dg, dim3(256), 0, s, C, (long)np, (long)n, (const double *)h->lam, 0);
-        } else {
-            GPX_TRY(spgp_solve_into_z(h, h->LB, h->DinvB));                                            // K_NM L_B^-T
-            GPX_TRY(vec_op(VEC_SQUARE, n, np, 0.0, h->ilam, nullptr, h->va, nullptr, s));               // 1/lambda
-            hipLaunchKernelGGL(scale_rows_inplace_kernel, dim3((unsigned)np), dim3(256), 0, s, h->Z, (long)mp, (long)mp, (const double *)h->va);
-            GPX_TRY(launch_gemm_nt(h->Z, mp, h->Z, mp, C, np, np, np, mp, -1.0, 0.0, 0, s, nullptr));
-            hipLaunchKernelGGL(add_diag_kernel, dg, dim3(256), 0, s, C, (long)np, (long)n, (const double *)h->ilam, 1);
-        }
-        GPX_HIP(hipGetLastError());
-        GPX_HIP(hipMemcpy2DAsync(out, sizeof(double) * n, C, sizeof(double) * np, sizeof(double) * n, n, hipMemcpyDefault, s));
-        GPX_HIP(hipStreamSynchronize(s));
-        return 0;
-    };
-    const int rc = body();
-    (void)hipStreamSynchronize(s);
-    dfree(C);
-    return rc;
+    Scratch sc(s);
+    GPX_TRY(sc.take(&C, np * np));
+    const dim3 dg((unsigned)((n + 255) / 256));
+    if (which == 0) {
+        GPX_TRY(spgp_solve_into_z(h, h->LM, h->DinvM));
+        GPX_TRY(launch_gemm_nt(h->Z, mp, h->Z, mp, C, np, np, np, mp, 1.0, 0.0, 0, s, nullptr));      // Q_N = Z Z^T
+        hipLaunchKernelGGL(add_diag_kernel, dg, dim3(256), 0, s, C, (long)np, (long)n, (const double *)h->lam, 0);
+    } else {
+        GPX_TRY(spgp_solve_into_z(h, h->LB, h->DinvB));                                            // K_NM L_B^-T
+        GPX_TRY(vec_op(VEC_SQUARE, n, np, 0.0, h->ilam, nullptr, h->va, nullptr, s));               // 1/lambda
+        hipLaunchKernelGGL(scale_rows_inplace_kernel, dim3((unsigned)np), dim3(256), 0, s, h->Z, (long)mp, (long)mp, (const double *)h->va);
+        GPX_TRY(launch_gemm_nt(h->Z, mp, h->Z, mp, C, np, np, np, mp, -1.0, 0.0, 0, s, nullptr));
+        hipLaunchKernelGGL(add_diag_kernel, dg, dim3(256), 0, s, C, (long)np, (long)n, (const double *)h->ilam, 1);
+    }
+    GPX_HIP(hipGetLastError());
+    GPX_HIP(hipMemcpy2DAsync(out, sizeof(double) * n, C, sizeof(double) * np, sizeof(double) * n, n, hipMemcpyDefault, s));
+    GPX_HIP(hipStreamSynchronize(s));
+    return 0;
 }
 
 // cov_matrix_ij(xi, xj) = Q_ij = K_iM (K_M + 1e-5 I)^-1 K_Mj   (Covariance.py:734-757), [n1, n2] row-major
@@ -753,19 +732,14 @@ extern "C" int gpx_spgp_cross(gpx_spgp *h, const double *xi, int64_t n1, const d
         GPX_TRY(launch_gram(xw, n, h->xbw, h->m, d, h->v, 0.0, 0, 1, Zout, mp, p, mp, s, nullptr));
         return trsm_right_lt(Zout, mp, p, h->LM, mp, h->DinvM, 0, h->mblk, s, nullptr);
     };
-    auto body = [&]() -> int {
-        const int64_t pm = std::max(p1, p2);
-        GPX_TRY(dalloc(&raw, pm * d)); GPX_TRY(dalloc(&xw, pm * d)); GPX_TRY(dalloc(&Z1, p1 * mp)); GPX_TRY(dalloc(&Z2, p2 * mp));
-        GPX_TRY(dalloc(&C, p1 * p2));
-        GPX_TRY(side(xi, n1, p1, Z1));
-        GPX_TRY(side(xj, n2, p2, Z2));
-        GPX_TRY(launch_gemm_nt(Z1, mp, Z2, mp, C, p2, p1, p2, mp, 1.0, 0.0, 0, s, nullptr));
-        GPX_HIP(hipMemcpy2DAsync(out, sizeof(double) * n2, C, sizeof(double) * p2, sizeof(double) * n2, n1, hipMemcpyDefault, s));
-        GPX_HIP(hipStreamSynchronize(s));
-        return 0;
-    };
-    const int rc = body();
-    (void)hipStreamSynchronize(s);
-    dfree(raw); dfree(xw); dfree(Z1); dfree(Z2); dfree(C);
-    return rc;
+    Scratch sc(s);
+    const int64_t pm = std::max(p1, p2);
+    GPX_TRY(sc.take(&raw, pm * d)); GPX_TRY(sc.take(&xw, pm * d)); GPX_TRY(sc.take(&Z1, p1 * mp)); GPX_TRY(sc.take(&Z2, p2 * mp));
+    GPX_TRY(sc.take(&C, p1 * p2));
+    GPX_TRY(side(xi, n1, p1, Z1));
+    GPX_TRY(side(xj, n2, p2, Z2));
+    GPX_TRY(launch_gemm_nt(Z1, mp, Z2, mp, C, p2, p1, p2, mp, 1.0, 0.0, 0, s, nullptr));
+    GPX_HIP(hipMemcpy2DAsync(out, sizeof(double) * n2, C, sizeof(double) * p2, sizeof(double) * n2, n1, hipMemcpyDefault, s));
+    GPX_HIP(hipStreamSynchronize(s));
+    return 0;
 }
