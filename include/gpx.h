@@ -259,6 +259,15 @@ int gpx_bench_emu_i8(int64_t rows, int64_t cols, int64_t K, int nmod, int iters,
  * doubles; C needs no more than its natural 8 bytes and ldc may be odd).  rows = 0 or cols = 0 is a valid empty product. */
 int gpx_emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t rows, int64_t cols,
                         int64_t K);
+/* The two integer kernels of the emulated update alone, on device buffers (tests).  Synchronous.
+ * gpx_emu_rebuild: C[rows, cols] -= X 2^-(sa[row] + sb[col]), X the integer in [-P/2, P/2) whose residues modulo the first nmod
+ * (2 .. 16) moduli are the bytes R[l * sr + row * ldr + col]; a scale of 0x7fffffff marks a non-finite row or column (NaN).  ldr and sr
+ * are multiples of 4 with ldr >= cols rounded up to 4 and sr >= rows * ldr, R is 4-byte aligned, ldc >= cols.
+ * gpx_emu_i8_gemm: R_l = (A_l B_l^T) mod p_l as one balanced byte (128 mod 256 stored as -128) for l < nmod (1 .. 16); dense planes
+ * A [nmod][rows][K], B [nmod][cols][K], R [nmod][rows][cols]; rows, cols multiples of 256, K of 128 below 2^17, A and B 16-byte aligned. */
+int gpx_emu_rebuild(const int8_t *R, int64_t ldr, int64_t sr, int nmod, const int *sa, const int *sb, double *C, int64_t ldc, int64_t rows,
+                    int64_t cols);
+int gpx_emu_i8_gemm(const int8_t *A, const int8_t *B, int64_t rows, int64_t cols, int64_t K, int nmod, int8_t *R);
 int gpx_bench_hbm(int64_t bytes, int iters, double *write_gbs, double *copy_gbs);
 /* mode 0: MFMA f64 only, 1: VALU v_fma_f64 only, 2: half the waves each; `blocks` workgroups of 4 waves.
  * cycles_per_inst from s_memtime, clock_ghz from s_memtime / s_memrealtime (the clock held under load). */

@@ -7,9 +7,10 @@
 //                moduli p_l (int8).
 //   2. products: one exact int8 -> int32 GEMM per modulus (|residue| <= 128, so |sum| <= K 2^14 < 2^31 for K < 2^17), reduced mod p_l in
 //                the epilogue and stored as one byte.
-//   3. rebuild : per entry, Garner's mixed-radix digits of the L residues (balanced digits, fp32 arithmetic on integers < 2^17: exact),
-//                then the integer X = sum_i a'_ik b'_jk by an exact 128-bit Horner pass, rounded once to fp64 (two roundings in all:
-//                |fl(X) - X| <= 1 ulp), and C_ij -= X 2^-(sig_i + tau_j).
+//   3. rebuild : per entry, the integer X = sum_k a'_ik b'_jk in [-P/2, P/2) from its L residues by the direct Chinese-remainder sum
+//                X = sum_l t_l M_l - q P (t_l = r_l M_l^-1 mod p_l in fp32, the sum over 40-bit limbs of M_l = P / p_l in exact fp64
+//                FMAs, q from the fp64 value of the sum, one exact correction by -+P: linear in L, see emu_rebuild_kernel), assembled
+//                into 128 bits and rounded once to fp64 (two roundings in all: |fl(X) - X| <= 1 ulp), and C_ij -= X 2^-(sig_i + tau_j).
 // alpha + beta is the largest integer with K 2^(alpha+beta) < P / 2 (P = p_1 .. p_L): the residues then determine X uniquely.  At L = 16
 // (log2 P = 125.2) and K = 8192 that is alpha = 56, beta = 55: every row's largest entries are converted exactly, an entry 2^-e below its
 // row's largest keeps 55 - e bits.  Each output row depends only on its own row of A and on B, whatever the tiling.
@@ -32,22 +33,53 @@ constexpr int EMU_BK = 128;   // k bytes per LDS stage (one 128-byte row per ope
 // pairwise coprime (256 = 2^8, 255 = 3 5 17, 253 = 11 23, 247 = 13 19, the rest prime); the first L are used
 constexpr int EMU_MODULI[EMU_MAXL] = {256, 255, 253, 251, 247, 241, 239, 233, 229, 227, 223, 211, 199, 197, 193, 191};
 
-struct EmuGarner { float c[EMU_MAXL][EMU_MAXL]; };   // c[j][k] = p_j^-1 mod p_k (j < k)
-constexpr EmuGarner emu_garner_table()
-{
-    EmuGarner g{};
-    for (int k = 0; k < EMU_MAXL; ++k)
-        for (int j = 0; j < k; ++j) {
-            const int pk = EMU_MODULI[k], a = EMU_MODULI[j] % pk;
-            int inv = 0;
-            for (int x = 1; x < pk; ++x)
-                if (a * x % pk == 1) { inv = x; break; }
-            g.c[j][k] = (float)inv;
-        }
-    return g;
-}
 static __constant__ const int emu_p[EMU_MAXL] = {256, 255, 253, 251, 247, 241, 239, 233, 229, 227, 223, 211, 199, 197, 193, 191};
-static __constant__ const EmuGarner emu_garner = emu_garner_table();
+
+// Chinese-remainder constants of the first L moduli (P = p_1 .. p_L, M_l = P / p_l): c[l] = M_l^-1 mod p_l, M_l and P cut into 40-bit
+// limbs (M_l < 2^118: three, P < 2^126: four), 1 / P, and P / 2 and P as two 64-bit words.  One table per L, passed to the kernel by value.
+typedef unsigned __int128 emu_u128;
+struct EmuCrt {
+    double m[EMU_MAXL][3], p[4], pinv;
+    float c[EMU_MAXL];
+    unsigned long p_lo, p_hi, half_lo, half_hi;
+};
+struct EmuCrtAll { EmuCrt t[EMU_MAXL + 1]; };   // t[L], L = 2 .. 16
+constexpr EmuCrtAll emu_crt_tables()
+{
+    EmuCrtAll all{};
+    constexpr emu_u128 mask = ((emu_u128)1 << 40) - 1;
+    for (int L = 2; L <= EMU_MAXL; ++L) {
+        EmuCrt &t = all.t[L];
+        emu_u128 P = 1;
+        for (int l = 0; l < L; ++l) P *= (emu_u128)EMU_MODULI[l];
+        for (int l = 0; l < L; ++l) {
+            const emu_u128 M = P / (emu_u128)EMU_MODULI[l];
+            const int p = EMU_MODULI[l], a = (int)(M % (emu_u128)p);
+            int inv = 0;
+            for (int x = 1; x < p; ++x)
+                if (a * x % p == 1) { inv = x; break; }
+            t.c[l] = (float)inv;
+            for (int j = 0; j < 3; ++j) t.m[l][j] = (double)(unsigned long)((M >> (40 * j)) & mask);
+        }
+        for (int j = 0; j < 4; ++j) t.p[j] = (double)(unsigned long)((P >> (40 * j)) & mask);
+        t.pinv = 1.0 / (double)P;
+        t.p_lo = (unsigned long)P;
+        t.p_hi = (unsigned long)(P >> 64);
+        t.half_lo = (unsigned long)(P >> 1);
+        t.half_hi = (unsigned long)(P >> 65);
+    }
+    return all;
+}
+static constexpr EmuCrtAll emu_crt = emu_crt_tables();
+
+#ifdef EMU_STAMP   // diagnostic build only (never the shipped library): s_memtime / s_memrealtime around the k loop of every workgroup
+constexpr int EMU_STAMP_SLOTS = 1 << 16;
+__device__ unsigned long emu_stamps[EMU_STAMP_SLOTS][4];
+extern "C" int gpx_emu_stamps(unsigned long *out, int n)
+{
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(emu_stamps), sizeof(unsigned long) * 4 * std::min(n, EMU_STAMP_SLOTS)) == hipSuccess ? 0 : GPX_ERR_HIP;
+}
+#endif
 
 constexpr int EMU_NONFINITE = 0x7fffffff;   // row scale of a row that holds a NaN or an Inf: its outputs are NaN
 
@@ -178,6 +210,9 @@ __global__ __launch_bounds__(512, 1) void emu_i8_gemm_kernel(const int8_t *__res
         for (int j = 0; j < 2; ++j) acc[i][j] = (v16i){};
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+#ifdef EMU_STAMP
+    const unsigned long stamp_c0 = __builtin_amdgcn_s_memtime(), stamp_r0 = __builtin_amdgcn_s_memrealtime();
+#endif
 
     const int fr = lane & 31, sw = (fr >> 1) & 7;
     int koff[4];
@@ -225,6 +260,12 @@ __global__ __launch_bounds__(512, 1) void emu_i8_gemm_kernel(const int8_t *__res
 #undef EMU_MMA
 #undef EMU_DMA_STAGE
 #undef EMU_DMA_ONE
+#ifdef EMU_STAMP
+    if (t == 0 && orig < EMU_STAMP_SLOTS) {
+        unsigned long *st = emu_stamps[orig];
+        st[0] = stamp_c0; st[1] = __builtin_amdgcn_s_memtime(); st[2] = stamp_r0; st[3] = __builtin_amdgcn_s_memrealtime();
+    }
+#endif
 
     // epilogue: accumulator register r of tile (i, j) is row (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column lane & 31; |v| < 2^31 is exact
     // in fp64 and v / p is never within 1 / (2p) of a half-integer for odd p (256: a tie wraps to the same byte)
@@ -242,8 +283,15 @@ __global__ __launch_bounds__(512, 1) void emu_i8_gemm_kernel(const int8_t *__res
 }
 
 // ---- rebuild: C_ij -= X_ij 2^-(sig_i + tau_j), four consecutive columns per thread ----------------------------------------------
-__global__ __launch_bounds__(256) void emu_rebuild_kernel(const int8_t *__restrict__ R, long ldr, long sr, int L, const int *__restrict__ sa,
-                                                          const int *__restrict__ sb, double *__restrict__ C, long ldc, long rows, long cols)
+// X is the integer in [-P/2, P/2) with the L residues r_l, by the direct CRT sum (linear in L):
+//   t_l = r_l c_l mod p_l, any representative with |t_l| <= (p_l + 1) / 2 (|r_l c_l| < 2^15: exact in fp32, one step per modulus);
+//   S = sum_l t_l M_l = X (mod P), summed limb by limb in fp64 (|t_l| <= 128 and limbs below 2^40: every partial sum is an integer
+//   below 2^51, so the 3 L FMAs are exact);  q = rint(S / P) from the fp64 value of S (|q| <= 8, off by one at most, and only when
+//   S / P is within 2^-40 of a half-integer);  X = S - q P limb by limb (exact), assembled into 128 bits;  one exact correction by
+//   -+P where X fell outside [-P/2, P/2) makes q's rounding immaterial.  The integer is rounded once to fp64, as before.
+__global__ __launch_bounds__(256) void emu_rebuild_kernel(const int8_t *__restrict__ R, long ldr, long sr, int L, const EmuCrt T,
+                                                          const int *__restrict__ sa, const int *__restrict__ sb, double *__restrict__ C,
+                                                          long ldc, long rows, long cols)
 {
     const long q4 = (cols + 3) >> 2;
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -252,35 +300,31 @@ __global__ __launch_bounds__(256) void emu_rebuild_kernel(const int8_t *__restri
     unsigned w[EMU_MAXL];
 #pragma unroll
     for (int l = 0; l < EMU_MAXL; ++l)
-        if (l < L) w[l] = *reinterpret_cast<const unsigned *>(R + l * sr + i * ldr + j0);
+        w[l] = l < L ? *reinterpret_cast<const unsigned *>(R + l * sr + i * ldr + j0) : 0u;   // (the table of L is zero from l = L on)
     const int si = sa[i];
     double *c = C + i * ldc + j0;
+    const __int128 P = (__int128)(((emu_u128)T.p_hi << 64) | T.p_lo), half = (__int128)(((emu_u128)T.half_hi << 64) | T.half_lo);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
         if (j0 + e >= cols) continue;
         const int tj = sb[j0 + e];
         if (si == EMU_NONFINITE || tj == EMU_NONFINITE) { c[e] = __builtin_nan(""); continue; }
-        // Garner: X = sum_k v_k p_0 .. p_(k-1), digit 0 in [-128, 127], digit k >= 1 in [-(p_k - 1) / 2, (p_k - 1) / 2]; every
-        // intermediate is an integer below 2^17 in magnitude, so the fp32 arithmetic is exact
-        float v[EMU_MAXL];
-        v[0] = (float)(int8_t)(w[0] >> (8 * e));
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
 #pragma unroll
-        for (int k = 1; k < EMU_MAXL; ++k) {
-            if (k >= L) continue;
-            const float pk = (float)emu_p[k], pkinv = 1.0f / pk, hk = 0.5f * (pk - 1.0f);
-            float tk = (float)(int8_t)(w[k] >> (8 * e));
-#pragma unroll
-            for (int jj = 0; jj < k; ++jj) {
-                tk = (tk - v[jj]) * emu_garner.c[jj][k];
-                tk = fmaf(-rintf(tk * pkinv), pk, tk);
-            }
-            tk = tk > hk ? tk - pk : (tk < -hk ? tk + pk : tk);
-            v[k] = tk;
+        for (int l = 0; l < EMU_MAXL; ++l) {
+            const float pl = (float)emu_p[l], plinv = 1.0f / pl;
+            float t = (float)(int8_t)(w[l] >> (8 * e)) * T.c[l];
+            t = fmaf(-rintf(t * plinv), pl, t);
+            const double td = (double)t;
+            s0 = fma(td, T.m[l][0], s0);
+            s1 = fma(td, T.m[l][1], s1);
+            s2 = fma(td, T.m[l][2], s2);
         }
-        __int128 X = (__int128)(int)v[L - 1];
-#pragma unroll
-        for (int k = EMU_MAXL - 2; k >= 0; --k)
-            if (k <= L - 2) X = X * emu_p[k] + (int)v[k];
+        const double q = rint(fma(fma(s2, 0x1p40, s1), 0x1p40, s0) * T.pinv);
+        const long x0 = (long)fma(-q, T.p[0], s0), x1 = (long)fma(-q, T.p[1], s1), x2 = (long)fma(-q, T.p[2], s2), x3 = (long)(-q * T.p[3]);
+        // the sum is below 3 P / 2 < 2^127 in magnitude; its terms are not, so they are added modulo 2^128
+        __int128 X = (__int128)((emu_u128)(__int128)x0 + ((emu_u128)(__int128)x1 << 40) + ((emu_u128)(__int128)x2 << 80) + ((emu_u128)(__int128)x3 << 120));
+        X = X >= half ? X - P : (X < -half ? X + P : X);
         const long hi = (long)(X >> 64);
         const unsigned long lo = (unsigned long)X;
         const double xd = (hi == ((long)lo >> 63)) ? (double)(long)lo : fma((double)hi, 0x1p64, (double)lo);
@@ -367,7 +411,7 @@ int emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t ldb, 
                                (long)(nrp * K), (long)(ncp * K), (int)K, rr, (long)ncp, (long)(nrp * ncp), tm, tn);
             const long thr = (long)nr * ((nc + 3) / 4);
             hipLaunchKernelGGL(emu_rebuild_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, (const int8_t *)rr, (long)ncp,
-                               (long)(nrp * ncp), L, (const int *)sga, (const int *)sgb, C + r0 * ldc + c0, (long)ldc, (long)nr, (long)nc);
+                               (long)(nrp * ncp), L, emu_crt.t[L], (const int *)sga, (const int *)sgb, C + r0 * ldc + c0, (long)ldc, (long)nr, (long)nc);
         }
         GPX_HIP(hipGetLastError());
     }
@@ -389,6 +433,42 @@ extern "C" int gpx_emu_gemm_nt_sub(const double *A, int64_t lda, const double *B
     int rc = emu_gemm_nt_sub(A, lda, B, ldb, C, ldc, rows, cols, K, w, 0, nullptr);
     if (hipStreamSynchronize(0) != hipSuccess && rc == 0) { gpx_set_error("gpx_emu_gemm_nt_sub: stream failed"); rc = GPX_ERR_HIP; }
     return rc;
+}
+
+// The two integer kernels alone on caller device buffers (tests/test_emulated_rebuild.py).  Synchronous.
+extern "C" int gpx_emu_rebuild(const int8_t *R, int64_t ldr, int64_t sr, int nmod, const int *sa, const int *sb, double *C, int64_t ldc, int64_t rows,
+                               int64_t cols)
+{
+    GPX_TRY(gpx_require_device());
+    // the kernel reads four residue bytes at once, also in the column tail: rows of R are 4-byte aligned and padded to a multiple of 4
+    if (!R || !sa || !sb || !C || rows < 0 || cols < 0 || nmod < 2 || nmod > EMU_MAXL || ldr < round_up(cols, 4) || (ldr | sr) & 3 ||
+        (uintptr_t)R & 3 || sr < rows * ldr || ldc < cols) {
+        gpx_set_error("gpx_emu_rebuild: bad arguments");
+        return GPX_ERR_BAD_ARG;
+    }
+    if (rows == 0 || cols == 0) return 0;
+    const long thr = (long)rows * ((cols + 3) / 4);
+    hipLaunchKernelGGL(emu_rebuild_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, 0, R, (long)ldr, (long)sr, nmod, emu_crt.t[nmod], sa, sb, C,
+                       (long)ldc, (long)rows, (long)cols);
+    GPX_HIP(hipGetLastError());
+    GPX_HIP(hipStreamSynchronize(0));
+    return 0;
+}
+
+extern "C" int gpx_emu_i8_gemm(const int8_t *A, const int8_t *B, int64_t rows, int64_t cols, int64_t K, int nmod, int8_t *R)
+{
+    GPX_TRY(gpx_require_device());
+    if (!A || !B || !R || rows <= 0 || cols <= 0 || rows % EMU_BT || cols % EMU_BT || K <= 0 || K % EMU_BK || K >= (1 << 17) || nmod < 1 ||
+        nmod > EMU_MAXL || ((uintptr_t)A | (uintptr_t)B) & 15 || rows / EMU_BT * (cols / EMU_BT) * nmod > INT32_MAX) {
+        gpx_set_error("gpx_emu_i8_gemm: bad arguments");
+        return GPX_ERR_BAD_ARG;
+    }
+    const int tm = (int)(rows / EMU_BT), tn = (int)(cols / EMU_BT);
+    hipLaunchKernelGGL(emu_i8_gemm_kernel, dim3((unsigned)(tm * tn * nmod)), dim3(512), 0, 0, A, B, (long)(rows * K), (long)(cols * K), (int)K, R,
+                       (long)cols, (long)(rows * cols), tm, tn);
+    GPX_HIP(hipGetLastError());
+    GPX_HIP(hipStreamSynchronize(0));
+    return 0;
 }
 
 __global__ void emu_fill_kernel(int8_t *p, long n, unsigned seed)

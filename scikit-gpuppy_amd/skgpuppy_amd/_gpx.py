@@ -85,6 +85,8 @@ SIGNATURES = {
     "gpx_bench_mfma_f64": (_int, [_int, ctypes.POINTER(_dbl)]),
     "gpx_bench_emu_i8": (_int, [_i64, _i64, _i64, _int, _int, ctypes.POINTER(_dbl)]),
     "gpx_emu_gemm_nt_sub": (_int, [_dp, _i64, _dp, _i64, _dp, _i64, _i64, _i64, _i64]),
+    "gpx_emu_rebuild": (_int, [_dp, _i64, _i64, _int, _dp, _dp, _dp, _i64, _i64, _i64]),
+    "gpx_emu_i8_gemm": (_int, [_dp, _dp, _i64, _i64, _i64, _int, _dp]),
     "gpx_bench_hbm": (_int, [_i64, _int, ctypes.POINTER(_dbl), ctypes.POINTER(_dbl)]),
     "gpx_bench_fp64_pipes": (_int, [_int, _int, _int] + [ctypes.POINTER(_dbl)] * 3),
     "gpx_dev_gram": (_int, [_dp, _i64, _dp, _i64, _int, _dp, _dbl, _int, _int, _dp, _i64, _i64, _i64, ctypes.c_void_p]),

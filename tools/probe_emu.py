@@ -1,5 +1,6 @@
 """The int8 residue product of the emulated update (csrc/emu.hip) alone at the C3 deep-update shape, against the vendor int8 GEMM
-(torch._int_mm, this script only).  Usage: python tools/probe_emu.py [rows cols K]"""
+(torch._int_mm, this script only).  Usage: python tools/probe_emu.py [rows cols K [warm_seconds]]
+warm_seconds > 0: that long of back-to-back 16-modulus launches first, so that the timed launches see the clock the chip settles at."""
 import ctypes
 import os
 import sys
@@ -10,6 +11,11 @@ import torch  # noqa: E402
 from skgpuppy_amd import _gpx  # noqa: E402
 
 rows, cols, K = (int(v) for v in sys.argv[1:4]) if len(sys.argv) > 3 else (16384, 8192, 8192)
+warm = float(sys.argv[4]) if len(sys.argv) > 4 else 0.0
+t_end = time.perf_counter() + warm
+while time.perf_counter() < t_end:
+    ms = ctypes.c_double()
+    _gpx.check(_gpx.lib.gpx_bench_emu_i8(rows, cols, K, 16, 8, ctypes.byref(ms)), "gpx_bench_emu_i8")
 for nmod, iters in ((1, 40), (16, 4), (16, 8)):
     ms = ctypes.c_double()
     _gpx.check(_gpx.lib.gpx_bench_emu_i8(rows, cols, K, nmod, iters, ctypes.byref(ms)), "gpx_bench_emu_i8")
