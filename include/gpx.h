@@ -295,6 +295,67 @@ int gpx_dev_syrk_trap(const double *A, int64_t lda, const double *B, int64_t ldb
                       int64_t K, double alpha, double beta, int *count_dev, void *stream);
 /* (lower_only: only the 128-tiles on/below the diagonal of a square C are computed; with N > M the first N - M columns are
  * full and the remaining M x M square is lower-triangular by tiles) */
+
+/* ---- the GEMM's launch forms, one at a time (tests/test_gemm_dispatch.py) ----
+ * one triangular operand of a product, square in its own index space: the contraction skips its zero part */
+enum {
+    GPX_GEMM_TRI_NONE = 0,
+    GPX_GEMM_TRI_A_UPPER = 1,   /* A[i][k] = 0 for k < i  (K == M) */
+    GPX_GEMM_TRI_A_LOWER = 2,   /* A[i][k] = 0 for k > i  (K == M) */
+    GPX_GEMM_TRI_B_LOWER = 3,   /* B[j][k] = 0 for k > j  (K == N) */
+    GPX_GEMM_TRI_B_UPPER = 5    /* B[j][k] = 0 for k < j  (K == N); 4 and 6 are internal */
+};
+/* which launch gpx_dev_gemm_nt_ex chose: block tile rows / 32, block tile columns / 32, lower-only or plain, and for a triangular B
+ * the form of its tile enumeration */
+#define GPX_GEMM_VARIANT(wm, wn, lower, form) ((wm) | ((wn) << 4) | ((lower) << 8) | ((form) << 12))
+enum { GPX_GEMM_FORM_NONE = 0, GPX_GEMM_FORM_FINE = 1, GPX_GEMM_FORM_LONGEST_FIRST = 2, GPX_GEMM_FORM_PAIRED = 3, GPX_GEMM_FORM_SMALL = 4 };
+enum {
+    GPX_GEMM_V_NONE = 0,                                              /* nothing was launched (refused, or an empty product) */
+    GPX_GEMM_V_128X128 = GPX_GEMM_VARIANT(4, 4, 0, 0),                /* the bulk launch: grouped walk, one chunk per XCD */
+    GPX_GEMM_V_64X64 = GPX_GEMM_VARIANT(2, 2, 0, 0),                  /* fewer than 192 tiles, or small_tiles */
+    GPX_GEMM_V_64X128 = GPX_GEMM_VARIANT(2, 4, 0, 0),                 /* one column tile, 96 row tiles or more */
+    GPX_GEMM_V_32X128 = GPX_GEMM_VARIANT(1, 4, 0, 0),                 /* one column tile, fewer */
+    GPX_GEMM_V_LOWER_128X128 = GPX_GEMM_VARIANT(4, 4, 1, 0),
+    GPX_GEMM_V_LOWER_64X64 = GPX_GEMM_VARIANT(2, 2, 1, 0),
+    GPX_GEMM_V_LOWER_32X32 = GPX_GEMM_VARIANT(1, 1, 1, 0),            /* at most 40 tiles with 512 <= K <= 2048 */
+    GPX_GEMM_V_TRIB_FINE = GPX_GEMM_VARIANT(2, 2, 0, 1),              /* triangular B, 192 .. 447 tiles: 64 x 64 tiles, longest first */
+    GPX_GEMM_V_TRIB_LONGEST_FIRST = GPX_GEMM_VARIANT(4, 4, 0, 2),     /* triangular B: 128 x 128 tiles, longest first */
+    GPX_GEMM_V_TRIB_PAIRED = GPX_GEMM_VARIANT(4, 4, 0, 3),            /* triangular B: column tiles bx and ncols - 1 - bx in one workgroup */
+    GPX_GEMM_V_TRIB_SMALL_64X64 = GPX_GEMM_VARIANT(2, 2, 0, 4),       /* triangular B, fewer than 192 tiles: the tile the plain rules give */
+    GPX_GEMM_V_TRIB_SMALL_64X128 = GPX_GEMM_VARIANT(2, 4, 0, 4),
+    GPX_GEMM_V_TRIB_SMALL_32X128 = GPX_GEMM_VARIANT(1, 4, 0, 4)
+};
+/* gpx_dev_gemm_nt with the launcher's remaining arguments:
+ *   ktrim != 0, lower_only (square C, K == M): BOTH operands are upper triangular (operand[i][k] = 0 for k < i), tile row by contracts
+ *     over k >= by * (tile rows) only;
+ *   ktrim != 0, plain: A alone is upper triangular with its diagonal ktrim - 1 columns to the left of its first column (A[i][k] = 0
+ *     for k < i - (ktrim - 1)); ktrim - 1 a multiple of 16;
+ *   tri: one of GPX_GEMM_TRI_* (plain launches, no ktrim); the internal values are refused with GPX_ERR_BAD_ARG;
+ *   small_tiles: 64 x 64 block tiles also where the product has 192 tiles or more;
+ *   variant_out: HOST int, may be NULL; receives the GPX_GEMM_V_* code of the launch that was chosen.
+ * Read contract of an operand declared triangular or shortened by ktrim: by 128 x 128 tiles of the operand (tile row = rows / 128, tile
+ * column = k / 128), a launch reads NOTHING in the tiles that lie wholly inside the zero part -- they may hold anything, NaN included --
+ * and inside the tiles that the diagonal crosses the CALLER supplies the zeros.  (gpx_adopt_factor relies on this: the strictly-upper
+ * tiles of L are scratch.) */
+int gpx_dev_gemm_nt_ex(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t M, int64_t N, int64_t K,
+                       double alpha, double beta, int lower_only, int ktrim, int tri, int small_tiles, int *variant_out, void *stream);
+/* C [M, N] = alpha A B^T with B lower triangular (K == N, read contract as above) on 128 x 128 tiles, M / 128 * N / 128 >= 192 of them,
+ * and of every row the partial sums over each 64-column piece c: p2[row * nslots + slot0 + c] = sum C[row][64 c + j]^2,
+ * py[row * nslots + slot0 + c] = sum C[row][64 c + j] y[64 c + j]; y [N], p2 and py [M, nslots] with nslots >= slot0 + N / 64.  No other
+ * slot is written. */
+int gpx_dev_gemm_nt_tri_reduce(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t M, int64_t N,
+                               double alpha, const double *y, double *p2, double *py, int64_t slot0, int64_t nslots, void *stream);
+/* `batch` independent products C_z = alpha A_z B_z^T + beta C_z on 64 x 64 tiles (M, N multiples of 64): problem z = (p, q) with
+ * q = z % nq has its operands at A + p a_sp + q a_sq, B + p b_sp + q b_sq, C + p c_sp + q c_sq (elements; the A and B strides even).
+ * tri: GPX_GEMM_TRI_* of every problem (then M == N == K). */
+int gpx_dev_gemm_nt_batched(const double *A, int64_t lda, int64_t a_sp, int64_t a_sq, const double *B, int64_t ldb, int64_t b_sp,
+                            int64_t b_sq, double *C, int64_t ldc, int64_t c_sp, int64_t c_sq, int nq, int tri, int64_t M, int64_t N,
+                            int64_t K, double alpha, double beta, int64_t batch, void *stream);
+/* split-K SYRK as one launch: parts [nchunks, m, m] (dense), the lower 128 x 128 tiles of parts[c] = alpha W_c W2_c^T with
+ * W_c = W[:, c kchunk : (c + 1) kchunk); W [m, nchunks kchunk] with leading dimension ldw, W2 the same shape and leading dimension or
+ * NULL (= W).  The tiles above the diagonal of every part are not written. */
+int gpx_dev_syrk_splitk(const double *W, int64_t ldw, const double *W2, double *parts, int64_t m, int64_t kchunk, int nchunks,
+                        double alpha, void *stream);
 /* factor one 128x128 diagonal block in place (lower) and write its inverse to dinv[128*128];
  * info_dev: device int, set to 1-based failing column + col_offset on a non-positive pivot */
 int gpx_dev_potrf_leaf(double *A, int64_t ld, double *dinv, double *diag_out, int *info_dev, int col_offset, void *stream);

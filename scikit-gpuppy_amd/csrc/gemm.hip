@@ -245,8 +245,10 @@ int launch_syrk_trap_signal(const double *A, int64_t lda, const double *B, int64
 constexpr double SMALL_GRID_TILES = 192.0;
 
 int launch_gemm_nt(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t M,
-                   int64_t N, int64_t K, double alpha, double beta, int lower_only, hipStream_t s, Profiler *prof, int ktrim, int tri, int small_tiles)
+                   int64_t N, int64_t K, double alpha, double beta, int lower_only, hipStream_t s, Profiler *prof, int ktrim, int tri, int small_tiles,
+                   int *variant)
 {
+    if (variant) *variant = GPX_GEMM_V_NONE;
     if (M % TILE || N % TILE || K % GEMM_BK || K <= 0 || (lda & 1) || (ldb & 1) ||
         ((uintptr_t)A & 15) || ((uintptr_t)B & 15)) {
         gpx_set_error("launch_gemm_nt: shape/alignment not supported (M=%ld N=%ld K=%ld lda=%ld ldb=%ld)", (long)M,
@@ -290,8 +292,11 @@ int launch_gemm_nt(const double *A, int64_t lda, const double *B, int64_t ldb, d
         return GPX_ERR_BAD_ARG;
     }
     const GemmBatch nb_ = {0, 0, 0, 0}, na_ = {0, 0, 0, tri};   // tri: one triangular operand (GEMM_TRI_*), square K == N or K == M
-#define GPX_LAUNCH(WM_, WN_)                                                                                          \
+    // *variant: the branch taken below, as a GPX_GEMM_V_* code (form: how a triangular B's tiles are enumerated)
+#define GPX_LAUNCH(WM_, WN_) GPX_LAUNCH_FORM(WM_, WN_, tri_b ? GPX_GEMM_FORM_SMALL : GPX_GEMM_FORM_NONE)
+#define GPX_LAUNCH_FORM(WM_, WN_, FORM_)                                                                              \
     do {                                                                                                              \
+        if (variant) *variant = GPX_GEMM_VARIANT(WM_, WN_, lower_only ? 1 : 0, FORM_);                                \
         dim3 grid((unsigned)(N / (32 * WN_)), (unsigned)(M / (32 * WM_)));                                            \
         const unsigned nt_ = (unsigned)(M / (32 * WM_)), off_ = (unsigned)(trap / (32 * WN_));                        \
         if (lower_only)                                                                                               \
@@ -307,13 +312,14 @@ int launch_gemm_nt(const double *A, int64_t lda, const double *B, int64_t ldb, d
     // below that plain 128 x 128 tiles, longest first (twice the workgroups); below THAT 64 x 64 tiles (eight times): a leaf of 4096 rows
     // took the same 0.28 ms as one of 16384.
     const double paired_wgs = (double)(M / TILE) * (double)(N / TILE / 2);
-    if (tri_fine) GPX_LAUNCH(2, 2);
+    if (tri_fine) GPX_LAUNCH_FORM(2, 2, GPX_GEMM_FORM_FINE);
     else if (tri_b && tiles >= SMALL_GRID_TILES && (N / TILE) % 2 == 0 && paired_wgs >= 448.0) {
         // column tiles of length (bx + 1) * 128 (resp. K - bx * 128): pair bx with its mirror image so that every workgroup does the same work
         const GemmBatch pa_ = {0, 0, 0, tri == GEMM_TRI_B_LOWER ? GEMM_TRI_B_LOWER_PAIRED : GEMM_TRI_B_UPPER_PAIRED};
+        if (variant) *variant = GPX_GEMM_V_TRIB_PAIRED;
         hipLaunchKernelGGL((gemm_nt_f64_kernel<4, 4, false>), dim3((unsigned)(N / TILE / 2), (unsigned)(M / TILE)), dim3(256), 0, s, A, (long)lda, B,
                            (long)ldb, C, (long)ldc, (int)K, alpha, beta, (int)(N / TILE), 0, 0, pa_, nb_, nb_);
-    } else if (tiles >= SMALL_GRID_TILES && !small_tiles) GPX_LAUNCH(4, 4);   // small_tiles: a short product (K = 128) issued next to a
+    } else if (tiles >= SMALL_GRID_TILES && !small_tiles) GPX_LAUNCH_FORM(4, 4, tri_b ? GPX_GEMM_FORM_LONGEST_FIRST : GPX_GEMM_FORM_NONE);   // small_tiles: a short product (K = 128) issued next to a
                                                                               // saturating launch -- 64 x 64 tiles find places sooner
     else if (lower_only && tiles <= 40.0 && K >= 512 && K <= 2048 && !ktrim) GPX_LAUNCH(1, 1);   // a 1024 x 1024 square with a long contraction (the update that
                                                                                      // gates the factorisation's next chain): 32 x 32 tiles put two
@@ -324,6 +330,7 @@ int launch_gemm_nt(const double *A, int64_t lda, const double *B, int64_t ldb, d
         else GPX_LAUNCH(1, 4);
     } else GPX_LAUNCH(2, 2);
 #undef GPX_LAUNCH
+#undef GPX_LAUNCH_FORM
     GPX_HIP(hipGetLastError());
     return 0;
 }
@@ -547,6 +554,56 @@ extern "C" int gpx_dev_gemm_nt(const double *A, int64_t lda, const double *B, in
                                int64_t M, int64_t N, int64_t K, double alpha, double beta, int lower_only, void *stream)
 {
     return launch_gemm_nt(A, lda, B, ldb, C, ldc, M, N, K, alpha, beta, lower_only, (hipStream_t)stream, nullptr);
+}
+
+static_assert(GPX_GEMM_TRI_NONE == GEMM_TRI_NONE && GPX_GEMM_TRI_A_UPPER == GEMM_TRI_A_UPPER && GPX_GEMM_TRI_A_LOWER == GEMM_TRI_A_LOWER &&
+              GPX_GEMM_TRI_B_LOWER == GEMM_TRI_B_LOWER && GPX_GEMM_TRI_B_UPPER == GEMM_TRI_B_UPPER, "gpx.h and common.h name the same operands");
+static bool public_tri(int tri)
+{
+    return tri == GEMM_TRI_NONE || tri == GEMM_TRI_A_UPPER || tri == GEMM_TRI_A_LOWER || tri == GEMM_TRI_B_LOWER || tri == GEMM_TRI_B_UPPER;
+}
+
+extern "C" int gpx_dev_gemm_nt_ex(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t M, int64_t N,
+                                  int64_t K, double alpha, double beta, int lower_only, int ktrim, int tri, int small_tiles, int *variant_out,
+                                  void *stream)
+{
+    if (variant_out) *variant_out = GPX_GEMM_V_NONE;
+    if (!public_tri(tri) || ktrim < 0) {
+        gpx_set_error("gpx_dev_gemm_nt_ex: tri must be one of GPX_GEMM_TRI_*, ktrim >= 0");
+        return GPX_ERR_BAD_ARG;
+    }
+    return launch_gemm_nt(A, lda, B, ldb, C, ldc, M, N, K, alpha, beta, lower_only, (hipStream_t)stream, nullptr, ktrim, tri, small_tiles, variant_out);
+}
+
+extern "C" int gpx_dev_gemm_nt_tri_reduce(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t M,
+                                          int64_t N, double alpha, const double *y, double *p2, double *py, int64_t slot0, int64_t nslots,
+                                          void *stream)
+{
+    if (slot0 < 0 || N < 0 || nslots < slot0 + N / 64) {
+        gpx_set_error("gpx_dev_gemm_nt_tri_reduce: needs 0 <= slot0 and slot0 + N / 64 <= nslots");
+        return GPX_ERR_BAD_ARG;
+    }
+    GemmReduce red;
+    red.y = y; red.p2 = p2; red.py = py; red.slot0 = (long)slot0; red.nslots = (long)nslots;
+    return launch_gemm_nt_tri_reduce(A, lda, B, ldb, C, ldc, M, N, alpha, red, (hipStream_t)stream, nullptr);
+}
+
+extern "C" int gpx_dev_gemm_nt_batched(const double *A, int64_t lda, int64_t a_sp, int64_t a_sq, const double *B, int64_t ldb, int64_t b_sp,
+                                       int64_t b_sq, double *C, int64_t ldc, int64_t c_sp, int64_t c_sq, int nq, int tri, int64_t M, int64_t N,
+                                       int64_t K, double alpha, double beta, int64_t batch, void *stream)
+{
+    if (!public_tri(tri) || (tri && (M != N || N != K))) {
+        gpx_set_error("gpx_dev_gemm_nt_batched: tri must be one of GPX_GEMM_TRI_*, and a triangular operand needs M == N == K");
+        return GPX_ERR_BAD_ARG;
+    }
+    const GemmBatch ba = {nq, (long)a_sp, (long)a_sq, tri}, bb = {nq, (long)b_sp, (long)b_sq, 0}, bc = {nq, (long)c_sp, (long)c_sq, 0};
+    return launch_gemm_nt_batched(A, lda, ba, B, ldb, bb, C, ldc, bc, M, N, K, alpha, beta, batch, (hipStream_t)stream);
+}
+
+extern "C" int gpx_dev_syrk_splitk(const double *W, int64_t ldw, const double *W2, double *parts, int64_t m, int64_t kchunk, int nchunks,
+                                   double alpha, void *stream)
+{
+    return launch_syrk_lower_splitk(W, ldw, parts, m, kchunk, nchunks, alpha, (hipStream_t)stream, W2);
 }
 
 extern "C" int gpx_dev_syrk_trap(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t M, int64_t off_cols,

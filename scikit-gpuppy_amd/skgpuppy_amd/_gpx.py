@@ -18,6 +18,22 @@ K_GRAM, K_GEMM, K_POTRF_LEAF, K_TRSV, K_REDUCE, K_QUAD, K_EXACT, K_GEMM_SMALL, K
 KERNEL_CLASS_NAMES = ["gram", "gemm_f64_mfma", "potrf_leaf", "trsv", "predict_reduce", "approx_quad", "exact_sum",
                       "gemm_f64_mfma_small_tiles", "trsv_under_factorisation", "gemm_f64_emulated_int8"]
 
+# GPX_GEMM_TRI_* and GPX_GEMM_V_* of include/gpx.h (gpx_dev_gemm_nt_ex; tests/test_gemm_exact_helpers.py holds the two copies together)
+GEMM_TRI_NONE, GEMM_TRI_A_UPPER, GEMM_TRI_A_LOWER, GEMM_TRI_B_LOWER, GEMM_TRI_B_UPPER = 0, 1, 2, 3, 5
+
+
+def gemm_variant(wm, wn, lower, form):
+    return wm | (wn << 4) | (lower << 8) | (form << 12)
+
+
+GEMM_VARIANTS = {
+    "NONE": 0,
+    "128X128": gemm_variant(4, 4, 0, 0), "64X64": gemm_variant(2, 2, 0, 0), "64X128": gemm_variant(2, 4, 0, 0), "32X128": gemm_variant(1, 4, 0, 0),
+    "LOWER_128X128": gemm_variant(4, 4, 1, 0), "LOWER_64X64": gemm_variant(2, 2, 1, 0), "LOWER_32X32": gemm_variant(1, 1, 1, 0),
+    "TRIB_FINE": gemm_variant(2, 2, 0, 1), "TRIB_LONGEST_FIRST": gemm_variant(4, 4, 0, 2), "TRIB_PAIRED": gemm_variant(4, 4, 0, 3),
+    "TRIB_SMALL_64X64": gemm_variant(2, 2, 0, 4), "TRIB_SMALL_64X128": gemm_variant(2, 4, 0, 4), "TRIB_SMALL_32X128": gemm_variant(1, 4, 0, 4),
+}
+
 if not os.path.exists(LIB_PATH):
     raise ImportError(
         "libgpx.so not found at %s: build it with `make -C scikit-gpuppy_amd/csrc` (or "
@@ -92,6 +108,12 @@ SIGNATURES = {
     "gpx_dev_gram": (_int, [_dp, _i64, _dp, _i64, _int, _dp, _dbl, _int, _int, _dp, _i64, _i64, _i64, ctypes.c_void_p]),
     "gpx_dev_gram_scaled": (_int, [_dp, _i64, _dp, _i64, _int, _dbl, _dbl, _int, _int, _dp, _i64, _i64, _i64, ctypes.c_void_p]),
     "gpx_dev_gemm_nt": (_int, [_dp, _i64, _dp, _i64, _dp, _i64, _i64, _i64, _i64, _dbl, _dbl, _int, ctypes.c_void_p]),
+    "gpx_dev_gemm_nt_ex": (_int, [_dp, _i64, _dp, _i64, _dp, _i64, _i64, _i64, _i64, _dbl, _dbl, _int, _int, _int, _int, ctypes.POINTER(_int),
+                                  ctypes.c_void_p]),
+    "gpx_dev_gemm_nt_tri_reduce": (_int, [_dp, _i64, _dp, _i64, _dp, _i64, _i64, _i64, _dbl, _dp, _dp, _dp, _i64, _i64, ctypes.c_void_p]),
+    "gpx_dev_gemm_nt_batched": (_int, [_dp, _i64, _i64, _i64, _dp, _i64, _i64, _i64, _dp, _i64, _i64, _i64, _int, _int, _i64, _i64, _i64, _dbl,
+                                       _dbl, _i64, ctypes.c_void_p]),
+    "gpx_dev_syrk_splitk": (_int, [_dp, _i64, _dp, _dp, _i64, _i64, _int, _dbl, ctypes.c_void_p]),
     "gpx_dev_syrk_trap": (_int, [_dp, _i64, _dp, _i64, _dp, _i64, _i64, _i64, _i64, _dbl, _dbl, ctypes.c_void_p, ctypes.c_void_p]),
     "gpx_dev_potrf_leaf": (_int, [_dp, _i64, _dp, _dp, ctypes.c_void_p, _int, ctypes.c_void_p]),
     "gpx_dev_chol_panel": (_int, [_dp, _i64, _i64, _i64, _i64, _dp, _dp, ctypes.c_void_p, ctypes.c_void_p]),
