@@ -6,7 +6,7 @@
 // (N^3/3 flop); everything downstream solves against L.
 //
 // Structure: two-level right-looking factorisation with look-ahead down to 128x128 diagonal blocks.  All O(N^3)
-// work is issued as calls of the one MFMA GEMM (gemm.hip); the leaf (potrf_trtri128_mfma_kernel) factors a diagonal
+// work is issued as calls of the one MFMA GEMM (gemm.hip); the leaf (potrf_trtri128_elim_kernel) factors a diagonal
 // block AND inverts its factor in one launch, both on MFMA out of LDS, so that every triangular solve against a
 // diagonal block becomes a GEMM with its inverse.
 #include <algorithm>
@@ -179,13 +179,10 @@ int chol_dataflow_fill_tables(int nbr, int first_rows, int *dst, int cap);
 
 static_assert(CHOL_NBP * TILE == CHOL_PANEL_COLS, "common.h: CHOL_PANEL_COLS");
 
-// factor block columns [B0,B1) of the rows >= B0 (all updates from columns < B0 already applied)
-// steps j in [j0,j1) of the diagonal square [B0,B1): leaf (factor + inverse), in-place TRSM leaf of the rows below
-// inside the square, rank-128 update of the square's remaining columns -- the latency-bound chain of small kernels
-// Optional pipelining of the "top slice": the rows [r0, r1) below the square (the next panel's diagonal-square rows) are
-// solved against the square's triangle column by column on a second stream, each column as soon as the chain step that
-// produces its diagonal-block inverse has finished -- instead of one recursive TRSM after the whole chain.
-__global__ void wait_count_kernel(const int *ctr, int want, unsigned long long limit_ticks, int *stall);
+// the schedule's switches: integers from the environment, each read once per process by a one-line getter
+static long env_long(const char *name, long dflt) { const char *e = getenv(name); return e ? atol(e) : dflt; }
+// GPX_DEBUG: the probes' verdicts and the host's enqueue marks (Lookahead::mark) on stderr
+static bool debug_enabled() { static const bool v = getenv("GPX_DEBUG") != nullptr; return v; }
 
 // time limit of the in-kernel waits (GPX_WAIT_LIMIT_MS, default 5000): generous -- it only ever expires when streams that were
 // probed as concurrent stop being so
@@ -195,10 +192,58 @@ static unsigned long long wait_limit_ticks()
     return v;   // s_memrealtime ticks at 100 MHz
 }
 
+// holds its stream until the producer launch has counted `want` finished tiles in *ctr.  A time limit that expires (it never should:
+// the producer does not depend on this stream) is reported through the factorisation's STALL word -- a word of its own, not the
+// potrf status: a scheduling stall is not a non-positive pivot, and the caller answers it by refitting on the plain schedule, never
+// with jitter (the consumers behind an expired wait read tiles that are not there: that factor is discarded).
+__global__ void wait_count_kernel(const int *ctr, int want, unsigned long long limit_ticks, int *stall)
+{
+    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+    while (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
+        if (__builtin_amdgcn_s_memrealtime() - t0 > limit_ticks) {
+            __hip_atomic_store(stall, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            break;
+        }
+        __builtin_amdgcn_s_sleep(8);
+    }
+}
+
+// that one-thread kernel queued on `on`: whatever follows on the stream runs once *counter has reached `want`
+static int queue_wait(hipStream_t on, const int *counter, int want, int *stall, unsigned long long limit_ticks = wait_limit_ticks())
+{
+    hipLaunchKernelGGL(wait_count_kernel, dim3(1), dim3(1), 0, on, counter, want, limit_ticks, stall);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// The events of one factorisation: created through make(), destroyed with the owner -- by then the caller has waited for every stream
+// that still refers to them, or has handed them on to a list that is swept later (retire_events).
+struct Events {
+    std::vector<hipEvent_t> all;
+    Events() = default;
+    Events(const Events &) = delete;
+    Events &operator=(const Events &) = delete;
+    ~Events() { clear(); }
+    void clear()
+    {
+        for (hipEvent_t e : all) (void)hipEventDestroy(e);
+        all.clear();
+    }
+    int make(hipEvent_t *e)
+    {
+        GPX_HIP(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        all.push_back(*e);
+        return 0;
+    }
+};
+
+// Pipelining of the rows below a diagonal square ("top slice"): the rows [r0, r1) are solved against the square's triangle column by
+// column on a second stream, each column as soon as the chain step that produces its diagonal-block inverse has finished -- instead
+// of one recursive TRSM after the whole chain.
 struct TopPipe {
     hipStream_t stream = nullptr;
     int64_t r0 = 0, r1 = 0;                 // block rows of the slice
-    std::vector<hipEvent_t> *events = nullptr;   // owned by the caller, destroyed after the final synchronisation
+    Events *events = nullptr;               // the caller's: they outlive the queued waits that refer to them
     const int *colsig = nullptr;            // column c of the slice may be read once colsig[c] has reached colwant (the trapezoid launch's
     int colwant = 0;                        // per-column counters); null: the stream is ordered behind the update some other way
     int *stall = nullptr;                   // the factorisation's stall word (an expired wait sets it)
@@ -209,6 +254,13 @@ struct TopPipe {
     int64_t sq_rows = 0;                    // block rows of the square
     int64_t sq_nbr = 0;                     // block rows the square launch owns (its state layout: the square's + the rows it solves below)
     const TopPipe *next = nullptr;          // further slices of the same panel (other rows, other streams) that trail the same chain
+    // the panel's chain is a square launch with these state words, `rows` block rows of square and `below` more that it solves itself
+    void follow_square(const int *state, int64_t rows, int64_t below)
+    {
+        sq_state = state;
+        sq_rows = rows;
+        sq_nbr = rows + below;
+    }
 };
 
 // a one-thread kernel that holds the slice's stream until the trapezoid launch has counted column c's narrow tiles (on the device it runs
@@ -219,10 +271,7 @@ static int colsig_wait(const TopPipe *top, int64_t c)
     static bool forced = false;
     const bool force = force_stall && !forced;
     forced = forced || force;
-    hipLaunchKernelGGL(wait_count_kernel, dim3(1), dim3(1), 0, top->stream, top->colsig + c, force ? 0x7fffffff : top->colwant,
-                       force ? 1000ull : wait_limit_ticks(), top->stall);
-    GPX_HIP(hipGetLastError());
-    return 0;
+    return queue_wait(top->stream, top->colsig + c, force ? 0x7fffffff : top->colwant, top->stall, force ? 1000ull : wait_limit_ticks());
 }
 
 // column j of the slice: X_j = (Z_j - X_{B0..j} L[j, B0..j)^T) Dinv_j^T   (left-looking, two small launches on top->stream)
@@ -244,13 +293,10 @@ static int top_column(double *L, int64_t ld, int64_t B0, int64_t j, const double
     }
     if (top->sq_state) {
         const int64_t B1 = B0 + top->sq_rows;
-        hipLaunchKernelGGL(wait_count_kernel, dim3(1), dim3(1), 0, top->stream, top->sq_state + chol_dataflow_word_steps(), (int)(j - B0 + 1), wait_limit_ticks(), top->stall);
-        GPX_HIP(hipGetLastError());
+        GPX_TRY(queue_wait(top->stream, top->sq_state + chol_dataflow_word_steps(), (int)(j - B0 + 1), top->stall));
         GPX_TRY(launch_gemm_nt(Zt + j * TILE, ld, Dinv + j * (int64_t)TILE * TILE, TILE, Zt + j * TILE, ld, M, TILE, TILE, 1.0, 0.0, 0, top->stream, prof));
         if (j + 1 < B1) {
-            hipLaunchKernelGGL(wait_count_kernel, dim3(1), dim3(1), 0, top->stream, top->sq_state + chol_dataflow_word_colc(top->sq_nbr, j - B0),
-                               (int)(4 * (B1 - 1 - j)), wait_limit_ticks(), top->stall);
-            GPX_HIP(hipGetLastError());
+            GPX_TRY(queue_wait(top->stream, top->sq_state + chol_dataflow_word_colc(top->sq_nbr, j - B0), (int)(4 * (B1 - 1 - j)), top->stall));
             // Z[:, j+1 .. B1) -= X_j L[j+1 .. B1, j]^T
             GPX_TRY(launch_gemm_nt(Zt + j * TILE, ld, L + ((j + 1) * TILE) * ld + j * TILE, ld, Zt + (j + 1) * TILE, ld, M, (B1 - 1 - j) * TILE, TILE,
                                    -1.0, 1.0, 0, top->stream, prof, 0, 0, 1));   // (64 x 64 tiles)
@@ -267,6 +313,9 @@ static int top_column(double *L, int64_t ld, int64_t B0, int64_t j, const double
                           top->stream, prof);
 }
 
+// steps j in [j0,j1) of the diagonal square [B0,B1): leaf (factor + inverse), in-place TRSM leaf of the rows below
+// inside the square, rank-128 update of the square's remaining columns -- the latency-bound chain of small kernels.
+// top (optional): the slices of the rows below the square that trail the chain column by column (TopPipe).
 static int chol_square_steps(double *L, int64_t ld, int64_t B0, int64_t B1, int64_t j0, int64_t j1, double *Dinv,
                              double *diagL, int *info_dev, hipStream_t s, Profiler *prof, const TopPipe *top = nullptr, int excl = 0)
 {
@@ -295,8 +344,7 @@ static int chol_square_steps(double *L, int64_t ld, int64_t B0, int64_t B1, int6
         for (const TopPipe *t = top; t; t = t->next) {
             if (!t->stream || t->r1 <= t->r0) continue;
             if (!e) {
-                GPX_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                t->events->push_back(e);
+                GPX_TRY(t->events->make(&e));
                 GPX_HIP(hipEventRecord(e, s));
             }
             GPX_HIP(hipStreamWaitEvent(t->stream, e, 0));
@@ -366,7 +414,6 @@ static void retire_buffers(const std::vector<void *> &bufs, const std::vector<hi
     }
     pending.push_back(std::move(fresh));
 }
-static void retire_buffers(const std::vector<void *> &bufs, hipStream_t behind) { retire_buffers(bufs, std::vector<hipStream_t>{behind}); }
 
 // status words of a square launch (dflow.hip: [0] potrf status, [1] stall) folded into the caller's ONE status word: a non-positive
 // pivot as it is, an expired in-kernel wait as GPX_INFO_STALLED (the multi-GPU host raises on it: that factor is invalid, and it is not
@@ -377,6 +424,39 @@ __global__ void merge_info_kernel(const int *two, int *one)
 {
     if (two[1]) atomicMax(one, (int)GPX_INFO_STALLED);
     else if (two[0]) atomicCAS(one, 0, two[0]);
+}
+
+// How many ranks share the trailing update this thread's owner steps run beside (gpx_dev_set_panel_share; 1 = all of it, the default).
+// At R ranks an owner's chain runs next to 1 / R of the update: "short trailing update -> square launch" is decided on the tiles divided
+// by R.  Measured where it can be on one GPU (profiles/r06_multi_device_abi_one_gpu.txt): square launches for EVERY panel cost one rank
+// nothing (C3 29.2 vs 29.3 ms, C4 1.371 vs 1.366 s) and take 6 % off two ranks that share the chip (39.2 vs 41.6 ms).
+static thread_local int g_panel_share = 1;
+extern "C" int gpx_dev_set_panel_share(int ranks)
+{
+    if (ranks < 1) { gpx_set_error("gpx_dev_set_panel_share: ranks must be >= 1"); return GPX_ERR_BAD_ARG; }
+    g_panel_share = ranks;
+    return 0;
+}
+
+// Square-kernel mode: the diagonal chain of a panel -- 8 x (leaf, in-square solve, rank-128 update) = 24 dependent launches -- is ONE
+// small launch of the dataflow kernel on the panel's square (leaf + side workers, dflow.hip; ~56 us per 128-column step instead of
+// ~100-250 us of dependent launches that wait for places), and the column solves of the rows below wait for its step counter instead
+// of for events.  THE rule for where, of the single-GPU schedule (chol_factor) and of the multi-GPU owner's panel step alike: where the
+// chain is the critical path and the chip has empty CUs for it -- a square launch needs whole CUs, which a long trailing update beside
+// it does not give up.  That is the first panel (nothing but the Gram kernel's remainder runs beside it) and the panels whose trailing
+// update has fewer than GPX_SQK_TILES tiles left (default 1000: the last six panels at N = 16384).  GPX_SQK_FROM = p forces it from
+// panel p on (0: everywhere; -1: never).
+//   b0: the panel's first block column, rows: block rows of its square, nrem: block rows below the square (the trailing update that
+//   runs beside the chain: nrem (nrem + 1) / 2 tiles of triangle + nrem x rows of the next panel's columns), share: ranks that split it
+//   from_p: GPX_SQK_FROM = p > 0 counts (the owner's panel step has always read only 0 and -1, and keeps doing so)
+static long sqk_from() { static const long v = env_long("GPX_SQK_FROM", -2); return v; }   // -2: the rule decides
+static bool square_launch_wanted(int64_t b0, int64_t rows, int64_t nrem, int share, bool from_p)
+{
+    static const long tiles = env_long("GPX_SQK_TILES", 1000);
+    if (sqk_from() == -1 || !chol_dataflow_supported(CHOL_NBP)) return false;
+    if (sqk_from() == 0) return true;
+    if (sqk_from() > 0 && from_p) return b0 >= sqk_from() * CHOL_NBP;
+    return b0 == 0 || (nrem * (nrem + 1) / 2 + nrem * rows) / share < tiles;
 }
 
 // The panel step of the multi-GPU host's panel owner (skgpuppy_amd/distributed.py -> gpx_dev_chol_panel / gpx_dev_chol_panel_next /
@@ -390,23 +470,9 @@ __global__ void merge_info_kernel(const int *two, int *one)
 //   NEXT panel's square, what its owner needs to start its chain -- on sh, the rest on sf; both are ordered behind `s` as it stood at
 //   the call (plus the square's update), are NOT joined back, and the caller orders whatever else their updates need (the arrival of
 //   P's far rows) on those streams before the call.  After the call `s` holds the square, Dinv and diag; sh the head rows; sf the rest.
-// The chain of the FIRST panel and of the panels with a short trailing matrix (fewer than 1000 tiles of trailing update left:
-// chol_factor's rule -- a square launch needs whole CUs, which a long trailing update beside it does not give up) is ONE square launch
-// of the dataflow kernel (dflow.hip; ~56 us per 128-column step instead of ~100-250 us of dependent launches that wait for places),
-// its column solves follow the launch's step counter.  (A panel solve by one product with the square's inverse was measured here too:
-// slower in the one-rank rehearsal, tools/native/rejected/r05_owner_step_square_launch_product_solve.patch.)
-// How many ranks share the trailing update this thread's owner steps run beside (gpx_dev_set_panel_share; 1 = all of it, the default).
-// At R ranks an owner's chain runs next to 1 / R of the update: "short trailing update -> square launch" is decided on the tiles divided
-// by R.  Measured where it can be on one GPU (profiles/r06_multi_device_abi_one_gpu.txt): square launches for EVERY panel cost one rank
-// nothing (C3 29.2 vs 29.3 ms, C4 1.371 vs 1.366 s) and take 6 % off two ranks that share the chip (39.2 vs 41.6 ms).
-static thread_local int g_panel_share = 1;
-extern "C" int gpx_dev_set_panel_share(int ranks)
-{
-    if (ranks < 1) { gpx_set_error("gpx_dev_set_panel_share: ranks must be >= 1"); return GPX_ERR_BAD_ARG; }
-    g_panel_share = ranks;
-    return 0;
-}
-
+// Where square_launch_wanted says so (full panels only) the chain is ONE square launch of the dataflow kernel and the column solves
+// follow the launch's step counter.  (A panel solve by one product with the square's inverse was measured here too: slower in the
+// one-rank rehearsal, tools/native/rejected/r05_owner_step_square_launch_product_solve.patch.)
 int chol_panel_factor_piped(double *L, int64_t ld, int64_t nblk_all, int64_t B0, int64_t B1, double *Dinv, double *diagL,
                             int *info_dev, hipStream_t s, Profiler *prof, const double *P, int64_t ldp, int64_t kp,
                             int64_t hb, hipStream_t sh, hipStream_t sf)
@@ -416,25 +482,14 @@ int chol_panel_factor_piped(double *L, int64_t ld, int64_t nblk_all, int64_t B0,
     double *Csq = L + c0 * ld + c0;
     if (P) GPX_TRY(launch_gemm_nt(P, ldp, P, ldp, Csq, ld, w, w, kp, -1.0, 1.0, 0, s, prof));
     const int64_t nrem = nblk_all - B1;
-    static const int64_t sqk_from = [] { const char *e = getenv("GPX_SQK_FROM"); return e ? atol(e) : (int64_t)-2; }();
-    const bool sqk = sqk_from != -1 && B1 - B0 == CHOL_NBP && B0 % CHOL_NBP == 0 && chol_dataflow_supported(CHOL_NBP) &&
-                     (sqk_from == 0 || B0 == 0 || (nrem * (nrem + 1) / 2 + nrem * CHOL_NBP) / g_panel_share < 1000);
+    const bool sqk = B1 - B0 == CHOL_NBP && B0 % CHOL_NBP == 0 && square_launch_wanted(B0, B1 - B0, nrem, g_panel_share, false);
+    // what the call leaves queued (buffer, events, internal stream): everything queued sits in body(), every way out passes the hand-over below it
     std::vector<void *> scratch;
+    Events events;
+    hipStream_t st_int = nullptr;
+    struct Slice { hipStream_t st; int64_t r0, r1; bool joined; };
+    std::vector<Slice> slices;   // of the rows below the square
     int *two = nullptr, *state = nullptr, *tab_dev = nullptr;
-    if (sqk) {
-        // status pair, state words and task tables of the launch: zeroed / uploaded on `s` BEFORE the fork, so that the column solves on
-        // the slices' streams never poll a recycled buffer's old counters
-        static thread_local std::vector<int> tab_host;   // (uploaded asynchronously: must outlive this call)
-        const int64_t nstate = chol_dataflow_state_ints(CHOL_NBP), ntab = chol_dataflow_table_ints(CHOL_NBP);
-        tab_host.assign((size_t)ntab, 0);
-        if (chol_dataflow_fill_tables((int)CHOL_NBP, (int)CHOL_NBP, tab_host.data(), (int)ntab) < 0) { gpx_set_error("chol_panel_factor_piped: task tables"); return GPX_ERR_STATE; }
-        double *buf = nullptr;
-        GPX_TRY(dalloc(&buf, (4 + nstate + ntab) / 2 + 2));
-        scratch.push_back(buf);
-        two = reinterpret_cast<int *>(buf); state = two + 4; tab_dev = state + nstate;
-        GPX_HIP(hipMemsetAsync(two, 0, sizeof(int) * (size_t)(4 + nstate), s));
-        GPX_HIP(hipMemcpyAsync(tab_dev, tab_host.data(), sizeof(int) * (size_t)ntab, hipMemcpyHostToDevice, s));
-    }
     auto chain = [&](const TopPipe *top) -> int {
         if (!sqk) return chol_square_steps(L, ld, B0, B1, B0, B1, Dinv, diagL, info_dev, s, prof, top);
         static thread_local std::vector<int> tab;
@@ -449,35 +504,39 @@ int chol_panel_factor_piped(double *L, int64_t ld, int64_t nblk_all, int64_t B0,
         GPX_HIP(hipGetLastError());
         return 0;
     };
-    // the slices of the rows below the square
-    struct Slice { hipStream_t st; int64_t r0, r1; bool joined; };
-    std::vector<Slice> slices;
-    hipStream_t st_int = nullptr;
-    if (nrem > 0) {
-        if (own_streams) {
-            const int64_t h = hb < 0 ? 0 : (hb > nrem ? nrem : hb);
-            if (h > 0) slices.push_back({sh, B1, B1 + h, false});
-            if (h < nrem) slices.push_back({sf, B1 + h, nblk_all, false});
-        } else if ((st_int = stream_acquire(1)) != nullptr) {
-            slices.push_back({st_int, B1, nblk_all, true});
+    auto body = [&]() -> int {
+        if (sqk) {
+            // status pair, state words and task tables of the launch: zeroed / uploaded on `s` BEFORE the fork, so that the column solves on
+            // the slices' streams never poll a recycled buffer's old counters
+            static thread_local std::vector<int> tab_host;   // (uploaded asynchronously: must outlive this call)
+            const int64_t nstate = chol_dataflow_state_ints(CHOL_NBP), ntab = chol_dataflow_table_ints(CHOL_NBP);
+            tab_host.assign((size_t)ntab, 0);
+            if (chol_dataflow_fill_tables((int)CHOL_NBP, (int)CHOL_NBP, tab_host.data(), (int)ntab) < 0) { gpx_set_error("chol_panel_factor_piped: task tables"); return GPX_ERR_STATE; }
+            double *buf = nullptr;
+            GPX_TRY(dalloc(&buf, (4 + nstate + ntab) / 2 + 2));
+            scratch.push_back(buf);
+            two = reinterpret_cast<int *>(buf); state = two + 4; tab_dev = state + nstate;
+            GPX_HIP(hipMemsetAsync(two, 0, sizeof(int) * (size_t)(4 + nstate), s));
+            GPX_HIP(hipMemcpyAsync(tab_dev, tab_host.data(), sizeof(int) * (size_t)ntab, hipMemcpyHostToDevice, s));
         }
-    }
-    if (slices.empty()) {   // no rows below -- or no second stream to be had: everything on s
-        int rc = 0;
-        if (nrem > 0 && P) rc = launch_gemm_nt(P + w * ldp, ldp, P, ldp, Csq + w * ld, ld, nrem * TILE, w, kp, -1.0, 1.0, 0, s, prof);
-        if (!rc) rc = chain(nullptr);
-        if (!rc) rc = merge_info(s);
-        if (!rc && nrem > 0) rc = trsm_right_lt(L + (B1 * TILE) * ld, ld, nrem * TILE, L, ld, Dinv, B0, B1, s, prof);
-        if (rc) (void)hipStreamSynchronize(s);
-        retire_buffers(scratch, s);
-        return rc;
-    }
-    std::vector<hipEvent_t> events;
-    std::vector<TopPipe> tops(slices.size());
-    auto run = [&]() -> int {
+        if (nrem > 0) {
+            if (own_streams) {
+                const int64_t h = hb < 0 ? 0 : (hb > nrem ? nrem : hb);
+                if (h > 0) slices.push_back({sh, B1, B1 + h, false});
+                if (h < nrem) slices.push_back({sf, B1 + h, nblk_all, false});
+            } else if ((st_int = stream_acquire(1)) != nullptr) {
+                slices.push_back({st_int, B1, nblk_all, true});
+            }
+        }
+        if (slices.empty()) {   // no rows below -- or no second stream to be had: everything on s
+            if (nrem > 0 && P) GPX_TRY(launch_gemm_nt(P + w * ldp, ldp, P, ldp, Csq + w * ld, ld, nrem * TILE, w, kp, -1.0, 1.0, 0, s, prof));
+            GPX_TRY(chain(nullptr));
+            GPX_TRY(merge_info(s));
+            return nrem > 0 ? trsm_right_lt(L + (B1 * TILE) * ld, ld, nrem * TILE, L, ld, Dinv, B0, B1, s, prof) : 0;
+        }
+        std::vector<TopPipe> tops(slices.size());
         hipEvent_t e0 = nullptr;
-        GPX_HIP(hipEventCreateWithFlags(&e0, hipEventDisableTiming));
-        events.push_back(e0);
+        GPX_TRY(events.make(&e0));
         GPX_HIP(hipEventRecord(e0, s));
         for (size_t i = 0; i < slices.size(); ++i) {
             const Slice &sl = slices[i];
@@ -486,15 +545,14 @@ int chol_panel_factor_piped(double *L, int64_t ld, int64_t nblk_all, int64_t B0,
                                           -1.0, 1.0, 0, sl.st, prof));
             TopPipe &top = tops[i];
             top.stream = sl.st; top.r0 = sl.r0; top.r1 = sl.r1; top.events = &events;
-            if (sqk) { top.sq_state = state; top.sq_rows = B1 - B0; top.sq_nbr = B1 - B0; top.stall = two + 1; }
+            if (sqk) { top.follow_square(state, B1 - B0, 0); top.stall = two + 1; }
             top.next = i + 1 < slices.size() ? &tops[i + 1] : nullptr;
         }
         GPX_TRY(chain(&tops[0]));
         for (const Slice &sl : slices) {
             if (sl.joined) {
                 hipEvent_t e1 = nullptr;
-                GPX_HIP(hipEventCreateWithFlags(&e1, hipEventDisableTiming));
-                events.push_back(e1);
+                GPX_TRY(events.make(&e1));
                 GPX_HIP(hipEventRecord(e1, sl.st));
                 GPX_HIP(hipStreamWaitEvent(s, e1, 0));
             } else {
@@ -503,9 +561,9 @@ int chol_panel_factor_piped(double *L, int64_t ld, int64_t nblk_all, int64_t B0,
         }
         return merge_info(s);
     };
-    const int rc = run();
-    // No host synchronisation here: the caller goes on queueing its trailing updates while the panel is being factored.
-    // The events are still referenced by queued waits, so they retire through a list that later calls sweep once
+    const int rc = body();
+    // No host synchronisation here (unless something failed): the caller goes on queueing its trailing updates while the panel is being
+    // factored.  The events are still referenced by queued waits, so they retire through a list that later calls sweep once
     // hipEventQuery says the GPU has passed them (the launch's state buffer likewise, behind every stream that polls it); the internal
     // stream goes back to the cache (whoever takes it next queues behind the work it still holds).
     std::vector<hipStream_t> behind{s};
@@ -513,7 +571,8 @@ int chol_panel_factor_piped(double *L, int64_t ld, int64_t nblk_all, int64_t B0,
     if (rc) for (hipStream_t q : behind) (void)hipStreamSynchronize(q);
     if (rc && st_int) (void)hipStreamSynchronize(st_int);
     retire_buffers(scratch, behind);
-    retire_events(events);
+    retire_events(events.all);
+    events.all.clear();
     if (st_int) stream_release(st_int, 1);
     return rc;
 }
@@ -552,22 +611,6 @@ __global__ void wait_placed_kernel(const int *placed, int want, unsigned long lo
         __builtin_amdgcn_s_sleep(16);
 }
 
-// holds its stream until the producer launch has counted `want` finished tiles in *ctr.  A time limit that expires (it never should:
-// the producer does not depend on this stream) is reported through the factorisation's STALL word -- a word of its own, not the
-// potrf status: a scheduling stall is not a non-positive pivot, and the caller answers it by refitting on the plain schedule, never
-// with jitter (the consumers behind an expired wait read tiles that are not there: that factor is discarded).
-__global__ void wait_count_kernel(const int *ctr, int want, unsigned long long limit_ticks, int *stall)
-{
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    while (__hip_atomic_load(ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want) {
-        if (__builtin_amdgcn_s_memrealtime() - t0 > limit_ticks) {
-            __hip_atomic_store(stall, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-        }
-        __builtin_amdgcn_s_sleep(8);
-    }
-}
-
 // The trapezoid hand-off and the CU reservation rely on kernels of DIFFERENT streams running at the same time (a one-thread kernel
 // waits for a count another launch produces; blockers sleep until a later launch releases them).  Counter-collecting profilers
 // (rocprofv3 --pmc) run one kernel at a time: the waits would sit out their time limits.  Checked once per process with a 2 ms probe: a
@@ -604,7 +647,7 @@ static bool streams_run_concurrently(hipStream_t a, hipStream_t b)
     if (dalloc(&wd, 2) == 0) {
         int *w = reinterpret_cast<int *>(wd);
         if (hipMemsetAsync(w, 0, 2 * sizeof(int), a) == hipSuccess && hipStreamSynchronize(a) == hipSuccess) {
-            hipLaunchKernelGGL(wait_count_kernel, dim3(1), dim3(1), 0, a, (const int *)w, 1, 200000ull, w + 1);   // <= 2 ms
+            hipLaunchKernelGGL(wait_count_kernel, dim3(1), dim3(1), 0, a, (const int *)w, 1, 200000ull, w + 1);   // <= 2 ms (its own check: a failed probe sets no error text)
             const bool l1 = hipGetLastError() == hipSuccess;
             hipLaunchKernelGGL(set_flag_kernel, dim3(1), dim3(1), 0, b, w, 1);
             const bool l2 = hipGetLastError() == hipSuccess;
@@ -616,29 +659,32 @@ static bool streams_run_concurrently(hipStream_t a, hipStream_t b)
         dfree(wd);
     }
     (void)hipGetLastError();
-    if (getenv("GPX_DEBUG")) fprintf(stderr, "[gpx] concurrent-streams probe (%p waits, %p releases): %d\n", (void *)a, (void *)b, (int)good);
+    if (debug_enabled()) fprintf(stderr, "[gpx] concurrent-streams probe (%p waits, %p releases): %d\n", (void *)a, (void *)b, (int)good);
     g_conc_seen[{a, b}] = good;
     return good;
 }
-
-static int reserve_cus()
+// the blockers sleep until a launch of any of the other three streams releases them
+static bool blockers_may_wait_on(hipStream_t s_blk, hipStream_t s, hipStream_t s_pan, hipStream_t s_top)
 {
-    static const int v = [] { const char *e = getenv("GPX_RESERVE_CUS"); const int r = e ? atoi(e) : 32; return r < 0 ? 0 : (r > 128 ? 128 : r); }();
-    return v;
+    return streams_run_concurrently(s_blk, s) && streams_run_concurrently(s_blk, s_pan) && (!s_top || streams_run_concurrently(s_blk, s_top));
 }
+
+static int reserve_cus() { static const int v = (int)std::min(128L, std::max(0L, env_long("GPX_RESERVE_CUS", 32))); return v; }
 // the reservation starts with the first panel whose bulk launch has fewer 128 x 128 tiles than this (the tail of the factorisation,
 // where the chain, not the bulk, is the critical path)
-static long reserve_below_tiles()
-{
-    static const long v = [] { const char *e = getenv("GPX_RESERVE_TILES"); return e ? atol(e) : 3000L; }();
-    return v;
-}
-
-static int blocker_stream_prio()
-{
-    static const int v = [] { const char *e = getenv("GPX_BLK_PRIO"); return e ? atoi(e) : 1; }();
-    return v;
-}
+static long reserve_below_tiles() { static const long v = env_long("GPX_RESERVE_TILES", 3000); return v; }
+// (high priority: that class has its own hardware queues, which an application's ordinary streams do not crowd)
+static int blocker_stream_prio() { static const int v = (int)env_long("GPX_BLK_PRIO", 1); return v; }
+static int sqk_workers() { static const int v = (int)env_long("GPX_SQK_WORKERS", 32); return v; }
+static bool trap_enabled() { static const bool v = env_long("GPX_TRAP", 1) != 0; return v; }
+// Fits of at most this many block rows (GPX_DFLOW_MAX_BLOCKS, default 0 = none) run as ONE launch of the persistent dataflow kernel
+// (dflow.hip) instead of the multi-stream schedule.  Measured at N = 4096 (32 block rows, round 5, profiles/r05_probe_c2_*): 3.0 ms
+// against 2.36 ms -- with four square launches the multi-stream schedule already pays one launch per panel, and the whole-matrix
+// kernel's workers poll queues in HBM between tasks: not the default at any size; tests/test_dataflow.py runs a fit through it.
+static int64_t dflow_max_blocks() { static const int64_t v = env_long("GPX_DFLOW_MAX_BLOCKS", 0); return v; }
+// Callers without look-ahead streams (SPGP's M x M blocks, gpx_spd_inverse) use the kernel between 9 and 64 block rows (GPX_DFLOW_SMALL=0:
+// never) -- a 2048 x 2048 factorisation is a chain of 16 steps, 1.0 ms there against 2.2 ms of dependent launches.
+static bool dflow_small_enabled() { static const bool v = env_long("GPX_DFLOW_SMALL", 1) != 0; return v; }
 
 // Probes every pair of streams the look-ahead schedule lets wait for each other (cached per pair).  Called by the fit while the
 // streams are still idle -- before the Gram launch is queued on `s`.
@@ -649,194 +695,214 @@ void chol_probe_streams(hipStream_t s, hipStream_t s_pan, hipStream_t s_top)
     if (!concurrent || reserve_cus() == 0) return;
     hipStream_t s_blk = stream_acquire(blocker_stream_prio());   // the cache hands the same stream to chol_factor's own acquire
     if (!s_blk) return;
-    (void)(streams_run_concurrently(s_blk, s) && streams_run_concurrently(s_blk, s_pan) && (!s_top || streams_run_concurrently(s_blk, s_top)));
+    (void)blockers_may_wait_on(s_blk, s, s_pan, s_top);
     stream_release(s_blk, blocker_stream_prio());
 }
 
-// Fits of at most this many block rows (GPX_DFLOW_MAX_BLOCKS, default 0 = none) run as ONE launch of the persistent dataflow kernel
-// (dflow.hip) instead of the multi-stream schedule.  Measured at N = 4096 (32 block rows, round 5, profiles/r05_probe_c2_*): 3.0 ms
-// against 2.36 ms -- with four square launches the multi-stream schedule already pays one launch per panel, and the whole-matrix
-// kernel's workers poll queues in HBM between tasks: not the default at any size; tests/test_dataflow.py runs a fit through it.
-// Callers without look-ahead streams (SPGP's M x M blocks, gpx_spd_inverse) use the kernel up to 64 block rows (GPX_DFLOW_SMALL=0:
-// never): 1.0 ms against 2.2 ms of dependent launches for a 2048 x 2048 block.
-static int64_t dflow_max_blocks()
+namespace {
+// The whole matrix as ONE launch of the dataflow kernel on `s`: take() the kernel's state words and task tables from the pool, launch().
+// The block and the host copy of the tables (uploaded asynchronously) live until the owner has waited for the stream: `tab` is declared
+// in front of `sc`, so it is destroyed after Scratch's wait.
+struct WholeDataflow {
+    std::vector<int> tab;
+    Scratch sc;
+    double *state = nullptr;
+    explicit WholeDataflow(hipStream_t s) : sc(s) {}
+    int take(int64_t nblk) { return sc.take(&state, (chol_dataflow_state_ints(nblk) + chol_dataflow_table_ints(nblk)) / 2 + 2); }
+    int launch(double *L, int64_t ld, int64_t nblk, double *Dinv, double *diagL, int *info_dev)
+    {
+        return launch_chol_dataflow(L, ld, nblk, 0, Dinv, diagL, info_dev, reinterpret_cast<int *>(state), tab, wait_limit_ticks(), sc.s, 0, 0);
+    }
+};
+
+// The small form (dflow_small_enabled).  The kernel's in-kernel waits are bounded; one that expires (it never has) is reported, not
+// retried: the matrix is overwritten by then.  The call synchronises the stream (the kernel's state words are freed here).
+int small_dataflow_factor(double *L, int64_t ld, int64_t nblk, double *Dinv, double *diagL, int *info_dev, hipStream_t s)
 {
-    static const int64_t v = [] { const char *e = getenv("GPX_DFLOW_MAX_BLOCKS"); return e ? atol(e) : 0L; }();
-    return v;
+    WholeDataflow df(s);
+    int st_host[2] = {0, 0};
+    GPX_TRY(df.take(nblk));
+    GPX_HIP(hipMemsetAsync(info_dev + 1, 0, sizeof(int), s));
+    GPX_TRY(df.launch(L, ld, nblk, Dinv, diagL, info_dev));
+    GPX_HIP(hipMemcpyAsync(st_host, info_dev, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
+    GPX_HIP(df.sc.wait_and_free());
+    if (!st_host[1]) return 0;
+    gpx_set_error("factorisation of a %ld-row block: an in-kernel hand-off timed out (GPX_WAIT_LIMIT_MS); GPX_DFLOW_SMALL=0 selects the launch chain",
+                  (long)(nblk * TILE));
+    return GPX_ERR_STATE;
 }
 
-int chol_factor(double *L, int64_t ld, int64_t nblk, double *Dinv, double *diagL, int *info_dev, hipStream_t s,
-                hipStream_t s_pan, Profiler *prof, hipStream_t s_top, const std::function<int()> *after_fork,
-                const std::function<int(int64_t, int64_t, bool, hipStream_t)> *panel_final)
-{
-    if (nblk <= CHOL_NBP || s_pan == nullptr) {
-        if (after_fork) GPX_TRY((*after_fork)());
-        // Callers without look-ahead streams (SPGP's M x M blocks, gpx_spd_inverse): between 9 and 64 block rows the whole matrix goes to
-        // the persistent dataflow kernel (dflow.hip) -- a 2048 x 2048 factorisation is a chain of 16 steps, 1.0 ms there against 2.2 ms
-        // of dependent launches.  Its in-kernel waits are bounded; one that expires (it never has) is reported, not retried: the
-        // matrix is overwritten by then.  The call synchronises the stream (the kernel's state words are freed here).
-        static const int small_df = [] { const char *e = getenv("GPX_DFLOW_SMALL"); return e ? atoi(e) : 1; }();
-        if (nblk > CHOL_NBP && nblk <= 64 && small_df && !g_force_plain && chol_dataflow_supported(nblk)) {
-            double *st = nullptr;
-            GPX_TRY(dalloc(&st, (chol_dataflow_state_ints(nblk) + chol_dataflow_table_ints(nblk)) / 2 + 2));
-            std::vector<int> tab;
-            int st_host[2] = {0, 0};
-            hipError_t e = hipMemsetAsync(info_dev + 1, 0, sizeof(int), s);
-            int rc = e == hipSuccess ? launch_chol_dataflow(L, ld, nblk, 0, Dinv, diagL, info_dev, reinterpret_cast<int *>(st), tab, wait_limit_ticks(), s, 0, 0) : 0;
-            if (e == hipSuccess && !rc) e = hipMemcpyAsync(st_host, info_dev, 2 * sizeof(int), hipMemcpyDeviceToHost, s);
-            const hipError_t e2 = hipStreamSynchronize(s);
-            dfree(st);
-            GPX_TRY(rc);
-            GPX_HIP(e);
-            GPX_HIP(e2);
-            if (st_host[1]) {
-                gpx_set_error("factorisation of a %ld-row block: an in-kernel hand-off timed out (GPX_WAIT_LIMIT_MS); GPX_DFLOW_SMALL=0 selects the launch chain",
-                              (long)(nblk * TILE));
-                return GPX_ERR_STATE;
-            }
-        } else
-        GPX_TRY((nblk <= CHOL_NBP) ? chol_panel_factor(L, ld, nblk, 0, nblk, Dinv, diagL, info_dev, s, prof)
-                                   : chol_rec(L, ld, 0, nblk, Dinv, diagL, info_dev, s, prof));
-        if (panel_final) GPX_TRY((*panel_final)((nblk + CHOL_NBP - 1) / CHOL_NBP - 1, 0, true, nullptr));
-        return 0;
-    }
+// ONE look-ahead factorisation per device at a time takes the schedule with CU blockers, exclusive square launches and kernels that
+// wait for counters of other streams: two of them side by side (two host threads, each with a handle of its own) hold 64 CUs with
+// blockers, compete for whole CUs with their square launches and sit in each other's way for milliseconds (measured: two threads,
+// four fits each at N = 12288 / 16384, 3.3x the serial sum; no stall, but nothing bounds the wait either).  A fit that finds another
+// one in flight on its device takes the plain schedule instead (events only, no reservation): the same tile arithmetic, the GPU is
+// the shared resource either way.
+struct SoloToken {
+    int dev = 0; bool solo = false;
+    static std::atomic<int> &count(int d) { static std::atomic<int> c[64]; return c[d & 63]; }
+    SoloToken() { (void)hipGetDevice(&dev); solo = count(dev).fetch_add(1) == 0; }
+    ~SoloToken() { count(dev).fetch_sub(1); }
+};
+
+// The look-ahead schedule of one factorisation (chol_factor): what its steps share, and the steps themselves in the order the host
+// queues them.  That order -- every launch, event record and stream wait -- is part of the schedule: the runtime binds a stream to a
+// hardware queue at its first use, and the tail of the factorisation is bound by the host's enqueue rate (about 60 launches per panel).
+// The object also owns the way out, however chol_factor returns (the destructor).
+struct Lookahead {
+    double *L;
+    int64_t ld, nblk;
+    double *Dinv, *diagL;
+    int *info_dev;
+    hipStream_t s, s_pan, s_top;   // main (bulk), chain, column solves
+    Profiler *prof;
+    const std::function<int()> *after_fork;
+    const std::function<int(int64_t, int64_t, bool)> *panel_final;
     // outer panel boundaries (block units).  Wider early panels (12..32 blocks) were measured and are slower.
     std::vector<int64_t> Bs{0};
-    while (Bs.back() < nblk) Bs.push_back(std::min<int64_t>(nblk, Bs.back() + CHOL_NBP));
-    const int64_t P = (int64_t)Bs.size() - 1;
-    auto bnd = [&](int64_t p) { return Bs[std::min<int64_t>(p, P)]; };
-    // the whole factorisation as one launch of the dataflow kernel (see dflow_max_blocks): pdf = 0, else pdf = P (never)
-    int64_t pdf = P;
-    if (!g_force_plain && nblk <= dflow_max_blocks() && chol_dataflow_supported(nblk)) pdf = 0;
-    double *dfl_state = nullptr;
-    std::vector<int> dfl_tab;
-    if (pdf < P) {
-        const int64_t nbr = nblk - bnd(pdf);
-        GPX_TRY(dalloc(&dfl_state, (chol_dataflow_state_ints(nbr) + chol_dataflow_table_ints(nbr)) / 2 + 2));
-    }
-    auto run_dataflow = [&](int64_t p_first) -> int {
-        GPX_TRY(launch_chol_dataflow(L, ld, nblk, bnd(p_first), Dinv, diagL, info_dev, reinterpret_cast<int *>(dfl_state), dfl_tab, wait_limit_ticks(), s, 0, 0));
-        if (panel_final) GPX_TRY((*panel_final)(P - 1, 0, true, nullptr));
-        return 0;
-    };
-    // ONE look-ahead factorisation per device at a time takes the schedule with CU blockers, exclusive square launches and kernels that
-    // wait for counters of other streams: two of them side by side (two host threads, each with a handle of its own) hold 64 CUs with
-    // blockers, compete for whole CUs with their square launches and sit in each other's way for milliseconds (measured: two threads,
-    // four fits each at N = 12288 / 16384, 3.3x the serial sum; no stall, but nothing bounds the wait either).  A fit that finds another
-    // one in flight on its device takes the plain schedule instead (events only, no reservation): the same tile arithmetic, the GPU is
-    // the shared resource either way.
-    struct SoloToken {
-        int dev = 0; bool solo = false;
-        static std::atomic<int> &count(int d) { static std::atomic<int> c[64]; return c[d & 63]; }
-        SoloToken() { (void)hipGetDevice(&dev); solo = count(dev).fetch_add(1) == 0; }
-        ~SoloToken() { count(dev).fetch_sub(1); }
-    } token;
-    // (its column solves wait for the kernel's counters from another stream: needs streams that run side by side, like the trapezoid hand-off)
-    const bool concurrent_ok = token.solo && streams_run_concurrently(s_pan, s) && (!s_top || streams_run_concurrently(s_top, s));
-    // Square-kernel mode: the diagonal chain of a panel -- 8 x (leaf, in-square solve,
-    // rank-128 update) = 24 dependent launches -- is ONE small launch of the dataflow kernel on the panel's square (leaf + side workers,
-    // dflow.hip), and the column solves of the rows below wait for its step counter instead of for events.
-    // Used where the chain is the critical path and the chip has empty CUs for it: for the panels whose trailing update has fewer than
-    // GPX_SQK_TILES tiles left (default 1000: the last six panels at N = 16384), and for the first panel
-    // (nothing but the Gram kernel's remainder runs beside it).  GPX_SQK_FROM = p forces it from panel p on (0: everywhere; -1: never).
-    static const int64_t sqk_from = [] { const char *e = getenv("GPX_SQK_FROM"); return e ? atol(e) : (int64_t)-2; }();
-    static const long sqk_tiles = [] { const char *e = getenv("GPX_SQK_TILES"); return e ? atol(e) : 1000L; }();
-    static const int sqk_workers = [] { const char *e = getenv("GPX_SQK_WORKERS"); return e ? atoi(e) : 32; }();
-    const bool sqk_on = !g_force_plain && concurrent_ok && sqk_from != -1 && chol_dataflow_supported(CHOL_NBP);
-    // State words: 1024 ints per panel (chol_dataflow_state_ints(8) = 656), zeroed on the MAIN stream in front of the factorisation's first
-    // event -- the column solves on s_top poll them, and a recycled buffer holds the previous fit's finished counters; the task tables of
-    // a full square and of a shorter last one are uploaded once, behind the states.
-    // The square launch also solves the NEXT diagonal square's rows for its columns (COL tasks of sqk_extra
-    // more workgroups, in step with the chain), so that the update of the next square -- what the next chain waits for -- follows the
-    // launch at once instead of waiting for the column solves of ALL rows below on the third stream; those keep the rows further down,
-    // which only the trailing update needs.  The rows reach the launch through another stream's update: gate word per panel, set behind it.
-    constexpr int64_t SQK_STATE = 1024, SQK_TAB = 256, SQK_GATE = 1008;
-    constexpr int sqk_extra = 32;
+    int64_t P = 0;
+    SoloToken token;
+    bool concurrent = false;   // the streams run side by side and no other look-ahead factorisation is in flight: kernels may wait for kernels
+    bool trap_on = false;      // trapezoid launches with in-kernel hand-off
+    // Square launches (square_launch_wanted).  State words: 1024 ints per panel (chol_dataflow_state_ints(8) = 656), zeroed on the MAIN
+    // stream in front of the factorisation's first event -- the column solves on s_top poll them, and a recycled buffer holds the previous
+    // fit's finished counters; the task tables of a full square and of a shorter last one are uploaded once, behind the states.
+    // The square launch also solves the NEXT diagonal square's rows for its columns (COL tasks of SQK_EXTRA more workgroups, in step
+    // with the chain), so that the update of the next square -- what the next chain waits for -- follows the launch at once instead of
+    // waiting for the column solves of ALL rows below on the third stream; those keep the rows further down, which only the trailing
+    // update needs.  The rows reach the launch through another stream's update: gate word per panel, set behind it.
+    static constexpr int64_t SQK_STATE = 1024, SQK_TAB = 256, SQK_GATE = 1008;
+    static constexpr int SQK_EXTRA = 32;
+    std::vector<char> sqk_use;   // per panel: its chain is a square launch
     double *sqk_buf = nullptr;
-    std::vector<std::vector<int>> sqk_tabs((size_t)P);
+    std::vector<std::vector<int>> sqk_tabs;
     std::vector<int> sqk_tab_host;
-    if (sqk_on) GPX_TRY(dalloc(&sqk_buf, (P * SQK_STATE + P * SQK_TAB) / 2 + 2));
-    auto sqk_state = [&](int64_t pp) { return reinterpret_cast<int *>(sqk_buf) + pp * SQK_STATE; };
-    auto sqk_tab = [&](int64_t pp) { return reinterpret_cast<int *>(sqk_buf) + P * SQK_STATE + pp * SQK_TAB; };
-    auto sqk_gate = [&](int64_t pp) { return sqk_state(pp) + SQK_GATE; };
+    std::vector<TopPipe> tops;   // per panel: the column solves of the rows below its square
+    // info_dev: [0] potrf status, [1] stall, [2] the blockers' stop flag, [3] their placement counter, then CHOL_NBP counters per
+    // panel: finished narrow tiles of its trapezoid launch by tile column
+    int *stall = nullptr, *stop_flag = nullptr, *placed = nullptr, *sig = nullptr;
+    hipStream_t s_blk = nullptr;   // CU reservation: the blockers (nres of them) run on a stream of their own
+    int nres = 0;
+    bool reserved = false, released = false;
+    bool sq_split_prev = false;   // T(p - 1) ran in the split tail form: diagonal square p + 1 has its tiles marked by ev_sqp[p - 1]
+    Events events;
+    hipEvent_t ev0 = nullptr, ev_blk = nullptr;
+    std::vector<hipEvent_t> ev_pf, ev_next, ev_top, ev_tu, ev_first, ev_sqp;
+    // GPX_DEBUG: host clock (us since the factorisation's first launch) at which each panel's launches had been queued -- in the tail the
+    // kernels are so short that the HOST's enqueue rate (60 launches per panel) can become the critical path
+    double host_t0 = 0.0;
+    std::vector<double> host_marks;
+    static double host_now() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+    void mark() { if (debug_enabled()) host_marks.push_back(host_now() - host_t0); }
+    // The way out, after a failure as after the last panel: the blockers leave; the host waits for the column solves' stream, the chain's
+    // and -- where there are blockers -- the main stream and theirs (events must not be destroyed while still referenced by queued
+    // waits, a buffer not go back to the pool while a kernel polls it); then the blocker stream returns to the cache, the main stream is
+    // waited for, and the events and the buffer go.
+    ~Lookahead()
+    {
+        if (debug_enabled()) {
+            fprintf(stderr, "[gpx] host enqueue marks, panel by panel (us): ");
+            for (double m : host_marks) fprintf(stderr, "%.0f ", m);
+            fprintf(stderr, "\n");
+        }
+        release_blockers();
+        if (s_top) (void)hipStreamSynchronize(s_top);
+        (void)hipStreamSynchronize(s_pan);
+        if (s_blk) {
+            (void)hipStreamSynchronize(s);
+            (void)hipStreamSynchronize(s_blk);
+            stream_release(s_blk, blocker_stream_prio());
+        }
+        (void)hipStreamSynchronize(s);
+        events.clear();
+        if (sqk_buf) dfree(sqk_buf);
+    }
+    int64_t bnd(int64_t p) const { return Bs[std::min<int64_t>(p, P)]; }
+    // work of the caller that rides along on the main stream, behind panel p's trailing update (common.h: panel_final)
+    int hook(int64_t p, int64_t slack, bool last) const { return panel_final ? (*panel_final)(p, slack, last) : 0; }
+    // panel q has rows below its square, and a stream to solve them on column by column alongside its chain
+    bool piped(int64_t q) const { return s_top && bnd(q + 1) < nblk; }
+    bool use_sqk(int64_t pp) const { return pp >= 0 && pp < P && sqk_use[(size_t)pp]; }
+    int *sqk_state(int64_t pp) const { return reinterpret_cast<int *>(sqk_buf) + pp * SQK_STATE; }
+    int *sqk_tab(int64_t pp) const { return reinterpret_cast<int *>(sqk_buf) + P * SQK_STATE + pp * SQK_TAB; }
+    int *sqk_gate(int64_t pp) const { return sqk_state(pp) + SQK_GATE; }
     // block rows below panel pp's square that its square launch solves as well (the next square's)
-    auto sqk_below = [&](int64_t pp) -> int64_t { return s_top ? bnd(pp + 2) - bnd(pp + 1) : 0; };
-    auto use_sqk = [&](int64_t pp) {
-        if (!sqk_on || pp < 0 || pp >= P) return false;
-        if (sqk_from >= 0) return pp >= sqk_from;
-        if (pp == 0) return true;
-        const int64_t nrem = nblk - bnd(pp + 1);               // block rows below panel pp: the trailing update that runs beside its chain is panel pp - 1's
-        return nrem * (nrem + 1) / 2 + nrem * CHOL_NBP < sqk_tiles;
-    };
+    int64_t sqk_below(int64_t pp) const { return s_top ? bnd(pp + 2) - bnd(pp + 1) : 0; }
+    // a square launch that solved the rows [B1, B2) itself: the square update needs nothing else -- the column solves of the rows
+    // further down are waited for behind it, in front of the updates that read them
+    bool top_late(int64_t p) const { return piped(p) && use_sqk(p) && sqk_below(p) == bnd(p + 2) - bnd(p + 1) && bnd(p + 2) > bnd(p + 1); }
+    bool q_on_chain(int64_t p) const { return sq_split_prev && piped(p); }   // Q(p) goes on the chain's stream (square_update)
+    // Everything the schedule needs before its first launch, none of it queued on a stream of the fit (the stream probes are cached from
+    // chol_probe_streams): which kernels may wait for kernels, which panels run as square launches and their buffer, every event of
+    // the per-panel hand-offs (created here, not inside the loop: the tail is bound by the host), the blockers' stream.
+    int setup()
+    {
+        while (Bs.back() < nblk) Bs.push_back(std::min<int64_t>(nblk, Bs.back() + CHOL_NBP));
+        P = (int64_t)Bs.size() - 1;
+        stall = info_dev + 1;
+        stop_flag = info_dev + 2;
+        placed = info_dev + 3;
+        sig = info_dev + 4;
+        // (the column solves wait for the kernels' counters from another stream: needs streams that run side by side)
+        concurrent = token.solo && streams_run_concurrently(s_pan, s) && (!s_top || streams_run_concurrently(s_top, s));
+        trap_on = trap_enabled() && concurrent;
+        sqk_use.assign((size_t)P, 0);
+        for (int64_t pp = 0; concurrent && pp < P; ++pp)
+            sqk_use[(size_t)pp] = square_launch_wanted(bnd(pp), bnd(pp + 1) - bnd(pp), nblk - bnd(pp + 1), 1, true);
+        sqk_tabs.resize((size_t)P);
+        tops.resize((size_t)P + 1);
+        if (std::count(sqk_use.begin(), sqk_use.end(), 1)) GPX_TRY(dalloc(&sqk_buf, (P * SQK_STATE + P * SQK_TAB) / 2 + 2));
+        for (std::vector<hipEvent_t> *v : {&ev_pf, &ev_next, &ev_top, &ev_tu, &ev_first, &ev_sqp}) v->resize((size_t)P + 1);
+        GPX_TRY(events.make(&ev0));
+        for (int64_t p = 0; p < P; ++p)
+            for (hipEvent_t *e : {&ev_pf[p], &ev_next[p], &ev_top[p], &ev_tu[p], &ev_first[p], &ev_sqp[p]}) GPX_TRY(events.make(e));
+        GPX_TRY(events.make(&ev_top[P]));
+        // CU reservation (above) for the tail of the factorisation: flag and placement counter live behind the status word
+        nres = concurrent ? reserve_cus() : 0;
+        s_blk = nres ? stream_acquire(blocker_stream_prio()) : nullptr;
+        if (s_blk && !blockers_may_wait_on(s_blk, s, s_pan, s_top)) {   // the blockers would sit in front of launches their release depends on
+            stream_release(s_blk, blocker_stream_prio());
+            s_blk = nullptr;
+        }
+        if (s_blk) GPX_TRY(events.make(&ev_blk));
+        host_t0 = debug_enabled() ? host_now() : 0.0;
+        return 0;
+    }
     // the chain of panel pp's square [Ba, Bb) as one launch on s_pan; its column solves (rows below, stream s_top) per finished step
-    auto sqk_launch = [&](int64_t pp, int64_t Ba, int64_t Bb) -> int {
+    int sqk_launch(int64_t pp, int64_t Ba, int64_t Bb)
+    {
         const int64_t below = sqk_below(pp);
         return launch_chol_dataflow(L, ld, Bb + below, Ba, Dinv, diagL, info_dev, sqk_state(pp), sqk_tabs[(size_t)pp], wait_limit_ticks(), s_pan,
-                                    std::min<int>(sqk_workers, (int)(4 * (Bb - Ba - 1) + 4)), 1, sqk_tab(pp), (int)(Bb - Ba),
-                                    below > 0 ? sqk_extra : 0, sqk_gate(pp));
-    };
-    auto sqk_prepare = [&]() -> int {   // on s, in front of ev0: states zeroed, every square launch's tables uploaded (one copy)
-        if (!sqk_on) return 0;
-        bool any = false;
-        sqk_tab_host.assign((size_t)(P * SQK_TAB), 0);
-        for (int64_t pp = 0; pp < P; ++pp)
-            if (use_sqk(pp)) {
-                any = true;
-                const int rows = (int)(bnd(pp + 1) - bnd(pp)), nbr = rows + (int)sqk_below(pp);
-                if (chol_dataflow_state_ints(nbr) > SQK_GATE || chol_dataflow_fill_tables(nbr, rows, sqk_tab_host.data() + pp * SQK_TAB, (int)SQK_TAB) < 0) {
-                    gpx_set_error("chol_factor: square launch of %d + %d block rows does not fit its state / table slot", rows, nbr - rows);
-                    return GPX_ERR_STATE;
-                }
-            }
-        if (!any) return 0;
-        GPX_HIP(hipMemsetAsync(sqk_buf, 0, sizeof(int) * (size_t)(P * SQK_STATE), s));
-        GPX_HIP(hipMemcpyAsync(sqk_tab(0), sqk_tab_host.data(), sizeof(int) * sqk_tab_host.size(), hipMemcpyHostToDevice, s));
-        return 0;
-    };
-    // the rows below panel pp's square have their update (queued on `on` just now): its square launch may solve them
-    auto sqk_open_gate = [&](int64_t pp, hipStream_t on) {
-        if (use_sqk(pp) && sqk_below(pp) > 0) hipLaunchKernelGGL(set_flag_kernel, dim3(1), dim3(1), 0, on, sqk_gate(pp), 1);
-    };
-    std::vector<hipEvent_t> ev_pf(P), ev_next(P), ev_top(P + 1), ev_tu(P), ev_first(P), ev_sqp(P), top_events;
-    hipEvent_t ev0;
-    GPX_HIP(hipEventCreateWithFlags(&ev0, hipEventDisableTiming));
-    for (int64_t p = 0; p < P; ++p) {
-        GPX_HIP(hipEventCreateWithFlags(&ev_pf[p], hipEventDisableTiming));
-        GPX_HIP(hipEventCreateWithFlags(&ev_next[p], hipEventDisableTiming));
-        GPX_HIP(hipEventCreateWithFlags(&ev_top[p], hipEventDisableTiming));
-        GPX_HIP(hipEventCreateWithFlags(&ev_tu[p], hipEventDisableTiming));
-        GPX_HIP(hipEventCreateWithFlags(&ev_first[p], hipEventDisableTiming));
-        GPX_HIP(hipEventCreateWithFlags(&ev_sqp[p], hipEventDisableTiming));
+                                    std::min<int>(sqk_workers(), (int)(4 * (Bb - Ba - 1) + 4)), 1, sqk_tab(pp), (int)(Bb - Ba),
+                                    below > 0 ? SQK_EXTRA : 0, sqk_gate(pp));
     }
-    GPX_HIP(hipEventCreateWithFlags(&ev_top[P], hipEventDisableTiming));
-    // CU reservation (above) for the tail of the factorisation: flag and placement counter live behind the status word; the
-    // blockers run on a stream of their own
+    // the rows below panel pp's square have their update (queued on `on` just now): its square launch may solve them
+    void sqk_open_gate(int64_t pp, hipStream_t on)
+    {
+        if (use_sqk(pp) && sqk_below(pp) > 0) hipLaunchKernelGGL(set_flag_kernel, dim3(1), dim3(1), 0, on, sqk_gate(pp), 1);
+    }
+    // the column solves of panel q follow its square launch's step counter (top_column waits for the step itself)
+    void follow_square(int64_t q) { tops[(size_t)q].follow_square(sqk_state(q), bnd(q + 1) - bnd(q), sqk_below(q)); }
+    // The blockers leave (the flag is set behind whatever the main stream holds): from the first tail panel that runs as a square
+    // launch, behind the last bulk launch, and on the way out.
+    void release_blockers()
+    {
+        if (!reserved || released) return;
+        hipLaunchKernelGGL(set_flag_kernel, dim3(1), dim3(1), 0, s, stop_flag, 1);
+        released = true;
+    }
+    // The reservation starts in front of panel p's square update, with the first panel whose bulk launch is short (reserve_below_tiles).
+    // (not where the next chain is a square launch already -- small factors, N <= 5120 at the default thresholds: the blockers
+    // would be released again a few lines below, 30 us of memset / placement wait / release on the critical path for nothing)
+    // (the column solves keep their small tiles and share the reserved CUs with the chain: measured better than 224-register
+    // tiles that stay off them, fit 28.9 -> 28.1 ms)
+    // Called where the main stream has just drained (it waits for panel p's chain): the blockers find an empty chip.
     // (the waiting kernel on the chain's stream, its release on the main stream: the order in which the fit first uses its streams --
     // the runtime binds a stream to a hardware queue at its first launch, and another order was measured to cost 5 ms per fit)
-    const bool concurrent = concurrent_ok;
-    int nres = concurrent ? reserve_cus() : 0;
-    // (high priority: that class has its own hardware queues, which an application's ordinary streams do not crowd)
-    const int blk_prio = blocker_stream_prio();
-    hipStream_t s_blk = nres ? stream_acquire(blk_prio) : nullptr;
-    if (s_blk && !(streams_run_concurrently(s_blk, s) && streams_run_concurrently(s_blk, s_pan) && (!s_top || streams_run_concurrently(s_blk, s_top)))) {
-        // the blockers would sit in front of launches their release depends on
-        stream_release(s_blk, blk_prio);
-        s_blk = nullptr;
-        nres = 0;
-    }
-    int *stall = info_dev + 1, *stop_flag = info_dev + 2, *placed = info_dev + 3;   // info_dev: [0] potrf status, [1] stall, then these, then sig
-    static const int trap_env = [] { const char *e = getenv("GPX_TRAP"); return e ? atoi(e) : 1; }();
-    const int trap_on = trap_env && concurrent;
-    int *sig = info_dev + 4;                                   // CHOL_NBP counters per panel: finished narrow tiles of its trapezoid launch by tile column
-    bool reserved = false, released = false;
-    hipEvent_t ev_blk = nullptr;
-    auto release_blockers = [&](hipStream_t on) {
-        if (reserved && !released) { hipLaunchKernelGGL(set_flag_kernel, dim3(1), dim3(1), 0, on, stop_flag, 1); released = true; }
-    };
-    // called where the main stream has just drained (it waits for panel p's chain): the blockers find an empty chip
-    auto reserve_now = [&]() -> int {
-        if (!s_blk || reserved) return 0;
-        GPX_HIP(hipEventCreateWithFlags(&ev_blk, hipEventDisableTiming));
+    int reserve_now(int64_t p)
+    {
+        const int64_t nrem = nblk - bnd(p + 2);
+        if (!s_blk || reserved || nrem <= 0 || nrem * (nrem + 1) / 2 >= reserve_below_tiles() || (sqk_from() < 0 && use_sqk(p + 1))) return 0;
         GPX_HIP(hipMemsetAsync(stop_flag, 0, 2 * sizeof(int), s));
         GPX_HIP(hipEventRecord(ev_blk, s));
         GPX_HIP(hipStreamWaitEvent(s_blk, ev_blk, 0));
@@ -848,312 +914,218 @@ int chol_factor(double *L, int64_t ld, int64_t nblk, double *Dinv, double *diagL
         GPX_HIP(hipGetLastError());
         reserved = true;
         return 0;
-    };
-    // GPX_DEBUG: host clock (us since the factorisation's first launch) at which each panel's launches had been queued -- in the tail the
-    // kernels are so short that the HOST's enqueue rate (60 launches per panel) can become the critical path
-    static const bool debug_host = getenv("GPX_DEBUG") != nullptr;
-    auto host_now = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double host_t0 = debug_host ? host_now() : 0.0;
-    std::vector<double> host_marks;
-    auto run = [&]() -> int {
-        // Per outer panel p the main stream runs, in order:
-        //   update of panel p+1's diagonal square (panel p's rows of that square are solved by then) -> event: the side
-        //   stream starts the next chain;  update of the remaining rows of panel p+1's columns;  bulk SYRK of everything
-        //   right of panel p+1
-        // the side stream runs the diagonal-square chain of panel p+1 (leaf kernels and tiny GEMMs, pure latency)
-        // underneath all of that, and the third stream solves ALL rows below panel p's square column by column alongside
-        // panel p's chain (TopPipe), so that neither a top slice nor a panel TRSM remains on the main stream.
-        if (pdf == 0) {   // the whole factorisation is the dataflow kernel's
-            if (after_fork) GPX_TRY((*after_fork)());
-            return run_dataflow(0);
-        }
+    }
+    // On the main stream, in front of the factorisation's first event: the trapezoid launches' counters and the square launches' state
+    // words zeroed, every square launch's tables uploaded (one copy), the first panel's gate opened (its columns are complete when the
+    // factorisation is called); then the chain's stream and the column solves' are forked off.
+    int prepare()
+    {
         if (trap_on) GPX_HIP(hipMemsetAsync(sig, 0, sizeof(int) * (size_t)(P * CHOL_NBP), s));
-        GPX_TRY(sqk_prepare());
-        sqk_open_gate(0, s);   // (the first panel's columns are complete when the factorisation is called)
+        if (sqk_buf) {
+            sqk_tab_host.assign((size_t)(P * SQK_TAB), 0);
+            for (int64_t pp = 0; pp < P; ++pp) {
+                const int rows = (int)(bnd(pp + 1) - bnd(pp)), nbr = rows + (int)sqk_below(pp);
+                if (use_sqk(pp) && (chol_dataflow_state_ints(nbr) > SQK_GATE || chol_dataflow_fill_tables(nbr, rows, sqk_tab_host.data() + pp * SQK_TAB, (int)SQK_TAB) < 0)) {
+                    gpx_set_error("chol_factor: square launch of %d + %d block rows does not fit its state / table slot", rows, nbr - rows);
+                    return GPX_ERR_STATE;
+                }
+            }
+            GPX_HIP(hipMemsetAsync(sqk_buf, 0, sizeof(int) * (size_t)(P * SQK_STATE), s));
+            GPX_HIP(hipMemcpyAsync(sqk_tab(0), sqk_tab_host.data(), sizeof(int) * sqk_tab_host.size(), hipMemcpyHostToDevice, s));
+        }
+        sqk_open_gate(0, s);
         GPX_HIP(hipEventRecord(ev0, s));
         GPX_HIP(hipStreamWaitEvent(s_pan, ev0, 0));
-        std::vector<TopPipe> tops(P + 1);
-        auto piped = [&](int64_t q) { return s_top && bnd(q + 1) < nblk; };
         for (int64_t q = 0; q < P; ++q) {
             tops[q].stream = piped(q) ? s_top : nullptr;
             tops[q].r0 = bnd(q + 1) + (use_sqk(q) ? sqk_below(q) : 0);   // (a square launch solves the next square's rows itself)
             tops[q].r1 = nblk;
-            tops[q].events = &top_events;
+            tops[q].events = &events;
         }
         if (piped(0)) GPX_HIP(hipStreamWaitEvent(s_top, ev0, 0));
-        // main-stream work of the caller that only the later panels need (the rest of the Gram matrix): queued now, it runs
-        // underneath the first panel's chain
-        // (the first step is queued ahead of that launch; its leaf is NOT exclusive: the Gram kernel, released on the main stream at
-        // the same moment, usually wins the race for the places, and an exclusive leaf would then wait for the whole launch to drain)
+        return 0;
+    }
+    // chain(0) and S(0).  after_fork -- main-stream work of the caller that only the later panels need (the rest of the Gram matrix) --
+    // is queued behind the square launch, or behind the chain's first step, and runs underneath the first panel's chain.
+    // (the first step is queued ahead of that launch; its leaf is NOT exclusive: the Gram kernel, released on the main stream at
+    // the same moment, usually wins the race for the places, and an exclusive leaf would then wait for the whole launch to drain)
+    int first_panel()
+    {
         if (use_sqk(0)) {
             GPX_TRY(sqk_launch(0, 0, bnd(1)));
-            tops[0].sq_state = sqk_state(0);
-            tops[0].sq_rows = bnd(1);
-            tops[0].sq_nbr = bnd(1) + sqk_below(0);
+            follow_square(0);
             if (after_fork) GPX_TRY((*after_fork)());
             if (tops[0].stream && tops[0].r1 > tops[0].r0)
                 for (int64_t j = 0; j < bnd(1); ++j) GPX_TRY(top_column(L, ld, 0, j, Dinv, &tops[0], prof));
         } else {
-        GPX_TRY(chol_square_steps(L, ld, 0, bnd(1), 0, 1, Dinv, diagL, info_dev, s_pan, prof, &tops[0], 0));
-        if (after_fork) GPX_TRY((*after_fork)());
-        GPX_TRY(chol_square_steps(L, ld, 0, bnd(1), 1, bnd(1), Dinv, diagL, info_dev, s_pan, prof, &tops[0], 2));   // nothing else fills the chip yet: every leaf finds an empty CU
+            GPX_TRY(chol_square_steps(L, ld, 0, bnd(1), 0, 1, Dinv, diagL, info_dev, s_pan, prof, &tops[0], 0));
+            if (after_fork) GPX_TRY((*after_fork)());
+            GPX_TRY(chol_square_steps(L, ld, 0, bnd(1), 1, bnd(1), Dinv, diagL, info_dev, s_pan, prof, &tops[0], 2));   // nothing else fills the chip yet: every leaf finds an empty CU
         }
         if (piped(0)) GPX_HIP(hipEventRecord(ev_top[0], s_top));
         GPX_HIP(hipEventRecord(ev_pf[0], s_pan));
-        // Tail of the factorisation (short trailing updates, issued as separate launches): T(p-1) computes the tiles of diagonal square
-        // p + 1 FIRST, as a launch of their own, and marks them (ev_sqp); the update of that square with panel p -- what chain(p + 1)
-        // waits for -- then runs on the CHAIN's stream right behind chain(p) instead of on the main stream behind all of T(p-1), which
-        // runs beside chain(p) at a fraction of the chip (65 CUs belong to the square launch) and used to end 60-240 us after it.
-        bool sq_split_prev = false;
-        for (int64_t p = 0; p < P; ++p) {
-            const int64_t B0 = bnd(p), B1 = bnd(p + 1), B2 = bnd(p + 2);
-            GPX_HIP(hipStreamWaitEvent(s, ev_pf[p], 0));   // diagonal square of panel p is factored
-            if (B1 >= nblk) {
-                if (panel_final) GPX_TRY((*panel_final)(p, 0, true, nullptr));
-                break;
-            }
-            if (s_blk && !reserved && B2 < nblk && (nblk - B2) * (nblk - B2 + 1) / 2 < reserve_below_tiles() && !(sqk_from < 0 && use_sqk(p + 1))) {
-                // (not where the next chain is a square launch already -- small factors, N <= 5120 at the default thresholds: the blockers
-                // would be released again a few lines below, 30 us of memset / placement wait / release on the critical path for nothing)
-                // (the column solves keep their small tiles and share the reserved CUs with the chain: measured better than 224-register
-                // tiles that stay off them, fit 28.9 -> 28.1 ms)
-                GPX_TRY(reserve_now());
-            }
-            const int64_t K = (B1 - B0) * TILE;
-            // (1) only rows [B1,B2) of panel p and the diagonal square of panel p+1 gate the next chain: update that
-            //     square before anything else so that the side stream starts early
-            // (a square launch that solved the rows [B1, B2) itself: the square update below needs nothing else -- the column solves of
-            // the rows further down are waited for behind it, in front of the updates that read them)
-            const bool top_late = piped(p) && use_sqk(p) && sqk_below(p) == B2 - B1 && B2 > B1;
-            if (piped(p) && !top_late) GPX_HIP(hipStreamWaitEvent(s, ev_top[p], 0));          // solved column by column alongside the chain
-            else if (!piped(p)) GPX_TRY(trsm_right_lt(L + (B1 * TILE) * ld, ld, (nblk - B1) * TILE, L, ld, Dinv, B0, B1, s, prof));
-            const double *Ptop = L + (B1 * TILE) * ld + B0 * TILE;         // panel p, rows [B1,B2)
-            const bool q_on_chain = sq_split_prev && piped(p);
-            if (q_on_chain) {
-                // (chain(p) precedes on s_pan; the rows [B1, B2) of panel p: a square launch solved them itself, else the column stream)
-                GPX_HIP(hipStreamWaitEvent(s_pan, ev_sqp[p - 1], 0));
-                if (!top_late) GPX_HIP(hipStreamWaitEvent(s_pan, ev_top[p], 0));
-            }
-            // (lower 32 x 32 tiles only: nothing reads the square above its diagonal -- the bulk launches never updated it there)
-            GPX_TRY(launch_gemm_nt(Ptop, ld, Ptop, ld, L + (B1 * TILE) * ld + B1 * TILE, ld, (B2 - B1) * TILE, (B2 - B1) * TILE, K,
-                                   -1.0, 1.0, 1, q_on_chain ? s_pan : s, prof));
-            if (!q_on_chain) GPX_HIP(hipEventRecord(ev_next[p], s));
-            // from the first tail panel that runs as a square launch the chain no longer lives on the reserved CUs (a square launch brings
-            // its own: one workgroup per CU): the blockers would only keep 32 CUs from the short bulk launches beside it
-            if (sqk_from < 0 && use_sqk(p + 1)) release_blockers(s);
-            // host enqueue order: first step of the chain, then the main stream's bulk work, then the rest of the chain,
-            // so neither stream starves while the other's launches are being queued
-            {
-                if (!q_on_chain) GPX_HIP(hipStreamWaitEvent(s_pan, ev_next[p], 0));
-                // (exclusive only where a free CU is certain -- reserved CUs, or no bulk launch left: next to the main stream's launch, which
-                // becomes ready at the same moment, an exclusive leaf that loses the race for a place waits for a whole CU to drain)
-                if (use_sqk(p + 1)) GPX_TRY(sqk_launch(p + 1, B1, B2));     // the whole chain of panel p + 1, now
-                else {
-                    GPX_TRY(chol_square_steps(L, ld, B1, B2, B1, B1 + 1, Dinv, diagL, info_dev, s_pan, prof, nullptr, (reserved || B2 >= nblk) ? 1 : 0));
-                    if (piped(p + 1)) GPX_HIP(hipEventRecord(ev_first[p], s_pan));
-                }
-            }
-            if (top_late) GPX_HIP(hipStreamWaitEvent(s, ev_top[p], 0));
-            sq_split_prev = false;
-            if (B2 < nblk) {
-                // (2) the rest of panel p+1's columns, then the bulk SYRK
-                const double *Pr = L + (B2 * TILE) * ld + B0 * TILE;       // panel p, rows >= B2
-                // One trapezoid launch for the next panel's columns AND the bulk SYRK (gemm.hip, launch_syrk_trap_signal): its narrow
-                // tiles come first and are counted in sig[p]; the next panel's column solves wait for the count, not for a launch
-                // boundary.  Small trailing matrices keep the two launches.
-                int merged = GPX_ERR_STATE;
-                const int64_t nrem = nblk - B2;
-                constexpr long trap_min = 1024;   // (smaller trailing matrices: 100 tiles measured, no difference)
-                if (trap_on && nrem * (nrem + 1) / 2 >= trap_min && B2 - B1 == CHOL_NBP)
-                    merged = launch_syrk_trap_signal(Pr, ld, Ptop, ld, L + (B2 * TILE) * ld + B1 * TILE, ld, nrem * TILE, (B2 - B1) * TILE, K, -1.0, 1.0,
-                                                     sig + p * CHOL_NBP, s, prof);
-                if (merged != 0 && merged != GPX_ERR_STATE) return merged;
-                // (beside a square kernel the next panel's column solves wait for this launch and the chip is nearly empty: 64 x 64 tiles
-                // finish in a third of a 128 x 128 tile's time -- GPX_SQK_NARROW_SMALL)
-                if (merged != 0)
-                    GPX_TRY(launch_gemm_nt(Pr, ld, Ptop, ld, L + (B2 * TILE) * ld + B1 * TILE, ld, (nblk - B2) * TILE, (B2 - B1) * TILE,
-                                           K, -1.0, 1.0, 0, s, prof, 0, 0, (use_sqk(p + 1) && p + 1 > 0) ? 1 : 0));
-                sqk_open_gate(p + 1, s);   // panel p+1's columns have their update: its square launch may solve the rows below its square
-                if (piped(p + 1)) {   // panel p+1's rows below its square are complete: its column solves may start (first column now)
-                    if (merged == 0) {
-                        // every column solve waits for its own column's narrow tiles (top_column).  Handing the count over as an event
-                        // from a stream of its own was measured too: one more cross-stream edge per panel, fit +1.4 ms.
-                        tops[p + 1].colsig = sig + p * CHOL_NBP;
-                        tops[p + 1].colwant = (int)nrem;
-                        tops[p + 1].stall = stall;
-                    } else {
-                        GPX_HIP(hipEventRecord(ev_tu[p], s));
-                        GPX_HIP(hipStreamWaitEvent(s_top, ev_tu[p], 0));
-                    }
-                    if (use_sqk(p + 1)) {   // (top_column waits for the step itself)
-                        tops[p + 1].sq_state = sqk_state(p + 1);
-                        tops[p + 1].sq_rows = B2 - B1;
-                        tops[p + 1].sq_nbr = B2 - B1 + sqk_below(p + 1);
-                    }
-                    else GPX_HIP(hipStreamWaitEvent(s_top, ev_first[p], 0));
-                    GPX_TRY(top_column(L, ld, B1, B1, Dinv, &tops[p + 1], prof));
-                }
-                // (measured: this short bulk launch on 64 x 64 tiles beside a square launch -- no difference)
-                const int64_t B3 = bnd(p + 3);
-                if (merged != 0 && p + 2 < P && B3 > B2) {
-                    // the tiles of diagonal square p + 2 first and marked, then the rows below them (trapezoid: the square's columns in
-                    // full, then the triangle): the same tiles with the same arithmetic as the one launch below
-                    GPX_TRY(launch_gemm_nt(Pr, ld, Pr, ld, L + (B2 * TILE) * ld + B2 * TILE, ld, (B3 - B2) * TILE, (B3 - B2) * TILE, K, -1.0, 1.0, 1, s, prof));
-                    GPX_HIP(hipEventRecord(ev_sqp[p], s));
-                    sq_split_prev = true;
-                    if (B3 < nblk)
-                        GPX_TRY(launch_gemm_nt(Pr + ((B3 - B2) * TILE) * ld, ld, Pr, ld, L + (B3 * TILE) * ld + B2 * TILE, ld, (nblk - B3) * TILE,
-                                               (nblk - B2) * TILE, K, -1.0, 1.0, 1, s, prof));
-                } else if (merged != 0)
-                    GPX_TRY(launch_gemm_nt(Pr, ld, Pr, ld, L + (B2 * TILE) * ld + B2 * TILE, ld, (nblk - B2) * TILE,
-                                           (nblk - B2) * TILE, K, -1.0, 1.0, 1, s, prof));
-                // once the remaining bulk launches no longer fill the chip the reservation has nothing left to protect
-                if (bnd(p + 3) >= nblk) release_blockers(s);   // the last bulk launch is queued
-            }
-            // work of the caller that rides along on the main stream, behind this panel's trailing update
-            if (panel_final) GPX_TRY((*panel_final)(p, (nblk - std::min(B2, nblk) + CHOL_NBP - 1) / CHOL_NBP, false, nullptr));
-            if (use_sqk(p + 1)) {
-                // the chain runs already (one launch); the column solves of the rows below follow its step counter
-                if (tops[p + 1].stream && tops[p + 1].r1 > tops[p + 1].r0)
-                    for (int64_t j = B1 + 1; j < B2; ++j) GPX_TRY(top_column(L, ld, B1, j, Dinv, &tops[p + 1], prof));
-            } else
-            GPX_TRY(chol_square_steps(L, ld, B1, B2, B1 + 1, B2, Dinv, diagL, info_dev, s_pan, prof, &tops[p + 1], (reserved || bnd(p + 3) >= nblk) ? 2 : 0));   // reserved CUs, or (last panels) a nearly empty chip: every leaf finds an empty CU
-            if (piped(p + 1)) GPX_HIP(hipEventRecord(ev_top[p + 1], s_top));
-            GPX_HIP(hipEventRecord(ev_pf[p + 1], s_pan));
-            if (debug_host) host_marks.push_back(host_now() - host_t0);
-        }
         return 0;
-    };
-    const int rc = run();
-    if (debug_host) {
-        fprintf(stderr, "[gpx] host enqueue marks, panel by panel (us): ");
-        for (double m : host_marks) fprintf(stderr, "%.0f ", m);
-        fprintf(stderr, "\n");
     }
-    release_blockers(s);
-    if (s_top) (void)hipStreamSynchronize(s_top);
-    (void)hipStreamSynchronize(s_pan);   // events must not be destroyed while still referenced by queued waits
-    if (s_blk) { (void)hipStreamSynchronize(s); (void)hipStreamSynchronize(s_blk); stream_release(s_blk, blk_prio); }
-    if (ev_blk) (void)hipEventDestroy(ev_blk);
-    (void)hipStreamSynchronize(s);
-    (void)hipEventDestroy(ev0);
-    for (int64_t p = 0; p < P; ++p) { (void)hipEventDestroy(ev_pf[p]); (void)hipEventDestroy(ev_next[p]); (void)hipEventDestroy(ev_top[p]); (void)hipEventDestroy(ev_tu[p]); (void)hipEventDestroy(ev_first[p]); (void)hipEventDestroy(ev_sqp[p]); }
-    (void)hipEventDestroy(ev_top[P]);
-    for (hipEvent_t e : top_events) (void)hipEventDestroy(e);
-    if (dfl_state) dfree(dfl_state);
-    if (sqk_buf) dfree(sqk_buf);
-    return rc;
-}
-
-// ------------------------------------------------------------------------------------------------
-// small reductions / fills
-// ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double wave_sum(double s)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    return s;
-}
-
-// logdet K = 2 sum_i log L_ii over the n real rows; single block, fixed order -> deterministic
-__global__ __launch_bounds__(256) void logdet_kernel(const double *diagL, long n, double *out)
-{
-    __shared__ double ws[4];
-    double s = 0.0;
-    for (long i = threadIdx.x; i < n; i += 256) s += log(diagL[i]);
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) *out = 2.0 * (ws[0] + ws[1] + ws[2] + ws[3]);
-}
-
-int launch_logdet(const double *diagL, int64_t n, double *out_dev, hipStream_t s)
-{
-    hipLaunchKernelGGL(logdet_kernel, dim3(1), dim3(256), 0, s, diagL, (long)n, out_dev);
-    GPX_HIP(hipGetLastError());
-    return 0;
-}
-
-// mean_m = sum_n Z[m][n] y[n];  var_m = (v+vt) - sum_n Z[m][n]^2 ; one wave per row, 16-byte loads
-__global__ __launch_bounds__(256) void predict_reduce_kernel(const double *__restrict__ Z, long ldz, long m, long npad,
-                                                            const double *__restrict__ y, double vplusvt,
-                                                            double *__restrict__ mean, double *__restrict__ var, const double *__restrict__ kdiag)
-{
-    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= m) return;
-    const int lane = threadIdx.x & 63;
-    const double *zr = Z + row * ldz;
-    double sm = 0.0, sq = 0.0;
-    for (long c = 2 * lane; c < npad; c += 128) {
-        const v2d z = *reinterpret_cast<const v2d *>(zr + c);
-        const v2d yy = *reinterpret_cast<const v2d *>(y + c);
-        sm = fma(z.x, yy.x, sm);
-        sm = fma(z.y, yy.y, sm);
-        sq = fma(z.x, z.x, sq);
-        sq = fma(z.y, z.y, sq);
+    // Q(p): the update of diagonal square p + 1 with panel p's rows [B1, B2).  Only those rows and that square gate the next chain: the
+    // square is updated before anything else so that the side stream starts early.  Without a column stream the rows below panel p are
+    // solved here first, in one recursive TRSM on the main stream.
+    // Which stream: the main one -- except in the tail of the factorisation (short trailing updates, issued as separate launches), where
+    // T(p-1) computed the tiles of diagonal square p + 1 FIRST, as a launch of their own, and marked them (ev_sqp): Q(p) -- what
+    // chain(p + 1) waits for -- then runs on the CHAIN's stream right behind chain(p) instead of on the main stream behind all of T(p-1),
+    // which runs beside chain(p) at a fraction of the chip (65 CUs belong to the square launch) and used to end 60-240 us after it.
+    int square_update(int64_t p)
+    {
+        const int64_t B0 = bnd(p), B1 = bnd(p + 1), B2 = bnd(p + 2);
+        const bool late = top_late(p), on_chain = q_on_chain(p);
+        if (piped(p) && !late) GPX_HIP(hipStreamWaitEvent(s, ev_top[p], 0));          // solved column by column alongside the chain
+        else if (!piped(p)) GPX_TRY(trsm_right_lt(L + (B1 * TILE) * ld, ld, (nblk - B1) * TILE, L, ld, Dinv, B0, B1, s, prof));
+        const double *Ptop = L + (B1 * TILE) * ld + B0 * TILE;         // panel p, rows [B1,B2)
+        if (on_chain) {
+            // (chain(p) precedes on s_pan; the rows [B1, B2) of panel p: a square launch solved them itself, else the column stream)
+            GPX_HIP(hipStreamWaitEvent(s_pan, ev_sqp[p - 1], 0));
+            if (!late) GPX_HIP(hipStreamWaitEvent(s_pan, ev_top[p], 0));
+        }
+        // (lower 32 x 32 tiles only: nothing reads the square above its diagonal -- the bulk launches never updated it there)
+        GPX_TRY(launch_gemm_nt(Ptop, ld, Ptop, ld, L + (B1 * TILE) * ld + B1 * TILE, ld, (B2 - B1) * TILE, (B2 - B1) * TILE, (B1 - B0) * TILE,
+                               -1.0, 1.0, 1, on_chain ? s_pan : s, prof));
+        if (!on_chain) GPX_HIP(hipEventRecord(ev_next[p], s));
+        // from the first tail panel that runs as a square launch the chain no longer lives on the reserved CUs (a square launch brings
+        // its own: one workgroup per CU): the blockers would only keep 32 CUs from the short bulk launches beside it
+        if (sqk_from() < 0 && use_sqk(p + 1)) release_blockers();
+        return 0;
     }
-    sm = wave_sum(sm);
-    sq = wave_sum(sq);
-    if (lane == 0) {
-        mean[row] = sm;
-        var[row] = (kdiag ? kdiag[row] : vplusvt) - sq;   // kdiag: the operator's own prior variances (gpx_predict_kv)
+    // The chain of panel q = p + 1 starts behind Q(p): the whole of it where it is a square launch, else its first step.
+    // Host enqueue order: first step of the chain, then the main stream's bulk work (trailing_update), then the rest of the chain
+    // (finish_chain), so neither stream starves while the other's launches are being queued.
+    // (the first leaf is exclusive only where a free CU is certain -- reserved CUs, or no bulk launch left: next to the main stream's
+    // launch, which becomes ready at the same moment, an exclusive leaf that loses the race for a place waits for a whole CU to drain)
+    int start_chain(int64_t q)
+    {
+        const int64_t p = q - 1, B1 = bnd(q), B2 = bnd(q + 1);
+        if (!q_on_chain(p)) GPX_HIP(hipStreamWaitEvent(s_pan, ev_next[p], 0));
+        if (use_sqk(q)) return sqk_launch(q, B1, B2);
+        GPX_TRY(chol_square_steps(L, ld, B1, B2, B1, B1 + 1, Dinv, diagL, info_dev, s_pan, prof, nullptr, (reserved || B2 >= nblk) ? 1 : 0));
+        if (piped(q)) GPX_HIP(hipEventRecord(ev_first[p], s_pan));
+        return 0;
     }
-}
-
-int launch_predict_reduce(const double *Z, int64_t ldz, int64_t m, int64_t npad, const double *y, double vplusvt,
-                          double *mean, double *var, hipStream_t s, Profiler *prof, const double *kdiag)
-{
-    if (m <= 0) return 0;
-    ProfScope ps(prof, s, GPX_K_REDUCE, 8.0 * (double)m * (double)npad);
-    hipLaunchKernelGGL(predict_reduce_kernel, dim3((unsigned)((m + 3) / 4)), dim3(256), 0, s, Z, (long)ldz, (long)m,
-                       (long)npad, y, vplusvt, mean, var, kdiag);
-    GPX_HIP(hipGetLastError());
-    return 0;
-}
-
-__global__ __launch_bounds__(256) void set_identity_kernel(double *Z, long ld, long n)
-{
-    const long row = blockIdx.x;
-    const long c = ((long)blockIdx.y * 256 + threadIdx.x) * 2;
-    if (c >= n) return;
-    v2d o;
-    o.x = (c == row) ? 1.0 : 0.0;
-    o.y = (c + 1 == row) ? 1.0 : 0.0;
-    *reinterpret_cast<v2d *>(Z + row * ld + c) = o;
-}
-
-int launch_set_identity(double *Z, int64_t ld, int64_t n, hipStream_t s)
-{
-    if (n <= 0) return 0;
-    dim3 grid((unsigned)n, (unsigned)((n / 2 + 255) / 256));
-    hipLaunchKernelGGL(set_identity_kernel, grid, dim3(256), 0, s, Z, (long)ld, (long)n);
-    GPX_HIP(hipGetLastError());
-    return 0;
-}
-
-// copy the strict lower triangle onto the upper one (A[j][i] = A[i][j], i > j), 32x32 LDS transposes
-__global__ __launch_bounds__(256) void symmetrize_lower_kernel(double *A, long ld, long n)
-{
-    __shared__ double tile[32][33];
-    const int bi = blockIdx.y, bj = blockIdx.x;
-    if (bj > bi) return;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
-    for (int r = ty; r < 32; r += 8) {
-        const long i = (long)bi * 32 + r, j = (long)bj * 32 + tx;
-        tile[r][tx] = (i < n && j < n) ? A[i * ld + j] : 0.0;
+    // T(p) on the main stream: the rest of panel p + 1's columns (the narrow part), then the bulk SYRK of everything right of them; and
+    // S(p + 1)'s first column, which may start as soon as the narrow part is through.  Three forms:
+    //  - ONE trapezoid launch for the narrow part AND the bulk (gemm.hip, launch_syrk_trap_signal): its narrow tiles come first and are
+    //    counted in sig[p]; every column solve of the next panel waits for its own column's count (top_column), not for a launch boundary.
+    //    Handing the count over as an event from a stream of its own was measured too: one more cross-stream edge per panel, fit +1.4 ms.
+    //  - small trailing matrices (fewer than trap_min tiles; 100 tiles measured, no difference) keep the two launches, narrow and bulk.
+    //    Beside a square launch the next panel's column solves wait for the narrow launch and the chip is nearly empty: it then runs on
+    //    64 x 64 tiles, which finish in a third of a 128 x 128 tile's time (the short bulk launch on such tiles: measured, no difference).
+    //  - the split tail form of the bulk: the tiles of diagonal square p + 2 first and marked (ev_sqp: see square_update), then the rows
+    //    below them (trapezoid: the square's columns in full, then the triangle) -- the same tiles with the same arithmetic as the one launch.
+    int trailing_update(int64_t p)
+    {
+        const int64_t B0 = bnd(p), B1 = bnd(p + 1), B2 = bnd(p + 2), B3 = bnd(p + 3), K = (B1 - B0) * TILE, nrem = nblk - B2;
+        if (top_late(p)) GPX_HIP(hipStreamWaitEvent(s, ev_top[p], 0));
+        sq_split_prev = false;
+        if (nrem <= 0) return 0;
+        const double *Ptop = L + (B1 * TILE) * ld + B0 * TILE;     // panel p, rows [B1,B2)
+        const double *Pr = L + (B2 * TILE) * ld + B0 * TILE;       // panel p, rows >= B2
+        int merged = GPX_ERR_STATE;
+        constexpr long trap_min = 1024;
+        if (trap_on && nrem * (nrem + 1) / 2 >= trap_min && B2 - B1 == CHOL_NBP)
+            merged = launch_syrk_trap_signal(Pr, ld, Ptop, ld, L + (B2 * TILE) * ld + B1 * TILE, ld, nrem * TILE, (B2 - B1) * TILE, K, -1.0, 1.0,
+                                             sig + p * CHOL_NBP, s, prof);
+        if (merged != 0 && merged != GPX_ERR_STATE) return merged;
+        if (merged != 0)
+            GPX_TRY(launch_gemm_nt(Pr, ld, Ptop, ld, L + (B2 * TILE) * ld + B1 * TILE, ld, nrem * TILE, (B2 - B1) * TILE,
+                                   K, -1.0, 1.0, 0, s, prof, 0, 0, (use_sqk(p + 1) && p + 1 > 0) ? 1 : 0));
+        sqk_open_gate(p + 1, s);   // panel p+1's columns have their update: its square launch may solve the rows below its square
+        if (piped(p + 1)) {   // panel p+1's rows below its square are complete: its column solves may start (first column now)
+            TopPipe &top = tops[(size_t)p + 1];
+            if (merged == 0) {
+                top.colsig = sig + p * CHOL_NBP;
+                top.colwant = (int)nrem;
+                top.stall = stall;
+            } else {
+                GPX_HIP(hipEventRecord(ev_tu[p], s));
+                GPX_HIP(hipStreamWaitEvent(s_top, ev_tu[p], 0));
+            }
+            if (use_sqk(p + 1)) follow_square(p + 1);
+            else GPX_HIP(hipStreamWaitEvent(s_top, ev_first[p], 0));
+            GPX_TRY(top_column(L, ld, B1, B1, Dinv, &top, prof));
+        }
+        if (merged != 0 && p + 2 < P && B3 > B2) {
+            GPX_TRY(launch_gemm_nt(Pr, ld, Pr, ld, L + (B2 * TILE) * ld + B2 * TILE, ld, (B3 - B2) * TILE, (B3 - B2) * TILE, K, -1.0, 1.0, 1, s, prof));
+            GPX_HIP(hipEventRecord(ev_sqp[p], s));
+            sq_split_prev = true;
+            if (B3 < nblk)
+                GPX_TRY(launch_gemm_nt(Pr + ((B3 - B2) * TILE) * ld, ld, Pr, ld, L + (B3 * TILE) * ld + B2 * TILE, ld, (nblk - B3) * TILE,
+                                       nrem * TILE, K, -1.0, 1.0, 1, s, prof));
+        } else if (merged != 0)
+            GPX_TRY(launch_gemm_nt(Pr, ld, Pr, ld, L + (B2 * TILE) * ld + B2 * TILE, ld, nrem * TILE, nrem * TILE, K, -1.0, 1.0, 1, s, prof));
+        // once the remaining bulk launches no longer fill the chip the reservation has nothing left to protect
+        if (B3 >= nblk) release_blockers();   // the last bulk launch is queued
+        return 0;
     }
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-        const long j = (long)bj * 32 + r, i = (long)bi * 32 + tx;   // write A[j][i] = tile[i-local][j-local]
-        if (i < n && j < n && i > j) A[j * ld + i] = tile[tx][r];
+    // The rest of chain(q) and of S(q), q = p + 1, behind the main stream's launches of this panel: a square launch runs already (one
+    // launch) and the column solves of the rows below follow its step counter; else the chain's remaining steps, each with its column
+    // solve, every leaf exclusive where it finds an empty CU -- reserved CUs, or (last panels) a nearly empty chip.
+    int finish_chain(int64_t q)
+    {
+        const int64_t B1 = bnd(q), B2 = bnd(q + 1);
+        const TopPipe &top = tops[(size_t)q];
+        if (!use_sqk(q))
+            GPX_TRY(chol_square_steps(L, ld, B1, B2, B1 + 1, B2, Dinv, diagL, info_dev, s_pan, prof, &top, (reserved || bnd(q + 2) >= nblk) ? 2 : 0));
+        else if (top.stream && top.r1 > top.r0)
+            for (int64_t j = B1 + 1; j < B2; ++j) GPX_TRY(top_column(L, ld, B1, j, Dinv, &top, prof));
+        if (piped(q)) GPX_HIP(hipEventRecord(ev_top[q], s_top));
+        GPX_HIP(hipEventRecord(ev_pf[q], s_pan));
+        return 0;
     }
-}
+};
+}   // namespace
 
-int launch_symmetrize_lower(double *A, int64_t ld, int64_t n, hipStream_t s)
+// The factorisation (the picture: DESIGN.md, section 5.1).  Per outer panel p the main stream runs, in order: update of panel p+1's diagonal
+// square (panel p's rows of that square are solved by then) -> event: the side stream starts the next chain;  update of the remaining rows
+// of panel p+1's columns;  bulk SYRK of everything right of panel p+1.  The side stream runs the diagonal-square chain of panel p+1 (leaf
+// kernels and tiny GEMMs, pure latency) underneath all of that, and the third stream solves ALL rows below panel p's square column by
+// column alongside panel p's chain (TopPipe), so that neither a top slice nor a panel TRSM remains on the main stream.
+int chol_factor(double *L, int64_t ld, int64_t nblk, double *Dinv, double *diagL, int *info_dev, hipStream_t s,
+                hipStream_t s_pan, Profiler *prof, hipStream_t s_top, const std::function<int()> *after_fork,
+                const std::function<int(int64_t, int64_t, bool)> *panel_final)
 {
-    if (n <= 0) return 0;
-    const unsigned nb = (unsigned)((n + 31) / 32);
-    hipLaunchKernelGGL(symmetrize_lower_kernel, dim3(nb, nb), dim3(256), 0, s, A, (long)ld, (long)n);
-    GPX_HIP(hipGetLastError());
+    const int64_t last = (nblk + CHOL_NBP - 1) / CHOL_NBP - 1;   // the last outer panel
+    const bool lookahead = nblk > CHOL_NBP && s_pan != nullptr;
+    const bool whole = !g_force_plain && chol_dataflow_supported(nblk);   // the whole factorisation may be the dataflow kernel's
+    if (!lookahead) {   // everything on s
+        if (after_fork) GPX_TRY((*after_fork)());
+        if (whole && nblk > CHOL_NBP && nblk <= 64 && dflow_small_enabled())
+            GPX_TRY(small_dataflow_factor(L, ld, nblk, Dinv, diagL, info_dev, s));
+        else
+            GPX_TRY((nblk <= CHOL_NBP) ? chol_panel_factor(L, ld, nblk, 0, nblk, Dinv, diagL, info_dev, s, prof)
+                                       : chol_rec(L, ld, 0, nblk, Dinv, diagL, info_dev, s, prof));
+        if (panel_final) GPX_TRY((*panel_final)(last, 0, true));
+        return 0;
+    }
+    if (whole && nblk <= dflow_max_blocks()) {
+        SoloToken token;       // (a look-ahead fit on another thread sees this one in flight)
+        WholeDataflow df(s);   // (waits for s on the way out, behind whatever the caller's hooks queue)
+        GPX_TRY(df.take(nblk));
+        if (after_fork) GPX_TRY((*after_fork)());
+        GPX_TRY(df.launch(L, ld, nblk, Dinv, diagL, info_dev));
+        if (panel_final) GPX_TRY((*panel_final)(last, 0, true));
+        return 0;
+    }
+    Lookahead la{L, ld, nblk, Dinv, diagL, info_dev, s, s_pan, s_top, prof, after_fork, panel_final};
+    GPX_TRY(la.setup());
+    GPX_TRY(la.prepare());
+    GPX_TRY(la.first_panel());
+    for (int64_t p = 0; p <= last; ++p) {
+        GPX_HIP(hipStreamWaitEvent(s, la.ev_pf[p], 0));   // diagonal square of panel p is factored
+        if (p == last) return la.hook(p, 0, true);
+        GPX_TRY(la.reserve_now(p));
+        GPX_TRY(la.square_update(p));
+        GPX_TRY(la.start_chain(p + 1));
+        GPX_TRY(la.trailing_update(p));
+        GPX_TRY(la.hook(p, (nblk - la.bnd(p + 2) + CHOL_NBP - 1) / CHOL_NBP, false));
+        GPX_TRY(la.finish_chain(p + 1));
+        la.mark();
+    }
     return 0;
 }
