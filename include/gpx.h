@@ -268,6 +268,13 @@ int gpx_emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t l
 int gpx_emu_rebuild(const int8_t *R, int64_t ldr, int64_t sr, int nmod, const int *sa, const int *sb, double *C, int64_t ldc, int64_t rows,
                     int64_t cols);
 int gpx_emu_i8_gemm(const int8_t *A, const int8_t *B, int64_t rows, int64_t cols, int64_t K, int nmod, int8_t *R);
+/* The left-looking form of estimate_many's solve alone (tests): Zs [rows, ldz] <- Z L^-T against the handle's factor (5 slabs of 1024
+ * columns or more), device buffers, rows a multiple of 128, ldz >= the padded size and even.  bound [rows] (device): a bound on the
+ * magnitude of every entry of the solved row, known before the solve; the residues of a solved slab are split once with the scale it
+ * gives.  Z is consumed: afterwards its slab p holds Z_p minus the slab's updates.  tile_rows > 0: a smaller row tile of the residue
+ * image.  *status_out != 0: an entry exceeded four times its bound (or a bound was negative or not finite): Zs is not to be used.
+ * A row of Z that holds a NaN or an Inf gives NaN from its first affected slab on and raises no status.  Synchronous. */
+int gpx_emu_trsm_left(gpx_handle *h, double *Z, int64_t ldz, int64_t rows, const double *bound, double *Zs, int64_t tile_rows, int *status_out);
 int gpx_bench_hbm(int64_t bytes, int iters, double *write_gbs, double *copy_gbs);
 /* mode 0: MFMA f64 only, 1: VALU v_fma_f64 only, 2: half the waves each; `blocks` workgroups of 4 waves.
  * cycles_per_inst from s_memtime, clock_ghz from s_memtime / s_memrealtime (the clock held under load). */

@@ -302,6 +302,49 @@ bool emu_enabled(int64_t K);
 int emu_moduli();                        // GPX_EMU_MODULI (default 16, 2 .. 16)
 int emu_scale_bits(int64_t K, int L);    // alpha + beta: the largest s with K 2^s < P / 2
 
+// The left-looking form of the many-row solve (tsolve.hip, trsm_right_lt_slabs): every solved slab is split ONCE into a persistent
+// residue image, with a row scale derived from a bound on the whole solved row that the caller knows at entry; slab p then takes one
+// emulated update of depth 1024 p.  plan sizes the image for `rows` rows of a solve over `slabs` slabs (tile_rows > 0: a smaller row
+// tile, for tests), alloc takes it into the caller's Scratch, begin derives a chunk's scales from its bounds and clears the status word
+// (device; non-zero after the chunk: a bound was wrong, the chunk's result is to be discarded).
+struct EmuLeft {
+    int8_t *img = nullptr, *rb = nullptr, *rr = nullptr;
+    int *sig = nullptr;
+    double *bound = nullptr;
+    int L = 0, abits = 0, bbits = 0;
+    int64_t lda = 0, rows_pad = 0, rt = 0, tiles = 0, img_bytes = 0, b_bytes = 0, r_bytes = 0;
+    int *status() const { return sig + rows_pad + 1024; }
+};
+bool emu_left_enabled();                 // GPX_EMU_LEFT (default 1)
+void emu_left_plan(EmuLeft &w, int64_t rows, int64_t slabs, int64_t tile_rows = 0);
+int emu_left_alloc(EmuLeft &w, Scratch &sc);
+int emu_left_begin(const EmuLeft &w, const double *bound, int64_t rows, hipStream_t s);
+int emu_left_split(const EmuLeft &w, const double *X, int64_t ldx, int64_t rows, int64_t q, hipStream_t s);
+int emu_left_update(const EmuLeft &w, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t rows, int64_t cols, int64_t K, hipStream_t s,
+                    Profiler *prof);
+// Zs <- Z L^-T over all slabs of the solver's factor, left-looking from slab 4 on (slabs 0 .. 3 as trsm_right_lt_squares, their updates
+// emulated through emu where emu_enabled(K) holds: with the default GPX_EMU_MIN_K none of them); w: planned and allocated for at least
+// these rows, begun with their bounds
+int trsm_right_lt_slabs(double *Z, double *Zs, int64_t ldz, int64_t rows, const TriSolver *ts, hipStream_t s, Profiler *prof, const GemmReduce *red,
+                        const EmuLeft &w, const EmuWork *emu = nullptr);
+int launch_row_bounds(const double *kdiag, double v, int64_t m, double *bound, hipStream_t s);   // bound_i = sqrt(kdiag_i), or sqrt(v) without kdiag
+// The two fall-back decisions of the route, apart from the image that does not fit (emu_left_alloc).  Which solves take it: the caller bounds
+// every solved row, the many-row solver runs (not the few-vector one) against prepared squares over five slabs or more, and the switches
+// allow it -- the factor's shape and the kind of call alone, never the number of rows beyond `few`.
+bool emu_left_route(bool bounded, bool few, bool ready, int64_t slabs);
+// One chunk under the guard: pass(left, &status) fills, solves and synchronises the chunk, left-looking first where use_left holds, and
+// leaves the status word it read in status; a word that is raised (a bound did not hold) sends the chunk through pass(false) once more.
+template <class Pass> int emu_left_guarded(bool use_left, Pass pass)
+{
+    for (int p = 0; p < 2; ++p) {
+        const bool left = use_left && p == 0;
+        int status = 0;
+        GPX_TRY(pass(left, &status));
+        if (!left || !status) break;
+    }
+    return 0;
+}
+
 // ---- launchers of propagate.hip ----------------------------------------------------------------
 int launch_nll_grad(const double *Kinv, int64_t ld, int64_t n, int64_t npad, int d, const double *alpha, const double *xw,
                     double v, double *partial, double *out_dev, int *dmax_used, hipStream_t s, Profiler *prof);
@@ -360,9 +403,12 @@ struct RowSolve {
     double *Zs = nullptr;   // [chunk, npad]
     EmuWork ew;
     const EmuWork *emu = nullptr;
+    EmuLeft left;           // the left-looking order's residue image and the chunk's row bounds (device), when the caller bounds its rows
+    bool use_left = false;
     explicit RowSolve(hipStream_t s) : sc(s) {}
 };
-int row_solve_begin(gpx_handle *h, int64_t m, RowSolve &rs);
+// bounded: the caller will give a bound on every solved row (left = true in row_solve_run after emu_left_begin with rs.left.bound filled)
+int row_solve_begin(gpx_handle *h, int64_t m, RowSolve &rs, bool bounded = false);
 // Zs[0 : mp) <- Z[0 : mp) L^-T (mc real rows, mp = mc rounded up to the tile); red: the fused row sums of tsolve.hip (many rows only)
-int row_solve_run(gpx_handle *h, const RowSolve &rs, int64_t mc, int64_t mp, const GemmReduce *red);
+int row_solve_run(gpx_handle *h, const RowSolve &rs, int64_t mc, int64_t mp, const GemmReduce *red, bool left = false);
 #pragma GCC visibility pop

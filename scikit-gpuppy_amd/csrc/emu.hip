@@ -28,6 +28,7 @@ typedef int v16i __attribute__((ext_vector_type(16)));
 
 constexpr int EMU_MAXL = 16;
 constexpr int EMU_BT = 256;   // int8 block tile: 256 x 256, 2 x 4 waves of 128 x 64 (4 x 2 MFMAs of 32 x 32), two waves per SIMD
+constexpr int EMU_SLAB = 1024; // columns of one slab of the left-looking solve (tsolve.hip: PB)
 constexpr int EMU_BK = 128;   // k bytes per LDS stage (one 128-byte row per operand row, the fp64 kernel's image geometry)
 
 // pairwise coprime (256 = 2^8, 255 = 3 5 17, 253 = 11 23, 247 = 13 19, the rest prime); the first L are used
@@ -103,6 +104,25 @@ int emu_scale_bits(int64_t K, int L)
     return (int)floor(log2p - 1.0 - log2((double)K) - 1e-9);
 }
 
+// the L residues of four consecutive integers a' (|a'| <= 2^56, exact in fp64) as one packed word per plane: a' - p q with q = rint(a' / p)
+// off by at most one (the fma is exact: the result is a small integer), then made symmetric
+static __device__ __forceinline__ void emu_store_residues(const double (&a)[4], int L, int8_t *__restrict__ out, long plane)
+{
+#pragma unroll
+    for (int l = 0; l < EMU_MAXL; ++l) {
+        if (l >= L) continue;
+        const double p = (double)emu_p[l], pinv = 1.0 / p, h = 0.5 * p;
+        unsigned packed = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            double r = fma(-rint(a[e] * pinv), p, a[e]);
+            r = r > h ? r - p : (r < -h ? r + p : r);      // [-p/2, p/2]; 256 wraps to -128 in the byte (same residue)
+            packed |= ((unsigned)(int)r & 0xffu) << (8 * e);
+        }
+        *reinterpret_cast<unsigned *>(out + l * plane) = packed;
+    }
+}
+
 // ---- split: one workgroup per row of X [rows, K] (fp64, ldx) -> residue planes res[l][row][K] (int8) and the row's scale exponent ----
 // rows >= rows_real are padding: zero residues.  The integer a' = rint(x 2^sig) (|a'| <= 2^bits) is exact in fp64; its residue mod p is
 // a' - p q with q = rint(a' / p) off by at most one (the fma is exact: the result is a small integer), then made symmetric.
@@ -141,20 +161,68 @@ __global__ __launch_bounds__(256) void emu_split_kernel(const double *__restrict
         const v2d v0 = *reinterpret_cast<const v2d *>(x + c), v1 = *reinterpret_cast<const v2d *>(x + c + 2);
         double a[4] = {rint(ldexp(v0.x, s)), rint(ldexp(v0.y, s)), rint(ldexp(v1.x, s)), rint(ldexp(v1.y, s))};
         if (bad) a[0] = a[1] = a[2] = a[3] = 0.0;
-#pragma unroll
-        for (int l = 0; l < EMU_MAXL; ++l) {
-            if (l >= L) continue;
-            const double p = (double)emu_p[l], pinv = 1.0 / p, h = 0.5 * p;
-            unsigned packed = 0;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                double r = fma(-rint(a[e] * pinv), p, a[e]);
-                r = r > h ? r - p : (r < -h ? r + p : r);      // [-p/2, p/2]; 256 wraps to -128 in the byte (same residue)
-                packed |= ((unsigned)(int)r & 0xffu) << (8 * e);
-            }
-            *reinterpret_cast<unsigned *>(out + l * plane + c) = packed;
-        }
+        emu_store_residues(a, L, out + c, plane);
     }
+}
+
+// ---- split with a given scale (the left-looking solve, tsolve.hip): the rows of one solved slab of `width` columns into the persistent
+// residue image res[l][row][ldr] at the slab's column offset, with the scale sig[row] that emu_scale_from_bound_kernel derived from the
+// row's bound before the row was known.  An entry with |x 2^s| > 2^bits (the bound was wrong) raises *status and is stored as 0: it never
+// wraps silently; a NaN or an Inf marks the row (sig = EMU_NONFINITE, sticky: every later product of the row is NaN) and raises nothing.
+__global__ __launch_bounds__(256) void emu_split_fixed_kernel(const double *__restrict__ X, long ldx, long rows_real, int width, int bits, int L,
+                                                              int8_t *__restrict__ res, long ldr, long plane, int *sig, int *status)
+{
+    const long row = blockIdx.x;
+    const int t = threadIdx.x;
+    int8_t *out = res + row * ldr;
+    if (row >= rows_real) {
+        for (int c = 4 * t; c < width; c += 1024)
+            for (int l = 0; l < L; ++l) *reinterpret_cast<int *>(out + l * plane + c) = 0;
+        return;
+    }
+    const double *x = X + row * ldx;
+    const int s0 = sig[row];
+    const bool dead = s0 == EMU_NONFINITE;
+    const int s = dead ? 0 : s0;
+    const double lim = ldexp(1.0, bits);
+    int bad = 0, over = 0;
+    for (int c = 4 * t; c < width; c += 1024) {
+        const v2d v0 = *reinterpret_cast<const v2d *>(x + c), v1 = *reinterpret_cast<const v2d *>(x + c + 2);
+        const double v[4] = {v0.x, v0.y, v1.x, v1.y};
+        double a[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            a[e] = rint(ldexp(v[e], s));
+            if (!isfinite(v[e])) { bad = 1; a[e] = 0.0; }
+            else if (fabs(a[e]) > lim) { over = 1; a[e] = 0.0; }
+            if (dead) a[e] = 0.0;
+        }
+        emu_store_residues(a, L, out + c, plane);
+    }
+    bad = __syncthreads_or(bad);
+    over = __syncthreads_or(over);
+    if (t == 0) {
+        if (bad) sig[row] = EMU_NONFINITE;
+        else if (over && !dead) atomicMax(status, 1);
+    }
+}
+
+// sig[i] = bits - 1 - ilogb(2 bound_i): |x| <= bound_i scales below 2^(bits - 1), one bit of headroom for the rounding of the solve that
+// the bound was derived without.  bound 0 (padding rows, an all-zero row): a scale at which every double of magnitude 2^(bits - 1000) or
+// more exceeds 2^bits and raises *status; a smaller non-zero one (down to about 2^-1000, below which x 2^1000 rounds to 0 unseen) is held
+// exactly or rounded to an integer, which is harmless next to a bound of 0.  A bound that is negative, NaN or Inf is no bound: *status is
+// raised and the caller takes the other route.
+constexpr int EMU_ZERO_BOUND_SCALE = 1000;
+__global__ __launch_bounds__(256) void emu_scale_from_bound_kernel(const double *__restrict__ bound, long rows, long rows_pad, int bits,
+                                                                   int *__restrict__ sig, int *status)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= rows_pad) return;
+    const double b = i < rows ? bound[i] : 0.0;
+    int s = 0;
+    if (!(b >= 0.0) || isinf(b)) atomicMax(status, 1);
+    else s = b == 0.0 ? EMU_ZERO_BOUND_SCALE : bits - 2 - ilogb(b);
+    sig[i] = s;
 }
 
 // ---- products: R_l = (A_l B_l^T) mod p_l, int8 in, int32 accumulate, one byte out -----------------------------------------------------
@@ -163,9 +231,11 @@ __global__ __launch_bounds__(256) void emu_split_kernel(const double *__restrict
 // LDS image, staging and swizzle as gemm_tile.h: per stage [256][128 B] of A then of B, filled by LDS-DMA (16 B per lane, 8 rows per
 // wave-instruction), granule index XOR (row >> 1) & 7 on the source address and on the fragment reads; a 32 x 32 x 32 fragment is one
 // ds_read_b128 per lane (row lane & 31, k-bytes 16 (lane >> 5) .. +15 of a 32-byte slice), conflict-free under that swizzle.
-// A, B: planes of [tm 256][K] and [tn 256][K] bytes (lda = ldb = K); R: planes of [tm 256][ldr] bytes.
+// A, B: planes of [tm 256][lda] and [tn 256][K] bytes (B packed: ldb = K; lda >= K is the row stride of A's planes, so that a product
+// reads columns 0 .. K of a wider residue image: a panel's byte offsets stay below 256 lda < 2^25, its 64-bit base comes from the
+// host's row tile and from z, by); R: planes of [tm 256][ldr] bytes.
 __global__ __launch_bounds__(512, 1) void emu_i8_gemm_kernel(const int8_t *__restrict__ A, const int8_t *__restrict__ B, long sa, long sb, int K,
-                                                             int8_t *__restrict__ R, long ldr, long sr, int tm, int tn)
+                                                             int8_t *__restrict__ R, long ldr, long sr, int tm, int tn, int lda)
 {
     __shared__ __attribute__((aligned(1024))) int8_t smem[2 * 2 * EMU_BT * EMU_BK];   // 128 KiB: two stages of A and B
     constexpr int STAGE = 2 * EMU_BT * EMU_BK;
@@ -181,13 +251,14 @@ __global__ __launch_bounds__(512, 1) void emu_i8_gemm_kernel(const int8_t *__res
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
     const int wr = wave >> 2, wc = wave & 3;
     const int drow = lane >> 3;
-    const char *Abase = reinterpret_cast<const char *>(A + z * sa + (long)by * EMU_BT * K);
+    const char *Abase = reinterpret_cast<const char *>(A + z * sa + (long)by * EMU_BT * lda);
     const char *Bbase = reinterpret_cast<const char *>(B + z * sb + (long)bx * EMU_BT * K);
-    unsigned off[4];   // instruction u of this wave covers rows 8 (wave + 8 u) .. +7 of either operand's 256-row panel
+    unsigned offa[4], offb[4];   // instruction u of this wave covers rows 8 (wave + 8 u) .. +7 of either operand's 256-row panel
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int row = 8 * (wave + 8 * u) + drow;
-        off[u] = (unsigned)((long)row * K + 16 * ((lane & 7) ^ ((row >> 1) & 7)));
+        offa[u] = (unsigned)((long)row * lda + 16 * ((lane & 7) ^ ((row >> 1) & 7)));
+        offb[u] = (unsigned)((long)row * K + 16 * ((lane & 7) ^ ((row >> 1) & 7)));
     }
     const unsigned lds_base = (unsigned)(unsigned long)(__attribute__((address_space(3))) int8_t *)smem;
 #define EMU_DMA_ONE(SBASE, VOFF, LDSBYTES) \
@@ -197,9 +268,9 @@ __global__ __launch_bounds__(512, 1) void emu_i8_gemm_kernel(const int8_t *__res
         const char *ak_ = gpx_uniform_ptr(Abase + (long)(KT) * EMU_BK);                                                     \
         const char *bk_ = gpx_uniform_ptr(Bbase + (long)(KT) * EMU_BK);                                                     \
         _Pragma("unroll") for (int u_ = 0; u_ < 4; ++u_)                                                                    \
-            EMU_DMA_ONE(ak_, off[u_], __builtin_amdgcn_readfirstlane(lds_base + (unsigned)((BUF) * STAGE + (wave + 8 * u_) * 1024)))  \
+            EMU_DMA_ONE(ak_, offa[u_], __builtin_amdgcn_readfirstlane(lds_base + (unsigned)((BUF) * STAGE + (wave + 8 * u_) * 1024)))  \
         _Pragma("unroll") for (int u_ = 0; u_ < 4; ++u_)                                                                    \
-            EMU_DMA_ONE(bk_, off[u_], __builtin_amdgcn_readfirstlane(lds_base + (unsigned)((BUF) * STAGE + EMU_BT * EMU_BK + (wave + 8 * u_) * 1024))) \
+            EMU_DMA_ONE(bk_, offb[u_], __builtin_amdgcn_readfirstlane(lds_base + (unsigned)((BUF) * STAGE + EMU_BT * EMU_BK + (wave + 8 * u_) * 1024))) \
     }
     const int nk = K / EMU_BK;
     EMU_DMA_STAGE(0, 0)
@@ -408,13 +479,112 @@ int emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t ldb, 
                                (long)(ncp * K), sgb);
             const int tm = (int)(nrp / EMU_BT), tn = (int)(ncp / EMU_BT);
             hipLaunchKernelGGL(emu_i8_gemm_kernel, dim3((unsigned)(tm * tn * L)), dim3(512), 0, s, (const int8_t *)ra, (const int8_t *)rb,
-                               (long)(nrp * K), (long)(ncp * K), (int)K, rr, (long)ncp, (long)(nrp * ncp), tm, tn);
+                               (long)(nrp * K), (long)(ncp * K), (int)K, rr, (long)ncp, (long)(nrp * ncp), tm, tn, (int)K);
             const long thr = (long)nr * ((nc + 3) / 4);
             hipLaunchKernelGGL(emu_rebuild_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, (const int8_t *)rr, (long)ncp,
                                (long)(nrp * ncp), L, emu_crt.t[L], (const int *)sga, (const int *)sgb, C + r0 * ldc + c0, (long)ldc, (long)nr, (long)nc);
         }
         GPX_HIP(hipGetLastError());
     }
+    return 0;
+}
+
+// ---- the left-looking solve's share (tsolve.hip, trsm_right_lt_slabs): a persistent residue image of the solved slabs -------------------
+// Slab p of the solve takes ONE update of depth K = 1024 p against every solved slab before it.  Each solved slab is split once, with the
+// scale its row's bound gave at entry, into the image [row tile][l][rt][lda] (lda = 1024 (P - 1) columns; a row tile's planes span at most
+// 2 GiB, its base is formed here in 64 bits); every later update reads columns 0 .. K of it through the int8 kernel's row stride.
+// abits / bbits come from the deepest K of the call, so one image serves every depth.
+bool emu_left_enabled()
+{
+    static const int on = [] { const char *e = getenv("GPX_EMU_LEFT"); return e ? atoi(e) : 1; }();
+    return on != 0;
+}
+
+bool emu_left_route(bool bounded, bool few, bool ready, int64_t slabs)
+{
+    return bounded && !few && ready && slabs >= 5 && emu_left_enabled() && emu_enabled(4 * EMU_SLAB);
+}
+
+void emu_left_plan(EmuLeft &w, int64_t rows, int64_t slabs, int64_t tile_rows)
+{
+    w.L = emu_moduli();
+    w.lda = EMU_SLAB * (slabs - 1);
+    const int bits = emu_scale_bits(w.lda, w.L);
+    w.abits = bits - bits / 2;
+    w.bbits = bits / 2;
+    w.rows_pad = round_up(rows, EMU_BT);
+    int64_t cap = emu_cap(w.lda, w.L);
+    if (tile_rows > 0) cap = std::min(cap, round_up(tile_rows, EMU_BT));
+    w.tiles = (w.rows_pad + cap - 1) / cap;
+    w.rt = round_up((w.rows_pad + w.tiles - 1) / w.tiles, EMU_BT);   // equal row tiles: 2 x 8192 rows at N = M = 16384, not 8704 + 7680
+    w.img_bytes = w.tiles * w.rt * w.lda * w.L;
+    w.b_bytes = EMU_SLAB * w.lda * w.L;
+    w.r_bytes = w.rt * EMU_SLAB * w.L;
+}
+
+int emu_left_alloc(EmuLeft &w, Scratch &sc)
+{
+    int rc = sc.take(&w.img, w.img_bytes);
+    if (!rc) rc = sc.take(&w.rb, w.b_bytes);
+    if (!rc) rc = sc.take(&w.rr, w.r_bytes);
+    if (!rc) rc = sc.take(&w.sig, w.rows_pad + EMU_SLAB + 1);   // row scales, the B tile's row scales, the status word
+    if (!rc) rc = sc.take(&w.bound, w.rows_pad);                // the chunk's row bounds (callers that derive them on the device)
+    if (rc) {   // no room: what was taken goes back at once (nothing is queued on it), the caller keeps its other route
+        for (void *p : {(void *)w.img, (void *)w.rb, (void *)w.rr, (void *)w.sig, (void *)w.bound})
+            if (p) dfree(sc.release((double *)p));
+        w.img = w.rb = w.rr = nullptr;
+        w.sig = nullptr;
+        w.bound = nullptr;
+    }
+    return rc;
+}
+
+// the row scales of one chunk from its bounds (device, `rows` of them; the padding rows take bound 0), status cleared
+int emu_left_begin(const EmuLeft &w, const double *bound, int64_t rows, hipStream_t s)
+{
+    if (rows > w.rows_pad) { gpx_set_error("emu_left_begin: %ld rows in a workspace of %ld", (long)rows, (long)w.rows_pad); return GPX_ERR_STATE; }
+    GPX_HIP(hipMemsetAsync(w.status(), 0, sizeof(int), s));
+    hipLaunchKernelGGL(emu_scale_from_bound_kernel, dim3((unsigned)((w.rows_pad + 255) / 256)), dim3(256), 0, s, bound, (long)rows, (long)w.rows_pad,
+                       w.abits, w.sig, w.status());
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// solved slab q (X: its first column, `rows` rows, 1024 columns) into the image
+int emu_left_split(const EmuLeft &w, const double *X, int64_t ldx, int64_t rows, int64_t q, hipStream_t s)
+{
+    for (int64_t t = 0, r0 = 0; r0 < rows; ++t, r0 += w.rt) {
+        const int64_t nr = std::min(w.rt, rows - r0), nrp = round_up(nr, EMU_BT);
+        hipLaunchKernelGGL(emu_split_fixed_kernel, dim3((unsigned)nrp), dim3(256), 0, s, X + r0 * ldx, (long)ldx, (long)nr, EMU_SLAB, w.abits, w.L,
+                           w.img + t * w.rt * w.lda * w.L + q * EMU_SLAB, (long)w.lda, (long)(w.rt * w.lda), w.sig + r0, w.status());
+    }
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// C[rows, cols] -= Zs[:, 0:K) B[cols, K]^T with Zs read from the image (K = 1024 p, cols <= 1024): split B, then per row tile one int8
+// launch and one rebuild
+int emu_left_update(const EmuLeft &w, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t rows, int64_t cols, int64_t K, hipStream_t s,
+                    Profiler *prof)
+{
+    if (K <= 0 || K > w.lda || K % EMU_SLAB || cols <= 0 || cols > EMU_SLAB || rows > w.rows_pad) {
+        gpx_set_error("emu_left_update: %ld x %ld x %ld outside the image", (long)rows, (long)cols, (long)K);
+        return GPX_ERR_STATE;
+    }
+    ProfScope ps(prof, s, GPX_K_GEMM_EMU, 2.0 * (double)rows * (double)cols * (double)K);
+    const int64_t ncp = round_up(cols, EMU_BT);
+    int *sgb = w.sig + w.rows_pad;
+    hipLaunchKernelGGL(emu_split_kernel, dim3((unsigned)ncp), dim3(256), 0, s, B, (long)ldb, (long)cols, (int)K, w.bbits, w.L, w.rb, (long)(ncp * K), sgb);
+    for (int64_t t = 0, r0 = 0; r0 < rows; ++t, r0 += w.rt) {
+        const int64_t nr = std::min(w.rt, rows - r0), nrp = round_up(nr, EMU_BT);
+        const int tm = (int)(nrp / EMU_BT), tn = (int)(ncp / EMU_BT);
+        hipLaunchKernelGGL(emu_i8_gemm_kernel, dim3((unsigned)(tm * tn * w.L)), dim3(512), 0, s, (const int8_t *)(w.img + t * w.rt * w.lda * w.L),
+                           (const int8_t *)w.rb, (long)(w.rt * w.lda), (long)(ncp * K), (int)K, w.rr, (long)ncp, (long)(nrp * ncp), tm, tn, (int)w.lda);
+        const long thr = (long)nr * ((cols + 3) / 4);
+        hipLaunchKernelGGL(emu_rebuild_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, (const int8_t *)w.rr, (long)ncp, (long)(nrp * ncp), w.L,
+                           emu_crt.t[w.L], (const int *)(w.sig + r0), (const int *)sgb, C + r0 * ldc, (long)ldc, (long)nr, (long)cols);
+    }
+    GPX_HIP(hipGetLastError());
     return 0;
 }
 
@@ -465,7 +635,7 @@ extern "C" int gpx_emu_i8_gemm(const int8_t *A, const int8_t *B, int64_t rows, i
     }
     const int tm = (int)(rows / EMU_BT), tn = (int)(cols / EMU_BT);
     hipLaunchKernelGGL(emu_i8_gemm_kernel, dim3((unsigned)(tm * tn * nmod)), dim3(512), 0, 0, A, B, (long)(rows * K), (long)(cols * K), (int)K, R,
-                       (long)cols, (long)(rows * cols), tm, tn);
+                       (long)cols, (long)(rows * cols), tm, tn, (int)K);
     GPX_HIP(hipGetLastError());
     GPX_HIP(hipStreamSynchronize(0));
     return 0;
@@ -503,7 +673,7 @@ extern "C" int gpx_bench_emu_i8(int64_t rows, int64_t cols, int64_t K, int nmod,
     for (int it = -1; it < iters && e == hipSuccess; ++it) {   // it = -1: warm-up
         if (it == 0) e = hipEventRecord(e0, 0);
         hipLaunchKernelGGL(emu_i8_gemm_kernel, dim3((unsigned)(tm * tn * nmod)), dim3(512), 0, 0, (const int8_t *)wa, (const int8_t *)wb,
-                           (long)(rows * K), (long)(cols * K), (int)K, wr, (long)cols, (long)(rows * cols), tm, tn);
+                           (long)(rows * K), (long)(cols * K), (int)K, wr, (long)cols, (long)(rows * cols), tm, tn, (int)K);
         if (e == hipSuccess) e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipEventRecord(e1, 0);

@@ -1,5 +1,7 @@
 // predict.hip -- the C-ABI of libgpx (include/gpx.h), part 2: everything that solves against the factor after a fit -- the
 // many-row solve behind estimate_many, the few-vector solves, K^-1 and its row panels.
+#include <stdio.h>
+#include <stdlib.h>
 #include <algorithm>
 #include <initializer_list>
 
@@ -15,7 +17,7 @@ int ensure_Z(gpx_handle *h, int64_t rows)
 }
 
 // ---- predict (RowSolve: common.h) ----------------------------------------------------------------
-int row_solve_begin(gpx_handle *h, int64_t m, RowSolve &rs)
+int row_solve_begin(gpx_handle *h, int64_t m, RowSolve &rs, bool bounded)
 {
     int64_t cap = ((int64_t)8 << 30) / (h->npad * (int64_t)sizeof(double));   // rows per 8 GB buffer (two of them: Z and Zs)
     cap = std::max<int64_t>(TILE, cap / TILE * TILE);
@@ -29,15 +31,26 @@ int row_solve_begin(gpx_handle *h, int64_t m, RowSolve &rs)
     if (!rs.few) trsm_emu_need(rs.ew, rs.chunk, &h->tri, 0, h->tri.P);
     if (rs.ew.a_bytes) GPX_TRY(emu_work_alloc(rs.ew, rs.sc));
     rs.emu = rs.ew.ra ? &rs.ew : nullptr;
+    // a caller that bounds every solved row (estimate_many) takes the left-looking order over five slabs or more; as above the choice
+    // depends on the factor's shape alone.  An image that does not fit leaves the recursion in charge.
+    if (emu_left_route(bounded, rs.few, h->tri.ready(), h->tri.P)) {
+        emu_left_plan(rs.left, rs.chunk, h->tri.P);
+        if (emu_left_alloc(rs.left, rs.sc) == 0) rs.use_left = true;
+        else {   // (the image, its tiles and arrays went back whole; the refusal is no error of this call)
+            if (getenv("GPX_DEBUG")) fprintf(stderr, "[gpx] left-looking solve: no room for the residue image (%s): binary recursion\n", gpx_last_error());
+            gpx_set_error("%s", "");
+        }
+    }
     return 0;
 }
 
-int row_solve_run(gpx_handle *h, const RowSolve &rs, int64_t mc, int64_t mp, const GemmReduce *red)
+int row_solve_run(gpx_handle *h, const RowSolve &rs, int64_t mc, int64_t mp, const GemmReduce *red, bool left)
 {
     // a handful of queries (estimate(x_star), plots): the solver for a few right-hand sides -- one forward sweep over the factor's
     // triangle (HBM-bound, ~0.5 ms at N = 16384) instead of the many-right-hand-side recursion on one 128-row tile (its products
     // would be 128 x K strips with K up to N/2: 2.5-3 ms)
     if (!red && rs.few) return h->tri.solve(h->Z, h->npad, (int)mc, rs.Zs, nullptr, h->stream, &h->prof);
+    if (left) return trsm_right_lt_slabs(h->Z, rs.Zs, h->npad, mp, &h->tri, h->stream, &h->prof, red, rs.left, rs.emu);
     return trsm_right_lt_squares(h->Z, rs.Zs, h->npad, mp, &h->tri, 0, h->tri.P, h->stream, &h->prof, red, rs.emu);
 }
 
@@ -48,7 +61,8 @@ static int predict_common(gpx_handle *h, const double *xs, const double *kv, con
     hipStream_t s = h->stream;
     const int d = h->d;
     RowSolve rs(s);
-    GPX_TRY(row_solve_begin(h, m, rs));
+    // |row of Zs|^2 = k*^T K^-1 k* <= k(x*, x*): sqrt(v) for the built-in kernel, sqrt(kdiag) for the caller's (tsolve.hip, launch_row_bounds)
+    GPX_TRY(row_solve_begin(h, m, rs, true));
     const int64_t chunk = rs.chunk;
     double *xq = nullptr, *xqw = nullptr, *mv = nullptr, *kd = nullptr, *part = nullptr;
     int rc = 0;
@@ -61,38 +75,56 @@ static int predict_common(gpx_handle *h, const double *xs, const double *kv, con
     GPX_TRY(rs.sc.take(&kd, chunk));
     if (fused) GPX_TRY(rs.sc.take(&part, 2 * chunk * nslots));
     double *Zs = rs.Zs;
-    for (int64_t m0 = 0; m0 < m && rc == 0; m0 += chunk) {
-        const int64_t mc = std::min<int64_t>(chunk, m - m0), mp = round_up(mc, TILE);
+    // Z <- the chunk's cross-covariance rows, zero padded
+    auto fill = [&](int64_t m0, int64_t mc, int64_t mp) -> int {
         hipError_t e = hipSuccess;
         if (xs) {
             e = hipMemcpyAsync(xq, xs + m0 * d, sizeof(double) * mc * d, hipMemcpyDefault, s);
-            if (e != hipSuccess) { gpx_set_error("copy xs failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
-            if ((rc = launch_scale_rows(xq, mc, mp, d, h->sw, xqw, s))) break;
+            if (e != hipSuccess) { gpx_set_error("copy xs failed: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
+            GPX_TRY(launch_scale_rows(xq, mc, mp, d, h->sw, xqw, s));
             // kv = cross-covariance (no vt), zero padded: rows >= mc and columns >= n are 0
-            if ((rc = launch_gram(xqw, mc, h->xs_w, h->n, d, h->v, 0.0, 0, 1, h->Z, h->npad, mp, h->npad, s, &h->prof))) break;
-        } else {
-            // the operator's own cross-covariance rows, zero padded to the tile grid
-            e = hipMemsetAsync(h->Z, 0, sizeof(double) * mp * h->npad, s);
-            if (e == hipSuccess) e = hipMemcpy2DAsync(h->Z, sizeof(double) * h->npad, kv + m0 * h->n, sizeof(double) * h->n, sizeof(double) * h->n, mc, hipMemcpyDefault, s);
-            if (e == hipSuccess) e = hipMemcpyAsync(kd, kdiag + m0, sizeof(double) * mc, hipMemcpyDefault, s);
-            if (e != hipSuccess) { gpx_set_error("copy kv / kdiag failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
+            return launch_gram(xqw, mc, h->xs_w, h->n, d, h->v, 0.0, 0, 1, h->Z, h->npad, mp, h->npad, s, &h->prof);
         }
-        // Z <- kv L^-T  : row m of Z is (L^-1 kv_m)^T
-        // var = k_mm - |z|^2 (k_mm = v + vt for the built-in kernel: k includes vt, GaussianProcess.py:75,78) ; mean = z . y
+        // the operator's own cross-covariance rows, zero padded to the tile grid
+        e = hipMemsetAsync(h->Z, 0, sizeof(double) * mp * h->npad, s);
+        if (e == hipSuccess) e = hipMemcpy2DAsync(h->Z, sizeof(double) * h->npad, kv + m0 * h->n, sizeof(double) * h->n, sizeof(double) * h->n, mc, hipMemcpyDefault, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(kd, kdiag + m0, sizeof(double) * mc, hipMemcpyDefault, s);
+        if (e != hipSuccess) { gpx_set_error("copy kv / kdiag failed: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
+        return 0;
+    };
+    // Z <- kv L^-T  : row m of Z is (L^-1 kv_m)^T
+    // var = k_mm - |z|^2 (k_mm = v + vt for the built-in kernel: k includes vt, GaussianProcess.py:75,78) ; mean = z . y
+    auto solve = [&](int64_t mc, int64_t mp, bool left) -> int {
         if (fused && mp >= 3072) {
             GemmReduce red;
             red.y = h->y; red.p2 = part; red.py = part + chunk * nslots; red.nslots = nslots;
-            if ((rc = row_solve_run(h, rs, mc, mp, &red))) break;
+            GPX_TRY(row_solve_run(h, rs, mc, mp, &red, left));
             ProfScope ps(&h->prof, s, GPX_K_REDUCE, 16.0 * (double)mc * (double)nslots);
-            if ((rc = launch_predict_finish(red.p2, red.py, nslots, mc, h->v + h->vt, mv, mv + chunk, s, xs ? nullptr : kd))) break;
-        } else {
-            if ((rc = row_solve_run(h, rs, mc, mp, nullptr))) break;
-            if ((rc = launch_predict_reduce(Zs, h->npad, mc, h->npad, h->y, h->v + h->vt, mv, mv + chunk, s, &h->prof, xs ? nullptr : kd))) break;
+            return launch_predict_finish(red.p2, red.py, nslots, mc, h->v + h->vt, mv, mv + chunk, s, xs ? nullptr : kd);
         }
-        e = hipMemcpyAsync(mean_out + m0, mv, sizeof(double) * mc, hipMemcpyDefault, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(var_out + m0, mv + chunk, sizeof(double) * mc, hipMemcpyDefault, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { gpx_set_error("predict copy-out failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
+        GPX_TRY(row_solve_run(h, rs, mc, mp, nullptr, left));
+        return launch_predict_reduce(Zs, h->npad, mc, h->npad, h->y, h->v + h->vt, mv, mv + chunk, s, &h->prof, xs ? nullptr : kd);
+    };
+    for (int64_t m0 = 0; m0 < m && rc == 0; m0 += chunk) {
+        const int64_t mc = std::min<int64_t>(chunk, m - m0), mp = round_up(mc, TILE);
+        // a bound that did not hold (the status word of emu.hip, read at the chunk's synchronisation) sends the chunk through the binary
+        // recursion once more: Z is consumed by the solve, so it is filled again first
+        rc = emu_left_guarded(rs.use_left, [&](bool left, int *status) -> int {
+            GPX_TRY(fill(m0, mc, mp));
+            if (left) {
+                GPX_TRY(launch_row_bounds(xs ? nullptr : kd, h->v, mc, rs.left.bound, s));
+                GPX_TRY(emu_left_begin(rs.left, rs.left.bound, mc, s));
+            }
+            GPX_TRY(solve(mc, mp, left));
+            // (the status word last: the host-side set-up of the two result copies then runs underneath the solve, as before)
+            hipError_t e = hipMemcpyAsync(mean_out + m0, mv, sizeof(double) * mc, hipMemcpyDefault, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(var_out + m0, mv + chunk, sizeof(double) * mc, hipMemcpyDefault, s);
+            if (e == hipSuccess && left) e = hipMemcpyAsync(status, rs.left.status(), sizeof(int), hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e != hipSuccess) { gpx_set_error("predict copy-out failed: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
+            if (*status && getenv("GPX_DEBUG")) fprintf(stderr, "[gpx] left-looking solve: a row bound did not hold in rows %ld..%ld: binary recursion\n", (long)m0, (long)(m0 + mc));
+            return 0;
+        });
     }
     return rc;
 }
@@ -115,6 +147,31 @@ extern "C" int gpx_predict_kv(gpx_handle *h, const double *kv, int64_t m, const 
     if (m < 0 || (m > 0 && (!kv || !kdiag || !mean_out || !var_out))) { gpx_set_error("gpx_predict_kv: bad arguments"); return GPX_ERR_BAD_ARG; }
     if (m == 0) return 0;
     return predict_common(h, nullptr, kv, kdiag, m, mean_out, var_out);
+}
+
+// The left-looking solve alone on caller device buffers against a fitted handle's factor (tests): Zs [rows, ldz] <- Z L^-T with Z
+// [rows, ldz] consumed (afterwards slab p of Z holds Z_p minus its updates: what the leaf products read), bound [rows] the caller's bound
+// on every solved row, tile_rows > 0 a smaller row tile of the residue image.  *status_out: the status word (non-zero: a bound did not
+// hold and Zs is not to be used).  Synchronous.
+extern "C" int gpx_emu_trsm_left(gpx_handle *h, double *Z, int64_t ldz, int64_t rows, const double *bound, double *Zs, int64_t tile_rows,
+                                 int *status_out)
+{
+    CHECK_H(h);
+    if (!Z || !Zs || !bound || !status_out || rows <= 0 || rows % TILE || ldz < h->npad || ldz & 1 || tile_rows < 0) {
+        gpx_set_error("gpx_emu_trsm_left: bad arguments (rows %ld a multiple of 128, ldz %ld >= %ld and even)", (long)rows, (long)ldz, (long)h->npad);
+        return GPX_ERR_BAD_ARG;
+    }
+    if (!h->tri.ready() || h->tri.P < 5 || !emu_enabled(4096)) { gpx_set_error("gpx_emu_trsm_left: needs a prepared solver over 5 slabs or more and the emulated update"); return GPX_ERR_STATE; }
+    hipStream_t s = h->stream;
+    Scratch sc(s);
+    EmuLeft w;
+    emu_left_plan(w, rows, h->tri.P, tile_rows);
+    GPX_TRY(emu_left_alloc(w, sc));
+    GPX_TRY(emu_left_begin(w, bound, rows, s));
+    GPX_TRY(trsm_right_lt_slabs(Z, Zs, ldz, rows, &h->tri, s, &h->prof, nullptr, w));
+    GPX_HIP(hipMemcpyAsync(status_out, w.status(), sizeof(int), hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipStreamSynchronize(s));
+    return 0;
 }
 
 // ---- a few vectors against the factor ----------------------------------------------------------------

@@ -468,26 +468,31 @@ int launch_predict_finish(const double *p2, const double *py, int64_t nslots, in
     return 0;
 }
 
+// the leaf of slab p: Zs_p = Z_p inv(L_pp)^T
+static int slab_leaf(double *Z, double *Zs, int64_t ldz, int64_t rows, const TriSolver *ts, int64_t p, hipStream_t s, Profiler *prof,
+                     const GemmReduce *red)
+{
+    const int64_t k0 = p * PB, K = std::min<int64_t>(PB, ts->npad - k0);
+    // the slab's final values leave this product: their row sums ride in its epilogue -- where its paired 128 x 128 tiles fill the chip
+    // (>= 448 of the 512 places); with fewer rows the product takes a finer tile shape (launch_gemm_nt) and the sums a pass of their own
+    if (red && (rows / TILE) * (K / TILE / 2) >= 448) {
+        GemmReduce r = *red;
+        r.y = red->y + k0;
+        r.slot0 = k0 / 64;
+        return launch_gemm_nt_tri_reduce(Z + k0, ldz, ts->Pl + p * (int64_t)PB * PB, PB, Zs + k0, ldz, rows, K, 1.0, r, s, prof);
+    }
+    GPX_TRY(launch_gemm_nt(Z + k0, ldz, ts->Pl + p * (int64_t)PB * PB, PB, Zs + k0, ldz, rows, K, K, 1.0, 0.0, 0, s, prof, 0, GEMM_TRI_B_LOWER));
+    if (red) GPX_TRY(launch_slab_reduce(Zs + k0, ldz, rows, K, red->y + k0, red->p2, red->py, red->nslots, k0 / 64, s));
+    return 0;
+}
+
 int trsm_right_lt_squares(double *Z, double *Zs, int64_t ldz, int64_t rows, const TriSolver *ts, int64_t p0, int64_t p1, hipStream_t s,
                           Profiler *prof, const GemmReduce *red, const EmuWork *emu)
 {
     const int64_t np = p1 - p0;
     if (np <= 0 || rows <= 0) return 0;
     if (!ts || !ts->Pl) { gpx_set_error("trsm_right_lt_squares: solver not prepared"); return GPX_ERR_STATE; }
-    if (np == 1) {
-        const int64_t k0 = p0 * PB, K = std::min<int64_t>(PB, ts->npad - k0);
-        // the slab's final values leave this product: their row sums ride in its epilogue -- where its paired 128 x 128 tiles fill the chip
-        // (>= 448 of the 512 places); with fewer rows the product takes a finer tile shape (launch_gemm_nt) and the sums a pass of their own
-        if (red && (rows / TILE) * (K / TILE / 2) >= 448) {
-            GemmReduce r = *red;
-            r.y = red->y + k0;
-            r.slot0 = k0 / 64;
-            return launch_gemm_nt_tri_reduce(Z + k0, ldz, ts->Pl + p0 * (int64_t)PB * PB, PB, Zs + k0, ldz, rows, K, 1.0, r, s, prof);
-        }
-        GPX_TRY(launch_gemm_nt(Z + k0, ldz, ts->Pl + p0 * (int64_t)PB * PB, PB, Zs + k0, ldz, rows, K, K, 1.0, 0.0, 0, s, prof, 0, GEMM_TRI_B_LOWER));
-        if (red) GPX_TRY(launch_slab_reduce(Zs + k0, ldz, rows, K, red->y + k0, red->p2, red->py, red->nslots, k0 / 64, s));
-        return 0;
-    }
+    if (np == 1) return slab_leaf(Z, Zs, ldz, rows, ts, p0, s, prof, red);
     int64_t h = 1;
     while (h * 2 < np) h *= 2;
     const int64_t pm = p0 + h;
@@ -518,6 +523,46 @@ void trsm_emu_need(EmuWork &w, int64_t rows, const TriSolver *ts, int64_t p0, in
     trsm_emu_need(w, rows, ts, p0, pm);
     if (emu_enabled(cm - c0)) emu_work_need(w, rows, c1 - cm, cm - c0);
     trsm_emu_need(w, rows, ts, pm, p1);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The same solve left-looking over the slabs (estimate_many with a bound on every solved row: predict.hip): slab p takes ONE update
+//     Zs_p = (Z_p - Zs[:, 0:p) L[p, 0:p)^T) inv(L_pp)^T
+// of depth K = 1024 p, so from p = 4 on every update is deep enough for the int8 path (emu_enabled(4096)), where the binary recursion
+// leaves 24 of its 120 slab pairs at K = 1024 and 2048 on the fp64 cores.  It pays because a solved slab is split once: its residues
+// stay in the image of emu.hip (EmuLeft) and every later update reads them there.  Slabs 0 .. 3 run as in the recursion.  On one stream
+// the split of Zs_p sits between slab p's leaf and slab p + 1's split of L[p + 1, 0:p + 1), which needs nothing of it.
+// ------------------------------------------------------------------------------------------------------------------
+int trsm_right_lt_slabs(double *Z, double *Zs, int64_t ldz, int64_t rows, const TriSolver *ts, hipStream_t s, Profiler *prof, const GemmReduce *red,
+                        const EmuLeft &w, const EmuWork *emu)
+{
+    if (rows <= 0) return 0;
+    if (!ts || !ts->Pl) { gpx_set_error("trsm_right_lt_slabs: solver not prepared"); return GPX_ERR_STATE; }
+    const int64_t head = 4;
+    if (ts->P <= head || w.lda != PB * (ts->P - 1)) { gpx_set_error("trsm_right_lt_slabs: image planned for another factor"); return GPX_ERR_STATE; }
+    GPX_TRY(trsm_right_lt_squares(Z, Zs, ldz, rows, ts, 0, head, s, prof, red, emu));
+    for (int64_t q = 0; q < head; ++q) GPX_TRY(emu_left_split(w, Zs + q * PB, ldz, rows, q, s));
+    for (int64_t p = head; p < ts->P; ++p) {
+        const int64_t k0 = p * PB, width = std::min<int64_t>(PB, ts->npad - k0);
+        GPX_TRY(emu_left_update(w, ts->L + k0 * ts->ld, ts->ld, Z + k0, ldz, rows, width, k0, s, prof));
+        GPX_TRY(slab_leaf(Z, Zs, ldz, rows, ts, p, s, prof, red));
+        if (p + 1 < ts->P) GPX_TRY(emu_left_split(w, Zs + k0, ldz, rows, p, s));
+    }
+    return 0;
+}
+
+// bound_i on |Zs_i.|: row i of Zs is L^-1 k*, |L^-1 k*|^2 = k*^T K^-1 k* <= k(x*, x*) for a positive semi-definite kernel
+__global__ __launch_bounds__(256) void row_bounds_kernel(const double *__restrict__ kdiag, double v, long m, double *__restrict__ bound)
+{
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i < m) bound[i] = sqrt(kdiag ? kdiag[i] : v);
+}
+
+int launch_row_bounds(const double *kdiag, double v, int64_t m, double *bound, hipStream_t s)
+{
+    hipLaunchKernelGGL(row_bounds_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, kdiag, v, (long)m, bound);
+    GPX_HIP(hipGetLastError());
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
