@@ -268,6 +268,20 @@ int gpx_emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t l
 int gpx_emu_rebuild(const int8_t *R, int64_t ldr, int64_t sr, int nmod, const int *sa, const int *sb, double *C, int64_t ldc, int64_t rows,
                     int64_t cols);
 int gpx_emu_i8_gemm(const int8_t *A, const int8_t *B, int64_t rows, int64_t cols, int64_t K, int nmod, int8_t *R);
+/* The two splits of the emulated update alone, on device buffers (tests).  Synchronous; GPX_ERR_BAD_ARG before anything is queued.
+ * Both store, for every row < rows_pad and l < nmod (1 .. 16), the balanced residue modulo the l-th modulus of a' = rint(x 2^s) as one
+ * byte (128 mod 256 stored as -128); rows >= rows are padding (zero residues).  bits is 1 .. 59; X is 16-byte aligned, ldx even.
+ * gpx_emu_split: X [rows, K] (ldx >= K; K a multiple of 128 below 2^17) -> res[l * plane + row * K + col], with the row's own scale
+ * sig[row] = bits - 1 - ilogb(max |x|) (0 for an all-zero or a padding row); a row that holds a NaN or an Inf gets sig = 0x7fffffff
+ * and zero residues.  plane >= rows_pad * K.
+ * gpx_emu_split_fixed: X [rows, width] (width a multiple of 16, at most 1024) -> res[l * plane + row * ldr + col] for col < width only
+ * (res points at the window's first column; ldr >= width and plane are multiples of 16, res 16-byte aligned), with the given scales
+ * sig[row].  An entry with |a'| > 2^bits sets *status to 1 and is stored as 0; a NaN or an Inf sets sig[row] = 0x7fffffff (the row's
+ * other entries are still split); a row whose sig is 0x7fffffff at entry is stored as zeros.  *status is never cleared. */
+int gpx_emu_split(const double *X, int64_t ldx, int64_t rows, int64_t rows_pad, int64_t K, int bits, int nmod, int8_t *res, int64_t plane,
+                  int *sig);
+int gpx_emu_split_fixed(const double *X, int64_t ldx, int64_t rows, int64_t rows_pad, int64_t width, int bits, int nmod, int8_t *res,
+                        int64_t ldr, int64_t plane, int *sig, int *status);
 /* The left-looking form of estimate_many's solve alone (tests): Zs [rows, ldz] <- Z L^-T against the handle's factor (5 slabs of 1024
  * columns or more), device buffers, rows a multiple of 128, ldz >= the padded size and even.  bound [rows] (device): a bound on the
  * magnitude of every entry of the solved row, known before the solve; the residues of a solved slab are split once with the scale it

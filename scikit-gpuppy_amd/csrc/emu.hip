@@ -25,6 +25,7 @@
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
+typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
 constexpr int EMU_MAXL = 16;
 constexpr int EMU_BT = 256;   // int8 block tile: 256 x 256, 2 x 4 waves of 128 x 64 (4 x 2 MFMAs of 32 x 32), two waves per SIMD
@@ -104,45 +105,134 @@ int emu_scale_bits(int64_t K, int L)
     return (int)floor(log2p - 1.0 - log2((double)K) - 1e-9);
 }
 
-// the L residues of four consecutive integers a' (|a'| <= 2^56, exact in fp64) as one packed word per plane: a' - p q with q = rint(a' / p)
-// off by at most one (the fma is exact: the result is a small integer), then made symmetric
-static __device__ __forceinline__ void emu_store_residues(const double (&a)[4], int L, int8_t *__restrict__ out, long plane)
+// ---- residues of one integer, without a division or an fp64 reduction per modulus ------------------------------------------------------
+// The integer a' (|a'| <= 2^59: emu_scale_bits(128, 16) = 117 gives abits = 59, the largest there is) is cut ONCE into two 32-bit words
+// of a'' = a' + 2^60 = 2^32 hi + lo:  hi = floor(a' 2^-32) + 2^28 in [2^27, 3 2^27],  lo = a' - 2^32 floor(a' 2^-32) in [0, 2^32) (the
+// fma is exact: lo is a multiple of a's ulp below 2^32).  The eight bytes d_0 .. d_7 of a'' (0 <= d_k <= 255, d_7 <= 0x18) are its limbs:
+//   x = k0 + sum_k d_k (2^(8k) mod p),   k0 = (-2^60) mod p,   so x = a' (mod p),   0 <= x <= 254 + 8 255 254 < 2^19,
+// two v_dot4_u32_u8 per modulus.  For odd p the symmetric residue is r = x - p q with q = floor((2 x + p) / (2 p)) (2 x + p is odd: no
+// tie), and q = (y m) >> 32 for y = 2 x + p < 2^21, m = ceil(2^31 / p) < 2^24: y m / 2^32 exceeds y / (2 p) by less than 2^-11, and
+// y / (2 p) lies at least 1 / (2 p) > 2^-9 below the next integer.  So |r| <= (p - 1) / 2 and the byte is r & 255.  Modulo 256 the byte
+// is d_0 (the representative in [-128, 127]: +128 is stored as -128, the same residue).  tests/test_emulated_split_model.py walks every
+// reachable x of every modulus through this arithmetic.
+struct EmuSplitMod { unsigned c0, c1, k0, m; };
+constexpr EmuSplitMod emu_split_mod(int l)
 {
+    const unsigned p = (unsigned)EMU_MODULI[l];
+    EmuSplitMod t{};
+    unsigned w = 1 % p;
+    for (int k = 0; k < 8; ++k) {
+        (k < 4 ? t.c0 : t.c1) |= w << (8 * (k & 3));
+        w = w * 256 % p;
+    }
+    unsigned b = 1 % p;
+    for (int i = 0; i < 60; ++i) b = 2 * b % p;
+    t.k0 = (p - b) % p;
+    t.m = (unsigned)((((unsigned long)1 << 31) + p - 1) / p);
+    return t;
+}
+static_assert(EMU_MODULI[0] == 256, "the first modulus takes the low byte as it is");
+
+// the two words of a'' for the integer a (|a| <= 2^59, exact in fp64)
+static __device__ __forceinline__ void emu_words(double a, unsigned &lo, unsigned &hi)
+{
+    const double h = floor(a * 0x1p-32);
+    lo = (unsigned)fma(-h, 0x1p32, a);
+    hi = (unsigned)((int)h + (1 << 28));
+}
+
+// sixteen consecutive entries' residues modulo EMU_MODULI[l], one byte each, as the 16 bytes of plane l
+template <int l> static __device__ __forceinline__ v4u emu_plane_bytes(const unsigned (&lo)[16], const unsigned (&hi)[16])
+{
+    int r[16];
+    if constexpr (l == 0) {
 #pragma unroll
-    for (int l = 0; l < EMU_MAXL; ++l) {
-        if (l >= L) continue;
-        const double p = (double)emu_p[l], pinv = 1.0 / p, h = 0.5 * p;
-        unsigned packed = 0;
+        for (int e = 0; e < 16; ++e) r[e] = (int)lo[e];
+    } else {
+        constexpr EmuSplitMod M = emu_split_mod(l);
+        constexpr int p = EMU_MODULI[l];
+        static_assert(p % 2 == 1 && p < 256 && M.m < (1u << 24), "the reduction below is for odd moduli of one byte");
+        // (the mask tells the compiler that the 24-bit multiply serves, and costs nothing; the multiply-add is named because the
+        // compiler takes a 32-bit one, at a quarter of the rate; 256 q is added to r: only its low byte is kept)
+        unsigned x[16], q[16];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            double r = fma(-rint(a[e] * pinv), p, a[e]);
-            r = r > h ? r - p : (r < -h ? r + p : r);      // [-p/2, p/2]; 256 wraps to -128 in the byte (same residue)
-            packed |= ((unsigned)(int)r & 0xffu) << (8 * e);
-        }
-        *reinterpret_cast<unsigned *>(out + l * plane) = packed;
+        for (int e = 0; e < 16; ++e) x[e] = __builtin_amdgcn_udot4(lo[e], M.c0, M.k0, false);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) x[e] = __builtin_amdgcn_udot4(hi[e], M.c1, x[e], false);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) q[e] = __umulhi((2u * x[e] + (unsigned)p) & 0xffffffu, M.m);
+#pragma unroll
+        for (int e = 0; e < 16; ++e) asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r[e]) : "v"(q[e]), "s"(256 - p), "v"(x[e]));
+    }
+    v4u out;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {   // byte 0 of four words into one
+        const unsigned w01 = __builtin_amdgcn_perm((unsigned)r[4 * g + 1], (unsigned)r[4 * g], 0x0c0c0400u);
+        const unsigned w23 = __builtin_amdgcn_perm((unsigned)r[4 * g + 3], (unsigned)r[4 * g + 2], 0x0c0c0400u);
+        out[g] = __builtin_amdgcn_perm(w23, w01, 0x05040100u);
+    }
+    return out;
+}
+
+template <int l> static __device__ __forceinline__ void emu_store_planes(const unsigned (&lo)[16], const unsigned (&hi)[16], int L,
+                                                                         int8_t *__restrict__ out, long plane)
+{
+    if constexpr (l < EMU_MAXL) {
+        if (l >= L) return;
+        *reinterpret_cast<v4u *>(out) = emu_plane_bytes<l>(lo, hi);
+        emu_store_planes<l + 1>(lo, hi, L, out + plane, plane);
     }
 }
 
-// ---- split: one workgroup per row of X [rows, K] (fp64, ldx) -> residue planes res[l][row][K] (int8) and the row's scale exponent ----
-// rows >= rows_real are padding: zero residues.  The integer a' = rint(x 2^sig) (|a'| <= 2^bits) is exact in fp64; its residue mod p is
-// a' - p q with q = rint(a' / p) off by at most one (the fma is exact: the result is a small integer), then made symmetric.
-__global__ __launch_bounds__(256) void emu_split_kernel(const double *__restrict__ X, long ldx, long rows_real, int K, int bits, int L,
-                                                        int8_t *__restrict__ res, long plane, int *__restrict__ sig)
+// ---- the split body: one lane takes 16 consecutive entries of a row (128 bytes of fp64 in, one 16-byte store per plane out), a wave a
+// stretch of 1024 columns.  a' = rint(x 2^s).  zero (wave-uniform: a padding row, a row that holds a NaN or an Inf): zero residues,
+// nothing is read.  CHECKED (the split with a given scale): a NaN or an Inf sets bad, an |a'| > lim sets over, either is stored as 0.
+template <bool CHECKED>
+static __device__ __forceinline__ void emu_split_lane(const double *__restrict__ x, bool zero, int s, double lim, int L, int8_t *__restrict__ out,
+                                                      long plane, int &bad, int &over)
+{
+    if (zero) {
+        for (int l = 0; l < L; ++l, out += plane) *reinterpret_cast<v4u *>(out) = (v4u){0u, 0u, 0u, 0u};
+        return;
+    }
+    v2d v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] = *reinterpret_cast<const v2d *>(x + 2 * j);
+    unsigned lo[16], hi[16];
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+        const double xe = (e & 1) ? v[e >> 1].y : v[e >> 1].x;
+        double a = rint(ldexp(xe, s));
+        if (CHECKED) {
+            const bool nf = !isfinite(xe), ok = fabs(a) <= lim;   // (a NaN or an Inf fails ok as well)
+            bad |= (int)nf;
+            over |= (int)(!ok && !nf);
+            a = ok ? a : 0.0;
+        }
+        emu_words(a, lo[e], hi[e]);
+    }
+    emu_store_planes<0>(lo, hi, L, out, plane);
+}
+
+// ---- split: X [rows, K] (fp64, ldx) -> residue planes res[l][row][K] (int8) and the rows' scale exponents, in two launches ------------
+// 1. one workgroup per row: the row's largest |x| gives sig[row] = bits - 1 - ilogb(max), so that |x| 2^sig < 2^bits for every entry (an
+//    all-zero row and the padding rows keep 0), or EMU_NONFINITE where the row holds a NaN or an Inf;
+// 2. one wave per (row, stretch of 1024 columns): the split body; nothing can exceed 2^bits, a padding or a non-finite row is zero.
+__global__ __launch_bounds__(256) void emu_row_scale_kernel(const double *__restrict__ X, long ldx, long rows_real, int K, int bits,
+                                                            int *__restrict__ sig)
 {
     const long row = blockIdx.x;
     const int t = threadIdx.x;
-    __shared__ double red_max[4];
-    __shared__ int red_bad[4];
-    int8_t *out = res + row * (long)K;
     if (row >= rows_real) {
-        for (int c = 4 * t; c < K; c += 1024)
-            for (int l = 0; l < L; ++l) *reinterpret_cast<int *>(out + l * plane + c) = 0;
         if (t == 0) sig[row] = 0;
         return;
     }
+    __shared__ double red_max[4];
+    __shared__ int red_bad[4];
     const double *x = X + row * ldx;
     double m = 0.0;
     int bad = 0;
+#pragma unroll 4
     for (int c = 2 * t; c < K; c += 512) {
         const v2d v = *reinterpret_cast<const v2d *>(x + c);
         bad |= (int)!isfinite(v.x) | (int)!isfinite(v.y);
@@ -152,58 +242,47 @@ __global__ __launch_bounds__(256) void emu_split_kernel(const double *__restrict
     for (int o = 32; o > 0; o >>= 1) { m = fmax(m, __shfl_xor(m, o)); bad |= __shfl_xor(bad, o); }
     if ((t & 63) == 0) { red_max[t >> 6] = m; red_bad[t >> 6] = bad; }
     __syncthreads();
-    m = fmax(fmax(red_max[0], red_max[1]), fmax(red_max[2], red_max[3]));
-    bad = red_bad[0] | red_bad[1] | red_bad[2] | red_bad[3];
-    // |x| 2^s < 2^bits for the row's largest |x| in [2^e, 2^(e+1)); an all-zero row keeps s = 0 (its residues are 0)
-    const int s = (bad || m == 0.0) ? 0 : bits - 1 - ilogb(m);
-    if (t == 0) sig[row] = bad ? EMU_NONFINITE : s;
-    for (int c = 4 * t; c < K; c += 1024) {
-        const v2d v0 = *reinterpret_cast<const v2d *>(x + c), v1 = *reinterpret_cast<const v2d *>(x + c + 2);
-        double a[4] = {rint(ldexp(v0.x, s)), rint(ldexp(v0.y, s)), rint(ldexp(v1.x, s)), rint(ldexp(v1.y, s))};
-        if (bad) a[0] = a[1] = a[2] = a[3] = 0.0;
-        emu_store_residues(a, L, out + c, plane);
+    if (t == 0) {
+        m = fmax(fmax(red_max[0], red_max[1]), fmax(red_max[2], red_max[3]));
+        bad = red_bad[0] | red_bad[1] | red_bad[2] | red_bad[3];
+        sig[row] = bad ? EMU_NONFINITE : (m == 0.0 ? 0 : bits - 1 - ilogb(m));
     }
 }
 
-// ---- split with a given scale (the left-looking solve, tsolve.hip): the rows of one solved slab of `width` columns into the persistent
-// residue image res[l][row][ldr] at the slab's column offset, with the scale sig[row] that emu_scale_from_bound_kernel derived from the
-// row's bound before the row was known.  An entry with |x 2^s| > 2^bits (the bound was wrong) raises *status and is stored as 0: it never
-// wraps silently; a NaN or an Inf marks the row (sig = EMU_NONFINITE, sticky: every later product of the row is NaN) and raises nothing.
-__global__ __launch_bounds__(256) void emu_split_fixed_kernel(const double *__restrict__ X, long ldx, long rows_real, int width, int bits, int L,
-                                                              int8_t *__restrict__ res, long ldr, long plane, int *sig, int *status)
+__global__ __launch_bounds__(256) void emu_split_kernel(const double *__restrict__ X, long ldx, long rows_real, long rows_pad, int K, int L,
+                                                        int8_t *__restrict__ res, long plane, const int *__restrict__ sig)
 {
-    const long row = blockIdx.x;
-    const int t = threadIdx.x;
-    int8_t *out = res + row * ldr;
-    if (row >= rows_real) {
-        for (int c = 4 * t; c < width; c += 1024)
-            for (int l = 0; l < L; ++l) *reinterpret_cast<int *>(out + l * plane + c) = 0;
-        return;
-    }
-    const double *x = X + row * ldx;
-    const int s0 = sig[row];
-    const bool dead = s0 == EMU_NONFINITE;
-    const int s = dead ? 0 : s0;
-    const double lim = ldexp(1.0, bits);
+    const int stretches = (K + 1023) >> 10;
+    const long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const long row = item / stretches;
+    const int c = (int)(item - row * stretches) * 1024 + 16 * (threadIdx.x & 63);
+    if (row >= rows_pad || c >= K) return;
+    const int s = row < rows_real ? sig[row] : EMU_NONFINITE;
     int bad = 0, over = 0;
-    for (int c = 4 * t; c < width; c += 1024) {
-        const v2d v0 = *reinterpret_cast<const v2d *>(x + c), v1 = *reinterpret_cast<const v2d *>(x + c + 2);
-        const double v[4] = {v0.x, v0.y, v1.x, v1.y};
-        double a[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            a[e] = rint(ldexp(v[e], s));
-            if (!isfinite(v[e])) { bad = 1; a[e] = 0.0; }
-            else if (fabs(a[e]) > lim) { over = 1; a[e] = 0.0; }
-            if (dead) a[e] = 0.0;
-        }
-        emu_store_residues(a, L, out + c, plane);
-    }
-    bad = __syncthreads_or(bad);
-    over = __syncthreads_or(over);
-    if (t == 0) {
+    emu_split_lane<false>(X + row * ldx + c, s == EMU_NONFINITE, s, 0.0, L, res + row * (long)K + c, plane, bad, over);
+}
+
+// ---- split with a given scale (the left-looking solve, tsolve.hip): the rows of one solved slab of `width` columns (a multiple of 16,
+// at most 1024: one wave per row) into the persistent residue image res[l][row][ldr] at the slab's column offset, with the scale sig[row]
+// that emu_scale_from_bound_kernel derived from the row's bound before the row was known.  An entry with |x 2^s| > 2^bits (the bound was
+// wrong) raises *status and is stored as 0: it never wraps silently; a NaN or an Inf marks the row (sig = EMU_NONFINITE, sticky: every
+// later product of the row is NaN) and raises nothing.  Rows >= rows_real (padding) and rows marked at entry are zero.
+__global__ __launch_bounds__(256) void emu_split_fixed_kernel(const double *__restrict__ X, long ldx, long rows_real, long rows_pad, int width,
+                                                              int bits, int L, int8_t *__restrict__ res, long ldr, long plane, int *sig, int *status)
+{
+    const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63, c = 16 * lane;
+    if (row >= rows_pad) return;
+    const int s = row < rows_real ? sig[row] : EMU_NONFINITE;
+    const bool dead = s == EMU_NONFINITE;
+    int bad = 0, over = 0;
+    if (c < width) emu_split_lane<true>(X + row * ldx + c, dead, s, ldexp(1.0, bits), L, res + row * ldr + c, plane, bad, over);
+    if (dead) return;
+    bad = __any(bad);
+    over = __any(over);
+    if (lane == 0) {
         if (bad) sig[row] = EMU_NONFINITE;
-        else if (over && !dead) atomicMax(status, 1);
+        else if (over) atomicMax(status, 1);
     }
 }
 
@@ -403,6 +482,21 @@ __global__ __launch_bounds__(256) void emu_rebuild_kernel(const int8_t *__restri
     }
 }
 
+// the two launches of the split with its own scale, and the one of the split with a given scale
+static void emu_launch_split(const double *X, long ldx, long rows, long rows_pad, int K, int bits, int L, int8_t *res, long plane, int *sig,
+                             hipStream_t s)
+{
+    const long waves = rows_pad * ((K + 1023) / 1024);
+    hipLaunchKernelGGL(emu_row_scale_kernel, dim3((unsigned)rows_pad), dim3(256), 0, s, X, ldx, rows, K, bits, sig);
+    hipLaunchKernelGGL(emu_split_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, X, ldx, rows, rows_pad, K, L, res, plane, (const int *)sig);
+}
+static void emu_launch_split_fixed(const double *X, long ldx, long rows, long rows_pad, int width, int bits, int L, int8_t *res, long ldr, long plane,
+                                   int *sig, int *status, hipStream_t s)
+{
+    hipLaunchKernelGGL(emu_split_fixed_kernel, dim3((unsigned)((rows_pad + 3) / 4)), dim3(256), 0, s, X, ldx, rows, rows_pad, width, bits, L, res, ldr,
+                       plane, sig, status);
+}
+
 // ---- workspace -------------------------------------------------------------------------------------------------------------
 // Residues of a row tile of A and a column tile of B and the product residues of their block, each at most 2 GiB: at N = M = 16384
 // (K = 8192) one tile of each; deeper products (K = 32768 at N = 65536) loop over row tiles and, inside, column tiles.  Every bound below
@@ -430,7 +524,7 @@ int emu_work_alloc(EmuWork &w, Scratch &sc)
 // What the kernels take for granted of a caller outside the library (gpx_emu_gemm_nt_sub; tsolve.hip passes slabs of 128-padded matrices at
 // offsets that are multiples of 1024), checked on the host before anything is allocated or queued: K a multiple of 128 below 2^17 (the
 // int8 k-stage; K 2^14 < 2^31 in the int32 accumulators), leading dimensions that hold a row (lda, ldb >= K, ldc >= cols), and rows of
-// A and B that start on 16 bytes (base pointers 16-byte aligned, lda and ldb even): emu_split_kernel reads pairs of doubles.
+// A and B that start on 16 bytes (base pointers 16-byte aligned, lda and ldb even): the split kernels read pairs of doubles.
 static int emu_check_args(const double *A, int64_t lda, const double *B, int64_t ldb, int64_t ldc, int64_t cols, int64_t K)
 {
     if (K <= 0 || K % EMU_BK || K >= (1 << 17)) {
@@ -471,12 +565,10 @@ int emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t ldb, 
     int *sga = w.sig, *sgb = sga + rt;
     for (int64_t r0 = 0; r0 < rows; r0 += rt) {
         const int64_t nr = std::min(rt, rows - r0), nrp = round_up(nr, EMU_BT);
-        hipLaunchKernelGGL(emu_split_kernel, dim3((unsigned)nrp), dim3(256), 0, s, A + r0 * lda, (long)lda, (long)nr, (int)K, abits, L, ra,
-                           (long)(nrp * K), sga);
+        emu_launch_split(A + r0 * lda, (long)lda, (long)nr, (long)nrp, (int)K, abits, L, ra, (long)(nrp * K), sga, s);
         for (int64_t c0 = 0; c0 < cols; c0 += ct) {
             const int64_t nc = std::min(ct, cols - c0), ncp = round_up(nc, EMU_BT);
-            hipLaunchKernelGGL(emu_split_kernel, dim3((unsigned)ncp), dim3(256), 0, s, B + c0 * ldb, (long)ldb, (long)nc, (int)K, bbits, L, rb,
-                               (long)(ncp * K), sgb);
+            emu_launch_split(B + c0 * ldb, (long)ldb, (long)nc, (long)ncp, (int)K, bbits, L, rb, (long)(ncp * K), sgb, s);
             const int tm = (int)(nrp / EMU_BT), tn = (int)(ncp / EMU_BT);
             hipLaunchKernelGGL(emu_i8_gemm_kernel, dim3((unsigned)(tm * tn * L)), dim3(512), 0, s, (const int8_t *)ra, (const int8_t *)rb,
                                (long)(nrp * K), (long)(ncp * K), (int)K, rr, (long)ncp, (long)(nrp * ncp), tm, tn, (int)K);
@@ -555,15 +647,15 @@ int emu_left_split(const EmuLeft &w, const double *X, int64_t ldx, int64_t rows,
 {
     for (int64_t t = 0, r0 = 0; r0 < rows; ++t, r0 += w.rt) {
         const int64_t nr = std::min(w.rt, rows - r0), nrp = round_up(nr, EMU_BT);
-        hipLaunchKernelGGL(emu_split_fixed_kernel, dim3((unsigned)nrp), dim3(256), 0, s, X + r0 * ldx, (long)ldx, (long)nr, EMU_SLAB, w.abits, w.L,
-                           w.img + t * w.rt * w.lda * w.L + q * EMU_SLAB, (long)w.lda, (long)(w.rt * w.lda), w.sig + r0, w.status());
+        emu_launch_split_fixed(X + r0 * ldx, (long)ldx, (long)nr, (long)nrp, EMU_SLAB, w.abits, w.L, w.img + t * w.rt * w.lda * w.L + q * EMU_SLAB,
+                               (long)w.lda, (long)(w.rt * w.lda), w.sig + r0, w.status(), s);
     }
     GPX_HIP(hipGetLastError());
     return 0;
 }
 
-// C[rows, cols] -= Zs[:, 0:K) B[cols, K]^T with Zs read from the image (K = 1024 p, cols <= 1024): split B, then per row tile one int8
-// launch and one rebuild
+// C[rows, cols] -= Zs[:, 0:K) B[cols, K]^T with Zs read from the image (K = 1024 p, cols <= 1024): split B (its scales, then its
+// residues), then per row tile one int8 launch and one rebuild
 int emu_left_update(const EmuLeft &w, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t rows, int64_t cols, int64_t K, hipStream_t s,
                     Profiler *prof)
 {
@@ -574,7 +666,7 @@ int emu_left_update(const EmuLeft &w, const double *B, int64_t ldb, double *C, i
     ProfScope ps(prof, s, GPX_K_GEMM_EMU, 2.0 * (double)rows * (double)cols * (double)K);
     const int64_t ncp = round_up(cols, EMU_BT);
     int *sgb = w.sig + w.rows_pad;
-    hipLaunchKernelGGL(emu_split_kernel, dim3((unsigned)ncp), dim3(256), 0, s, B, (long)ldb, (long)cols, (int)K, w.bbits, w.L, w.rb, (long)(ncp * K), sgb);
+    emu_launch_split(B, (long)ldb, (long)cols, (long)ncp, (int)K, w.bbits, w.L, w.rb, (long)(ncp * K), sgb, s);
     for (int64_t t = 0, r0 = 0; r0 < rows; ++t, r0 += w.rt) {
         const int64_t nr = std::min(w.rt, rows - r0), nrp = round_up(nr, EMU_BT);
         const int tm = (int)(nrp / EMU_BT), tn = (int)(ncp / EMU_BT);
@@ -620,6 +712,45 @@ extern "C" int gpx_emu_rebuild(const int8_t *R, int64_t ldr, int64_t sr, int nmo
     const long thr = (long)rows * ((cols + 3) / 4);
     hipLaunchKernelGGL(emu_rebuild_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, 0, R, (long)ldr, (long)sr, nmod, emu_crt.t[nmod], sa, sb, C,
                        (long)ldc, (long)rows, (long)cols);
+    GPX_HIP(hipGetLastError());
+    GPX_HIP(hipStreamSynchronize(0));
+    return 0;
+}
+
+// The two splits alone on caller device buffers (tests/test_emulated_split.py).  Synchronous.
+static bool emu_split_args_ok(const double *X, int64_t ldx, int64_t rows, int64_t rows_pad, int64_t width, int bits, int nmod, const int8_t *res,
+                              int64_t ldr, int64_t plane, const int *sig)
+{
+    return X && res && sig && rows >= 0 && rows <= rows_pad && rows_pad < ((int64_t)1 << 31) && width > 0 && bits >= 1 && bits <= 59 && nmod >= 1 &&
+           nmod <= EMU_MAXL && ldx >= width && !(ldx & 1) && !((uintptr_t)X & 15) && !((uintptr_t)res & 15) && ldr >= width && !(ldr & 15) &&
+           !(plane & 15) && plane >= (rows_pad - 1) * ldr + width;
+}
+
+extern "C" int gpx_emu_split(const double *X, int64_t ldx, int64_t rows, int64_t rows_pad, int64_t K, int bits, int nmod, int8_t *res, int64_t plane,
+                             int *sig)
+{
+    GPX_TRY(gpx_require_device());
+    if (K % EMU_BK || K >= (1 << 17) || !emu_split_args_ok(X, ldx, rows, rows_pad, K, bits, nmod, res, K, plane, sig)) {
+        gpx_set_error("gpx_emu_split: bad arguments");
+        return GPX_ERR_BAD_ARG;
+    }
+    if (rows_pad == 0) return 0;
+    emu_launch_split(X, (long)ldx, (long)rows, (long)rows_pad, (int)K, bits, nmod, res, (long)plane, sig, 0);
+    GPX_HIP(hipGetLastError());
+    GPX_HIP(hipStreamSynchronize(0));
+    return 0;
+}
+
+extern "C" int gpx_emu_split_fixed(const double *X, int64_t ldx, int64_t rows, int64_t rows_pad, int64_t width, int bits, int nmod, int8_t *res,
+                                   int64_t ldr, int64_t plane, int *sig, int *status)
+{
+    GPX_TRY(gpx_require_device());
+    if (!status || width % 16 || width > EMU_SLAB || !emu_split_args_ok(X, ldx, rows, rows_pad, width, bits, nmod, res, ldr, plane, sig)) {
+        gpx_set_error("gpx_emu_split_fixed: bad arguments");
+        return GPX_ERR_BAD_ARG;
+    }
+    if (rows_pad == 0) return 0;
+    emu_launch_split_fixed(X, (long)ldx, (long)rows, (long)rows_pad, (int)width, bits, nmod, res, (long)ldr, (long)plane, sig, status, 0);
     GPX_HIP(hipGetLastError());
     GPX_HIP(hipStreamSynchronize(0));
     return 0;

@@ -88,27 +88,33 @@ hipError_t hipLaunchKernel(const void *f, dim3 g, dim3, void **a, size_t, hipStr
         CHECK((long)g.x * 256 >= rp && rows <= rp, "scale grid");
         CHECK(inside(arg<int *>(a, 4), 0, 4 * rp - 1) && inside(arg<int *>(a, 5), 0, 3), "scales / status outside their block");
         printf("  scales %ld rows (%ld padded)\n", rows, rp);
-    } else if (f == (const void *)emu_split_fixed_kernel) {
-        const long ldx = arg<long>(a, 1), real = arg<long>(a, 2), ldr = arg<long>(a, 7), plane = arg<long>(a, 8);
-        const int width = arg<int>(a, 3), L = arg<int>(a, 5);
-        int8_t *res = arg<int8_t *>(a, 6);
+    } else if (f == (const void *)emu_split_fixed_kernel) {      // one wave per row, four rows per workgroup
+        const long ldx = arg<long>(a, 1), real = arg<long>(a, 2), rp = arg<long>(a, 3), ldr = arg<long>(a, 8), plane = arg<long>(a, 9);
+        const int width = arg<int>(a, 4), L = arg<int>(a, 6);
+        int8_t *res = arg<int8_t *>(a, 7);
         (void)ldx;
-        CHECK(real <= (long)g.x && g.x % 256 == 0, "split rows");
-        CHECK(inside(res, 0, (size_t)(L - 1) * plane + (size_t)(g.x - 1) * ldr + width - 1), "fixed split writes outside the image");
+        CHECK(real <= rp && rp % 256 == 0 && (long)g.x * 4 >= rp, "split rows");
+        CHECK(width % 16 == 0 && width <= 1024 && ldr % 16 == 0 && plane % 16 == 0 && (uintptr_t)res % 16 == 0, "fixed split: 16-byte stores");
+        CHECK(inside(res, 0, (size_t)(L - 1) * plane + (size_t)(rp - 1) * ldr + width - 1), "fixed split writes outside the image");
         CHECK((size_t)L * plane <= ((size_t)1 << 31), "a row tile's image spans more than 2 GiB");
-        CHECK(inside(arg<int *>(a, 9), 0, 4 * real - 1), "fixed split scales");
+        CHECK(inside(arg<int *>(a, 10), 0, 4 * real - 1) && inside(arg<int *>(a, 11), 0, 3), "fixed split scales / status");
         auto it = g_blocks.upper_bound((char *)res);
         const long off = it == g_blocks.begin() ? 0 : (long)((char *)res - (--it)->first), q = off % ldr / 1024;
         if (off < ldr) CHECK(g_split.insert(q).second, "slab %ld split twice", q);      // (the first row tile's launch)
         else CHECK(g_split.count(q) == 1, "slab %ld: a later row tile first", q);
-        printf("  split slab rows %u\n", g.x);
-    } else if (f == (const void *)emu_split_kernel) {
-        const long real = arg<long>(a, 2), plane = arg<long>(a, 7);
-        const int K = arg<int>(a, 3), L = arg<int>(a, 5);
-        CHECK(real <= (long)g.x && plane == (long)g.x * K, "B split shape");
-        CHECK(inside(arg<int8_t *>(a, 6), 0, (size_t)L * plane - 1) && inside(arg<int *>(a, 8), 0, 4 * g.x - 1), "B split writes outside its tile");
+        printf("  split slab rows %ld\n", rp);
+    } else if (f == (const void *)emu_row_scale_kernel) {        // one workgroup per padded row: writes every scale of the tile
+        const long real = arg<long>(a, 2);
+        CHECK(real <= (long)g.x && inside(arg<int *>(a, 5), 0, 4 * g.x - 1), "B scales outside their block");
+        printf("  B scales %u x %d\n", g.x, arg<int>(a, 3));
+    } else if (f == (const void *)emu_split_kernel) {            // one wave per (row, stretch of 1024 columns)
+        const long real = arg<long>(a, 2), rp = arg<long>(a, 3), plane = arg<long>(a, 7);
+        const int K = arg<int>(a, 4), L = arg<int>(a, 5);
+        CHECK(real <= rp && plane == rp * K && (long)g.x * 4 >= rp * ((K + 1023) / 1024), "B split shape");
+        CHECK(K % 16 == 0 && plane % 16 == 0 && (uintptr_t)arg<int8_t *>(a, 6) % 16 == 0, "B split: 16-byte stores");
+        CHECK(inside(arg<int8_t *>(a, 6), 0, (size_t)L * plane - 1) && inside(arg<const int *>(a, 8), 0, 4 * real - 1), "B split writes outside its tile");
         for (long q = 0; q < K / 1024; ++q) CHECK(g_split.count(q) == 1, "slab %ld read before it was split", q);
-        printf("  split B %u x %d\n", g.x, K);
+        printf("  split B %ld x %d\n", rp, K);
     } else if (f == (const void *)emu_i8_gemm_kernel) {
         const long sa = arg<long>(a, 2), sb = arg<long>(a, 3), ldr = arg<long>(a, 6), sr = arg<long>(a, 7);
         const int K = arg<int>(a, 4), tm = arg<int>(a, 8), tn = arg<int>(a, 9), lda = arg<int>(a, 10);
