@@ -206,7 +206,9 @@ int gpx_symv(const double *M, int64_t n, const double *V, int nrhs, double *out)
  * matrix.  gpx_spgp_predict returns what GaussianProcess.estimate_many (GaussianProcess.py:68-80) computes with
  * cov = SPGPCovariance: mean = Q_*N Kinv t (WITHOUT meant), var = v + vt - diag(Q_*N Kinv Q_N*), Kinv the Woodbury
  * inverse of :835-863.  gpx_spgp_nll is Snelson's likelihood (:981-1019, jitter 1e-6).  gpx_spgp_dense / _cross
- * materialise cov_matrix(x) (which=0), inv_cov_matrix(x) (which=1) and cov_matrix_ij(xi,xj) for the accessors. */
+ * materialise cov_matrix(x) (which=0), inv_cov_matrix(x) (which=1) and cov_matrix_ij(xi,xj) for the accessors.
+ * Every input (x, xb, the queries) is taken from the first training row before it is scaled: results do not change when all
+ * inputs are translated together (exactly so when the translation is exact in fp64). */
 typedef struct gpx_spgp gpx_spgp;
 int gpx_spgp_fit(const double *x, const double *t_centered, int64_t n, int d, const double *theta, const double *xb,
                  int64_t m, gpx_spgp **out);
@@ -222,6 +224,9 @@ int gpx_spgp_nll(gpx_spgp *h, double *nll);
 int gpx_spgp_nll_grad(gpx_spgp *h, double *grad_out);
 int gpx_spgp_dense(gpx_spgp *h, int which, double *out /* [n,n] */);
 int gpx_spgp_cross(gpx_spgp *h, const double *xi, int64_t n1, const double *xj, int64_t n2, double *out /* [n1,n2] */);
+/* *chunks = the number of K-chunks the fit chose for this model's rank-N products (K_MN Lambda^-1 K_NM, A, the gradient's Qb), 0 when each
+ * runs as one plain launch.  GPX_SPGP_SPLIT (read at every fit) overrides the choice; a value that does not divide npad / 128 gives 0. */
+int gpx_spgp_split(const gpx_spgp *h, int *chunks);
 
 /* ---- measurement: per-kernel-class GPU timings taken with HIP events on the handle's stream ----
  * gpx_profile_enable(h,1) brackets every launch of the listed kernel classes with an event pair;

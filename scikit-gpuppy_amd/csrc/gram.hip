@@ -13,14 +13,15 @@ constexpr int GR_COLS = 128;   // columns of one block tile (64 lanes x 2 adjace
 enum { PAD_NONE = 0, PAD_ZERO = 1, PAD_IDENT = 2 };
 
 __global__ __launch_bounds__(256) void scale_rows_kernel(const double *__restrict__ x, long n, long npad, int d,
-                                                        const double *__restrict__ sw, double *__restrict__ out)
+                                                        const double *__restrict__ sw, double *__restrict__ out,
+                                                        const double *__restrict__ origin)
 {
     long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
     long total = npad * d;
     if (e >= total) return;
     long i = e / d;
     int k = (int)(e - i * d);
-    out[e] = (i < n) ? x[e] * sw[k] : 0.0;
+    out[e] = (i < n) ? (origin ? x[e] - origin[k] : x[e]) * sw[k] : 0.0;
 }
 
 // The rows' inputs are WAVE-UNIFORM (a wave owns 16 rows, a lane two columns): they are read straight from global memory through
@@ -129,12 +130,12 @@ __global__ __launch_bounds__(256) void gram_kernel(const double *__restrict__ xi
     }
 }
 
-int launch_scale_rows(const double *x, int64_t n, int64_t npad, int d, const double *sw_dev, double *out, hipStream_t s)
+int launch_scale_rows(const double *x, int64_t n, int64_t npad, int d, const double *sw_dev, double *out, hipStream_t s, const double *origin_dev)
 {
     long total = npad * d;
     if (total == 0) return 0;
     int blocks = (int)((total + 255) / 256);
-    hipLaunchKernelGGL(scale_rows_kernel, dim3(blocks), dim3(256), 0, s, x, (long)n, (long)npad, d, sw_dev, out);
+    hipLaunchKernelGGL(scale_rows_kernel, dim3(blocks), dim3(256), 0, s, x, (long)n, (long)npad, d, sw_dev, out, origin_dev);
     GPX_HIP(hipGetLastError());
     return 0;
 }

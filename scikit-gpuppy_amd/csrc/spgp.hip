@@ -25,6 +25,7 @@ struct gpx_spgp {
     double v = 0, vt = 0;
     hipStream_t stream = nullptr;
     double *xw = nullptr, *xbw = nullptr, *sw = nullptr, *t = nullptr;
+    double *org = nullptr;   // [d] the origin every input is taken from before the sqrt(w) scaling: the first training row (spgp_fit_body)
     double *Knm = nullptr;   // [npad, mpad] K_NM, zero padded
     double *Z = nullptr;     // [npad, mpad] scratch (K_NM L^-T for whichever L was applied last)
     double *Wt = nullptr;    // [mpad, npad] scratch: a row-scaled transpose of K_NM or Z
@@ -198,7 +199,7 @@ extern "C" void gpx_spgp_free(gpx_spgp *h)
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void *bufs[] = {h->xw, h->xbw, h->sw, h->t, h->Knm, h->Z, h->Wt, h->LM, h->DinvM, h->diagM, h->LB, h->DinvB, h->diagB, h->scrA, h->scrB, h->LinvM, h->LinvB, h->lam,
+    void *bufs[] = {h->xw, h->xbw, h->sw, h->org, h->t, h->Knm, h->Z, h->Wt, h->LM, h->DinvM, h->diagM, h->LB, h->DinvB, h->diagB, h->scrA, h->scrB, h->LinvM, h->LinvB, h->lam,
                     h->ilam, h->va, h->vb, h->vc, h->ma, h->mb, h->mzero, h->beta, h->mscr, h->outd};
     for (void *p : bufs) dfree(p);
     if (h->info) dfree(h->info);
@@ -265,7 +266,7 @@ static int spgp_fit_body(gpx_spgp *h, const double *x, const double *t_centered,
     if (!(h->stream = stream_acquire(0))) { gpx_set_error("stream creation failed"); return GPX_ERR_HIP; }
     hipStream_t s = h->stream;
     const int64_t tt = h->mblk * (int64_t)TILE * TILE;
-    GPX_TRY(dalloc(&h->xw, np * d)); GPX_TRY(dalloc(&h->xbw, mp * d)); GPX_TRY(dalloc(&h->sw, d)); GPX_TRY(dalloc(&h->t, np));
+    GPX_TRY(dalloc(&h->xw, np * d)); GPX_TRY(dalloc(&h->xbw, mp * d)); GPX_TRY(dalloc(&h->sw, d)); GPX_TRY(dalloc(&h->org, d)); GPX_TRY(dalloc(&h->t, np));
     GPX_TRY(dalloc(&h->Knm, np * mp)); GPX_TRY(dalloc(&h->Z, np * mp)); GPX_TRY(dalloc(&h->Wt, mp * np));
     GPX_TRY(dalloc(&h->LM, mp * mp)); GPX_TRY(dalloc(&h->DinvM, tt)); GPX_TRY(dalloc(&h->diagM, mp));
     GPX_TRY(dalloc(&h->LB, mp * mp)); GPX_TRY(dalloc(&h->DinvB, tt)); GPX_TRY(dalloc(&h->diagB, mp));
@@ -291,12 +292,17 @@ static int spgp_fit_body(gpx_spgp *h, const double *x, const double *t_centered,
     GPX_HIP(hipMemcpyAsync(h->Z, x, sizeof(double) * n * d, hipMemcpyDefault, s));
     GPX_HIP(hipMemcpyAsync(h->LB, xb, sizeof(double) * m * d, hipMemcpyDefault, s));
     GPX_HIP(hipMemcpyAsync(h->sw, sw, sizeof(double) * d, hipMemcpyHostToDevice, s));
+    // The Gram kernel takes direct differences, but the gradient assembles sum E (xb - x)^2 from the moments sum E, sum E x, sum E x^2
+    // (spgp_epass_kernel), which lose (|x| / |xb - x|)^2 digits for data far from zero.  So every input -- x, xb, and later the queries of
+    // gpx_spgp_predict / gpx_spgp_cross -- is taken from one origin, the first training row, in the pass that scales it.  A common
+    // translation changes no difference, so no formula gains a term; inputs translated together on a grid give the same bits.
+    GPX_HIP(hipMemcpyAsync(h->org, x, sizeof(double) * d, hipMemcpyDefault, s));
     GPX_HIP(hipMemsetAsync(h->t, 0, sizeof(double) * np, s));
     GPX_HIP(hipMemcpyAsync(h->t, t_centered, sizeof(double) * n, hipMemcpyDefault, s));
     GPX_HIP(hipMemsetAsync(h->mzero, 0, sizeof(double) * mp, s));
     GPX_HIP(hipStreamSynchronize(s));
-    GPX_TRY(launch_scale_rows(h->Z, n, np, d, h->sw, h->xw, s));
-    GPX_TRY(launch_scale_rows(h->LB, m, mp, d, h->sw, h->xbw, s));
+    GPX_TRY(launch_scale_rows(h->Z, n, np, d, h->sw, h->xw, s, h->org));
+    GPX_TRY(launch_scale_rows(h->LB, m, mp, d, h->sw, h->xbw, s, h->org));
     GPX_HIP(hipStreamSynchronize(s));
 
     // K_NM and L_M = chol(K_M + 1e-5 I)                                        (Covariance.py:843-846)
@@ -356,6 +362,14 @@ extern "C" int gpx_spgp_fit(const double *x, const double *t_centered, int64_t n
     return 0;
 }
 
+// K-chunks of the rank-N products of this model (spgp_wtw): 0 when they run as one plain launch
+extern "C" int gpx_spgp_split(const gpx_spgp *h, int *chunks)
+{
+    if (!h || !chunks) { gpx_set_error("gpx_spgp_split: null argument"); return GPX_ERR_BAD_ARG; }
+    *chunks = h->split_buf ? h->split : 0;
+    return 0;
+}
+
 extern "C" int gpx_spgp_predict(gpx_spgp *h, const double *xs, int64_t ms, double *mean_out, double *var_out)
 {
     GPX_TRY(spgp_require(h));
@@ -375,7 +389,7 @@ extern "C" int gpx_spgp_predict(gpx_spgp *h, const double *xs, int64_t ms, doubl
     for (int64_t q0 = 0; q0 < ms; q0 += chunk) {
         const int64_t qc = std::min<int64_t>(chunk, ms - q0), qp = round_up(qc, TILE);
         GPX_HIP(hipMemcpyAsync(xq, xs + q0 * d, sizeof(double) * qc * d, hipMemcpyDefault, s));
-        GPX_TRY(launch_scale_rows(xq, qc, qp, d, h->sw, xqw, s));
+        GPX_TRY(launch_scale_rows(xq, qc, qp, d, h->sw, xqw, s, h->org));
         GPX_TRY(launch_gram(xqw, qc, h->xbw, h->m, d, h->v, 0.0, 0, 1, Ka, mp, qp, mp, s, nullptr));   // K_*M
         GPX_TRY(launch_predict_reduce(Ka, mp, qc, mp, h->beta, 0.0, mean, unused, s, nullptr));       // K_*M beta
         // K_*M L^-T for both factors: one product each with the explicit inverse (zero triangle skipped)
@@ -661,7 +675,7 @@ extern "C" int gpx_spgp_nll_grad(gpx_spgp *h, double *grad_out)
     GPX_HIP(hipMemcpyAsync(xbw.data(), h->xbw, sizeof(double) * mp * d, hipMemcpyDeviceToHost, s));
     GPX_HIP(hipMemcpyAsync(&sg, sgd, sizeof(double), hipMemcpyDeviceToHost, s));
     GPX_HIP(hipStreamSynchronize(s));
-    // assemble (coordinates scaled by sqrt(w): (xb - x)^2 w = (xbw - xw)^2)
+    // assemble (coordinates centred on the origin and scaled by sqrt(w): (xb - x)^2 w = (xbw - xw)^2)
     std::vector<double> g((size_t)(2 + d + m * d));
     double sE = 0.0, sF = 0.0;
     for (int64_t j = 0; j < m; ++j) { sE += PE[(size_t)j * W]; sF += PF[(size_t)j * W]; }
@@ -728,7 +742,7 @@ extern "C" int gpx_spgp_cross(gpx_spgp *h, const double *xi, int64_t n1, const d
     double *raw = nullptr, *xw = nullptr, *Z1 = nullptr, *Z2 = nullptr, *C = nullptr;
     auto side = [&](const double *x, int64_t n, int64_t p, double *Zout) -> int {
         GPX_HIP(hipMemcpyAsync(raw, x, sizeof(double) * n * d, hipMemcpyDefault, s));
-        GPX_TRY(launch_scale_rows(raw, n, p, d, h->sw, xw, s));
+        GPX_TRY(launch_scale_rows(raw, n, p, d, h->sw, xw, s, h->org));
         GPX_TRY(launch_gram(xw, n, h->xbw, h->m, d, h->v, 0.0, 0, 1, Zout, mp, p, mp, s, nullptr));
         return trsm_right_lt(Zout, mp, p, h->LM, mp, h->DinvM, 0, h->mblk, s, nullptr);
     };

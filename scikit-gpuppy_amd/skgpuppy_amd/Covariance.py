@@ -479,6 +479,12 @@ class _SPGPDeviceModel(object):
         _gpx.check(_gpx.lib.gpx_spgp_nll_grad(self.handle, _gpx.ptr(out)), "gpx_spgp_nll_grad")
         return out
 
+    def split(self):
+        """K-chunks of this model's rank-N products (0: one plain launch each)"""
+        out = ctypes.c_int()
+        _gpx.check(_gpx.lib.gpx_spgp_split(self.handle, ctypes.byref(out)), "gpx_spgp_split")
+        return out.value
+
     def dense(self, which):
         out = np.empty((self.n, self.n))
         _gpx.check(_gpx.lib.gpx_spgp_dense(self.handle, which, _gpx.ptr(out)), "gpx_spgp_dense")

@@ -1109,10 +1109,11 @@ def test_spgp_gradient_and_bad_arguments():
     assert np.isfinite(cov._negativeloglikelihood(x, tc, start))
 
 
-@pytest.mark.parametrize("N,d,m", [(300, 2, 7), (1500, 3, 130), (5000, 10, 257), (20000, 4, 300)])
+@pytest.mark.parametrize("N,d,m", [(300, 2, 7), (1500, 3, 130), (5000, 10, 257), (20000, 4, 300), (20480, 4, 300)])
 def test_spgp_analytic_gradient_against_oracle(N, d, m):
     """gpx_spgp_nll_grad on ragged shapes: m below / across / above a 128-tile, d above one 8-coordinate chunk of the
-    E-pass, N across the split-K threshold of the rank-N products."""
+    E-pass, N beyond the split-K threshold of the rank-N products -- where 20000 still runs unsplit (npad / 128 = 157 is prime)
+    and 20480 splits."""
     rng = np.random.RandomState(N + m)
     x = rng.uniform(0, 10, (N, d))
     t = np.sin(0.3 * x.sum(1)) + 0.1 * rng.randn(N)
@@ -1128,6 +1129,7 @@ def test_spgp_analytic_gradient_against_oracle(N, d, m):
     # likelihood and gradient share their N m^2 part (spgp_snelson_prepare): a gradient right behind a likelihood on the same device model
     # (an L-BFGS step) finds it done, any other call in between clears it -- the same bits either way
     dev = cov._fit_model(x, t, th)
+    assert (dev.split() >= 2) == (N == 20480)
     np.testing.assert_array_equal(cov._d_nll_d_theta(x, t, th), gr)            # behind the likelihood above
     assert dev.nll() == nll and dev.nll() == nll                                 # behind a gradient (reuses the factor of A), then behind a likelihood
     np.testing.assert_array_equal(dev.nll_grad(), gr)                            # behind likelihoods that followed a gradient (Z was overwritten: rebuilt)
@@ -1167,13 +1169,16 @@ def test_spgp_full_size_properties():
     np.testing.assert_allclose(vs, vd, rtol=0, atol=5e-3)
 
 
-def test_spgp_split_k_path():
-    """N >= 16384 takes the split-K product for K_MN Lambda^-1 K_NM (eight concurrent K-chunks + a summation pass):
-    Snelson's likelihood against the oracle's O(N m^2) restatement, predictions against a numpy transcription of the
-    Woodbury algebra (no N x N matrix on either side)."""
-    from scipy.linalg import cholesky, solve_triangular
+@pytest.mark.parametrize("N", [20000, 20480])
+def test_spgp_split_k_path(N):
+    """From N = 16384 on the rank-N products (K_MN Lambda^-1 K_NM, A) may run split over K: one launch over equal chunks of whole
+    128-tiles into partial buffers and a summation pass, the chunk count a divisor of npad / 128 (spgp_pick_split).  N = 20000 has
+    npad / 128 = 157, a prime: no divisor, one plain launch; N = 20480 has 160 and splits (the rule gives 10 chunks).  Which of the
+    two ran is asserted through gpx_spgp_split.  Snelson's likelihood against the oracle's O(N m^2) restatement, predictions against
+    a numpy transcription of the Woodbury algebra (tests/_spgp_ld.py: woodbury_predict; no N x N matrix on either side)."""
+    from _spgp_ld import woodbury_predict
     rng = np.random.RandomState(31)
-    N, d, m = 20000, 4, 300
+    d, m = 4, 300
     x = rng.uniform(0, 10, (N, d))
     t = np.sin(0.3 * x.sum(1)) + 0.1 * rng.randn(N)
     th_gc = np.log(np.array([2.0, 0.01] + [0.04] * d))
@@ -1185,15 +1190,11 @@ def test_spgp_split_k_path():
     assert cov._negativeloglikelihood(x, tc, th) == pytest.approx(orc.spgp_nll(x, tc, th, m), rel=1e-8)
     gp = sk.GaussianProcess(x, t, cov, th.copy())
     mu, var = gp.estimate_many(xs)
-    Knm, Km = orc.gram_ij(x, xb, th_gc), orc.gram_ij(xb, xb, th_gc)
-    Lm = cholesky(Km + 1e-5 * np.eye(m), lower=True)
-    lam = 2.0 + 0.01 - (solve_triangular(Lm, Knm.T, lower=True) ** 2).sum(0)
-    B = Km + 1e-5 * np.eye(m) + (Knm.T / lam).dot(Knm)
-    Lb = cholesky(B, lower=True)
-    beta = np.linalg.solve(B, (Knm.T / lam).dot(tc))
-    Ks = orc.gram_ij(xs, xb, th_gc)
-    want_mu = Ks.dot(beta) + t.mean()
-    want_var = 2.01 - (solve_triangular(Lm, Ks.T, lower=True) ** 2).sum(0) + (solve_triangular(Lb, Ks.T, lower=True) ** 2).sum(0)
+    for dev in (cov._fit_model(x, tc, th), gp._dev()):
+        chunks = dev.split()
+        assert chunks == 0 if N == 20000 else chunks >= 2, chunks
+    want_mu, want_var = woodbury_predict(x, tc, th, m, xs)
+    want_mu = want_mu + t.mean()
     np.testing.assert_allclose(mu, want_mu, rtol=0, atol=2e-5)
     np.testing.assert_allclose(var, want_var, rtol=0, atol=2e-6)
 
