@@ -37,6 +37,10 @@ static inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * 
 // Plain Cody-Waite: n = rint(x log2 e), r = x - n ln2 (two-term), degree-12 Taylor polynomial on |r| <= ln2/2
 // (truncation 1.7e-16), scaled by v_ldexp_f64 (which also produces the denormal / zero results for very negative x).
 // ~18 fp64 ops instead of the ~45 of the generic exp; within 2 ulp of it.
+// Nothing in it needs x <= 0: the reduction is exact for |n| < 2^20 (ln2's high part ends in 21 zero bits) and ldexp scales
+// either way, so a positive x below 709 is as accurate -- the explicit Exact path (exact_build_generic_kernel) sends exponents of
+// +200 through it (tests/test_dense_bounds.py, test_exact_explicit_positive_exponents).  Only the clamp is one-sided: from 709.8
+// on the result is +inf, as exp's.
 static __device__ __forceinline__ double exp_nonpos(double x)
 {
     x = fmax(x, -750.0);

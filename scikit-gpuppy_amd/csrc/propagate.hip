@@ -470,8 +470,9 @@ __global__ __launch_bounds__(256) void exact_build_kernel(const double *__restri
     lm[i] = Ci * nc1 * exp(0.5 * qd);
 }
 
-// exp(x) for the pair kernel: x = e_i + e_j + b_i.a_j is <= ~0 by construction (it is the log of L_ij / (F_i F_j nc2),
-// a product of Gaussian factors), so exp_nonpos (common.h) serves.
+// exp(x) for the pair kernel: on the built-in path x = e_i + e_j + b_i.a_j is <= ~0 by construction (it is the log of
+// L_ij / (F_i F_j nc2), a product of Gaussian factors); on the explicit path (exact_build_generic_kernel) the kernel's own factor
+// stays in F and x = z^T Ls z / 2 >= 0.  exp_nonpos (common.h) serves both: it is as accurate for positive arguments.
 // S = sum_ij (Kinv_ij - beta_i beta_j) F_i F_j exp(e_i + e_j + b_i . a_j); the caller multiplies by nc2.
 // Kinv and L_ij are symmetric: only the pairs j <= i are visited (weight 2 off the diagonal), halving both the
 // HBM bytes (4 N^2) and the exp count of the reference's full double loop (UncertaintyPropagation2.pyx:173-179).

@@ -127,6 +127,39 @@ def test_against_oracle_ragged_batches(N, B):
     print("oracle N=%d B=%d: worst dmean %.3e dvar %.3e dsigma2 %.3e drest %.3e" % ((N, B) + tuple(worst)))
 
 
+_EDGE = {}       # d -> (gp, x)
+
+
+def _edge_gp(d, N=640):
+    """the ragged recipe with the length scales kept alive at large d (w = 0.04 * 3 / d)"""
+    if d not in _EDGE:
+        rng = np.random.RandomState(100 + N + d)
+        x = rng.uniform(0, 10, (N, d))
+        t = np.sin(0.3 * x.sum(1)) + 0.1 * rng.randn(N)
+        theta = np.log(np.array([2.0, 0.01] + [0.04 * 3.0 / d] * d))
+        _EDGE[d] = (sk.GaussianProcess(x, t, sk.GaussianCovariance(), theta.copy()), x)
+    return _EDGE[d]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B", [3, 130])
+@pytest.mark.parametrize("d", [1, 9, 64])
+def test_ragged_batches_against_the_single_call_at_the_variant_edges(d, B):
+    """(2b) d = 9 is the first d of approx_build_many_kernel<0> (differences recomputed from the LDS tile), d = 1 and d = 64 are the ends of
+    the range (64: a 64 KB tile); N = 640, the inputs of (2), every input of the batch against propagate_GA.  Bound: twice the oracle
+    tolerance of each device path (module docstring), v = 2."""
+    gp, x = _edge_gp(d)
+    U, S = _inputs(x, B, d, 640 + B)
+    mean, var = sk.UncertaintyPropagationApprox(gp).propagate_GA_many(U, S)
+    assert np.isfinite(mean).all() and np.isfinite(var).all()
+    dm = dv = 0.0
+    for i in range(B):
+        m1, v1 = sk.UncertaintyPropagationApprox(gp).propagate_GA(U[i], S[i])
+        dm, dv = max(dm, abs(mean[i] - m1)), max(dv, abs(var[i] - v1))
+        assert mean[i] == pytest.approx(m1, abs=2 * 1e-9) and var[i] == pytest.approx(v1, abs=2 * 1e-8 * 2.0), i
+    print("single call d=%d B=%d: worst dmean %.3e dvar %.3e" % (d, B, dm, dv))
+
+
 def _child(args, extra, timeout=600):
     env = dict(os.environ)
     env.update(extra)
