@@ -163,6 +163,19 @@ int gpx_propagate_dvh(gpx_handle *h, const double *u, double *dvh_out /* [d] */)
  * (skgpuppy/UncertaintyPropagation.py:246-379, UncertaintyPropagation2.pyx:57-184) ----
  * mean WITHOUT meant; var = (v+vt) - sum_ij (Kinv_ij - beta_i beta_j) L_ij - mean^2. */
 int gpx_propagate_exact(gpx_handle *h, const double *u, const double *Sigma, double *mean, double *var);
+/* The same for b inputs in ONE call (no reference counterpart: it replaces a caller's loop over propagate_GA).  U [b, d]; Sigma [b, d, d], or
+ * ONE [d, d] matrix for every input when sigma_shared != 0; mean [b] (WITHOUT meant) is required, var [b] may be NULL: the means alone, K^-1
+ * is then neither built nor read and no GEMM is launched.  Host or device pointers; b = 0 is a no-op.  For inputs that share Sigma the pair
+ * weight factorises (a_i = u - x_i, A = Sigma + W^-1 / 2, Ls = sym(2 W - A^-1), F_i = v or v + vt on exact equality):
+ *   L_ij / nc2 = h_i(u) h_j(u) E_ij,   h_i(u) = F_i exp(-1/4 a_i^T A^-1 a_i),   E_ij = exp(-1/8 (x_i - x_j)^T Ls (x_i - x_j)),
+ *   so the double sum is h^T M h with M = (Kinv - beta beta^T) o E built once per Sigma: one pass over the lower half of K^-1, then
+ *   Y = H Lo^T for a slab of inputs on the fp64 GEMM with a triangular B (GPX_GEMM_TRI_B_LOWER) and 2 sum_j Y_ij H_ij per input.
+ * With per-input Sigma the batch is cut into runs of consecutive bit-equal Sigma: a run of GPX_EXACT_MANY_MIN_RUN (default 5) inputs or more
+ * takes that path, a shorter one the arithmetic of gpx_propagate_exact (the same bits), queued without a synchronisation in between.
+ * GPX_EXACT_MANY_SLAB (default 4096, a multiple of 128): inputs per product.  Both are read at every call.  Every Sigma is checked before the
+ * first launch (a singular W/2 + Sigma: GPX_ERR_BAD_ARG, nothing written).  An input's result does not depend on its place in the batch; the
+ * state of the single-input calls is left alone; the call may build K^-1 on the handle, as gpx_propagate_exact does. */
+int gpx_propagate_exact_many(gpx_handle *h, const double *U, const double *Sigma, int sigma_shared, int64_t b, double *mean, double *var);
 /* row-sharded form (multi-GPU host): partial_out[3] = { sum_{i in rows} beta_i l_i, the rows' share of the double sum / nc2,
  * nc2 }; summed over the row panels: mean = p0, var = v + vt - nc2 p1 - p0^2.  Same row alignment as gpx_propagate_approx_rows. */
 int gpx_propagate_exact_rows(gpx_handle *h, const double *u, const double *Sigma, int64_t row0, int64_t row1, double *partial_out);

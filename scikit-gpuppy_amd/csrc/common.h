@@ -378,6 +378,18 @@ int launch_exact_build_generic(const double *x, int64_t n, int64_t npad, int d, 
                                const double *dinv_diag_dev, const double *C_dev, double nc1, double *aT, double *bT, double *e, double *F,
                                double *lm, hipStream_t s);
 
+// batched Exact (gpx_propagate_exact_many): coordinates transformed for a signed sum of squares, the weighted lower half of K^-1,
+// a slab's H and mean partials (H == nullptr: the means alone), the row products with Y = H Lo^T
+int launch_exact_many_transform(const double *x, int64_t n, int64_t npad, int d, const double *x0_dev, const double *T_dev, double *out,
+                                hipStream_t s);
+int launch_exact_weight(const double *Kinv, int64_t ld, int64_t n, int64_t npad, int d, const double *beta, const double *xt,
+                        const double *sgn_dev, double *Lo, hipStream_t s, Profiler *prof);
+int launch_exact_many_build(const double *x, const double *xh, int64_t n, int64_t npad, int d, const double *U_dev, const double *Uh_dev,
+                            int64_t nb, int64_t rows_pad, const double *w_dev, const double *dinv_diag_dev, const double *sgn_dev,
+                            const double *beta, double v, double vt, double nc1, double *H, double *mpart, hipStream_t s, Profiler *prof);
+int launch_exact_many_finish(const double *Y, const double *H, int64_t npad, const double *mpart, int64_t nb, double vplusvt, double nc2,
+                             double *out, int64_t ldo, hipStream_t s, Profiler *prof);
+
 // ---- host orchestration shared by fit.hip, predict.hip and propagate_api.hip ---------------------
 // (helpers, not interface: they stay out of the library's dynamic symbol table)
 #pragma GCC visibility push(hidden)

@@ -751,3 +751,230 @@ int launch_exact_build(const double *x, int64_t n, int64_t npad, int d, const do
     GPX_HIP(hipGetLastError());
     return 0;
 }
+
+// ---------------------------------------------------------------------------------------------
+// Batched Exact (gpx_propagate_exact_many): for every input u that shares one Sigma the pair weight factorises,
+//   L_ij / nc2 = h_i(u) h_j(u) E_ij,   h_i(u) = F_i exp(-1/4 a_i^T A^-1 a_i),   E_ij = exp(-1/8 (x_i - x_j)^T Ls (x_i - x_j)),
+// (a_i = u - x_i, A = Sigma + W^-1 / 2; a_i - a_j does not hold u and -W / 2 + Ls / 4 = -A^-1 / 4), so the double sum of
+// exact_sum_kernel is the quadratic form h^T M h with M = (Kinv - beta beta^T) o E built ONCE per Sigma.  Both quadratic forms run on
+// coordinates transformed by the eigenvectors of their matrix (sym_eig.h): a signed sum of d squared DIFFERENCES per pair.
+// ---------------------------------------------------------------------------------------------
+// out[i][k] = sum_m T[k][m] (x[i][m] - x0[m]) for i < n, zero rows from n to npad
+__global__ __launch_bounds__(256) void exact_many_transform_kernel(const double *__restrict__ x, long n, long npad, int d,
+                                                                  const double *__restrict__ x0, const double *__restrict__ T,
+                                                                  double *__restrict__ out)
+{
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= npad * d) return;
+    const long i = e / d;
+    const int k = (int)(e - i * d);
+    double s = 0.0;
+    if (i < n)
+        for (int m = 0; m < d; ++m) s = fma(T[k * d + m], x[i * d + m] - x0[m], s);
+    out[e] = s;
+}
+
+int launch_exact_many_transform(const double *x, int64_t n, int64_t npad, int d, const double *x0_dev, const double *T_dev, double *out,
+                                hipStream_t s)
+{
+    if (npad <= 0) return 0;
+    hipLaunchKernelGGL(exact_many_transform_kernel, dim3((unsigned)((npad * d + 255) / 256)), dim3(256), 0, s, x, (long)n, (long)npad, d,
+                       x0_dev, T_dev, out);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// Lo (ld = npad) from the j <= i half of Kinv, one 64 x 64 tile per workgroup:
+//   Lo_ij = (Kinv_ij - beta_i beta_j) exp(-sum_k s_k (xt_ik - xt_jk)^2) for j < i, half of it for j == i, 0 for j > i and for i, j >= n.
+// The workgroups past the triangle clear the one 64 x 64 tile above the diagonal inside every 128 x 128 tile that the diagonal crosses
+// (the read contract of a triangular GEMM operand, gpx.h); tiles wholly above the diagonal are neither written nor read.
+// LDS: the tile's rows [64][d] (broadcast reads) and columns [d][64] (k-major, lane = column): 64 KB at d = 64, two workgroups per CU.
+// Thread = column j (512-byte loads and stores per wave and row), wave w = rows w, w + 4, ..
+constexpr int EW_T = 64;
+__global__ __launch_bounds__(256, 2) void exact_weight_kernel(const double *__restrict__ Kinv, long ld, long n, long npad, int d,
+                                                             const double *__restrict__ beta, const double *__restrict__ xt,
+                                                             const double *__restrict__ sgn, double *__restrict__ Lo)
+{
+    extern __shared__ __attribute__((aligned(16))) double ew_smem[];
+    double *xi_s = ew_smem;                // [64][d]
+    double *xj_s = ew_smem + EW_T * d;     // [d][64]
+    const int t = threadIdx.x, c = t & 63, w = t >> 6;
+    const long nt = npad / EW_T, ntri = nt * (nt + 1) / 2;
+    const long idx = blockIdx.x;
+    if (idx >= ntri) {
+        const long ti = 2 * (idx - ntri);          // even tile row: the tile to its right lies in the same 128 x 128 diagonal tile
+        if (ti + 1 >= nt) return;
+        const long i0 = ti * EW_T, j0 = (ti + 1) * EW_T;
+        for (int r = w; r < EW_T; r += 4) Lo[(i0 + r) * ld + j0 + c] = 0.0;
+        return;
+    }
+    long ti = (long)((sqrt(8.0 * (double)idx + 1.0) - 1.0) * 0.5);
+    while (ti * (ti + 1) / 2 > idx) --ti;
+    while ((ti + 1) * (ti + 2) / 2 <= idx) ++ti;
+    const long tj = idx - ti * (ti + 1) / 2;
+    const long i0 = ti * EW_T, j0 = tj * EW_T;
+    for (int e = t; e < EW_T * d; e += 256) {
+        xi_s[e] = xt[i0 * d + e];
+        const int cc = e / d, k = e - cc * d;
+        xj_s[k * EW_T + cc] = xt[j0 * d + e];
+    }
+    __syncthreads();
+    double acc[EW_T / 4];
+#pragma unroll
+    for (int r = 0; r < EW_T / 4; ++r) acc[r] = 0.0;
+    for (int k = 0; k < d; ++k) {
+        const double xj = xj_s[k * EW_T + c], sk = sgn[k];
+#pragma unroll
+        for (int r = 0; r < EW_T / 4; ++r) {
+            const double df = xi_s[(w + 4 * r) * d + k] - xj;
+            acc[r] = fma(sk * df, df, acc[r]);
+        }
+    }
+    const long j = j0 + c;
+    const double bj = beta[j];
+#pragma unroll
+    for (int r = 0; r < EW_T / 4; ++r) {
+        const long i = i0 + w + 4 * r;
+        const double val = (Kinv[i * ld + j] - beta[i] * bj) * exp_nonpos(-acc[r]);
+        Lo[i * ld + j] = (i >= n || j > i) ? 0.0 : (j == i ? 0.5 * val : val);
+    }
+}
+
+int launch_exact_weight(const double *Kinv, int64_t ld, int64_t n, int64_t npad, int d, const double *beta, const double *xt,
+                        const double *sgn_dev, double *Lo, hipStream_t s, Profiler *prof)
+{
+    if (npad % TILE || ld < npad) { gpx_set_error("exact_weight: bad shape"); return GPX_ERR_BAD_ARG; }
+    const int64_t nt = npad / EW_T;
+    ProfScope ps(prof, s, GPX_K_EXACT, 0.5 * (double)npad * (double)npad * (2.0 * d + 25.0));
+    hipLaunchKernelGGL(exact_weight_kernel, dim3((unsigned)(nt * (nt + 1) / 2 + nt / 2)), dim3(256), sizeof(double) * 2 * EW_T * d, s, Kinv,
+                       (long)ld, (long)n, (long)npad, d, beta, xt, sgn_dev, Lo);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// A slab of inputs: H [rows, npad] with H_ij = F_ij exp(-sum_k s_k (uh_ik - xh_jk)^2) (= F exp(-1/4 a^T A^-1 a), a = u_i - x_j, ONE signed
+// sum of squares; F = v + vt iff x_j == u_i elementwise, else v; zero for j >= n), and in the same pass the mean's terms
+// beta_j lm_ij, lm as exact_build_kernel defines it, summed over the workgroup's 64 columns into mpart[i][column tile] (wave shuffle,
+// fixed order; exact_many_finish_kernel adds the tiles).  A workgroup owns 64 columns and EM_INPUTS inputs, four per wave; the raw
+// and the transformed inputs of its columns sit in LDS k-major (64 KB at d = 64); u, uh, w, dd, sgn are wave-uniform loads.
+// WANT_H = false: the means alone, nothing of xh / Uh / sgn / H is touched.
+constexpr int EM_COLS = 64;
+constexpr int EM_INPUTS = 16;
+template <bool WANT_H>
+__global__ __launch_bounds__(256) void exact_many_build_kernel(const double *__restrict__ x, const double *__restrict__ xh, long n, long npad,
+                                                              int d, const double *__restrict__ U, const double *__restrict__ Uh, long nb,
+                                                              const double *__restrict__ w, const double *__restrict__ dinv_diag,
+                                                              const double *__restrict__ sgn, const double *__restrict__ beta, double v,
+                                                              double vt, double nc1, double *__restrict__ H, double *__restrict__ mpart,
+                                                              long npart)
+{
+    extern __shared__ __attribute__((aligned(16))) double em_smem[];
+    double *x_s = em_smem;                  // [d][64] raw inputs of the tile's columns
+    double *xh_s = em_smem + EM_COLS * d;   // [d][64] transformed ones (WANT_H)
+    const int t = threadIdx.x;
+    const long col0 = (long)blockIdx.x * EM_COLS;
+    for (int e = t; e < EM_COLS * d; e += 256) {
+        const int cc = e / d, k = e - cc * d;
+        const long gc = col0 + cc;
+        x_s[k * EM_COLS + cc] = (gc < n) ? x[gc * d + k] : 0.0;
+        if constexpr (WANT_H) xh_s[k * EM_COLS + cc] = xh[gc * d + k];
+    }
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
+    const long j = col0 + lane;
+    const bool inb = j < n;
+    const double bj = beta[j];
+    for (int q = 0; q < EM_INPUTS / 4; ++q) {
+        const long i = (long)blockIdx.y * EM_INPUTS + 4 * q + wave;   // wave-uniform
+        if (i >= nb) break;
+        const double *u = U + i * d;
+        double qw = 0.0, qd = 0.0, qa = 0.0;
+        bool same = true;
+        for (int k = 0; k < d; ++k) {
+            const double xv = x_s[k * EM_COLS + lane], uk = u[k];
+            same = same && (xv == uk);
+            const double ak = uk - xv;
+            qw = fma(w[k] * ak, ak, qw);
+            qd = fma(dinv_diag[k] * ak, ak, qd);
+            if constexpr (WANT_H) {
+                const double df = Uh[i * d + k] - xh_s[k * EM_COLS + lane];
+                qa = fma(sgn[k] * df, df, qa);
+            }
+        }
+        const double c = v * exp(-0.5 * qw);
+        const double Ci = same ? c + vt : c;
+        const double lm = inb ? Ci * nc1 * exp(0.5 * qd) : 0.0;
+        if constexpr (WANT_H) H[i * npad + j] = inb ? (same ? (v + vt) : v) * exp_nonpos(-qa) : 0.0;
+        const double m = wave_sum_p(bj * lm);
+        if (lane == 0) mpart[i * npart + blockIdx.x] = m;
+    }
+}
+
+// H [rows_pad, npad]: rows [0, nb) written by the kernel (every column), the rest of the last 128-row tile cleared; mpart [nb, npad / 64]
+int launch_exact_many_build(const double *x, const double *xh, int64_t n, int64_t npad, int d, const double *U_dev, const double *Uh_dev,
+                            int64_t nb, int64_t rows_pad, const double *w_dev, const double *dinv_diag_dev, const double *sgn_dev,
+                            const double *beta, double v, double vt, double nc1, double *H, double *mpart, hipStream_t s, Profiler *prof)
+{
+    if (nb <= 0) return 0;
+    const bool want_h = H != nullptr;
+    const int64_t ygrid = (nb + EM_INPUTS - 1) / EM_INPUTS;
+    if (npad % EM_COLS || (want_h && nb > rows_pad) || ygrid > 65535) { gpx_set_error("exact_many_build: bad block shape"); return GPX_ERR_BAD_ARG; }
+    // algorithmic flops per (input, column): 7 d for the three sums (4 d without H) and three exponentials at ~20
+    ProfScope ps(prof, s, GPX_K_EXACT, (double)nb * (double)npad * ((want_h ? 7.0 : 4.0) * d + (want_h ? 65.0 : 45.0)));
+    if (want_h && rows_pad > nb) GPX_HIP(hipMemsetAsync(H + nb * npad, 0, sizeof(double) * (rows_pad - nb) * npad, s));
+    const dim3 grid((unsigned)(npad / EM_COLS), (unsigned)ygrid);
+    const long npart = (long)(npad / EM_COLS);
+    if (want_h)
+        hipLaunchKernelGGL(exact_many_build_kernel<true>, grid, dim3(256), sizeof(double) * 2 * EM_COLS * d, s, x, xh, (long)n, (long)npad, d, U_dev,
+                           Uh_dev, (long)nb, w_dev, dinv_diag_dev, sgn_dev, beta, v, vt, nc1, H, mpart, npart);
+    else
+        hipLaunchKernelGGL(exact_many_build_kernel<false>, grid, dim3(256), sizeof(double) * EM_COLS * d, s, x, xh, (long)n, (long)npad, d, U_dev,
+                           Uh_dev, (long)nb, w_dev, dinv_diag_dev, sgn_dev, beta, v, vt, nc1, H, mpart, npart);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// One workgroup per input, fixed order: mean_i = sum of its column-tile partials, S_i = 2 sum_j Y_ij H_ij (Y = H Lo^T: the diagonal of
+// Lo carries half its weight, so twice the lower sum is the full quadratic form), var_i = (v + vt) - nc2 S_i - mean_i^2
+// (UncertaintyPropagation.py:377).  out: [2][ldo] = mean | var; Y == nullptr: the means alone.
+__global__ __launch_bounds__(256) void exact_many_finish_kernel(const double *__restrict__ Y, const double *__restrict__ H, long npad,
+                                                               const double *__restrict__ mpart, long npart, double vplusvt, double nc2,
+                                                               double *__restrict__ out, long ldo)
+{
+    __shared__ double ws[2][4];
+    const long i = blockIdx.x;
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    double m = 0.0, s0 = 0.0, s1 = 0.0;
+    for (long p = t; p < npart; p += 256) m += mpart[i * npart + p];
+    if (Y) {
+        const double *y = Y + i * npad, *hh = H + i * npad;
+        for (long c = 2 * t; c < npad; c += 512) {
+            const v2d a = *reinterpret_cast<const v2d *>(y + c), b = *reinterpret_cast<const v2d *>(hh + c);
+            s0 = fma(a.x, b.x, s0);
+            s1 = fma(a.y, b.y, s1);
+        }
+    }
+    m = wave_sum_p(m);
+    const double sv = wave_sum_p(s0 + s1);
+    if (lane == 0) { ws[0][wave] = m; ws[1][wave] = sv; }
+    __syncthreads();
+    if (t == 0) {
+        const double mean = (ws[0][0] + ws[0][1]) + (ws[0][2] + ws[0][3]);
+        out[i] = mean;
+        if (Y) {
+            const double S = 2.0 * ((ws[1][0] + ws[1][1]) + (ws[1][2] + ws[1][3]));
+            out[ldo + i] = vplusvt - nc2 * S - mean * mean;
+        }
+    }
+}
+
+int launch_exact_many_finish(const double *Y, const double *H, int64_t npad, const double *mpart, int64_t nb, double vplusvt, double nc2,
+                             double *out, int64_t ldo, hipStream_t s, Profiler *prof)
+{
+    if (nb <= 0) return 0;
+    ProfScope ps(prof, s, GPX_K_EXACT, (Y ? 2.0 : 0.0) * (double)nb * (double)npad + (double)nb * (double)(npad / EM_COLS));
+    hipLaunchKernelGGL(exact_many_finish_kernel, dim3((unsigned)nb), dim3(256), 0, s, Y, H, (long)npad, mpart, (long)(npad / EM_COLS), vplusvt,
+                       nc2, out, (long)ldo);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}

@@ -8,6 +8,7 @@
 #include <new>
 
 #include "common.h"
+#include "sym_eig.h"
 
 // ---- propagation -----------------------------------------------------------------------------------
 // layout of h->V: [128][npad] rows 0 = C, 1..d = J_k (rest zero, so the block is one GEMM row tile)
@@ -342,7 +343,7 @@ static int small_inverse(const double *A, int d, double *inv)
 
 // Girard's constants of the Exact moments (UncertaintyPropagation.py:247-257, :292-303; Winv of the reference holds w): the diagonal dd,
 // the normalisers nc1 / nc2 and Ls = the symmetric part of Lambda = 2 W - (Sigma + W^-1 / 2)^-1
-struct ExactConstants { std::vector<double> Ls, dd; double nc1 = 1.0, nc2 = 1.0; };
+struct ExactConstants { std::vector<double> Ls, dd, Ai; double nc1 = 1.0, nc2 = 1.0; };   // Ai = (Sigma + W^-1 / 2)^-1, kept for the batched form
 static int exact_constants(const double *w, const double *Sigma, int d, ExactConstants &c)
 {
     std::vector<double> A((size_t)d * d), Ai((size_t)d * d);
@@ -360,6 +361,7 @@ static int exact_constants(const double *w, const double *Sigma, int d, ExactCon
     for (int i = 0; i < d; ++i)
         for (int j = 0; j < d; ++j) A[(size_t)i * d + j] = Sigma[i * d + j] + (i == j ? 0.5 / w[i] : 0.0);
     if (small_inverse(A.data(), d, Ai.data())) { gpx_set_error("W/2 + Sigma is singular"); return GPX_ERR_BAD_ARG; }
+    c.Ai = Ai;
     for (int i = 0; i < d; ++i)
         for (int j = 0; j < d; ++j) {
             const double lij = (i == j ? 2.0 * w[i] : 0.0) - Ai[(size_t)i * d + j];
@@ -448,6 +450,146 @@ extern "C" int gpx_exact_mean(gpx_handle *h, const double *u, const double *Sigm
     NEED_KERNEL(h, "gpx_exact_mean");
     if (!u || !Sigma || !mean) { gpx_set_error("null argument"); return GPX_ERR_BAD_ARG; }
     return exact_common(h, u, Sigma, false, mean, nullptr);
+}
+
+// Batched Exact: with per-input Sigma the batch is cut into runs of consecutive inputs whose Sigma are bit-equal (one shared Sigma: one
+// run, always on the matrix path).  A run of at least MIN_RUN inputs takes
+// the matrix path -- Lo = the weighted lower half of K^-1 built once (exact_weight_kernel), then per slab of inputs H, Y = H Lo^T on the
+// fp64 GEMM with a triangular B, and the row products (propagate.hip) --, a shorter one the arithmetic of gpx_propagate_exact, input
+// by input, queued without a host synchronisation into device result slots.  Every Sigma's constants are formed, and a singular
+// W/2 + Sigma refused, before the first launch; they travel to the device in ONE block that the host keeps until the call's one
+// synchronisation.  The staged u / Sigma and the cached u of the single-input calls are not touched.
+// MIN_RUN = 5: the smallest run from which the matrix path (one weight pass + one 128-row product, 1.31-1.37 ms at N = 16384, d = 8 whatever
+// the run) stays faster than the pair path (0.31 ms per input), measured at N = 2048 and N = 16384 (profiles/r14_exact_many.txt).
+static int64_t env_count(const char *name, int64_t dflt)
+{
+    const char *e = getenv(name);
+    if (!e || !*e) return dflt;
+    char *end = nullptr;
+    const long long v = strtoll(e, &end, 10);
+    return end == e ? dflt : (int64_t)v;
+}
+
+extern "C" int gpx_propagate_exact_many(gpx_handle *h, const double *U, const double *Sigma, int sigma_shared, int64_t b, double *mean,
+                                        double *var)
+{
+    CHECK_H(h);
+    NEED_KERNEL(h, "gpx_propagate_exact_many");
+    if (b < 0 || (b > 0 && (!U || !Sigma || !mean))) { gpx_set_error("gpx_propagate_exact_many: bad arguments"); return GPX_ERR_BAD_ARG; }
+    if (b == 0) return 0;
+    const int d = h->d;
+    const int64_t n = h->n, np = h->npad, d2 = (int64_t)d * d;
+    const bool want_var = var != nullptr;
+    hipStream_t s = h->stream;
+    const int64_t min_run = std::max<int64_t>(1, env_count("GPX_EXACT_MANY_MIN_RUN", 5));
+    int64_t slab = env_count("GPX_EXACT_MANY_SLAB", 4096);
+    if (slab < TILE || slab % TILE || slab > (1 << 19)) slab = 4096;
+
+    // runs of bit-equal Sigma and their constants, on the host: [Ls d^2 | dd d] and, for a matrix run with variances,
+    // [T of Ls / 8 d^2 | its signs d | T of A^-1 / 4 d^2 | its signs d]
+    struct Run { int64_t i0, cnt; int64_t off; bool matrix; double nc1, nc2; };
+    std::vector<Run> runs;
+    std::vector<double> Sh, arena, res;
+    int64_t max_matrix = 0;
+    bool any_pair = false;
+    try {
+        Sh.resize((size_t)((sigma_shared ? 1 : b) * d2));
+        res.resize((size_t)(2 * b));
+    } catch (const std::bad_alloc &) { gpx_set_error("gpx_propagate_exact_many: out of host memory"); return GPX_ERR_HIP; }
+    GPX_TRY(fetch_small(Sh.data(), Sigma, Sh.size()));
+    for (int64_t i = 0; i < b;) {
+        int64_t j = sigma_shared ? b : i + 1;
+        while (j < b && memcmp(&Sh[(size_t)(i * d2)], &Sh[(size_t)(j * d2)], sizeof(double) * d2) == 0) ++j;
+        runs.push_back({i, j - i, 0, sigma_shared != 0 || j - i >= min_run, 1.0, 1.0});   // one shared Sigma: the matrix path whatever b
+        i = j;
+    }
+    try {
+        for (Run &r : runs) {
+            const double *Sg = &Sh[(size_t)(sigma_shared ? 0 : r.i0 * d2)];
+            ExactConstants c;
+            GPX_TRY(exact_constants(h->w, Sg, d, c));
+            r.nc1 = c.nc1;
+            r.nc2 = c.nc2;
+            r.off = (int64_t)arena.size();
+            arena.insert(arena.end(), c.Ls.begin(), c.Ls.end());
+            arena.insert(arena.end(), c.dd.begin(), c.dd.end());
+            if (r.matrix) max_matrix = std::max(max_matrix, r.cnt);
+            else any_pair = true;
+            if (r.matrix && want_var) {
+                const size_t at = arena.size();
+                arena.resize(at + 2 * (size_t)(d2 + d));
+                sym_square_transform(c.Ls.data(), d, 0.125, &arena[at], &arena[at + d2]);
+                sym_square_transform(c.Ai.data(), d, 0.25, &arena[at + d2 + d], &arena[at + 2 * d2 + d]);
+            }
+        }
+    } catch (const std::bad_alloc &) { gpx_set_error("gpx_propagate_exact_many: out of host memory"); return GPX_ERR_HIP; }
+
+    if (want_var) GPX_TRY(ensure_kinv(h));
+    Scratch sc(s);
+    double *cd = nullptr, *Ud = nullptr, *od = nullptr;
+    GPX_TRY(sc.take(&cd, (int64_t)arena.size()));
+    GPX_TRY(sc.take(&Ud, b * d));
+    GPX_TRY(sc.take(&od, 2 * b));
+    // matrix path: slab rows of H and Y, the transformed inputs, Lo; pair path: ONE block of exact_common's per-input scratch, used by
+    // the inputs of every short run in stream order
+    const int64_t rows = std::min(slab, round_up(std::max<int64_t>(max_matrix, 1), TILE)), npart = np / 64;
+    double *mpart = nullptr, *Hd = nullptr, *Yd = nullptr, *Lo = nullptr, *xt = nullptr, *xh = nullptr, *Uh = nullptr, *pb = nullptr;
+    if (max_matrix > 0) {
+        GPX_TRY(sc.take(&mpart, rows * npart));
+        if (want_var) {
+            GPX_TRY(sc.take(&xt, np * d));
+            GPX_TRY(sc.take(&xh, np * d));
+            GPX_TRY(sc.take(&Uh, rows * d));
+            GPX_TRY(sc.take(&Hd, rows * np));
+            GPX_TRY(sc.take(&Yd, rows * np));
+            GPX_TRY(sc.take(&Lo, np * np));
+        }
+    }
+    if (any_pair) GPX_TRY(sc.take(&pb, (2 * (int64_t)d + 4) * np));
+    GPX_HIP(hipMemcpyAsync(cd, arena.data(), sizeof(double) * arena.size(), hipMemcpyHostToDevice, s));
+    GPX_HIP(hipMemcpyAsync(Ud, U, sizeof(double) * b * d, hipMemcpyDefault, s));
+    const double vpv = h->v + h->vt;
+    // the means alone are N-fold work, like gpx_exact_mean's launches: outside the Exact class, which counts the N^2 passes
+    Profiler *prof = want_var ? &h->prof : nullptr;
+    for (const Run &r : runs) {
+        const double *Lsd = cd + r.off, *ddd = Lsd + d2;
+        if (!r.matrix) {
+            double *aT = pb, *bT = aT + (int64_t)d * np, *e = bT + (int64_t)d * np, *F = e + np, *lm = F + np, *partial = lm + np;
+            for (int64_t i = r.i0; i < r.i0 + r.cnt; ++i) {   // exact_common's launches; od[i] = beta . l, od[b + i] = the double sum / nc2
+                GPX_TRY(launch_exact_build(h->x, n, np, d, Ud + i * d, h->wdev, Lsd, ddd, h->v, h->vt, r.nc1, aT, bT, e, F, lm, s));
+                GPX_TRY(launch_dot_pairs({{h->alpha, lm}}, np, od + i, s));
+                if (want_var) GPX_TRY(launch_exact_sum(h->Kinv, np, np, d, h->alpha, aT, bT, e, F, partial, od + b + i, s, &h->prof));
+            }
+            continue;
+        }
+        const double *T1 = ddd + d, *s1 = T1 + d2, *T2 = s1 + d, *s2 = T2 + d2;
+        if (want_var) {
+            GPX_TRY(launch_exact_many_transform(h->x, n, np, d, h->x, T1, xt, s));
+            GPX_TRY(launch_exact_weight(h->Kinv, np, n, np, d, h->alpha, xt, s1, Lo, s, &h->prof));
+            GPX_TRY(launch_exact_many_transform(h->x, n, np, d, h->x, T2, xh, s));
+        }
+        for (int64_t b0 = 0; b0 < r.cnt; b0 += rows) {
+            const int64_t bc = std::min(rows, r.cnt - b0), bp = round_up(bc, TILE), i0 = r.i0 + b0;
+            if (want_var) GPX_TRY(launch_exact_many_transform(Ud + i0 * d, bc, bc, d, h->x, T2, Uh, s));
+            GPX_TRY(launch_exact_many_build(h->x, xh, n, np, d, Ud + i0 * d, Uh, bc, bp, h->wdev, ddd, s2, h->alpha, h->v, h->vt, r.nc1,
+                                            want_var ? Hd : nullptr, mpart, s, prof));
+            if (want_var) GPX_TRY(launch_gemm_nt(Hd, np, Lo, np, Yd, np, bp, np, np, 1.0, 0.0, 0, s, &h->prof, 0, GEMM_TRI_B_LOWER));
+            GPX_TRY(launch_exact_many_finish(want_var ? Yd : nullptr, Hd, np, mpart, bc, vpv, r.nc2, od + i0, b, s, prof));
+        }
+    }
+    GPX_HIP(hipMemcpyAsync(res.data(), od, sizeof(double) * (want_var ? 2 : 1) * b, hipMemcpyDeviceToHost, s));
+    const hipError_t e = sc.wait_and_free();                  // the call's one synchronisation
+    if (e != hipSuccess) { gpx_set_error("gpx_propagate_exact_many: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
+    if (want_var)
+        for (const Run &r : runs)
+            if (!r.matrix)
+                for (int64_t i = r.i0; i < r.i0 + r.cnt; ++i) {
+                    const double mu = res[(size_t)i], nc2 = r.nc2;
+                    res[(size_t)(b + i)] = (h->v + h->vt) - nc2 * res[(size_t)(b + i)] - mu * mu;   // as exact_common finishes
+                }
+    GPX_HIP(hipMemcpy(mean, res.data(), sizeof(double) * b, hipMemcpyDefault));
+    if (want_var) GPX_HIP(hipMemcpy(var, res.data() + b, sizeof(double) * b, hipMemcpyDefault));
+    return 0;
 }
 
 // ---- a14 for ANY operator.  The reference's UncertaintyPropagationExact talks to the GP only through _get_beta, _get_W_inv,

@@ -27,6 +27,17 @@ class UncertaintyPropagationGA(object):
     def propagate_GA(self, u, Sigma_x):
         return 0, 0
 
+    # argument forms of the many-input calls of both subclasses: U (B, d); Sigma_x (d, d) for every input, or (B, d, d)
+    def _many_args(self, U, Sigma_x):
+        d = self.gp.d
+        UU = _gpx.f64(U)
+        S = _gpx.f64(Sigma_x)
+        if UU.ndim != 2 or UU.shape[1] != d:
+            raise ValueError("U must be (B, %d), got %s" % (d, UU.shape))
+        if S.shape != (d, d) and S.shape != (len(UU), d, d):
+            raise ValueError("Sigma_x must be (%d, %d) or (%d, %d, %d), got %s" % (d, d, len(UU), d, d, S.shape))
+        return UU, S
+
 
 def _u_sigma(gp, u, Sigma_x):
     uu = _gpx.f64(u)
@@ -147,16 +158,6 @@ class UncertaintyPropagationApprox(UncertaintyPropagationGA):
         return np.float64(mean + self.gp._get_mean_t()), np.float64(var)
 
     # ---- many inputs in one call (no reference counterpart: what a caller's loop over propagate_GA computes) ----
-    def _many_args(self, U, Sigma_x):
-        d = self.gp.d
-        UU = _gpx.f64(U)
-        S = _gpx.f64(Sigma_x)
-        if UU.ndim != 2 or UU.shape[1] != d:
-            raise ValueError("U must be (B, %d), got %s" % (d, UU.shape))
-        if S.shape != (d, d) and S.shape != (len(UU), d, d):
-            raise ValueError("Sigma_x must be (%d, %d) or (%d, %d, %d), got %s" % (d, d, len(UU), d, d, S.shape))
-        return UU, S
-
     def _parts_many(self, U, Sigma_x):
         """(mean without meant, variance, sigma2, rest), each [B].  Built-in kernel: ONE gpx_propagate_approx_many call -- every
         input's C, tr, J_1..J_d are d + 2 rows of the many-right-hand-side solve behind estimate_many; K^-1 is not built and the
@@ -389,3 +390,37 @@ class UncertaintyPropagationExact(UncertaintyPropagationGA):
                                           ctypes.byref(var))
         _gpx.check(st, "gpx_propagate_exact")
         return np.float64(mean.value + self.gp._get_mean_t()), np.float64(var.value)
+
+    # ---- many inputs in one call (no reference counterpart: what a caller's loop over propagate_GA computes) ----
+    def _moments_many(self, U, Sigma_x, want_var):
+        """(means without meant, variances or None), each [B].  Built-in kernel: ONE gpx_propagate_exact_many call -- for the inputs that
+        share a Sigma the double sum is the quadratic form h^T M h with M = (Kinv - beta beta^T) o E built once (gpx.h); with
+        want_var = False K^-1 is neither built nor read.  Any other route (a generic operator, SPGP): a loop over the single-input path on
+        a fresh instance -- correct, not accelerated.  Neither sets Winv, Sigma_x, Deltainv, LambdaInv or the normalisers on this instance."""
+        UU, S = self._many_args(U, Sigma_x)
+        B = len(UU)
+        shared = S.ndim == 2
+        mean, var = np.empty(B), (np.empty(B) if want_var else None)
+        if self.gp._route() != "gaussian":
+            one = type(self)(self.gp)
+            for i in range(B):
+                Si = S if shared else S[i]
+                one._set_constants(UU[i], Si)                    # what propagate_GA / propagate_mean do first
+                m, v = one._generic_moments(UU[i], Si, None, want_var)
+                mean[i] = m
+                if want_var:
+                    var[i] = v
+            return mean, var
+        st = _gpx.lib.gpx_propagate_exact_many(self.gp._dev().handle, _gpx.ptr(UU), _gpx.ptr(S), int(shared), B, _gpx.ptr(mean),
+                                               _gpx.ptr(var) if want_var else None)
+        _gpx.check(st, "gpx_propagate_exact_many")
+        return mean, var
+
+    def propagate_mean_many(self, U, Sigma_x):
+        """propagate_mean for the rows of U (B, d); Sigma_x (d, d) for all of them or (B, d, d): means [B] WITHOUT meant"""
+        return self._moments_many(U, Sigma_x, False)[0]
+
+    def propagate_GA_many(self, U, Sigma_x):
+        """propagate_GA for the rows of U (B, d); Sigma_x (d, d) for all of them or (B, d, d): (means [B] with meant, variances [B])"""
+        mean, var = self._moments_many(U, Sigma_x, True)
+        return mean + self.gp._get_mean_t(), var
