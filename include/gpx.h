@@ -159,6 +159,17 @@ int gpx_propagate_approx_rhs(gpx_handle *h, const double *u, const double *Sigma
  * (skgpuppy/UncertaintyPropagation.py:564-630, UncertaintyPropagation2.pyx:340-380) ---- */
 int gpx_propagate_dvh(gpx_handle *h, const double *u, double *dvh_out /* [d] */);
 
+/* d values of _get_variance_dv_h and _get_sigma2 for b inputs in ONE call (no reference counterpart: it replaces a caller's loop over
+ * InverseUncertaintyPropagationApprox.get_best_solution, skgpuppy/InverseUncertaintyPropagation.py:139-173, each turn of which runs
+ * skgpuppy/UncertaintyPropagation.py:564-630 d times and :412-481 once).  U [b, d].  Input i's vectors C, J_1..J_d, H_11..H_dd are
+ * 2 d + 1 right-hand sides of the many-right-hand-side triangular solver of gpx_predict (z_v = L^-1 v, y = L^-1 t):
+ *   dvh_k = -(|z_Jk|^2 - (z_Jk.y)^2) - z_C.z_Hkk  (:564-630)      sigma2 = (v + vt) - |z_C|^2  (:412-433)
+ * and the variance rest of a DIAGONAL Sigma = diag(s) is sum_k s_k dvh_k (:435-481, tr(H Sigma) = sum_k H_kk s_k), so _getFactor
+ * (:526-560) needs no second call.  K^-1 is neither built nor read and the cache of the single-input calls is left alone.  dvh_out [b, d]
+ * is required, sigma2_out [b] may be NULL; host or device pointers.  An input's result does not depend on its place in the batch.
+ * b = 0 is a no-op. */
+int gpx_propagate_dvh_many(gpx_handle *h, const double *U, int64_t b, double *dvh_out /* [b, d] */, double *sigma2_out /* [b], may be NULL */);
+
 /* ---- a14: UncertaintyPropagationExact.propagate_GA / propagate_mean
  * (skgpuppy/UncertaintyPropagation.py:246-379, UncertaintyPropagation2.pyx:57-184) ----
  * mean WITHOUT meant; var = (v+vt) - sum_ij (Kinv_ij - beta_i beta_j) L_ij - mean^2. */

@@ -371,6 +371,11 @@ int launch_approx_build_many(const double *x, int64_t n, int64_t npad, int d, co
                              hipStream_t s, Profiler *prof);
 int launch_approx_reduce_many(const double *Zs, int64_t npad, int d, const double *y, const double *Sigma_dev, int64_t sigma_stride,
                               int64_t nb, double vplusvt, double *out, int64_t ldo, hipStream_t s, Profiler *prof);
+// batched inverse propagation (gpx_propagate_dvh_many): rows [C, J_1..J_d, H_11..H_dd] per input; dvh [nb, d], sigma2 [nb] or null
+int launch_dvh_build_many(const double *x, int64_t n, int64_t npad, int d, const double *U_dev, int64_t nb, int64_t rows_pad,
+                          const double *w_dev, double v, double vt, double *Z, hipStream_t s, Profiler *prof);
+int launch_dvh_reduce_many(const double *Zs, int64_t npad, int d, const double *y, int64_t nb, double vplusvt, double *dvh, double *sigma2,
+                           hipStream_t s, Profiler *prof);
 int launch_exact_build(const double *x, int64_t n, int64_t npad, int d, const double *u_dev, const double *w_dev,
                        const double *Ls_dev, const double *dinv_diag_dev, double v, double vt, double nc1, double *aT,
                        double *bT, double *e, double *F, double *lm, hipStream_t s);

@@ -332,6 +332,208 @@ int launch_approx_reduce_many(const double *Zs, int64_t npad, int d, const doubl
 }
 
 // ---------------------------------------------------------------------------------------------
+// Batched inverse propagation (gpx_propagate_dvh_many): the 2 d + 1 vectors of MANY inputs as right-hand sides of the same solver.
+// Row b (2 d + 1) + r of Z (leading dimension npad):
+//   r = 0: C_i (+vt iff x_i == u_b elementwise)   r = 1 + k: J_ik = -w_k delta_k c_i   r = 1 + d + k: H_i,kk = ((w_k delta_k)^2 - w_k) c_i
+// (the arithmetic of approx_build_kernel).  The structure is approx_build_many_kernel's: 128 columns of x k-major in LDS, AB_INPUTS
+// inputs per workgroup, four per wave, u and w wave-uniform, 16-byte stores, one exp per (input, column); there is no Sigma.
+// DR > 0: d <= DR, the scaled differences stay in registers; DR = 0: any d, recomputed from the LDS tile.
+// ---------------------------------------------------------------------------------------------
+template <int DR>
+__global__ __launch_bounds__(256) void dvh_build_many_kernel(const double *__restrict__ x, long n, long npad, int d,
+                                                            const double *__restrict__ U, long nb, const double *__restrict__ w, double v,
+                                                            double vt, double *__restrict__ Z)
+{
+    extern __shared__ __attribute__((aligned(16))) double ab_smem[];
+    double *x_s = ab_smem;   // [d][128] raw inputs of the tile's columns, k-major
+    const int t = threadIdx.x;
+    const long col0 = (long)blockIdx.x * AB_COLS;
+    for (int e = t; e < AB_COLS * d; e += 256) {
+        const int c = e & (AB_COLS - 1), k = e >> 7;
+        const long gc = col0 + c;
+        x_s[k * AB_COLS + c] = (gc < n) ? x[gc * d + k] : 0.0;
+    }
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
+    const long c = col0 + 2 * lane;
+    const bool in0 = c < n, in1 = c + 1 < n;
+    const long nrow = 2 * d + 1;
+    for (int j = 0; j < AB_INPUTS / 4; ++j) {
+        const long b = (long)blockIdx.y * AB_INPUTS + 4 * j + wave;   // wave-uniform
+        if (b >= nb) break;
+        const double *u = U + b * d;
+        double *zrow = Z + b * nrow * npad + c;
+        double wd0[DR > 0 ? DR : 1], wd1[DR > 0 ? DR : 1];
+        double q0 = 0.0, q1 = 0.0;
+        bool same0 = true, same1 = true;
+        if constexpr (DR > 0) {
+#pragma unroll
+            for (int k = 0; k < DR; ++k) {
+                wd0[k] = 0.0; wd1[k] = 0.0;
+                if (k < d) {
+                    const v2d xv = *reinterpret_cast<const v2d *>(&x_s[k * AB_COLS + 2 * lane]);
+                    const double uk = u[k], wk = w[k];
+                    const double d0 = xv.x - uk, d1 = xv.y - uk;
+                    same0 = same0 && (xv.x == uk);
+                    same1 = same1 && (xv.y == uk);
+                    wd0[k] = wk * d0; wd1[k] = wk * d1;
+                    q0 = fma(wd0[k], d0, q0);
+                    q1 = fma(wd1[k], d1, q1);
+                }
+            }
+        } else {
+            for (int k = 0; k < d; ++k) {
+                const v2d xv = *reinterpret_cast<const v2d *>(&x_s[k * AB_COLS + 2 * lane]);
+                const double uk = u[k], wk = w[k];
+                const double d0 = xv.x - uk, d1 = xv.y - uk;
+                same0 = same0 && (xv.x == uk);
+                same1 = same1 && (xv.y == uk);
+                q0 = fma(wk * d0, d0, q0);
+                q1 = fma(wk * d1, d1, q1);
+            }
+        }
+        const double c0 = in0 ? v * exp(-0.5 * q0) : 0.0, c1 = in1 ? v * exp(-0.5 * q1) : 0.0;
+        v2d o;
+        o.x = (in0 && same0) ? c0 + vt : c0;
+        o.y = (in1 && same1) ? c1 + vt : c1;
+        *reinterpret_cast<v2d *>(zrow) = o;
+        if constexpr (DR > 0) {
+#pragma unroll
+            for (int a = 0; a < DR; ++a) {
+                if (a < d) {
+                    const double wa = w[a];
+                    v2d jk, hk;
+                    jk.x = -wd0[a] * c0; jk.y = -wd1[a] * c1;
+                    hk.x = (wd0[a] * wd0[a] - wa) * c0; hk.y = (wd1[a] * wd1[a] - wa) * c1;
+                    *reinterpret_cast<v2d *>(zrow + (long)(1 + a) * npad) = jk;
+                    *reinterpret_cast<v2d *>(zrow + (long)(1 + d + a) * npad) = hk;
+                }
+            }
+        } else {
+            for (int a = 0; a < d; ++a) {
+                const v2d xa = *reinterpret_cast<const v2d *>(&x_s[a * AB_COLS + 2 * lane]);
+                const double wa = w[a], ua = u[a];
+                const double a0 = wa * (xa.x - ua), a1 = wa * (xa.y - ua);
+                v2d jk, hk;
+                jk.x = -a0 * c0; jk.y = -a1 * c1;
+                hk.x = (a0 * a0 - wa) * c0; hk.y = (a1 * a1 - wa) * c1;
+                *reinterpret_cast<v2d *>(zrow + (long)(1 + a) * npad) = jk;
+                *reinterpret_cast<v2d *>(zrow + (long)(1 + d + a) * npad) = hk;
+            }
+        }
+    }
+}
+
+// Z [rows_pad, npad]: rows [0, nb (2 d + 1)) written by the kernel (every column, zeros from n on), the rest of the last 128-row tile cleared
+int launch_dvh_build_many(const double *x, int64_t n, int64_t npad, int d, const double *U_dev, int64_t nb, int64_t rows_pad,
+                          const double *w_dev, double v, double vt, double *Z, hipStream_t s, Profiler *prof)
+{
+    if (nb <= 0) return 0;
+    const int64_t rows = nb * (2 * d + 1);
+    if (npad % AB_COLS || rows > rows_pad || d < 1 || d > GPX_MAX_D) { gpx_set_error("dvh_build_many: bad block shape"); return GPX_ERR_BAD_ARG; }
+    ProfScope ps(prof, s, GPX_K_GRAM, 8.0 * (double)rows_pad * (double)npad);
+    if (rows_pad > rows) GPX_HIP(hipMemsetAsync(Z + rows * npad, 0, sizeof(double) * (rows_pad - rows) * npad, s));
+    const dim3 grid((unsigned)(npad / AB_COLS), (unsigned)((nb + AB_INPUTS - 1) / AB_INPUTS));
+    const size_t lds = sizeof(double) * AB_COLS * d;
+    if (d <= 8)
+        hipLaunchKernelGGL(dvh_build_many_kernel<8>, grid, dim3(256), lds, s, x, (long)n, (long)npad, d, U_dev, (long)nb, w_dev, v, vt, Z);
+    else
+        hipLaunchKernelGGL(dvh_build_many_kernel<0>, grid, dim3(256), lds, s, x, (long)n, (long)npad, d, U_dev, (long)nb, w_dev, v, vt, Z);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// One pass over the solved block Zs (row b (2 d + 1) + r = L^-1 of the vector above), one workgroup per input: |z_C|^2 and per k
+// |z_Jk|^2, z_Jk . y and z_C . z_Hkk, then (UncertaintyPropagation.py:564-630 and :412-433 with K^-1 = L^-T L^-1, y = L^-1 t)
+//   dvh[b][k] = -(|z_Jk|^2 - (z_Jk.y)^2) - z_C.z_Hkk      sigma2[b] = (v + vt) - |z_C|^2      (sigma2 may be null)
+// DR > 0 (d <= DR): columns outside, k inside, the 3 d + 1 sums in registers, every solved row read once.  DR = 0 (any d): rows outside;
+// the z_C row (8 npad bytes, it stays in L2) is read again for every k.  No atomics; thread -> column, wave -> LDS slot and the final sum
+// are fixed, so an input's result does not depend on its place in the batch.
+template <int DR>
+__global__ __launch_bounds__(256) void dvh_reduce_many_kernel(const double *__restrict__ Zs, long npad, int d, const double *__restrict__ y,
+                                                             double vplusvt, double *__restrict__ dvh, double *__restrict__ sigma2)
+{
+    __shared__ double part[3 * GPX_MAX_D + 1][4];   // 3 k: |z_Jk|^2   3 k + 1: z_Jk.y   3 k + 2: z_C.z_Hkk   3 d: |z_C|^2
+    const long b = blockIdx.x;
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const double *zc = Zs + b * (2 * d + 1) * npad;
+    if constexpr (DR > 0) {
+        double qj[DR], yj[DR], ch[DR], qc = 0.0;
+#pragma unroll
+        for (int k = 0; k < DR; ++k) { qj[k] = 0.0; yj[k] = 0.0; ch[k] = 0.0; }
+        for (long c = 2 * t; c < npad; c += 512) {
+            const v2d a = *reinterpret_cast<const v2d *>(zc + c);
+            const v2d yy = *reinterpret_cast<const v2d *>(y + c);
+            qc = fma(a.x, a.x, qc); qc = fma(a.y, a.y, qc);
+#pragma unroll
+            for (int k = 0; k < DR; ++k) {
+                if (k < d) {
+                    const v2d zj = *reinterpret_cast<const v2d *>(zc + (long)(1 + k) * npad + c);
+                    const v2d zh = *reinterpret_cast<const v2d *>(zc + (long)(1 + d + k) * npad + c);
+                    qj[k] = fma(zj.x, zj.x, qj[k]); qj[k] = fma(zj.y, zj.y, qj[k]);
+                    yj[k] = fma(zj.x, yy.x, yj[k]); yj[k] = fma(zj.y, yy.y, yj[k]);
+                    ch[k] = fma(a.x, zh.x, ch[k]); ch[k] = fma(a.y, zh.y, ch[k]);
+                }
+            }
+        }
+        qc = wave_sum_p(qc);
+        if (lane == 0) part[3 * d][wave] = qc;
+#pragma unroll
+        for (int k = 0; k < DR; ++k) {
+            if (k < d) {
+                const double q = wave_sum_p(qj[k]), sy = wave_sum_p(yj[k]), sh = wave_sum_p(ch[k]);
+                if (lane == 0) { part[3 * k][wave] = q; part[3 * k + 1][wave] = sy; part[3 * k + 2][wave] = sh; }
+            }
+        }
+    } else {
+        double qc = 0.0;
+        for (long c = 2 * t; c < npad; c += 512) {
+            const v2d a = *reinterpret_cast<const v2d *>(zc + c);
+            qc = fma(a.x, a.x, qc); qc = fma(a.y, a.y, qc);
+        }
+        qc = wave_sum_p(qc);
+        if (lane == 0) part[3 * d][wave] = qc;
+        for (int k = 0; k < d; ++k) {
+            const double *zjr = zc + (long)(1 + k) * npad, *zhr = zc + (long)(1 + d + k) * npad;
+            double q = 0.0, sy = 0.0, sh = 0.0;
+            for (long c = 2 * t; c < npad; c += 512) {
+                const v2d a = *reinterpret_cast<const v2d *>(zc + c);
+                const v2d yy = *reinterpret_cast<const v2d *>(y + c);
+                const v2d zj = *reinterpret_cast<const v2d *>(zjr + c), zh = *reinterpret_cast<const v2d *>(zhr + c);
+                q = fma(zj.x, zj.x, q); q = fma(zj.y, zj.y, q);
+                sy = fma(zj.x, yy.x, sy); sy = fma(zj.y, yy.y, sy);
+                sh = fma(a.x, zh.x, sh); sh = fma(a.y, zh.y, sh);
+            }
+            q = wave_sum_p(q); sy = wave_sum_p(sy); sh = wave_sum_p(sh);
+            if (lane == 0) { part[3 * k][wave] = q; part[3 * k + 1][wave] = sy; part[3 * k + 2][wave] = sh; }
+        }
+    }
+    __syncthreads();
+    auto tot = [&](int i) { return (part[i][0] + part[i][1]) + (part[i][2] + part[i][3]); };
+    if (t < d) {
+        const double zy = tot(3 * t + 1);
+        const double v2 = -(tot(3 * t) - zy * zy);   // UncertaintyPropagation.py:593-607
+        const double v3 = -tot(3 * t + 2);           // :614-627
+        dvh[b * d + t] = v2 + v3;
+    }
+    if (t == 0 && sigma2) sigma2[b] = vplusvt - tot(3 * d);
+}
+
+int launch_dvh_reduce_many(const double *Zs, int64_t npad, int d, const double *y, int64_t nb, double vplusvt, double *dvh, double *sigma2,
+                           hipStream_t s, Profiler *prof)
+{
+    if (nb <= 0) return 0;
+    if (npad % 2 || d < 1 || d > GPX_MAX_D) { gpx_set_error("dvh_reduce_many: bad block shape"); return GPX_ERR_BAD_ARG; }
+    ProfScope ps(prof, s, GPX_K_REDUCE, 8.0 * (double)nb * (double)(2 * d + 1) * (double)npad);
+    if (d <= 8)
+        hipLaunchKernelGGL(dvh_reduce_many_kernel<8>, dim3((unsigned)nb), dim3(256), 0, s, Zs, (long)npad, d, y, vplusvt, dvh, sigma2);
+    else
+        hipLaunchKernelGGL(dvh_reduce_many_kernel<0>, dim3((unsigned)nb), dim3(256), 0, s, Zs, (long)npad, d, y, vplusvt, dvh, sigma2);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
 // KV[c][i] = sum_j Kinv[i][j] V[c][j] for c < nc: the ONE pass over Kinv that feeds every quadratic form of
 // the Approx propagation (loops K2..K6 of the reference, UncertaintyPropagation2.pyx:221-257,340-380, each of
 // which re-reads the whole N x N matrix serially).  HBM-bound: 8 N^2 bytes.

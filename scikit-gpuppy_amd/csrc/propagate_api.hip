@@ -314,6 +314,42 @@ extern "C" int gpx_propagate_dvh(gpx_handle *h, const double *u, double *dvh_out
     return 0;
 }
 
+// Batched inverse propagation: b inputs as b (2 d + 1) right-hand sides [C, J_1..J_d, H_11..H_dd] of the many-right-hand-side solver, the
+// loop of gpx_propagate_approx_many.  With y = L^-1 t and z_v = L^-1 v the three sums of gpx_propagate_dvh are row products of the solved
+// block: J_k.Kinv J_k = |z_Jk|^2, beta.J_k = z_Jk.y, (Kinv C).H_kk = z_C.z_Hkk; sigma2 = (v + vt) - |z_C|^2.  No K^-1, no use of the handle's
+// single-u cache (have_u, V, KV), one synchronisation per chunk; an input never straddles two chunks.
+extern "C" int gpx_propagate_dvh_many(gpx_handle *h, const double *U, int64_t b, double *dvh_out, double *sigma2_out)
+{
+    CHECK_H(h);
+    NEED_KERNEL(h, "gpx_propagate_dvh_many");
+    if (b < 0 || (b > 0 && (!U || !dvh_out))) { gpx_set_error("gpx_propagate_dvh_many: bad arguments"); return GPX_ERR_BAD_ARG; }
+    if (b == 0) return 0;
+    hipStream_t s = h->stream;
+    const int d = h->d, nrow = 2 * d + 1;
+    RowSolve rs(s);
+    GPX_TRY(row_solve_begin(h, b * nrow, rs));
+    const int64_t bchunk = rs.chunk / nrow;           // inputs per chunk
+    if (bchunk < 1) { gpx_set_error("gpx_propagate_dvh_many: a chunk of %ld rows holds no input of %d rows", (long)rs.chunk, nrow); return GPX_ERR_STATE; }
+    double *ud = nullptr, *od = nullptr;
+    int rc = 0;
+    GPX_TRY(rs.sc.take(&ud, bchunk * d));
+    GPX_TRY(rs.sc.take(&od, bchunk * (d + 1)));       // dvh [bchunk, d] | sigma2 [bchunk]
+    double *s2d = od + bchunk * d;
+    for (int64_t b0 = 0; b0 < b && rc == 0; b0 += bchunk) {
+        const int64_t bc = std::min<int64_t>(bchunk, b - b0), mc = bc * nrow, mp = round_up(mc, TILE);
+        hipError_t e = hipMemcpyAsync(ud, U + b0 * d, sizeof(double) * bc * d, hipMemcpyDefault, s);
+        if (e != hipSuccess) { gpx_set_error("copy U failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
+        if ((rc = launch_dvh_build_many(h->x, h->n, h->npad, d, ud, bc, mp, h->wdev, h->v, h->vt, h->Z, s, &h->prof))) break;
+        if ((rc = row_solve_run(h, rs, mc, mp, nullptr))) break;
+        if ((rc = launch_dvh_reduce_many(rs.Zs, h->npad, d, h->y, bc, h->v + h->vt, od, s2d, s, &h->prof))) break;
+        e = hipMemcpyAsync(dvh_out + b0 * d, od, sizeof(double) * bc * d, hipMemcpyDefault, s);
+        if (e == hipSuccess && sigma2_out) e = hipMemcpyAsync(sigma2_out + b0, s2d, sizeof(double) * bc, hipMemcpyDefault, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { gpx_set_error("propagate copy-out failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
+    }
+    return rc;
+}
+
 // small dense inverse (Gauss-Jordan, partial pivoting) for (W/2 + Sigma), d <= 64
 static int small_inverse(const double *A, int d, double *inv)
 {

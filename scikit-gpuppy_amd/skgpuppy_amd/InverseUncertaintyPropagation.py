@@ -95,3 +95,48 @@ class InverseUncertaintyPropagationApprox(InverseUncertaintyPropagation):
         optimum = factor * weights
         assert (optimum > 0).all()
         return optimum
+
+    # ---- many operating points in one call (no reference counterpart: what a caller's loop over get_best_solution computes) ----
+    @staticmethod
+    def _closed_form(dvh, sigma2, c, I, coestimated, output_variance):
+        """The steps of get_best_solution (InverseUncertaintyPropagation.py:139-173) for B operating points at once: dvh [B, d] (the d
+        values of _get_variance_dv_h per point), sigma2 and output_variance [B] or scalar; returns the optimal input variances [B, d].
+        `_getFactor` needs no propagation of its own: with Sigma = diag(w) the variance rest is sum_k w_k dvh_k (unfolded dvh).
+
+        Unlike get_best_solution, which asserts, an infeasible point does not stop the batch: a row with a folded derivative <= 0, a
+        weight that is not finite and positive, or a factor that is not positive (target variance at or below sigma2) comes back as a
+        row of NaN, silently; the other rows are unaffected."""
+        dvh = np.asarray(dvh, dtype=float)
+        if dvh.ndim != 2:
+            raise ValueError("dvh must be (B, d), got %s" % (dvh.shape,))
+        B, d = dvh.shape
+        c = np.asarray(c, dtype=float)
+        I = np.asarray(I, dtype=float)
+        if c.shape != (d,) or I.shape != (d,):
+            raise ValueError("c and I must be (%d,), got %s and %s" % (d, c.shape, I.shape))
+        sigma2 = np.broadcast_to(np.asarray(sigma2, dtype=float), (B,))
+        target = np.broadcast_to(np.asarray(output_variance, dtype=float), (B,))
+        followers = _followers(coestimated)
+        dd = dvh.copy()
+        with np.errstate(all="ignore"):
+            for lead, i in followers:
+                dd[:, lead] += dd[:, i] * I[lead] / I[i]
+            weights = np.sqrt(c / dd / I)
+            for lead, i in followers:
+                weights[:, i] = weights[:, lead] * I[lead] / I[i]
+            rest = np.zeros(B)
+            for k in range(d):                               # fixed order: a row's result does not depend on the batch
+                rest += weights[:, k] * dvh[:, k]
+            factor = (target - sigma2) / rest
+            optimum = factor[:, None] * weights
+            good = (np.isfinite(weights) & (weights > 0)).all(axis=1) & np.isfinite(factor) & (factor > 0)
+        optimum[~good] = np.nan
+        return optimum
+
+    def get_best_solution_many(self, U, output_variance=None):
+        """get_best_solution for the rows of U (B, d) in one call: optimal input variances [B, d], NaN rows where the problem has no
+        solution (_closed_form).  output_variance: [B] or scalar, default self.output_variance.  self.u is not used."""
+        upga = self.upga_class(self.gp)
+        dvh, sigma2 = upga._get_variance_dv_many(U)
+        target = self.output_variance if output_variance is None else output_variance
+        return self._closed_form(dvh, sigma2, self.c, self.I, self.coestimated, target)

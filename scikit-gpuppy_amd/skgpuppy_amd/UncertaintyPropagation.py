@@ -260,6 +260,27 @@ class UncertaintyPropagationApprox(UncertaintyPropagationGA):
         _gpx.check(st, "gpx_propagate_dvh")
         return out[h]
 
+    def _get_variance_dv_many(self, U):
+        """(dvh [B, d], sigma2 [B]): _get_variance_dv_h for every h and _get_sigma2 for the rows of U (B, d) -- all the closed form of
+        InverseUncertaintyPropagationApprox needs (the variance rest of a diagonal Sigma = diag(s) is sum_k s_k dvh_k).  Built-in kernel:
+        ONE gpx_propagate_dvh_many call -- every input's C, J_1..J_d, H_11..H_dd are 2 d + 1 rows of the many-right-hand-side solve
+        behind estimate_many; K^-1 is not built and the single-input caches (self.u, C_ux, ...) are not touched.  Generic route (any other
+        Covariance, SPGP): a loop over the single-input path on a fresh instance -- correct, not accelerated."""
+        d = self.gp.d
+        UU, _S = self._many_args(U, np.zeros((d, d)))
+        B = len(UU)
+        dvh, sigma2 = np.empty((B, d)), np.empty(B)
+        if self._generic():
+            one = type(self)(self.gp)
+            for i in range(B):
+                for h in range(d):
+                    dvh[i, h] = one._get_variance_dv_h(UU[i], h)
+                sigma2[i] = one._get_sigma2(UU[i])
+            return dvh, sigma2
+        st = _gpx.lib.gpx_propagate_dvh_many(self.gp._dev().handle, _gpx.ptr(UU), B, _gpx.ptr(dvh), _gpx.ptr(sigma2))
+        _gpx.check(st, "gpx_propagate_dvh_many")
+        return dvh, sigma2
+
 
 class _ExplicitInverse(object):
     """Owner of one gpx_kinv_model: an explicit K^-1 / beta resident in HBM (gpx.h)."""
