@@ -223,6 +223,30 @@ int gpx_nll_grad_matrix(gpx_handle *h, const double *dK, double *grad_out);
  * (skgpuppy/UncertaintyPropagation.py:412-481) when it is not the fitted model's own. */
 int gpx_symv(const double *M, int64_t n, const double *V, int nrhs, double *out);
 
+/* ---- PeriodicCovariance (skgpuppy/Covariance.py:361-433): ARD squared exponential times a periodic factor per dimension ----
+ * theta = (log v, log vt, log w_1..d, log p_1..d, log w2_1..d), 2 + 3 d entries, a host pointer.  With delta = xi - xj
+ *   q = 1/2 sum_k [ w_k delta_k^2 + w2_k sin^2(pi delta_k / p_k) ],   k(xi, xj) = v exp(-q) + (vt iff xi == xj in every component).
+ * The class inherits the base class's cov_matrix AND cov_matrix_ij (:137-164), so both carry the +vt on exact equality -- also a query
+ * row that equals a training row; duplicate training rows make K exactly singular, as in the reference.
+ * gpx_periodic_gram replaces those two (deriv = -1) and Covariance._d_cov_matrix_d_theta_ij (:236-253 over :399-433; deriv = j >= 0:
+ * d K / d theta_j): out [n1, n2]; xj may alias xi.  K_ij and K_ji are the same bits.  n1, n2 >= 1. */
+int gpx_periodic_gram(const double *xi, int64_t n1, const double *xj, int64_t n2, int d, const double *theta, int deriv, double *out);
+/* GaussianProcess.__init__ with cov = PeriodicCovariance (skgpuppy/GaussianProcess.py:19-41 over Covariance.py:137-187): K is assembled
+ * on the device straight into the factor's buffer (no N x N transfer), then factored with gpx_fit's schedule and its single +1e-5 I
+ * retry.  The handle answers whatever a gpx_fit_matrix handle answers (gpx_alpha, gpx_solve, gpx_chol_mul, gpx_kinv*, gpx_chol*,
+ * gpx_logdet, gpx_nll, gpx_predict_kv, gpx_nll_grad_matrix, gpx_jitter_used) and the two calls below; the entry points that evaluate the
+ * GaussianCovariance kernel (gpx_predict, gpx_cjh, gpx_propagate_*, gpx_exact_mean, gpx_nll_grad) return GPX_ERR_STATE on it, as
+ * gpx_periodic_predict / gpx_periodic_nll_grad do on every other handle.  gpx_n reports its d. */
+int gpx_periodic_fit(const double *x, const double *t_centered, int64_t n, int d, const double *theta, void *stream, gpx_handle **out);
+/* estimate_many / estimate (GaussianProcess.py:68-111): mean_out[m] = kv alpha (WITHOUT meant), var_out[m] = v + vt - kv K^-1 kv^T, kv
+ * the cross-covariance with the +vt on equality.  Host or device pointers; m = 0 is a no-op.  A query's result does not depend on its
+ * place in the batch or on the chunking (GPX_PERIODIC_CHUNK, read at every call: at most that many queries per chunk, a multiple of 128). */
+int gpx_periodic_predict(gpx_handle *h, const double *xs, int64_t m, double *mean_out, double *var_out);
+/* Covariance._d_nll_d_theta (Covariance.py:266-282 with PeriodicCovariance._d_cov_d_theta, :399-433): grad_out [2 + 3 d] from ONE pass
+ * over the lower half of K^-1 with the kernel recomputed on the fly -- none of the 2 + 3 d derivative matrices is formed.  Fixed-order
+ * reduction: two calls give the same bits. */
+int gpx_periodic_nll_grad(gpx_handle *h, double *grad_out);
+
 /* ---- "next" row f3: Snelson sparse pseudo-input GP (SPGPCovariance, skgpuppy/Covariance.py:692-1019) ----
  * theta = [log v, log vt, log w_1..d] (the GaussianCovariance part of the reference's theta), xb = the m x d
  * pseudo-inputs (the tail of the reference's theta, reshaped).  The fit keeps K_NM, chol(K_M + 1e-5 I),

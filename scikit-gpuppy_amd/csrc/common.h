@@ -160,8 +160,35 @@ struct gpx_handle {
     double u[GPX_MAX_D];
     double *V = nullptr;        // [ncolV, npad] column-major block of C, J_k, hh_k, tr
     double *KV = nullptr;       // [ncolV, npad] Kinv * V
+    struct PeriodicData *per = nullptr;   // gpx_periodic_fit only (periodic.hip): inputs and parameters of the periodic kernel; d stays 0
     Profiler prof;
 };
+
+// ---- PeriodicCovariance (periodic.hip; skgpuppy/Covariance.py:361-433) -------------------------------------------------
+// theta = (log v, log vt, log w_1..d, log p_1..d, log w2_1..d).  A periodic handle is a matrix handle (d == 0: K was assembled on the
+// device instead of supplied) that keeps what gpx_periodic_predict / gpx_periodic_nll_grad evaluate the kernel on.
+struct PeriodicData {
+    int d = 0;
+    double v = 0, vt = 0;
+    double w[GPX_MAX_D], p[GPX_MAX_D], w2[GPX_MAX_D];   // exp(theta)
+    double *x = nullptr;      // [n, d] raw inputs
+    double *xT = nullptr;     // [d, npad] the same k-major (the gradient pass reads a column of K^-1 per lane)
+    double *par = nullptr;    // [4, d]: w / 2, fl(1 / p), its correction (periodic_math.h), w2 / 2
+};
+int periodic_parse(const double *theta, int d, PeriodicData *out);          // host; GPX_ERR_BAD_ARG with text
+int periodic_upload(PeriodicData *pd, const double *x, int64_t n, int64_t npad, hipStream_t s);   // x (host or device) -> pd->x, xT, par; synchronises
+void periodic_release(PeriodicData *pd);
+// out[i][j] = v exp(-q_ij) (+ vt where x_i == x_j in every component) (+ add_diag where row == col), q = 1/2 sum_k w_k delta_k^2 +
+// w2_k sin^2(pi delta_k / p_k), from the raw inputs; lower_only / pad_mode / padding contract as launch_gram.
+// deriv >= 0: d K / d theta_deriv instead (no add_diag; pd carries the parameters the factor is made of)
+int launch_periodic_gram(const double *xi, int64_t n1, const double *xj, int64_t n2, const PeriodicData *pd, double add_diag,
+                         int lower_only, int pad_mode, double *out, int64_t ld, int64_t rows_pad, int64_t cols_pad, hipStream_t s,
+                         Profiler *prof, int deriv = -1);
+constexpr int PER_KC = 8;                        // parameters per sweep of the gradient pass
+constexpr int PER_NC = 3 * PER_KC + 2;           // sums per sweep: S_0, (A_k, B_k, C_k) of the sweep's k, T
+// partial [sweeps, npad / 8, PER_NC] scratch, out_dev [sweeps, PER_NC]; sweeps = ceil(d / PER_KC)
+int launch_periodic_nll_grad(const double *Kinv, int64_t ld, int64_t n, int64_t npad, const PeriodicData *pd, const double *alpha,
+                             double *partial, double *out_dev, hipStream_t s, Profiler *prof);
 
 // ---- kernels / host launchers implemented across the .hip files -------------------------------
 int launch_gram(const double *xi_w, int64_t n1, const double *xj_w, int64_t n2, int d, double v, double add_diag,
@@ -354,6 +381,7 @@ template <class Pass> int emu_left_guarded(bool use_left, Pass pass)
 // ---- launchers of propagate.hip ----------------------------------------------------------------
 int launch_nll_grad(const double *Kinv, int64_t ld, int64_t n, int64_t npad, int d, const double *alpha, const double *xw,
                     double v, double *partial, double *out_dev, int *dmax_used, hipStream_t s, Profiler *prof);
+int launch_sum_columns(const double *partial, int64_t nb, int nc, double *out_dev, hipStream_t s);   // out[c] = sum_b partial[b][c], fixed order
 int launch_kinv_pass(const double *Kinv, int64_t ld, int64_t npad, int nc, const double *V, double *KV, hipStream_t s,
                      Profiler *prof, int64_t nrows = 0);
 int launch_dot_pairs(const std::vector<std::pair<const double *, const double *>> &pr, long n, double *out_dev, hipStream_t s);
@@ -406,6 +434,7 @@ int launch_exact_many_finish(const double *Y, const double *H, int64_t npad, con
 // entry points that evaluate the GaussianCovariance kernel need the handle's inputs and theta: not a gpx_fit_matrix handle
 #define NEED_KERNEL(h, what)                                                                                             \
     do {                                                                                                                 \
+        if ((h)->per) { gpx_set_error(what ": the handle holds a PeriodicCovariance model (gpx_periodic_fit): use the gpx_periodic_* entry points"); return GPX_ERR_STATE; } \
         if ((h)->d == 0) { gpx_set_error(what ": the handle was built from a supplied matrix (gpx_fit_matrix): no inputs / theta to evaluate the kernel on"); return GPX_ERR_STATE; } \
     } while (0)
 
@@ -431,7 +460,9 @@ struct RowSolve {
     explicit RowSolve(hipStream_t s) : sc(s) {}
 };
 // bounded: the caller will give a bound on every solved row (left = true in row_solve_run after emu_left_begin with rs.left.bound filled)
-int row_solve_begin(gpx_handle *h, int64_t m, RowSolve &rs, bool bounded = false);
+// allow_few = false: the many-row solver whatever m is (a caller that promises results independent of the batch); chunk_cap > 0: at
+// most that many rows a chunk (a multiple of 128)
+int row_solve_begin(gpx_handle *h, int64_t m, RowSolve &rs, bool bounded = false, bool allow_few = true, int64_t chunk_cap = 0);
 // Zs[0 : mp) <- Z[0 : mp) L^-T (mc real rows, mp = mc rounded up to the tile); red: the fused row sums of tsolve.hip (many rows only)
 int row_solve_run(gpx_handle *h, const RowSolve &rs, int64_t mc, int64_t mp, const GemmReduce *red, bool left = false);
 #pragma GCC visibility pop

@@ -161,6 +161,8 @@ extern "C" void gpx_free(gpx_handle *h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     h->prof.destroy();
     h->tri.release();
+    periodic_release(h->per);
+    h->per = nullptr;
     if (h->external_factor) { h->L = nullptr; h->Dinv = nullptr; h->diagL = nullptr; }
     double *bufs[] = {h->Ksrc, h->x, h->xs_w, h->sw, h->wdev, h->L, h->Dinv, h->diagL, h->t, h->y, h->alpha, h->Kinv, h->KinvRows, h->Z, h->small, h->V, h->KV};
     for (double *p : bufs)
@@ -223,6 +225,24 @@ static int factor_once(gpx_handle *h, double add_diag, int *info_host)
         hipLaunchKernelGGL(pad_copy_kernel, dim3((unsigned)h->npad), dim3(256), 0, s, (const double *)h->Ksrc, (long)h->n, h->L, (long)h->npad, add_diag);
         GPX_HIP(hipGetLastError());
         GPX_TRY(chol_factor(h->L, h->npad, h->nblk, h->Dinv, h->diagL, h->info_dev, s, h->s_pan, &h->prof, h->s_top, nullptr, &ride));
+    } else if (h->per) {
+        // PeriodicCovariance (gpx_periodic_fit): K assembled straight into the padded factor buffer, +vt where two rows are equal (the
+        // kernel's own test), add_diag = the retry's jitter alone; the same split as below -- the first panel's columns now, the rest of
+        // the lower half underneath the first panel's diagonal chain
+        const double *px = h->per->x;
+        const int pdim = h->per->d;
+        if (h->npad <= c1 || !h->s_pan) {
+            GPX_TRY(launch_periodic_gram(px, h->n, px, h->n, h->per, add_diag, 1, 2, h->L, h->npad, h->npad, h->npad, s, &h->prof));
+            GPX_TRY(chol_factor(h->L, h->npad, h->nblk, h->Dinv, h->diagL, h->info_dev, s, h->s_pan, &h->prof, h->s_top, nullptr, &ride));
+        } else {
+            GPX_TRY(launch_periodic_gram(px, h->n, px, std::min<int64_t>(h->n, c1), h->per, add_diag, 1, 2, h->L, h->npad, h->npad, c1, s, &h->prof));
+            const std::function<int()> rest = [&]() -> int {
+                const double *xr = px + c1 * pdim;
+                return launch_periodic_gram(xr, h->n - c1, xr, h->n - c1, h->per, add_diag, 1, 2, h->L + c1 * h->npad + c1, h->npad,
+                                            h->npad - c1, h->npad - c1, s, &h->prof);
+            };
+            GPX_TRY(chol_factor(h->L, h->npad, h->nblk, h->Dinv, h->diagL, h->info_dev, s, h->s_pan, &h->prof, h->s_top, &rest, &ride));
+        }
     } else if (h->npad <= c1 || !h->s_pan) {
         GPX_TRY(launch_gram(h->xs_w, h->n, h->xs_w, h->n, h->d, h->v, add_diag, 1, 2, h->L, h->npad, h->npad, h->npad, s, &h->prof));
         GPX_TRY(chol_factor(h->L, h->npad, h->nblk, h->Dinv, h->diagL, h->info_dev, s, h->s_pan, &h->prof, h->s_top, nullptr, &ride));
@@ -256,14 +276,20 @@ static void setup_lookahead_streams(gpx_handle *h)
 
 // Kmat != nullptr: the handle of a SUPPLIED covariance matrix (gpx_fit_matrix; n x n, host or device): no inputs, no kernel
 // parameters (d = 0) -- the factor, alpha, K^-1 and the solves work as for any handle, everything that evaluates the kernel does not.
+// pspec != nullptr: a PeriodicCovariance model (gpx_periodic_fit): as a matrix handle (d = 0), but K is assembled on the device from x
+// and the parsed parameters, which the handle keeps (h->per)
 static int make_handle(const double *x, const double *t_centered, int64_t n, int d, const double *theta, void *stream,
-                       const ExternalFactor *ext, gpx_handle **out, const double *Kmat = nullptr)
+                       const ExternalFactor *ext, gpx_handle **out, const double *Kmat = nullptr, const PeriodicData *pspec = nullptr)
 {
     gpx_handle *h = new (std::nothrow) gpx_handle();
     if (!h) { gpx_set_error("out of host memory"); return GPX_ERR_HIP; }
     h->device = gpx_thread_device();
     int rc = 0;
-    if (!Kmat) {
+    if (pspec) {
+        h->v = pspec->v;
+        h->vt = pspec->vt;
+        d = 0;
+    } else if (!Kmat) {
         rc = parse_theta(theta, d, &h->v, &h->vt, h->w);
         if (rc) { delete h; return rc; }
         memcpy(h->theta, theta, sizeof(double) * (d + 2));
@@ -304,7 +330,11 @@ static int make_handle(const double *x, const double *t_centered, int64_t n, int
     }
 #define FIT_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { gpx_set_error("%s failed: %s", #call, hipGetErrorString(e_)); return fail(GPX_ERR_HIP); } } while (0)
     FIT_HIP(hipMemsetAsync(h->info_dev, 0, sizeof(int) * (16 + 2 * h->nblk), s));
-    if (Kmat) {
+    if (pspec) {
+        h->per = new (std::nothrow) PeriodicData(*pspec);
+        if (!h->per) { gpx_set_error("out of host memory"); return fail(GPX_ERR_HIP); }
+        if ((rc = periodic_upload(h->per, x, n, h->npad, s))) return fail(rc);
+    } else if (Kmat) {
         if ((rc = dalloc(&h->Ksrc, n * n))) return fail(rc);
         FIT_HIP(hipMemcpyAsync(h->Ksrc, Kmat, sizeof(double) * n * n, hipMemcpyDefault, s));
     } else {
@@ -316,7 +346,7 @@ static int make_handle(const double *x, const double *t_centered, int64_t n, int
     FIT_HIP(hipMemcpyAsync(h->t, t_centered, sizeof(double) * n, hipMemcpyDefault, s));
     FIT_HIP(hipStreamSynchronize(s));   // sw is a stack buffer: its copy must be complete before any return path
     if (!ext) chol_probe_streams(s, h->s_pan, h->s_top);   // while every stream of the fit is idle (cached per pair of streams)
-    if (!Kmat && (rc = launch_scale_rows(h->x, n, h->npad, d, h->sw, h->xs_w, s))) return fail(rc);
+    if (!Kmat && !pspec && (rc = launch_scale_rows(h->x, n, h->npad, d, h->sw, h->xs_w, s))) return fail(rc);
 
     if (!ext) {
         // A stalled hand-off (an in-kernel wait of the look-ahead schedule expired: streams that were probed as concurrent no longer
@@ -338,11 +368,12 @@ static int make_handle(const double *x, const double *t_centered, int64_t n, int
             return 0;
         };
         int info = 0;
-        if ((rc = factor(Kmat ? 0.0 : h->vt, &info))) return fail(rc);
+        const double diag0 = (Kmat || pspec) ? 0.0 : h->vt;   // (a supplied K carries its own diagonal; the periodic Gram adds vt itself)
+        if ((rc = factor(diag0, &info))) return fail(rc);
         if (info > 0) {
             // reference fallback: cholesky(K + 1e-5 I)   (skgpuppy/Covariance.py:180-185)
             h->jitter = 1e-5;
-            if ((rc = factor((Kmat ? 0.0 : h->vt) + h->jitter, &info))) return fail(rc);
+            if ((rc = factor(diag0 + h->jitter, &info))) return fail(rc);
             if (info > 0) {
                 gpx_set_error("covariance matrix not positive definite (leading minor %d), also with +1e-5 jitter", info);
                 return fail(info);
@@ -392,11 +423,24 @@ extern "C" int gpx_fit_matrix(const double *K, const double *t_centered, int64_t
     return make_handle(nullptr, t_centered, n, 0, nullptr, stream, nullptr, out, K);
 }
 
+// ---- PeriodicCovariance: K = cov_matrix(x, theta) of skgpuppy/Covariance.py:361-386 (through the base class's :137-164) assembled on
+// the device, then GaussianProcess.__init__'s inverse (skgpuppy/GaussianProcess.py:39-41, Covariance.py:167-187) as for every handle ----
+extern "C" int gpx_periodic_fit(const double *x, const double *t_centered, int64_t n, int d, const double *theta, void *stream,
+                                gpx_handle **out)
+{
+    if (out) *out = nullptr;
+    GPX_TRY(gpx_require_device());
+    if (!x || !t_centered || !out || n < 1) { gpx_set_error("gpx_periodic_fit: null pointer or n < 1"); return GPX_ERR_BAD_ARG; }
+    PeriodicData pd;
+    GPX_TRY(periodic_parse(theta, d, &pd));
+    return make_handle(x, t_centered, n, 0, nullptr, stream, nullptr, out, nullptr, &pd);
+}
+
 extern "C" int gpx_n(const gpx_handle *h, int64_t *n, int *d)
 {
     if (!h) { gpx_set_error("null handle"); return GPX_ERR_BAD_ARG; }
     if (n) *n = h->n;
-    if (d) *d = h->d;
+    if (d) *d = h->per ? h->per->d : h->d;
     return 0;
 }
 

@@ -1,0 +1,431 @@
+// periodic.hip -- PeriodicCovariance on the device: Gram / cross-covariance assembly and the one-pass likelihood gradient.
+//
+// Replaces PeriodicCovariance.__call__ evaluated N1 x N2 times in Python by the base class's cov_matrix_ij
+// (skgpuppy/Covariance.py:361-386 through :137-164) and the 2 + 3 d derivative matrices of Covariance._d_nll_d_theta
+// (:266-282 with :399-433).  theta = (log v, log vt, log w_1..d, log p_1..d, log w2_1..d); with delta = xi - xj
+//   q = 1/2 sum_k [ w_k delta_k^2 + w2_k sin^2(pi delta_k / p_k) ],   k(xi, xj) = v exp(-q) + (vt iff delta == 0 in every component).
+// The periodic factor needs delta itself, so the inputs are NOT pre-scaled: w / 2, 1 / p and w2 / 2 are a block of 4 d
+// wave-uniform constants read through the scalar cache.  sin(pi delta / p) comes from a reduced argument (periodic_math.h).
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "common.h"
+#include "periodic_math.h"
+
+constexpr int PG_ROWS = 64;    // rows of one block tile (4 waves x 16 rows)
+constexpr int PG_COLS = 128;   // columns of one block tile (64 lanes x 2 adjacent columns)
+enum { PAD_NONE = 0, PAD_ZERO = 1, PAD_IDENT = 2 };
+// what the deriv variant writes (the parameter's group; its coordinate is a second argument)
+enum { PD_V = 0, PD_VT = 1, PD_W = 2, PD_P = 3, PD_W2 = 4 };
+
+__device__ __forceinline__ double wave_sum_q(double s)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    return s;
+}
+
+// one entry of d K / d theta_j from Kf = v exp(-q) and the difference e of the parameter's coordinate (Covariance.py:417-433)
+__device__ __forceinline__ double periodic_deriv_entry(int kind, double e, double kf, bool equal, double vt, double hk, double ih, double il,
+                                                       double dscale)
+{
+    if (kind == PD_V) return kf;
+    if (kind == PD_VT) return equal ? vt : 0.0;
+    if (kind == PD_W) return -(hk * e) * e * kf;                      // hk = w / 2
+    const double rr = periodic_reduce(e, ih, il), sn = sinpi_half(rr);
+    if (kind == PD_P) return dscale * e * (sn * cospi_half(rr)) * kf;   // dscale = pi w2 / p
+    return -(hk * sn) * sn * kf;                                      // hk = w2 / 2
+}
+
+// gram_kernel's memory shape: the column tile of xj k-major in LDS, a wave's 16 rows of xi wave-uniform (scalar loads), a lane owns
+// two adjacent columns and stores 16 bytes.  Per k and entry: the difference, max |delta| (the equality test: delta == 0 in EVERY
+// component, not q == 0, which a zero w or an underflowing delta^2 would fool), two products into q and one sin(pi r): 24 fp64
+// operations, so the kernel is bound by the fp64 VALU from d = 2 on, not by its 8 B / entry store.
+// K_ij and K_ji are the same bits: delta changes sign, and every term of q is even in delta operation by operation.
+// DERIV: d K / d theta_j instead of K -- kind (PD_*) and coordinate kd select the factor on Kf = v exp(-q); dscale = pi w2 / p (PD_P).
+template <bool DERIV>
+__global__ __launch_bounds__(256) void periodic_gram_kernel(const double *__restrict__ xi, long n1, const double *__restrict__ xj, long n2,
+                                                           int d, const double *__restrict__ par, double v, double vt, double add_diag,
+                                                           int lower_only, int pad_mode, double *__restrict__ out, long ld, int kind, int kd,
+                                                           double dscale)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    double *b_s = smem;               // [d][128] columns of xj, k-major so a lane reads 2 adjacent columns
+
+    long ry = blockIdx.y, cx = blockIdx.x;
+    if (lower_only == 2) {
+        // 1-D grid over the tiles that touch the lower triangle (gram_kernel): row pair m holds m + 1 column tiles per row tile
+        const long lid = blockIdx.x;
+        long m = (long)((sqrt(4.0 * (double)lid + 1.0) - 1.0) * 0.5);
+        while (m * (m + 1) > lid) --m;
+        while ((m + 1) * (m + 2) <= lid) ++m;
+        const long rem = lid - m * (m + 1);
+        ry = 2 * m + (rem > m ? 1 : 0);
+        cx = rem > m ? rem - (m + 1) : rem;
+    }
+    const long row0 = ry * PG_ROWS;
+    const long col0 = cx * PG_COLS;
+    if (lower_only && col0 > row0 + (PG_ROWS - 1)) return;   // tile entirely above the diagonal
+
+    const int t = threadIdx.x;
+    for (int e = t; e < PG_COLS * d; e += 256) {
+        int c = e & (PG_COLS - 1), k = e >> 7;
+        long gc = col0 + c;
+        b_s[k * PG_COLS + c] = (gc < n2) ? xj[gc * d + k] : 0.0;
+    }
+    __syncthreads();
+
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
+    double acc0[16], acc1[16], m0[16], m1[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc0[r] = 0.0; acc1[r] = 0.0; m0[r] = 0.0; m1[r] = 0.0; }
+
+    // rows past n1 (padding) read the last real row: their outputs are overwritten below
+    const long rbase = row0 + wave * 16;
+    const double *arow[16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) arow[r] = xi + (rbase + r < n1 ? rbase + r : n1 - 1) * d;
+    for (int k = 0; k < d; ++k) {
+        const double hw = par[k], ih = par[d + k], il = par[2 * d + k], hw2 = par[3 * d + k];
+        const v2d b = *reinterpret_cast<const v2d *>(&b_s[k * PG_COLS + 2 * lane]);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const double a = arow[r][k];
+            const double e0 = a - b.x, e1 = a - b.y;
+            m0[r] = fmax(m0[r], fabs(e0));
+            m1[r] = fmax(m1[r], fabs(e1));
+            acc0[r] = fma(hw * e0, e0, acc0[r]);
+            acc1[r] = fma(hw * e1, e1, acc1[r]);
+            const double s0 = sinpi_half(periodic_reduce(e0, ih, il)), s1 = sinpi_half(periodic_reduce(e1, ih, il));
+            acc0[r] = fma(hw2 * s0, s0, acc0[r]);
+            acc1[r] = fma(hw2 * s1, s1, acc1[r]);
+        }
+    }
+
+    const long gc = col0 + 2 * lane;
+    if (DERIV) {
+        const double hk = par[(kind == PD_W2 ? 3 * d : 0) + kd], ih = par[d + kd], il = par[2 * d + kd];
+        const v2d b = *reinterpret_cast<const v2d *>(&b_s[kd * PG_COLS + 2 * lane]);
+        const bool pad = pad_mode != PAD_NONE;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const long gr = rbase + r;
+            const double a = arow[r][kd];
+            v2d o;
+            o.x = periodic_deriv_entry(kind, a - b.x, v * exp_nonpos(-acc0[r]), m0[r] == 0.0, vt, hk, ih, il, dscale);
+            o.y = periodic_deriv_entry(kind, a - b.y, v * exp_nonpos(-acc1[r]), m1[r] == 0.0, vt, hk, ih, il, dscale);
+            if (pad && (gr >= n1 || gc >= n2)) o.x = 0.0;
+            if (pad && (gr >= n1 || gc + 1 >= n2)) o.y = 0.0;
+            *reinterpret_cast<v2d *>(&out[gr * ld + gc]) = o;
+        }
+        return;
+    }
+    // a tile that touches neither the diagonal nor the padding skips the per-entry tests of those two (not the equality test: a query
+    // may equal a training row anywhere)
+    if (row0 + PG_ROWS <= n1 && col0 + PG_COLS <= n2 && (col0 >= row0 + PG_ROWS || col0 + PG_COLS <= row0)) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            v2d o;
+            o.x = v * exp_nonpos(-acc0[r]) + (m0[r] == 0.0 ? vt : 0.0);
+            o.y = v * exp_nonpos(-acc1[r]) + (m1[r] == 0.0 ? vt : 0.0);
+            *reinterpret_cast<v2d *>(&out[(rbase + r) * ld + gc]) = o;
+        }
+        return;
+    }
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const long gr = rbase + r;
+        double k0 = v * exp_nonpos(-acc0[r]) + (m0[r] == 0.0 ? vt : 0.0);
+        double k1 = v * exp_nonpos(-acc1[r]) + (m1[r] == 0.0 ? vt : 0.0);
+        if (gr == gc) k0 += add_diag;
+        if (gr == gc + 1) k1 += add_diag;
+        if (pad_mode != PAD_NONE) {
+            if (gr >= n1 || gc >= n2) k0 = (pad_mode == PAD_IDENT && gr == gc) ? 1.0 : 0.0;
+            if (gr >= n1 || gc + 1 >= n2) k1 = (pad_mode == PAD_IDENT && gr == gc + 1) ? 1.0 : 0.0;
+        }
+        v2d o;
+        o.x = k0;
+        o.y = k1;
+        *reinterpret_cast<v2d *>(&out[gr * ld + gc]) = o;
+    }
+}
+
+// out must hold rows_pad x ld doubles with rows_pad % 64 == 0, cols_pad % 128 == 0, ld >= cols_pad, ld even, out 16-byte aligned
+int launch_periodic_gram(const double *xi, int64_t n1, const double *xj, int64_t n2, const PeriodicData *pd, double add_diag,
+                         int lower_only, int pad_mode, double *out, int64_t ld, int64_t rows_pad, int64_t cols_pad, hipStream_t s,
+                         Profiler *prof, int deriv)
+{
+    const int d = pd->d;
+    if (rows_pad % PG_ROWS || cols_pad % PG_COLS || ld < cols_pad || (ld & 1) || d < 1 || d > GPX_MAX_D || n1 < 1 || n2 < 1 ||
+        n1 > rows_pad || n2 > cols_pad || deriv < -1 || deriv >= 2 + 3 * d) {
+        gpx_set_error("launch_periodic_gram: bad shape (n1=%ld n2=%ld rows_pad=%ld cols_pad=%ld ld=%ld d=%d deriv=%d)", (long)n1, (long)n2,
+                      (long)rows_pad, (long)cols_pad, (long)ld, d, deriv);
+        return GPX_ERR_BAD_ARG;
+    }
+    dim3 grid((unsigned)(cols_pad / PG_COLS), (unsigned)(rows_pad / PG_ROWS));
+    const size_t lds = (size_t)PG_COLS * d * sizeof(double);
+    const double stored = lower_only ? 0.5 * (double)rows_pad * (double)cols_pad : (double)rows_pad * (double)cols_pad;
+    ProfScope ps(prof, s, GPX_K_GRAM, 8.0 * stored);
+    if (lower_only && rows_pad == cols_pad && rows_pad % (2 * PG_ROWS) == 0) {
+        const int64_t m = rows_pad / (2 * PG_ROWS);
+        grid = dim3((unsigned)(m * (m + 1)), 1);
+        lower_only = 2;
+    }
+    if (deriv < 0) {
+        hipLaunchKernelGGL(periodic_gram_kernel<false>, grid, dim3(256), lds, s, xi, (long)n1, xj, (long)n2, d, (const double *)pd->par, pd->v,
+                           pd->vt, add_diag, lower_only, pad_mode, out, (long)ld, 0, 0, 0.0);
+    } else {
+        const int kind = deriv < 2 ? deriv : 2 + (deriv - 2) / d, kd = deriv < 2 ? 0 : (deriv - 2) % d;
+        const double dscale = kind == PD_P ? M_PI * pd->w2[kd] / pd->p[kd] : 0.0;
+        hipLaunchKernelGGL(periodic_gram_kernel<true>, grid, dim3(256), lds, s, xi, (long)n1, xj, (long)n2, d, (const double *)pd->par, pd->v,
+                           pd->vt, 0.0, lower_only, pad_mode, out, (long)ld, kind, kd, dscale);
+    }
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Gradient of the negative log likelihood (Covariance._d_nll_d_theta, skgpuppy/Covariance.py:266-282, with
+// PeriodicCovariance._d_cov_d_theta, :399-433): ONE pass over the j <= i half of K^-1 recomputes Kf_ij = v exp(-q_ij) on the fly and
+// accumulates, with M_ij = Kinv_ij - a_i a_j and s, c = sin, cos(pi delta_k / p_k),
+//   S_0 = sum M Kf,  A_k = sum M Kf delta_k^2,  B_k = sum M Kf delta_k s c,  C_k = sum M Kf s^2,  T = sum over the pairs with x_i == x_j of M
+// (T = tr Kinv - a.a without duplicate rows), so that
+//   g_0 = S_0 / 2,  g_1 = vt T / 2,  g_{w_k} = -w_k A_k / 4,  g_{p_k} = (pi w2_k / p_k) B_k / 2,  g_{w2_k} = -w2_k C_k / 4.
+// 3 d + 2 accumulators do not fit in registers at d = 64: grid.y sweeps of KC coordinates each.  A sweep forms q over ALL d
+// coordinates (a runtime loop: no coordinate beyond d is ever evaluated, no per-thread array is indexed by it), then the three
+// weighted terms of its own KC coordinates with the sine and cosine formed once more -- per pair d + KC sines and KC cosines,
+// 3 KC + 2 accumulators, whatever d is.  From d = 9 on every sweep repeats q: 2 x the sines at d = 16, 4.5 x at d = 64.
+// A lane owns a column j and reads it from the k-major copy of the inputs (coalesced); the block's 8 rows sit in LDS.
+// partial[sweep][block][3 KC + 2]: [0] = S_0, [1 + 3 kk ..] = A, B, C of coordinate sweep KC + kk, [3 KC + 1] = T.
+// ---------------------------------------------------------------------------------------------
+template <int KC>
+__global__ __launch_bounds__(256) void periodic_nll_grad_kernel(const double *__restrict__ Kinv, long ld, long n, long npad, int d,
+                                                               const double *__restrict__ alpha, const double *__restrict__ x,
+                                                               const double *__restrict__ xT, const double *__restrict__ par, double v,
+                                                               double *__restrict__ partial)
+{
+    constexpr int R = 8, NC = 3 * KC + 2;
+    __shared__ double xs[R][GPX_MAX_D];
+    __shared__ double as[R];
+    __shared__ double red[4][NC];
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const int rb = gridDim.x - 1 - blockIdx.x;
+    const long i0 = (long)rb * R;
+    const int k0 = blockIdx.y * KC;
+    for (int q = t; q < R * GPX_MAX_D; q += 256) {
+        const int r = q / GPX_MAX_D, k = q - r * GPX_MAX_D;
+        xs[r][k] = (k < d && i0 + r < n) ? x[(i0 + r) * d + k] : 0.0;
+    }
+    if (t < R) as[t] = alpha[i0 + t];
+    __syncthreads();
+    double acc[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) acc[c] = 0.0;
+    for (long j = t; j < i0 + R && j < n; j += 256) {
+        const double aj = alpha[j];
+        double q[R], mx[R], wq[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) { q[r] = 0.0; mx[r] = 0.0; }
+        for (int k = 0; k < d; ++k) {
+            const double hw = par[k], ih = par[d + k], il = par[2 * d + k], hw2 = par[3 * d + k];
+            const double xjk = xT[(long)k * npad + j];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const double e = xs[r][k] - xjk;
+                mx[r] = fmax(mx[r], fabs(e));
+                q[r] = fma(hw * e, e, q[r]);
+                const double sn = sinpi_half(periodic_reduce(e, ih, il));
+                q[r] = fma(hw2 * sn, sn, q[r]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const long i = i0 + r;
+            const bool live = i < n && j <= i;
+            const double mij = live ? Kinv[i * ld + j] - as[r] * aj : 0.0;
+            const double wgt = (j < i) ? 2.0 : 1.0;
+            wq[r] = mij * wgt * v * exp_nonpos(-q[r]);
+            acc[0] += wq[r];
+            if (live && mx[r] == 0.0) acc[NC - 1] += mij * wgt;
+        }
+#pragma unroll
+        for (int kk = 0; kk < KC; ++kk) {
+            const int k = k0 + kk;
+            if (k < d) {
+                const double ih = par[d + k], il = par[2 * d + k];
+                const double xjk = xT[(long)k * npad + j];
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const double e = xs[r][k] - xjk;
+                    const double rr = periodic_reduce(e, ih, il), sn = sinpi_half(rr), cs = cospi_half(rr);
+                    acc[1 + 3 * kk] = fma(wq[r], e * e, acc[1 + 3 * kk]);
+                    acc[2 + 3 * kk] = fma(wq[r], e * (sn * cs), acc[2 + 3 * kk]);
+                    acc[3 + 3 * kk] = fma(wq[r], sn * sn, acc[3 + 3 * kk]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const double s = wave_sum_q(acc[c]);
+        if (lane == 0) red[wave][c] = s;
+    }
+    __syncthreads();
+    if (t < NC) partial[((long)blockIdx.y * gridDim.x + rb) * NC + t] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+}
+
+int launch_periodic_nll_grad(const double *Kinv, int64_t ld, int64_t n, int64_t npad, const PeriodicData *pd, const double *alpha,
+                             double *partial, double *out_dev, hipStream_t s, Profiler *prof)
+{
+    const unsigned nblk = (unsigned)(npad / 8);
+    const int sweeps = (pd->d + PER_KC - 1) / PER_KC;
+    {
+        ProfScope ps(prof, s, GPX_K_QUAD, 4.0 * (double)npad * (double)npad * sweeps);
+        hipLaunchKernelGGL(periodic_nll_grad_kernel<PER_KC>, dim3(nblk, (unsigned)sweeps), dim3(256), 0, s, Kinv, (long)ld, (long)n, (long)npad,
+                           pd->d, alpha, (const double *)pd->x, (const double *)pd->xT, (const double *)pd->par, pd->v, partial);
+        GPX_HIP(hipGetLastError());
+    }
+    for (int y = 0; y < sweeps; ++y) GPX_TRY(launch_sum_columns(partial + (int64_t)y * nblk * PER_NC, nblk, PER_NC, out_dev + y * PER_NC, s));
+    return 0;
+}
+
+// ---- parameters and inputs of a periodic model -------------------------------------------------------------------
+int periodic_parse(const double *theta, int d, PeriodicData *out)
+{
+    if (!theta || d < 1 || d > GPX_MAX_D) {
+        gpx_set_error("periodic kernel: bad theta / d=%d (1..%d supported)", d, GPX_MAX_D);
+        return GPX_ERR_BAD_ARG;
+    }
+    out->d = d;
+    out->v = exp(theta[0]);
+    out->vt = exp(theta[1]);   // theta[1] = -inf gives vt = 0
+    if (!(out->v > 0.0) || !isfinite(out->v) || !isfinite(out->vt)) {
+        gpx_set_error("periodic kernel: theta gives v=%g vt=%g", out->v, out->vt);
+        return GPX_ERR_BAD_ARG;
+    }
+    for (int k = 0; k < d; ++k) {
+        out->w[k] = exp(theta[2 + k]);
+        out->p[k] = exp(theta[2 + d + k]);
+        out->w2[k] = exp(theta[2 + 2 * d + k]);
+        if (!(out->w[k] >= 0.0) || !isfinite(out->w[k]) || !(out->p[k] > 0.0) || !isfinite(out->p[k]) || !(out->w2[k] >= 0.0) ||
+            !isfinite(out->w2[k])) {
+            gpx_set_error("periodic kernel: theta gives w[%d]=%g p[%d]=%g w2[%d]=%g", k, out->w[k], k, out->p[k], k, out->w2[k]);
+            return GPX_ERR_BAD_ARG;
+        }
+    }
+    return 0;
+}
+
+__global__ __launch_bounds__(256) void periodic_transpose_kernel(const double *__restrict__ x, long n, long npad, int d, double *__restrict__ xT)
+{
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= npad * d) return;
+    const long k = e / npad, j = e - k * npad;
+    xT[e] = j < n ? x[j * d + k] : 0.0;
+}
+
+// the kernels' constant block [4][d]: w / 2, ih = fl(1 / p), il = fl((1 - ih p) ih) (periodic_math.h), w2 / 2
+static void periodic_pack(const PeriodicData &pd, double *host)
+{
+    const int d = pd.d;
+    for (int k = 0; k < d; ++k) {
+        const double ih = 1.0 / pd.p[k];
+        host[k] = 0.5 * pd.w[k];
+        host[d + k] = ih;
+        host[2 * d + k] = isfinite(ih) ? fma(-ih, pd.p[k], 1.0) * ih : 0.0;   // (a subnormal p: ih = inf is refused by nothing, q is then NaN)
+        host[3 * d + k] = 0.5 * pd.w2[k];
+    }
+}
+
+int periodic_upload(PeriodicData *pd, const double *x, int64_t n, int64_t npad, hipStream_t s)
+{
+    const int d = pd->d;
+    double host[4 * GPX_MAX_D];
+    periodic_pack(*pd, host);
+    GPX_TRY(dalloc(&pd->par, 4 * d));
+    GPX_HIP(hipMemcpyAsync(pd->par, host, sizeof(double) * 4 * d, hipMemcpyHostToDevice, s));
+    {
+        GPX_TRY(dalloc(&pd->x, n * d));
+        GPX_TRY(dalloc(&pd->xT, npad * d));
+        GPX_HIP(hipMemcpyAsync(pd->x, x, sizeof(double) * n * d, hipMemcpyDefault, s));
+        hipLaunchKernelGGL(periodic_transpose_kernel, dim3((unsigned)((npad * d + 255) / 256)), dim3(256), 0, s, (const double *)pd->x, (long)n,
+                           (long)npad, d, pd->xT);
+        GPX_HIP(hipGetLastError());
+    }
+    GPX_HIP(hipStreamSynchronize(s));   // host is a stack buffer
+    return 0;
+}
+
+void periodic_release(PeriodicData *pd)
+{
+    if (!pd) return;
+    for (double *p : {pd->x, pd->xT, pd->par})
+        if (p) dfree(p);
+    delete pd;
+}
+
+// ---- C-ABI: the stand-alone Gram --------------------------------------------------------------------------------
+extern "C" int gpx_periodic_gram(const double *xi, int64_t n1, const double *xj, int64_t n2, int d, const double *theta, int deriv,
+                                 double *out)
+{
+    GPX_TRY(gpx_require_device());
+    if (!xi || !xj || !out || n1 < 1 || n2 < 1) { gpx_set_error("gpx_periodic_gram: null pointer or n < 1"); return GPX_ERR_BAD_ARG; }
+    PeriodicData pd;
+    GPX_TRY(periodic_parse(theta, d, &pd));
+    if (deriv < -1 || deriv >= 2 + 3 * d) { gpx_set_error("gpx_periodic_gram: deriv=%d (-1 .. %d)", deriv, 1 + 3 * d); return GPX_ERR_BAD_ARG; }
+    const int64_t rp = round_up(n1, TILE), cp = round_up(n2, TILE);
+    hipStream_t s = nullptr;
+    Scratch sc(s);
+    double *a = nullptr, *b = nullptr, *o = nullptr, *par = nullptr;
+    GPX_TRY(sc.take(&par, 4 * d));
+    {
+        // (the parameter block through the call's own scratch: nothing of pd outlives the call)
+        double host[4 * GPX_MAX_D];
+        periodic_pack(pd, host);
+        GPX_HIP(hipMemcpy(par, host, sizeof(double) * 4 * d, hipMemcpyHostToDevice));
+    }
+    pd.par = par;
+    GPX_TRY(sc.take(&a, n1 * d));
+    GPX_HIP(hipMemcpy(a, xi, sizeof(double) * n1 * d, hipMemcpyDefault));
+    if (xj == xi && n1 == n2) b = a;
+    else {
+        GPX_TRY(sc.take(&b, n2 * d));
+        GPX_HIP(hipMemcpy(b, xj, sizeof(double) * n2 * d, hipMemcpyDefault));
+    }
+    GPX_TRY(sc.take(&o, rp * cp));
+    GPX_TRY(launch_periodic_gram(a, n1, b, n2, &pd, 0.0, 0, PAD_ZERO, o, cp, rp, cp, s, nullptr, deriv));
+    GPX_HIP(hipMemcpy2D(out, sizeof(double) * n2, o, sizeof(double) * cp, sizeof(double) * n2, n1, hipMemcpyDefault));
+    return 0;
+}
+
+// d nll / d theta [2 + 3 d] at the handle's theta
+extern "C" int gpx_periodic_nll_grad(gpx_handle *h, double *grad_out)
+{
+    CHECK_H(h);
+    if (!h->per) { gpx_set_error("gpx_periodic_nll_grad: not a gpx_periodic_fit handle"); return GPX_ERR_STATE; }
+    if (!grad_out) { gpx_set_error("null argument"); return GPX_ERR_BAD_ARG; }
+    GPX_TRY(ensure_kinv(h));
+    const PeriodicData *pd = h->per;
+    const int d = pd->d, sweeps = (d + PER_KC - 1) / PER_KC;
+    Scratch sc(h->stream);
+    double *buf = nullptr;
+    const int64_t nb = h->npad / 8;
+    GPX_TRY(sc.take(&buf, (nb + 1) * sweeps * PER_NC));
+    double *outd = buf + nb * sweeps * PER_NC;
+    GPX_TRY(launch_periodic_nll_grad(h->Kinv, h->npad, h->n, h->npad, pd, h->alpha, buf, outd, h->stream, &h->prof));
+    double o[(GPX_MAX_D / PER_KC) * PER_NC];
+    GPX_HIP(hipMemcpyAsync(o, outd, sizeof(double) * sweeps * PER_NC, hipMemcpyDeviceToHost, h->stream));
+    GPX_HIP(hipStreamSynchronize(h->stream));
+    std::vector<double> g(2 + 3 * d);
+    g[0] = 0.5 * o[0];                                        // dK/dtheta_0 = Kf                     (Covariance.py:417-419)
+    g[1] = 0.5 * pd->vt * o[PER_NC - 1];                      // vt on equality                        (:420-422)
+    for (int k = 0; k < d; ++k) {
+        const double *ok = o + (k / PER_KC) * PER_NC + 1 + 3 * (k % PER_KC);
+        g[2 + k] = -0.25 * pd->w[k] * ok[0];                  // -1/2 w_k delta_k^2 Kf                 (:423-425)
+        g[2 + d + k] = 0.5 * (M_PI * pd->w2[k] / pd->p[k]) * ok[1];   // pi delta_k w2_k / p_k sin cos Kf   (:426-429)
+        g[2 + 2 * d + k] = -0.25 * pd->w2[k] * ok[2];         // -1/2 w2_k sin^2 Kf                    (:430-433)
+    }
+    GPX_HIP(hipMemcpy(grad_out, g.data(), sizeof(double) * (2 + 3 * d), hipMemcpyDefault));
+    return 0;
+}

@@ -17,16 +17,17 @@ int ensure_Z(gpx_handle *h, int64_t rows)
 }
 
 // ---- predict (RowSolve: common.h) ----------------------------------------------------------------
-int row_solve_begin(gpx_handle *h, int64_t m, RowSolve &rs, bool bounded)
+int row_solve_begin(gpx_handle *h, int64_t m, RowSolve &rs, bool bounded, bool allow_few, int64_t chunk_cap)
 {
     int64_t cap = ((int64_t)8 << 30) / (h->npad * (int64_t)sizeof(double));   // rows per 8 GB buffer (two of them: Z and Zs)
     cap = std::max<int64_t>(TILE, cap / TILE * TILE);
     cap = std::min<int64_t>(cap, 32768);
+    if (chunk_cap > 0) cap = std::min<int64_t>(cap, std::max<int64_t>(TILE, chunk_cap / TILE * TILE));
     rs.chunk = std::min<int64_t>(round_up(m, TILE), cap);
     GPX_TRY(ensure_Z(h, rs.chunk));
     // the triangular solve runs out of place against the inverted diagonal squares (tsolve.hip): second slab-major buffer
     GPX_TRY(rs.sc.take(&rs.Zs, rs.chunk * h->npad));
-    rs.few = m <= 32 && h->tri.ready() && h->tri.P >= 2;
+    rs.few = allow_few && m <= 32 && h->tri.ready() && h->tri.P >= 2;
     // the emulated updates' workspace (emu.hip), once per call: sized for the chunk, it serves every shorter one
     if (!rs.few) trsm_emu_need(rs.ew, rs.chunk, &h->tri, 0, h->tri.P);
     if (rs.ew.a_bytes) GPX_TRY(emu_work_alloc(rs.ew, rs.sc));
@@ -56,19 +57,27 @@ int row_solve_run(gpx_handle *h, const RowSolve &rs, int64_t mc, int64_t mp, con
 
 // xs != nullptr: the cross-covariance rows come from the Gram kernel (gpx_predict); otherwise kv [m, n] is the caller's
 // (gpx_predict_kv) and kdiag [m] the prior variance of each query (the diagonal of cov_matrix(x_star), GaussianProcess.py:75)
+// A periodic handle (xs with h->per): the rows come from periodic_gram_kernel, +vt on equality included, and the prior variance is
+// v + vt.  That call promises a result that does not depend on the query's place in the batch or on the chunking: always the many-row
+// solver and the stand-alone row reduction (the few-vector solver and the reduction fused into a slab's last product sum in other
+// orders), chunks of at most GPX_PERIODIC_CHUNK rows (read at every call; default: the solver's own cap).
 static int predict_common(gpx_handle *h, const double *xs, const double *kv, const double *kdiag, int64_t m, double *mean_out, double *var_out)
 {
     hipStream_t s = h->stream;
-    const int d = h->d;
+    const PeriodicData *per = xs ? h->per : nullptr;
+    const int d = per ? per->d : h->d;
     RowSolve rs(s);
     // |row of Zs|^2 = k*^T K^-1 k* <= k(x*, x*): sqrt(v) for the built-in kernel, sqrt(kdiag) for the caller's (tsolve.hip, launch_row_bounds)
-    GPX_TRY(row_solve_begin(h, m, rs, true));
+    int64_t chunk_cap = 0;
+    if (per)
+        if (const char *e = getenv("GPX_PERIODIC_CHUNK")) chunk_cap = atoll(e);
+    GPX_TRY(row_solve_begin(h, m, rs, true, !per, chunk_cap));
     const int64_t chunk = rs.chunk;
     double *xq = nullptr, *xqw = nullptr, *mv = nullptr, *kd = nullptr, *part = nullptr;
     int rc = 0;
     // the row sums |z|^2 and z.y ride in the epilogue of each slab's last product (tsolve.hip): per row one partial pair per 64 columns
     const int64_t nslots = h->npad / 64;
-    const bool fused = chunk >= 3072;
+    const bool fused = chunk >= 3072 && !per;
     GPX_TRY(rs.sc.take(&xq, chunk * std::max(d, 1)));
     GPX_TRY(rs.sc.take(&xqw, chunk * std::max(d, 1)));
     GPX_TRY(rs.sc.take(&mv, 2 * chunk));
@@ -81,6 +90,7 @@ static int predict_common(gpx_handle *h, const double *xs, const double *kv, con
         if (xs) {
             e = hipMemcpyAsync(xq, xs + m0 * d, sizeof(double) * mc * d, hipMemcpyDefault, s);
             if (e != hipSuccess) { gpx_set_error("copy xs failed: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
+            if (per) return launch_periodic_gram(xq, mc, per->x, h->n, per, 0.0, 0, 1, h->Z, h->npad, mp, h->npad, s, &h->prof);
             GPX_TRY(launch_scale_rows(xq, mc, mp, d, h->sw, xqw, s));
             // kv = cross-covariance (no vt), zero padded: rows >= mc and columns >= n are 0
             return launch_gram(xqw, mc, h->xs_w, h->n, d, h->v, 0.0, 0, 1, h->Z, h->npad, mp, h->npad, s, &h->prof);
@@ -112,7 +122,7 @@ static int predict_common(gpx_handle *h, const double *xs, const double *kv, con
         rc = emu_left_guarded(rs.use_left, [&](bool left, int *status) -> int {
             GPX_TRY(fill(m0, mc, mp));
             if (left) {
-                GPX_TRY(launch_row_bounds(xs ? nullptr : kd, h->v, mc, rs.left.bound, s));
+                GPX_TRY(launch_row_bounds(xs ? nullptr : kd, per ? h->v + h->vt : h->v, mc, rs.left.bound, s));
                 GPX_TRY(emu_left_begin(rs.left, rs.left.bound, mc, s));
             }
             GPX_TRY(solve(mc, mp, left));
@@ -134,6 +144,17 @@ extern "C" int gpx_predict(gpx_handle *h, const double *xs, int64_t m, double *m
     CHECK_H(h);
     NEED_KERNEL(h, "gpx_predict");
     if (m < 0 || (m > 0 && (!xs || !mean_out || !var_out))) { gpx_set_error("gpx_predict: bad arguments"); return GPX_ERR_BAD_ARG; }
+    if (m == 0) return 0;
+    return predict_common(h, xs, nullptr, nullptr, m, mean_out, var_out);
+}
+
+// estimate_many / estimate with cov = PeriodicCovariance (skgpuppy/GaussianProcess.py:68-80, :94-111): kv = cov_matrix_ij(x_star, x) with the
+// base class's +vt on equality, k = v + vt for every query; mean WITHOUT meant
+extern "C" int gpx_periodic_predict(gpx_handle *h, const double *xs, int64_t m, double *mean_out, double *var_out)
+{
+    CHECK_H(h);
+    if (!h->per) { gpx_set_error("gpx_periodic_predict: not a gpx_periodic_fit handle"); return GPX_ERR_STATE; }
+    if (m < 0 || (m > 0 && (!xs || !mean_out || !var_out))) { gpx_set_error("gpx_periodic_predict: bad arguments"); return GPX_ERR_BAD_ARG; }
     if (m == 0) return 0;
     return predict_common(h, xs, nullptr, nullptr, m, mean_out, var_out);
 }

@@ -809,6 +809,13 @@ __global__ __launch_bounds__(256) void sum_columns_kernel(const double *__restri
     if (threadIdx.x == 0) out[c] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
 }
 
+int launch_sum_columns(const double *partial, int64_t nb, int nc, double *out_dev, hipStream_t s)
+{
+    hipLaunchKernelGGL(sum_columns_kernel, dim3((unsigned)nc), dim3(256), 0, s, partial, (long)nb, nc, out_dev);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
 // out_dev[0..dmax+1] (layout above); returns the DMAX used so the caller can index T
 int launch_nll_grad(const double *Kinv, int64_t ld, int64_t n, int64_t npad, int d, const double *alpha, const double *xw,
                     double v, double *partial, double *out_dev, int *dmax_used, hipStream_t s, Profiler *prof)

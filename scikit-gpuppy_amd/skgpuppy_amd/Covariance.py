@@ -438,6 +438,203 @@ class GaussianCovariance(Covariance):
         return np.atleast_2d(-diff * w * e).T
 
 
+class _PeriodicModel(_MatrixModel):
+    """Owner of one gpx_periodic_fit handle: K of the periodic kernel assembled and factored on the device.  Everything a matrix
+    model answers, plus the kernel's own prediction and likelihood gradient."""
+
+    def __init__(self, x, t_centered, theta):
+        x = _gpx.f64(x)
+        if x.ndim != 2:
+            raise ValueError("x must be an (n, d) array")
+        self.n, self.d = x.shape
+        theta = _periodic_theta(theta, self.d)
+        t = np.zeros(self.n) if t_centered is None else _gpx.f64(t_centered)
+        if t.shape != (self.n,):
+            raise ValueError("t must have %d entries" % self.n)
+        self._h = ctypes.c_void_p()
+        _gpx.check(_gpx.lib.gpx_periodic_fit(_gpx.ptr(x), _gpx.ptr(t), self.n, self.d, _gpx.ptr(theta), None, ctypes.byref(self._h)),
+                   "gpx_periodic_fit")
+
+    def predict(self, xs):
+        m = xs.shape[0]
+        mean = np.empty(m)
+        var = np.empty(m)
+        _gpx.check(_gpx.lib.gpx_periodic_predict(self.handle, _gpx.ptr(xs), m, _gpx.ptr(mean), _gpx.ptr(var)), "gpx_periodic_predict")
+        return mean, var
+
+    def nll_grad(self):
+        g = np.empty(2 + 3 * self.d)
+        _gpx.check(_gpx.lib.gpx_periodic_nll_grad(self.handle, _gpx.ptr(g)), "gpx_periodic_nll_grad")
+        return g
+
+
+def _periodic_theta(theta, d):
+    th = _gpx.f64(theta)
+    if th.ndim != 1 or th.shape[0] != 2 + 3 * d:
+        raise ValueError("theta must have 2 + 3 d = %d entries, got shape %r" % (2 + 3 * d, th.shape))
+    return th
+
+
+class PeriodicCovariance(Covariance):
+    """ARD squared exponential times a periodic factor per dimension, theta = (log v, log vt, log w_1..d, log p_1..d, log w2_1..d)
+    (skgpuppy/Covariance.py:361-433):  k(xi, xj) = v exp(-1/2 sum_k [w_k delta_k^2 + w2_k sin^2(pi delta_k / p_k)]) + (vt iff xi == xj).
+
+    The reference class defines the scalar kernel, its theta derivatives and get_theta only and inherits every matrix method from the
+    base class -- so cov_matrix AND cov_matrix_ij carry the +vt on exact equality (also for a query that equals a training row), and
+    duplicate training rows make K singular.  Here the matrix methods are the fused HIP path (periodic_gram_kernel, Cholesky on the
+    Gram tiles, one-pass likelihood gradient) with those semantics; a subclass that overrides one of the matrix builders falls back to
+    the generic device route of `Covariance` (`_fused()`), as for GaussianCovariance.  Like the reference's it offers no Jacobian /
+    Hessian: the propagation classes treat it as any generic operator."""
+
+    _MATRIX_METHODS = GaussianCovariance._MATRIX_METHODS
+
+    def _fused(self):
+        """True when every matrix-defining method of this instance is PeriodicCovariance's own"""
+        cls = type(self)
+        return cls is PeriodicCovariance or all(getattr(cls, m) is getattr(PeriodicCovariance, m) for m in self._MATRIX_METHODS)
+
+    @staticmethod
+    def _split(xi, theta):
+        d, = np.shape(xi)
+        with np.errstate(divide="ignore"):
+            v = np.exp(theta[0])
+            vt = np.exp(theta[1])
+            w = np.exp(np.asarray(theta[2:2 + d], dtype=float))
+            p = np.exp(np.asarray(theta[2 + d:2 + 2 * d], dtype=float))
+            w2 = np.exp(np.asarray(theta[2 + 2 * d:], dtype=float))
+        return d, v, vt, w, p, w2
+
+    def __call__(self, xi, xj, theta):
+        # (Covariance.py:369-386), the "+vt iff xi == xj elementwise" hack included
+        xi = np.asarray(xi)
+        xj = np.asarray(xj)
+        d, v, vt, w, p, w2 = self._split(xi, theta)
+        diff = xi - xj
+        return v * np.exp(-0.5 * ((np.sin(np.pi / p * diff) ** 2 * w2).sum() + np.dot(diff.T, w * diff))) + (vt if (xi == xj).all() else 0)
+
+    def get_theta(self, x, t):
+        # (Covariance.py:388-396)
+        n, d = np.shape(x)
+        theta = np.ones(2 + 3 * d)
+        theta[0] = np.log(np.var(t)) if t is not None else 1
+        theta[1] = np.log(np.var(t) / 100) if t is not None else 1
+        theta[2:2 + d] = -2 * np.log((np.max(x, 0) - np.min(x, 0)) / 2.0)
+        theta[2 + d:2 + 2 * d] = np.ones(d)
+        theta[2 + 2 * d:] = -2 * np.log((np.max(x, 0) - np.min(x, 0)) / 2.0) + np.log(100)
+        return theta
+
+    def _d_cov_d_theta(self, xi, xj, theta, j):
+        # (Covariance.py:399-433): theta is the LOG of the parameters
+        xi = np.asarray(xi)
+        xj = np.asarray(xj)
+        d, v, vt, w, p, w2 = self._split(xi, theta)
+        diff = xi - xj
+        if j == 1:
+            return vt if (xi == xj).all() else 0
+        kf = v * np.exp(-0.5 * ((np.sin(np.pi / p * diff) ** 2 * w2).sum() + np.dot(diff.T, w * diff)))
+        if j == 0:
+            return kf
+        if j < 2 + d:
+            return -0.5 * (diff[j - 2] ** 2 * w[j - 2]) * kf
+        if j < 2 + 2 * d:
+            i = j - (2 + d)
+            return np.pi * diff[i] * w2[i] / p[i] * np.sin(np.pi / p[i] * diff[i]) * np.cos(np.pi / p[i] * diff[i]) * kf
+        if j < 2 + 3 * d:
+            i = j - (2 + 2 * d)
+            return -0.5 * (np.sin(np.pi / p[i] * diff[i]) ** 2 * w2[i]) * kf
+        return None
+
+    def _gram(self, xi, xj, theta, deriv):
+        a = _gpx.f64(xi)
+        b = a if xj is xi else _gpx.f64(xj)
+        if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1]:
+            raise ValueError("inputs must be (n, d) arrays with equal d")
+        th = _periodic_theta(theta, a.shape[1])
+        K = np.empty((a.shape[0], b.shape[0]), dtype=np.float64)
+        if K.size:
+            _gpx.check(_gpx.lib.gpx_periodic_gram(_gpx.ptr(a), a.shape[0], _gpx.ptr(b), b.shape[0], a.shape[1], _gpx.ptr(th), int(deriv),
+                                                  _gpx.ptr(K)), "gpx_periodic_gram")
+        return K
+
+    def cov_matrix_ij(self, xi, xj, theta):
+        """N1 x N2 matrix of the kernel, +vt wherever two rows are equal (Covariance.py:137-152 over :369-386) -- HIP Gram kernel."""
+        return self._gram(xi, xj, theta, -1)
+
+    def cov_matrix(self, x, theta):
+        # (Covariance.py:155-164): cov_matrix_ij(x, x) -- a subclass's own cross-covariance if it has one
+        return self.cov_matrix_ij(x, x, theta)
+
+    def _d_cov_matrix_d_theta_ij(self, xi, xj, theta, j):
+        """d K / d theta_j entry-wise (Covariance.py:236-253 over :399-433) from the kernel's derivative variant.  An accessor: the
+        likelihood gradient never forms these matrices (periodic_nll_grad_kernel)."""
+        if not 0 <= j < len(theta):
+            raise ValueError("j must be in [0, %d)" % len(theta))
+        return self._gram(xi, xj, theta, j)
+
+    def _d_cov_matrix_d_theta(self, x, theta, j):
+        # (Covariance.py:256-265)
+        return self._d_cov_matrix_d_theta_ij(x, x, theta, j)
+
+    def inv_cov_matrix(self, x, theta, cov_matrix=None):
+        """K^-1 (Covariance.py:167-187) from a device fit: K never leaves the device"""
+        if cov_matrix is not None or not self._fused():
+            return Covariance.inv_cov_matrix(self, x, theta, cov_matrix)
+        model = _PeriodicModel(x, None, theta)
+        try:
+            return model.kinv()
+        finally:
+            model.close()
+
+    def _log_det_cov_matrix(self, x, theta):
+        """log det K (Covariance.py:189-195) from the Cholesky factor of a device fit"""
+        if not self._fused():
+            return Covariance._log_det_cov_matrix(self, x, theta)
+        model = _PeriodicModel(x, None, theta)
+        try:
+            return model.logdet()
+        finally:
+            model.close()
+
+    def _model_at(self, x, t, theta):
+        """device model fitted at theta, cached on (x, t, theta) identity/bytes: L-BFGS-B asks for the value and the
+        gradient at the same theta in two separate calls."""
+        xa = _gpx.f64(x)
+        ta = _gpx.f64(t)
+        th = _periodic_theta(theta, xa.shape[1]).copy()
+        key = (xa.ctypes.data if xa is x else id(x), xa.shape, ta.tobytes(), th.tobytes())
+        cached = getattr(self, "_ml_cache", None)
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        if cached is not None:
+            cached[1].close()
+        self._ml_cache = None
+        model = _PeriodicModel(xa, ta, th)
+        self._ml_cache = (key, model)
+        return model
+
+    def _negativeloglikelihood(self, x, t, theta):
+        """N/2 log 2pi + 1/2 log det K + 1/2 t^T K^-1 t on the GPU (Covariance.py:197-216); 1e20 when K cannot be factored, like the
+        reference's except branch."""
+        if not self._fused():
+            return Covariance._negativeloglikelihood(self, x, t, theta)
+        try:
+            return self._model_at(x, t, theta).nll()
+        except (np.linalg.LinAlgError, ValueError, ZeroDivisionError):
+            return 1.0e+20
+
+    def _d_nll_d_theta(self, x, t, theta):
+        """gradient of the NLL (Covariance.py:266-282 with :399-433): one fused pass over K^-1 on the GPU instead of 2 + 3 d
+        derivative matrices evaluated entry by entry in Python."""
+        if not self._fused():
+            return Covariance._d_nll_d_theta(self, x, t, theta)
+        return self._model_at(x, t, theta).nll_grad()
+
+    def __getstate__(self):
+        state = Covariance.__getstate__(self)
+        state.pop("_ml_cache", None)     # device handles never enter a pickle
+        return state
+
+
 class _SPGPDeviceModel(object):
     """Owner of one gpx_spgp handle: K_NM, chol(K_M + 1e-5 I), Lambda and chol(B + 1e-5 I) resident in HBM."""
 

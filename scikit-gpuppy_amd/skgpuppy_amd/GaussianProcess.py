@@ -10,7 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _gpx
-from .Covariance import GaussianCovariance, SPGPCovariance, _MatrixModel
+from .Covariance import GaussianCovariance, PeriodicCovariance, SPGPCovariance, _MatrixModel, _PeriodicModel
 
 
 class _DeviceModel(object):
@@ -122,7 +122,7 @@ class GaussianProcess(object):
     # ---- device model management -----------------------------------------------------------
     def _route(self):
         """which device path serves this operator.  The reference's GaussianProcess talks to `cov` only through its interface
-        (GaussianProcess.py:39-41, :75-78); here the two built-in kernels have fused paths and EVERY other operator -- a
+        (GaussianProcess.py:39-41, :75-78); here the three built-in kernels have fused paths and EVERY other operator -- a
         from-scratch Covariance, or a subclass of a built-in one that overrides a matrix builder -- takes the generic route:
         its own cov_matrix / cov_matrix_ij, factored and solved on the GPU (gpx_fit_matrix / gpx_predict_kv)."""
         cov = self.cov
@@ -130,6 +130,8 @@ class GaussianProcess(object):
             return "spgp"
         if isinstance(cov, GaussianCovariance) and cov._fused():
             return "gaussian"
+        if isinstance(cov, PeriodicCovariance) and cov._fused():
+            return "periodic"
         return "generic"
 
     def _fit(self):
@@ -139,6 +141,9 @@ class GaussianProcess(object):
             self._model = self.cov._model(self.x, self.t, self.theta_min)
         elif route == "gaussian":
             self._model = _DeviceModel(_gpx.f64(self.x), _gpx.f64(self.t), _gpx.f64(self.theta_min))
+        elif route == "periodic":
+            # K assembled on the device straight into the factor's buffer (gpx_periodic_fit): no N x N transfer
+            self._model = _PeriodicModel(self.x, self.t, self.theta_min)
         else:
             self._model = _MatrixModel(np.array(self.cov.cov_matrix(self.x, self.theta_min)), self.t)
 

@@ -352,8 +352,9 @@ class UncertaintyPropagationExact(UncertaintyPropagationGA):
         cuu = float(gp._covariance(u, u)) if want_var else 0.0
         mean, var = ctypes.c_double(), ctypes.c_double()
         pvar = ctypes.byref(var) if want_var else None      # mean only: the library neither builds nor reads K^-1
-        if gp._route() in ("generic", "gaussian"):
-            # (any fitted handle: a gpx_fit_matrix one, or -- a caller-supplied C_ux on the built-in route -- the gpx_fit one)
+        if gp._route() in ("generic", "gaussian", "periodic"):
+            # (any fitted handle: a gpx_fit_matrix one, a gpx_periodic_fit one -- the reference has no input derivatives for that kernel,
+            # it is propagated as any generic operator --, or -- a caller-supplied C_ux on the built-in route -- the gpx_fit one)
             st = _gpx.lib.gpx_propagate_exact_matrix(gp._dev().handle, None, None, _gpx.ptr(x), gp.n, gp.d, _gpx.ptr(w), _gpx.ptr(C),
                                                      _gpx.ptr(uu), _gpx.ptr(S), cuu, ctypes.byref(mean), pvar)
         else:

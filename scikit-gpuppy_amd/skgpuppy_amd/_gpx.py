@@ -90,6 +90,10 @@ SIGNATURES = {
     "gpx_propagate_exact_model": (_int, [_hp, _dp, _int, _dp, _dp, _dp, _dp, _dbl, ctypes.POINTER(_dbl), ctypes.POINTER(_dbl)]),
     "gpx_nll": (_int, [_hp, ctypes.POINTER(_dbl)]),
     "gpx_nll_grad": (_int, [_hp, _dp]),
+    "gpx_periodic_gram": (_int, [_dp, _i64, _dp, _i64, _int, _dp, _int, _dp]),
+    "gpx_periodic_fit": (_int, [_dp, _dp, _i64, _int, _dp, ctypes.c_void_p, ctypes.POINTER(_hp)]),
+    "gpx_periodic_predict": (_int, [_hp, _dp, _i64, _dp, _dp]),
+    "gpx_periodic_nll_grad": (_int, [_hp, _dp]),
     "gpx_spgp_fit": (_int, [_dp, _dp, _i64, _int, _dp, _dp, _i64, ctypes.POINTER(_hp)]),
     "gpx_spgp_free": (None, [_hp]),
     "gpx_spgp_predict": (_int, [_hp, _dp, _i64, _dp, _dp]),
