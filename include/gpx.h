@@ -349,6 +349,9 @@ int gpx_bench_fp64_pipes(int blocks, int iters, int mode, double *tflops, double
 
 /* ---- building blocks on device pointers (used by the multi-GPU host and by tests) ----
  * All pointers are DEVICE pointers; leading dimensions in elements; sizes multiples of GPX_TILE. */
+/* out [rows_pad, cols_pad] in a buffer of leading dimension ld: rows_pad a multiple of 64 and >= n1, cols_pad a multiple of 128 and >= n2;
+ * zeros (pad_identity: the identity) outside [n1, n2].  Refused with GPX_ERR_BAD_ARG before anything is queued: a null input with rows,
+ * a null output, rows_pad < n1, cols_pad < n2 and padded rows without a single row (n1 == 0 with rows_pad > 0). */
 int gpx_dev_gram(const double *xi_dev, int64_t n1, const double *xj_dev, int64_t n2, int d, const double *theta,
                  double add_diag, int lower_only, int pad_identity,
                  double *out_dev, int64_t ld, int64_t rows_pad, int64_t cols_pad, void *stream);

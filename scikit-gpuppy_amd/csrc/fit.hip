@@ -47,6 +47,20 @@ __global__ __launch_bounds__(256) void pad_copy_kernel(const double *K, long n, 
 }
 
 // ---- Gram (stand-alone) --------------------------------------------------------------------------
+// What the device entry points refuse before anything is queued.  gram_kernel reads row min(r, n1 - 1) of xi for EVERY row of the
+// padded grid (the padding rows' results are overwritten): with n1 == 0 that is row -1.  A grid smaller than the data would leave
+// entries unwritten without a word.
+static int check_gram_args(const char *who, const double *xi, int64_t n1, const double *xj, int64_t n2, const double *out, int64_t rows_pad,
+                           int64_t cols_pad)
+{
+    if (n1 < 0 || n2 < 0 || !out || (n1 > 0 && !xi) || (n2 > 0 && !xj) || (n1 == 0 && rows_pad > 0) || rows_pad < n1 || cols_pad < n2) {
+        gpx_set_error("%s: bad arguments (n1=%ld n2=%ld rows_pad=%ld cols_pad=%ld: no null input or output, no padded rows without a row, "
+                      "rows_pad >= n1, cols_pad >= n2)", who, (long)n1, (long)n2, (long)rows_pad, (long)cols_pad);
+        return GPX_ERR_BAD_ARG;
+    }
+    return 0;
+}
+
 extern "C" int gpx_dev_gram(const double *xi_dev, int64_t n1, const double *xj_dev, int64_t n2, int d, const double *theta,
                             double add_diag, int lower_only, int pad_identity, double *out_dev, int64_t ld,
                             int64_t rows_pad, int64_t cols_pad, void *stream)
@@ -54,7 +68,7 @@ extern "C" int gpx_dev_gram(const double *xi_dev, int64_t n1, const double *xj_d
     GPX_TRY(gpx_require_device());
     double v, vt, w[GPX_MAX_D], sw[GPX_MAX_D];
     GPX_TRY(parse_theta(theta, d, &v, &vt, w));
-    if (n1 < 0 || n2 < 0 || !out_dev) { gpx_set_error("gpx_dev_gram: bad sizes"); return GPX_ERR_BAD_ARG; }
+    GPX_TRY(check_gram_args("gpx_dev_gram", xi_dev, n1, xj_dev, n2, out_dev, rows_pad, cols_pad));
     for (int k = 0; k < d; ++k) sw[k] = sqrt(w[k]);
     hipStream_t s = (hipStream_t)stream;
     Scratch sc(s);   // its synchronisation also covers the copy out of the stack array `sw`
@@ -80,7 +94,8 @@ extern "C" int gpx_dev_gram_scaled(const double *xiw_dev, int64_t n1, const doub
                                    void *stream)
 {
     GPX_TRY(gpx_require_device());
-    if (n1 < 0 || n2 < 0 || !out_dev || !xiw_dev || !xjw_dev || !(v > 0.0)) { gpx_set_error("gpx_dev_gram_scaled: bad arguments"); return GPX_ERR_BAD_ARG; }
+    if (!xiw_dev || !xjw_dev || !(v > 0.0)) { gpx_set_error("gpx_dev_gram_scaled: bad arguments"); return GPX_ERR_BAD_ARG; }
+    GPX_TRY(check_gram_args("gpx_dev_gram_scaled", xiw_dev, n1, xjw_dev, n2, out_dev, rows_pad, cols_pad));
     return launch_gram(xiw_dev, n1, xjw_dev, n2, d, v, add_diag, lower_only, pad_identity ? 2 : 1, out_dev, ld, rows_pad, cols_pad,
                        (hipStream_t)stream, nullptr);
 }

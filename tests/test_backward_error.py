@@ -9,7 +9,8 @@ Backward error does not depend on kappa(K): |L L^T - K|_ij <= gamma_{N+1} sqrt(K
   C  designed SPD matrices (kappa up to 1e12, graded, a tiny Schur complement on a panel boundary) go through gpx_fit_matrix,
   D  L(4^k K) = 2^k L(K) is checked to a few ulp,
   E  gpx_spd_inverse (panel factor, small dataflow kernel, chol_rec; the launch chain) by its residual K X - I,
-  F  the solves, estimate_many and K^-1 against the device's own L (which takes kappa(K) out of the comparison).
+  F  the solves, estimate_many (more than one chunk of queries included) and K^-1 against the device's own L (which takes kappa(K)
+     out of the comparison).
 
 Bounds (tests/_accuracy.py): a factor / solve / inverse metric <= 16 x max(LAPACK's value for the same input, u), a factor metric also
 <= N u.  The forward quantities of F have fixed tolerances, 10x the worst value measured on an unmodified build and at least 100x tighter
@@ -51,7 +52,9 @@ def _report(section, what, dev, lap, bnd, kappa=float("nan"), same=""):
 
 
 def _dev_gram(x, theta):
-    """gpx_gram(x, x, theta, add_diag = vt): the matrix gpx_fit factors (Gram accuracy is pinned by test_gram_golden)"""
+    """gpx_gram(x, x, theta, add_diag = vt): the matrix gpx_fit factors.  Its own accuracy is held entry by entry to a long-double model
+    within a derived bound by tests/test_gauss_gram.py (every d, both tile paths, the subnormal range, every launch mode of the device
+    entry points); test_gram_golden adds six cases of the reference at rtol 1e-13."""
     return sk.GaussianCovariance().cov_matrix(x, theta)
 
 
@@ -386,4 +389,53 @@ def test_solves_and_predictions_against_the_device_factor(N):
             _report("F", "gpx_kinv_rows N=%d [%d, %d) (/max|K^-1|)" % (N, r0, r1), e, 0.0, KINV_RTOL)
             assert e <= KINV_RTOL, (r0, r1, e)
     gp._dev().close()
+    _gpx.lib.gpx_pool_trim()
+
+
+SEAM_M = 32768 + 130      # predict_common's chunk is at most 32768 rows: one full chunk on the fused row sums, then a 130-row tail on the stand-alone reduction
+
+
+@pytest.mark.parametrize("N,d", [(127, 3), (200, 8)])
+def test_predictions_across_a_chunk_seam(N, d):
+    """More than one chunk through gpx_predict (estimate_many) and gpx_predict_kv: the second chunk reads xs + m0 d, kv + m0 n and
+    kdiag + m0 and writes mean_out + m0 and var_out + m0, and takes the other row reduction.  npad = 128 and 256.  Queries 32767 and 32768
+    (the seam) and the last one are bit-equal to training rows, query 100 lies far outside the data (k* = 0: a zero row solves to a zero
+    row, so it returns the prior exactly); kdiag of the kv call is v + vt plus a per-query offset that must reappear in the variance.
+    Against mean = k* . beta_dev and var = kdiag - ||L_dev^-1 k*||^2 on the tolerances of this section; the tail and the seam queries called
+    alone against the big call at the 1e-11 that test_estimate_many_fused_row_sums_ragged uses for path agreement."""
+    M = SEAM_M
+    x, t, _xs, theta = acc.recipe(N, d)
+    rng = np.random.RandomState(N + d + 1)
+    xs = rng.uniform(0, 10, (M, d))
+    xs[32767], xs[32768], xs[M - 1], xs[100] = x[5], x[6], x[N - 1], 1.0e3
+    v, vt = np.exp(theta[0]), np.exp(theta[1])
+    gp = sk.GaussianProcess(x, t, sk.GaussianCovariance(), theta.copy())
+    mm = _MatrixModel(_dev_gram(x, theta), gp.t)
+    ks = sk.GaussianCovariance().cov_matrix_ij(xs, x, theta)              # gpx_gram, no noise term
+    assert ks[32767, 5] == v and ks[32768, 6] == v and ks[M - 1, N - 1] == v and not ks[100].any()
+    koff = 1e-3 * (np.arange(M) % 17)
+    kdiag = v + vt + koff
+    alone = [slice(32768, M), slice(32767, 32768), slice(32768, 32769)]
+
+    def check(what, L, beta, predict, offset, shift):
+        W = acc.lapack_trsv(L, ks.T)
+        mean_ref = ks.dot(beta) + shift
+        var_ref = v + vt + offset - np.einsum("ij,ij->j", W, W)
+        mean, var = predict(slice(0, M))
+        for name, lo, hi in (("first chunk", 0, 32768), ("tail", 32768, M)):
+            em = float(np.abs(mean - mean_ref)[lo:hi].max()) / v
+            ev = float(np.abs(var - var_ref)[lo:hi].max()) / v
+            _report("F", "%s N=%d M=%d %s mean (/v)" % (what, N, M, name), em, 0.0, MEAN_ATOL_V)
+            _report("F", "%s N=%d M=%d %s var (/v)" % (what, N, M, name), ev, 0.0, VAR_ATOL_V)
+            assert em <= MEAN_ATOL_V and ev <= VAR_ATOL_V, (what, name, em, ev)
+        assert mean[100] == shift and var[100] == v + vt + offset[100], (what, mean[100], var[100])
+        for sl in alone:
+            m1, v1 = predict(sl)
+            np.testing.assert_allclose(m1, mean[sl], rtol=0, atol=1e-11, err_msg="%s %r" % (what, sl))
+            np.testing.assert_allclose(v1, var[sl], rtol=0, atol=1e-11, err_msg="%s %r" % (what, sl))
+
+    check("estimate_many", gp._dev().chol(), gp._get_beta(), lambda sl: gp.estimate_many(xs[sl]), np.zeros(M), gp.meant)
+    check("gpx_predict_kv", _chol_of(mm.handle, N), mm.alpha(), lambda sl: mm.predict_kv(ks[sl], kdiag[sl]), koff, 0.0)
+    gp._dev().close()
+    mm.close()
     _gpx.lib.gpx_pool_trim()
