@@ -170,6 +170,31 @@ int gpx_propagate_dvh(gpx_handle *h, const double *u, double *dvh_out /* [d] */)
  * b = 0 is a no-op. */
 int gpx_propagate_dvh_many(gpx_handle *h, const double *U, int64_t b, double *dvh_out /* [b, d] */, double *sigma2_out /* [b], may be NULL */);
 
+/* ---- numerical propagation: UncertaintyPropagationNumericalHG / UncertaintyPropagationMC
+ * (skgpuppy/UncertaintyPropagation.py:90-162 with Utilities.py:144-185) ----
+ * Under x ~ N(u, Sigma) the output is the mixture  p(y) = sum_s wq_s N(y; mu(x_s), sigma^2(x_s))  over the nodes x_s = u + A z_s of a
+ * Gauss-Hermite grid (A = sqrt(2) times a square root of Sigma, wq = prod w / pi^(d/2)) or of a sample (A a square root of Sigma, wq = 1 / S).
+ * b inputs, S nodes each: the rows U_i + A_i z_s (one fma chain over the columns of A_i in increasing order, starting from U_i) go through
+ * estimate_many's solver; mom [5, b] = m | var | Ev | m3 | m4 with
+ *   m = sum wq mu (WITHOUT meant)   Ev = sum wq sigma^2   var = Ev + sum wq (mu - m)^2   (the central second moment, taken about m)
+ *   m3 = sum wq ((mu - m)^3 + 3 (mu - m) sigma^2)   m4 = sum wq ((mu - m)^4 + 6 (mu - m)^2 sigma^2 + 3 sigma^4)
+ * -- the mixture's central moments -- and, with ny > 0, dens [b, ny]:  dens[i][j] = p_i(y_j - shift)  (shift = meant evaluates at the
+ * caller's y); dens may be NULL when ny == 0.  There is no clamping: a node with sigma^2 <= 0 makes the densities of its input
+ * non-finite, as the reference's expression does, and leaves the moments alone.  U [b, d]; A [b, d, d] row-major, or ONE [d, d] when
+ * a_shared != 0; z [S, d]; wq [S]; y [b, ny], or ONE [ny] when y_shared != 0.  Gaussian (gpx_fit) and periodic (gpx_periodic_fit) handles;
+ * gpx_fit_matrix handles are refused (GPX_ERR_STATE).  The nodes never cross the host, mu and sigma^2 never leave the device.  Host or device
+ * pointers.  Bad arguments are refused before anything is queued; b = 0 is a no-op. */
+int gpx_propagate_quadrature_many(gpx_handle *h, const double *U, const double *A, int a_shared, int64_t b,
+                                  const double *z, const double *wq, int64_t S,
+                                  const double *y, int64_t ny, int y_shared, double shift,
+                                  double *mom, double *dens);
+/* the reduction alone on caller arrays (host or device pointers): mu, var [b, S] are any model's estimate_many output.  No atomics, a fixed
+ * summation order: an input's results do not depend on b or on its place in the batch. */
+int gpx_mixture_reduce(const double *mu, const double *var, const double *wq, int64_t S, int64_t b,
+                       const double *y, int64_t ny, int y_shared, double shift, double *mom, double *dens);
+/* test / tool access: the node rows alone, out [b S, d] */
+int gpx_quadrature_nodes(const double *U, const double *A, int a_shared, int64_t b, const double *z, int64_t S, int d, double *out);
+
 /* ---- a14: UncertaintyPropagationExact.propagate_GA / propagate_mean
  * (skgpuppy/UncertaintyPropagation.py:246-379, UncertaintyPropagation2.pyx:57-184) ----
  * mean WITHOUT meant; var = (v+vt) - sum_ij (Kinv_ij - beta_i beta_j) L_ij - mean^2. */

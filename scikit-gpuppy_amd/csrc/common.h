@@ -465,4 +465,30 @@ struct RowSolve {
 int row_solve_begin(gpx_handle *h, int64_t m, RowSolve &rs, bool bounded = false, bool allow_few = true, int64_t chunk_cap = 0);
 // Zs[0 : mp) <- Z[0 : mp) L^-T (mc real rows, mp = mc rounded up to the tile); red: the fused row sums of tsolve.hip (many rows only)
 int row_solve_run(gpx_handle *h, const RowSolve &rs, int64_t mc, int64_t mp, const GemmReduce *red, bool left = false);
+
+// The predictor's chunk loop on device-resident queries and outputs (predict.hip): begin sizes the chunk as gpx_predict does (bounded rows;
+// a periodic handle: the many-row solver always, and its chunk cap) and takes the query, prior-variance and partial-sum buffers; chunk
+// runs load -> (scale + Gram | periodic Gram) -> guarded solve -> row reduction for one chunk.  gpx_predict, gpx_predict_kv,
+// gpx_periodic_predict and gpx_propagate_quadrature_many all go through it.
+struct PredictRun {
+    RowSolve rs;
+    const PeriodicData *per = nullptr;
+    int d = 0;
+    bool from_x = false, fused = false;
+    int64_t nslots = 0;
+    double *xq = nullptr, *xqw = nullptr, *kd = nullptr, *part = nullptr;   // [chunk, d] queries, the same scaled, [chunk] prior variances, fused row sums
+    explicit PredictRun(hipStream_t s) : rs(s) {}
+};
+int predict_run_begin(gpx_handle *h, bool from_x, int64_t m, PredictRun &pr);
+int predict_run_chunk(gpx_handle *h, PredictRun &pr, int64_t m0, int64_t mc, const std::function<int(int64_t, int64_t)> &load, double *mean_dev,
+                      double *var_dev, const std::function<hipError_t()> &done);
+
+// ---- numerical propagation (quadrature.hip) ----
+// X [rows, d] <- rows row0 .. row0 + rows of the node set: X[i S + s][k] = U[i][k] + sum_e A_i[k][e] z[s][e]; a_stride = 0: one A for all inputs
+int launch_quad_nodes(const double *U, const double *A, int64_t a_stride, const double *z, int64_t S, int d, int64_t row0, int64_t rows, double *X,
+                      hipStream_t s, Profiler *prof);
+// mom [5, b] = m | var | Ev | m3 | m4 and dens [b, ny] (ny > 0) of the b mixtures of S Gaussians (mu, var [b S], weights wq [S]); everything on the
+// device; y_stride = 0: one y [ny] for all inputs, ny: one row per input.  Work buffers come from sc.
+int launch_mixture_reduce(const double *mu, const double *var, const double *wq, int64_t S, int64_t b, const double *y, int64_t ny, int64_t y_stride,
+                          double shift, double *mom, double *dens, Scratch &sc, Profiler *prof);
 #pragma GCC visibility pop

@@ -55,85 +55,119 @@ int row_solve_run(gpx_handle *h, const RowSolve &rs, int64_t mc, int64_t mp, con
     return trsm_right_lt_squares(h->Z, rs.Zs, h->npad, mp, &h->tri, 0, h->tri.P, h->stream, &h->prof, red, rs.emu);
 }
 
-// xs != nullptr: the cross-covariance rows come from the Gram kernel (gpx_predict); otherwise kv [m, n] is the caller's
-// (gpx_predict_kv) and kdiag [m] the prior variance of each query (the diagonal of cov_matrix(x_star), GaussianProcess.py:75)
-// A periodic handle (xs with h->per): the rows come from periodic_gram_kernel, +vt on equality included, and the prior variance is
+// The chunk loop behind gpx_predict / gpx_predict_kv / gpx_periodic_predict and gpx_propagate_quadrature_many (PredictRun: common.h).
+// from_x: the cross-covariance rows come from the Gram kernel on queries that the caller's load leaves on the device in pr.xq; otherwise
+// load fills h->Z with the caller's rows kv [m, n] and pr.kd with the prior variance of each query (the diagonal of cov_matrix(x_star),
+// GaussianProcess.py:75).
+// A periodic handle (from_x with h->per): the rows come from periodic_gram_kernel, +vt on equality included, and the prior variance is
 // v + vt.  That call promises a result that does not depend on the query's place in the batch or on the chunking: always the many-row
 // solver and the stand-alone row reduction (the few-vector solver and the reduction fused into a slab's last product sum in other
 // orders), chunks of at most GPX_PERIODIC_CHUNK rows (read at every call; default: the solver's own cap).
-static int predict_common(gpx_handle *h, const double *xs, const double *kv, const double *kdiag, int64_t m, double *mean_out, double *var_out)
+int predict_run_begin(gpx_handle *h, bool from_x, int64_t m, PredictRun &pr)
 {
-    hipStream_t s = h->stream;
-    const PeriodicData *per = xs ? h->per : nullptr;
-    const int d = per ? per->d : h->d;
-    RowSolve rs(s);
+    pr.from_x = from_x;
+    pr.per = from_x ? h->per : nullptr;
+    pr.d = pr.per ? pr.per->d : h->d;
+    RowSolve &rs = pr.rs;
     // |row of Zs|^2 = k*^T K^-1 k* <= k(x*, x*): sqrt(v) for the built-in kernel, sqrt(kdiag) for the caller's (tsolve.hip, launch_row_bounds)
     int64_t chunk_cap = 0;
-    if (per)
+    if (pr.per)
         if (const char *e = getenv("GPX_PERIODIC_CHUNK")) chunk_cap = atoll(e);
-    GPX_TRY(row_solve_begin(h, m, rs, true, !per, chunk_cap));
+    GPX_TRY(row_solve_begin(h, m, rs, true, !pr.per, chunk_cap));
     const int64_t chunk = rs.chunk;
-    double *xq = nullptr, *xqw = nullptr, *mv = nullptr, *kd = nullptr, *part = nullptr;
-    int rc = 0;
     // the row sums |z|^2 and z.y ride in the epilogue of each slab's last product (tsolve.hip): per row one partial pair per 64 columns
-    const int64_t nslots = h->npad / 64;
-    const bool fused = chunk >= 3072 && !per;
-    GPX_TRY(rs.sc.take(&xq, chunk * std::max(d, 1)));
-    GPX_TRY(rs.sc.take(&xqw, chunk * std::max(d, 1)));
-    GPX_TRY(rs.sc.take(&mv, 2 * chunk));
-    GPX_TRY(rs.sc.take(&kd, chunk));
-    if (fused) GPX_TRY(rs.sc.take(&part, 2 * chunk * nslots));
-    double *Zs = rs.Zs;
+    pr.nslots = h->npad / 64;
+    pr.fused = chunk >= 3072 && !pr.per;
+    GPX_TRY(rs.sc.take(&pr.xq, chunk * std::max(pr.d, 1)));
+    GPX_TRY(rs.sc.take(&pr.xqw, chunk * std::max(pr.d, 1)));
+    GPX_TRY(rs.sc.take(&pr.kd, chunk));
+    if (pr.fused) GPX_TRY(rs.sc.take(&pr.part, 2 * chunk * pr.nslots));
+    return 0;
+}
+
+// One chunk of mc <= pr.rs.chunk rows (m0: the chunk's first row, for the diagnostic alone): load, Gram, solve, row reduction into
+// mean_dev / var_dev [mc] (device), then done() -- whatever the caller queues behind the reduction -- the status word and the chunk's one
+// synchronisation.
+int predict_run_chunk(gpx_handle *h, PredictRun &pr, int64_t m0, int64_t mc, const std::function<int(int64_t, int64_t)> &load, double *mean_dev,
+                      double *var_dev, const std::function<hipError_t()> &done)
+{
+    hipStream_t s = h->stream;
+    RowSolve &rs = pr.rs;
+    const PeriodicData *per = pr.per;
+    const int d = pr.d;
+    const bool from_x = pr.from_x;
+    const int64_t chunk = rs.chunk, nslots = pr.nslots, mp = round_up(mc, TILE);
+    double *xq = pr.xq, *xqw = pr.xqw, *kd = pr.kd, *part = pr.part, *Zs = rs.Zs;
     // Z <- the chunk's cross-covariance rows, zero padded
-    auto fill = [&](int64_t m0, int64_t mc, int64_t mp) -> int {
-        hipError_t e = hipSuccess;
-        if (xs) {
-            e = hipMemcpyAsync(xq, xs + m0 * d, sizeof(double) * mc * d, hipMemcpyDefault, s);
-            if (e != hipSuccess) { gpx_set_error("copy xs failed: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
-            if (per) return launch_periodic_gram(xq, mc, per->x, h->n, per, 0.0, 0, 1, h->Z, h->npad, mp, h->npad, s, &h->prof);
-            GPX_TRY(launch_scale_rows(xq, mc, mp, d, h->sw, xqw, s));
-            // kv = cross-covariance (no vt), zero padded: rows >= mc and columns >= n are 0
-            return launch_gram(xqw, mc, h->xs_w, h->n, d, h->v, 0.0, 0, 1, h->Z, h->npad, mp, h->npad, s, &h->prof);
-        }
-        // the operator's own cross-covariance rows, zero padded to the tile grid
-        e = hipMemsetAsync(h->Z, 0, sizeof(double) * mp * h->npad, s);
-        if (e == hipSuccess) e = hipMemcpy2DAsync(h->Z, sizeof(double) * h->npad, kv + m0 * h->n, sizeof(double) * h->n, sizeof(double) * h->n, mc, hipMemcpyDefault, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(kd, kdiag + m0, sizeof(double) * mc, hipMemcpyDefault, s);
-        if (e != hipSuccess) { gpx_set_error("copy kv / kdiag failed: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
-        return 0;
+    auto fill = [&]() -> int {
+        GPX_TRY(load(mc, mp));
+        if (!from_x) return 0;   // the operator's own cross-covariance rows, zero padded to the tile grid by load
+        if (per) return launch_periodic_gram(xq, mc, per->x, h->n, per, 0.0, 0, 1, h->Z, h->npad, mp, h->npad, s, &h->prof);
+        GPX_TRY(launch_scale_rows(xq, mc, mp, d, h->sw, xqw, s));
+        // kv = cross-covariance (no vt), zero padded: rows >= mc and columns >= n are 0
+        return launch_gram(xqw, mc, h->xs_w, h->n, d, h->v, 0.0, 0, 1, h->Z, h->npad, mp, h->npad, s, &h->prof);
     };
     // Z <- kv L^-T  : row m of Z is (L^-1 kv_m)^T
     // var = k_mm - |z|^2 (k_mm = v + vt for the built-in kernel: k includes vt, GaussianProcess.py:75,78) ; mean = z . y
-    auto solve = [&](int64_t mc, int64_t mp, bool left) -> int {
-        if (fused && mp >= 3072) {
+    auto solve = [&](bool left) -> int {
+        if (pr.fused && mp >= 3072) {
             GemmReduce red;
             red.y = h->y; red.p2 = part; red.py = part + chunk * nslots; red.nslots = nslots;
             GPX_TRY(row_solve_run(h, rs, mc, mp, &red, left));
             ProfScope ps(&h->prof, s, GPX_K_REDUCE, 16.0 * (double)mc * (double)nslots);
-            return launch_predict_finish(red.p2, red.py, nslots, mc, h->v + h->vt, mv, mv + chunk, s, xs ? nullptr : kd);
+            return launch_predict_finish(red.p2, red.py, nslots, mc, h->v + h->vt, mean_dev, var_dev, s, from_x ? nullptr : kd);
         }
         GPX_TRY(row_solve_run(h, rs, mc, mp, nullptr, left));
-        return launch_predict_reduce(Zs, h->npad, mc, h->npad, h->y, h->v + h->vt, mv, mv + chunk, s, &h->prof, xs ? nullptr : kd);
+        return launch_predict_reduce(Zs, h->npad, mc, h->npad, h->y, h->v + h->vt, mean_dev, var_dev, s, &h->prof, from_x ? nullptr : kd);
     };
+    // a bound that did not hold (the status word of emu.hip, read at the chunk's synchronisation) sends the chunk through the binary
+    // recursion once more: Z is consumed by the solve, so it is filled again first
+    return emu_left_guarded(rs.use_left, [&](bool left, int *status) -> int {
+        GPX_TRY(fill());
+        if (left) {
+            GPX_TRY(launch_row_bounds(from_x ? nullptr : kd, per ? h->v + h->vt : h->v, mc, rs.left.bound, s));
+            GPX_TRY(emu_left_begin(rs.left, rs.left.bound, mc, s));
+        }
+        GPX_TRY(solve(left));
+        // (the status word last: the host-side set-up of the caller's result copies then runs underneath the solve, as before)
+        hipError_t e = done();
+        if (e == hipSuccess && left) e = hipMemcpyAsync(status, rs.left.status(), sizeof(int), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { gpx_set_error("predict copy-out failed: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
+        if (*status && getenv("GPX_DEBUG")) fprintf(stderr, "[gpx] left-looking solve: a row bound did not hold in rows %ld..%ld: binary recursion\n", (long)m0, (long)(m0 + mc));
+        return 0;
+    });
+}
+
+// xs != nullptr: gpx_predict / gpx_periodic_predict; otherwise kv [m, n] and kdiag [m] are the caller's (gpx_predict_kv)
+static int predict_common(gpx_handle *h, const double *xs, const double *kv, const double *kdiag, int64_t m, double *mean_out, double *var_out)
+{
+    hipStream_t s = h->stream;
+    PredictRun pr(s);
+    GPX_TRY(predict_run_begin(h, xs != nullptr, m, pr));
+    const int64_t chunk = pr.rs.chunk;
+    const int d = pr.d;
+    double *mv = nullptr;
+    GPX_TRY(pr.rs.sc.take(&mv, 2 * chunk));
+    int rc = 0;
     for (int64_t m0 = 0; m0 < m && rc == 0; m0 += chunk) {
-        const int64_t mc = std::min<int64_t>(chunk, m - m0), mp = round_up(mc, TILE);
-        // a bound that did not hold (the status word of emu.hip, read at the chunk's synchronisation) sends the chunk through the binary
-        // recursion once more: Z is consumed by the solve, so it is filled again first
-        rc = emu_left_guarded(rs.use_left, [&](bool left, int *status) -> int {
-            GPX_TRY(fill(m0, mc, mp));
-            if (left) {
-                GPX_TRY(launch_row_bounds(xs ? nullptr : kd, per ? h->v + h->vt : h->v, mc, rs.left.bound, s));
-                GPX_TRY(emu_left_begin(rs.left, rs.left.bound, mc, s));
+        const int64_t mc = std::min<int64_t>(chunk, m - m0);
+        rc = predict_run_chunk(h, pr, m0, mc, [&](int64_t, int64_t mp) -> int {
+            hipError_t e = hipSuccess;
+            if (xs) {
+                e = hipMemcpyAsync(pr.xq, xs + m0 * d, sizeof(double) * mc * d, hipMemcpyDefault, s);
+                if (e != hipSuccess) { gpx_set_error("copy xs failed: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
+                return 0;
             }
-            GPX_TRY(solve(mc, mp, left));
-            // (the status word last: the host-side set-up of the two result copies then runs underneath the solve, as before)
+            e = hipMemsetAsync(h->Z, 0, sizeof(double) * mp * h->npad, s);
+            if (e == hipSuccess) e = hipMemcpy2DAsync(h->Z, sizeof(double) * h->npad, kv + m0 * h->n, sizeof(double) * h->n, sizeof(double) * h->n, mc, hipMemcpyDefault, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(pr.kd, kdiag + m0, sizeof(double) * mc, hipMemcpyDefault, s);
+            if (e != hipSuccess) { gpx_set_error("copy kv / kdiag failed: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
+            return 0;
+        }, mv, mv + chunk, [&]() -> hipError_t {
             hipError_t e = hipMemcpyAsync(mean_out + m0, mv, sizeof(double) * mc, hipMemcpyDefault, s);
             if (e == hipSuccess) e = hipMemcpyAsync(var_out + m0, mv + chunk, sizeof(double) * mc, hipMemcpyDefault, s);
-            if (e == hipSuccess && left) e = hipMemcpyAsync(status, rs.left.status(), sizeof(int), hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) { gpx_set_error("predict copy-out failed: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
-            if (*status && getenv("GPX_DEBUG")) fprintf(stderr, "[gpx] left-looking solve: a row bound did not hold in rows %ld..%ld: binary recursion\n", (long)m0, (long)(m0 + mc));
-            return 0;
+            return e;
         });
     }
     return rc;

@@ -350,6 +350,114 @@ extern "C" int gpx_propagate_dvh_many(gpx_handle *h, const double *U, int64_t b,
     return rc;
 }
 
+// ---- numerical propagation (UncertaintyPropagation.py:90-162; kernels: quadrature.hip) -----------------------------------------------
+// a caller's array (host or device pointer) into a block of the call's scratch, queued on its stream
+static int stage_in(Scratch &sc, const double *src, int64_t count, double **dst)
+{
+    GPX_TRY(sc.take(dst, std::max<int64_t>(count, 1)));
+    if (count > 0) GPX_HIP(hipMemcpyAsync(*dst, src, sizeof(double) * count, hipMemcpyDefault, sc.s));
+    return 0;
+}
+
+static bool mixture_args_bad(const double *wq, int64_t S, int64_t b, const double *y, int64_t ny, const double *mom, const double *dens)
+{
+    return b < 0 || S < 1 || ny < 0 || (b > 0 && (!wq || !mom || (ny > 0 && (!y || !dens)))) || (b > 0 && S > ((int64_t)1 << 40) / b);
+}
+
+// The b S query rows U_i + A_i z_s go through the predictor's chunk loop (predict.hip, PredictRun: the chunks are cut over the ROWS, so an
+// input may straddle a seam and S is not bounded by the chunk): per chunk the node kernel writes the rows straight into the query buffer,
+// mu and sigma^2 land in a [2, b S] device block of the call's scratch, and the only device-to-host traffic per chunk is the status word of
+// the left-looking solve.  One reduction after the last chunk; its five moment rows and the densities are the call's only results.
+extern "C" int gpx_propagate_quadrature_many(gpx_handle *h, const double *U, const double *A, int a_shared, int64_t b, const double *z,
+                                             const double *wq, int64_t S, const double *y, int64_t ny, int y_shared, double shift, double *mom,
+                                             double *dens)
+{
+    CHECK_H(h);
+    if (mixture_args_bad(wq, S, b, y, ny, mom, dens) || (b > 0 && (!U || !A || !z))) { gpx_set_error("gpx_propagate_quadrature_many: bad arguments"); return GPX_ERR_BAD_ARG; }
+    if (!h->per && h->d == 0) {
+        gpx_set_error("gpx_propagate_quadrature_many: the handle was built from a supplied matrix (gpx_fit_matrix): no inputs / theta to evaluate the kernel on");
+        return GPX_ERR_STATE;
+    }
+    if (b == 0) return 0;
+    hipStream_t s = h->stream;
+    const int64_t rows = b * S;
+    PredictRun pr(s);
+    GPX_TRY(predict_run_begin(h, true, rows, pr));
+    Scratch &sc = pr.rs.sc;
+    const int d = pr.d;
+    const int64_t d2 = (int64_t)d * d;
+    double *Ud = nullptr, *Ad = nullptr, *zd = nullptr, *wqd = nullptr, *yd = nullptr, *mv = nullptr, *momd = nullptr, *densd = nullptr;
+    GPX_TRY(stage_in(sc, U, b * d, &Ud));
+    GPX_TRY(stage_in(sc, A, (a_shared ? 1 : b) * d2, &Ad));
+    GPX_TRY(stage_in(sc, z, S * d, &zd));
+    GPX_TRY(stage_in(sc, wq, S, &wqd));
+    GPX_TRY(stage_in(sc, y, ny > 0 ? (y_shared ? 1 : b) * ny : 0, &yd));
+    GPX_TRY(sc.take(&mv, 2 * rows));
+    GPX_TRY(sc.take(&momd, 5 * b));
+    if (ny > 0) GPX_TRY(sc.take(&densd, b * ny));
+    const int64_t chunk = pr.rs.chunk;
+    for (int64_t m0 = 0; m0 < rows; m0 += chunk) {
+        const int64_t mc = std::min<int64_t>(chunk, rows - m0);
+        GPX_TRY(predict_run_chunk(h, pr, m0, mc,
+                                  [&](int64_t, int64_t) -> int { return launch_quad_nodes(Ud, Ad, a_shared ? 0 : d2, zd, S, d, m0, mc, pr.xq, s, &h->prof); },
+                                  mv + m0, mv + rows + m0, []() -> hipError_t { return hipSuccess; }));
+    }
+    GPX_TRY(launch_mixture_reduce(mv, mv + rows, wqd, S, b, yd, ny, y_shared ? 0 : ny, shift, momd, densd, sc, &h->prof));
+    GPX_HIP(hipMemcpyAsync(mom, momd, sizeof(double) * 5 * b, hipMemcpyDefault, s));
+    if (ny > 0) GPX_HIP(hipMemcpyAsync(dens, densd, sizeof(double) * b * ny, hipMemcpyDefault, s));
+    const hipError_t e = sc.wait_and_free();
+    if (e != hipSuccess) { gpx_set_error("gpx_propagate_quadrature_many: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
+    return 0;
+}
+
+// the reduction alone, on any model's estimate_many output (mean WITHOUT meant, or pass shift = 0 and keep it in)
+extern "C" int gpx_mixture_reduce(const double *mu, const double *var, const double *wq, int64_t S, int64_t b, const double *y, int64_t ny, int y_shared,
+                                  double shift, double *mom, double *dens)
+{
+    if (mixture_args_bad(wq, S, b, y, ny, mom, dens) || (b > 0 && (!mu || !var))) { gpx_set_error("gpx_mixture_reduce: bad arguments"); return GPX_ERR_BAD_ARG; }
+    GPX_TRY(gpx_require_device());
+    if (b == 0) return 0;
+    Scratch sc(nullptr);
+    double *mv = nullptr, *wqd = nullptr, *yd = nullptr, *momd = nullptr, *densd = nullptr;
+    const int64_t rows = b * S;
+    GPX_TRY(sc.take(&mv, 2 * rows));
+    GPX_HIP(hipMemcpyAsync(mv, mu, sizeof(double) * rows, hipMemcpyDefault, sc.s));
+    GPX_HIP(hipMemcpyAsync(mv + rows, var, sizeof(double) * rows, hipMemcpyDefault, sc.s));
+    GPX_TRY(stage_in(sc, wq, S, &wqd));
+    GPX_TRY(stage_in(sc, y, ny > 0 ? (y_shared ? 1 : b) * ny : 0, &yd));
+    GPX_TRY(sc.take(&momd, 5 * b));
+    if (ny > 0) GPX_TRY(sc.take(&densd, b * ny));
+    GPX_TRY(launch_mixture_reduce(mv, mv + rows, wqd, S, b, yd, ny, y_shared ? 0 : ny, shift, momd, densd, sc, nullptr));
+    GPX_HIP(hipMemcpyAsync(mom, momd, sizeof(double) * 5 * b, hipMemcpyDefault, sc.s));
+    if (ny > 0) GPX_HIP(hipMemcpyAsync(dens, densd, sizeof(double) * b * ny, hipMemcpyDefault, sc.s));
+    const hipError_t e = sc.wait_and_free();
+    if (e != hipSuccess) { gpx_set_error("gpx_mixture_reduce: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
+    return 0;
+}
+
+// test / tool access: the node rows alone, out [b S, d] (host or device)
+extern "C" int gpx_quadrature_nodes(const double *U, const double *A, int a_shared, int64_t b, const double *z, int64_t S, int d, double *out)
+{
+    if (b < 0 || S < 1 || d < 1 || d > GPX_MAX_D || (b > 0 && (!U || !A || !z || !out)) || (b > 0 && S > ((int64_t)1 << 31) / ((int64_t)b * d))) {
+        gpx_set_error("gpx_quadrature_nodes: bad arguments");
+        return GPX_ERR_BAD_ARG;
+    }
+    GPX_TRY(gpx_require_device());
+    if (b == 0) return 0;
+    Scratch sc(nullptr);
+    const int64_t rows = b * S, d2 = (int64_t)d * d;
+    double *Ud = nullptr, *Ad = nullptr, *zd = nullptr, *X = nullptr;
+    GPX_TRY(stage_in(sc, U, b * d, &Ud));
+    GPX_TRY(stage_in(sc, A, (a_shared ? 1 : b) * d2, &Ad));
+    GPX_TRY(stage_in(sc, z, S * d, &zd));
+    GPX_TRY(sc.take(&X, rows * d));
+    GPX_TRY(launch_quad_nodes(Ud, Ad, a_shared ? 0 : d2, zd, S, d, 0, rows, X, sc.s, nullptr));
+    GPX_HIP(hipMemcpyAsync(out, X, sizeof(double) * rows * d, hipMemcpyDefault, sc.s));
+    const hipError_t e = sc.wait_and_free();
+    if (e != hipSuccess) { gpx_set_error("gpx_quadrature_nodes: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
+    return 0;
+}
+
 // small dense inverse (Gauss-Jordan, partial pivoting) for (W/2 + Sigma), d <= 64
 static int small_inverse(const double *A, int d, double *inv)
 {

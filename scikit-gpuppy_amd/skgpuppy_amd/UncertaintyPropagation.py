@@ -5,6 +5,7 @@ The reference swaps its pure-Python classes for the compiled Cython twins at imp
 methods, the O(N^2) loops K1..K8 run as HIP kernels on the handle of the GaussianProcess.
 """
 import ctypes
+import math
 
 import numpy as np
 
@@ -446,3 +447,164 @@ class UncertaintyPropagationExact(UncertaintyPropagationGA):
         """propagate_GA for the rows of U (B, d); Sigma_x (d, d) for all of them or (B, d, d): (means [B] with meant, variances [B])"""
         mean, var = self._moments_many(U, Sigma_x, True)
         return mean + self.gp._get_mean_t(), var
+
+
+# ---- the numerical family (UncertaintyPropagation.py:28-52, :90-162) ---------------------------------------------------------------
+class UncertaintyPropagation(object):
+    """Superclass of the propagators that return the output density itself (UncertaintyPropagation.py:28-52)."""
+
+    def propagate(self, y, u, Sigma_x):
+        """p(y) under x ~ N(u, Sigma_x) (Girard 2004, p. 32)"""
+
+    def propagate_many(self, yvec, u, Sigma_x):
+        return np.array([self.propagate(y, u, Sigma_x) for y in yvec])
+
+
+MAX_NODES = 1 << 22
+
+
+class _MixturePropagation(UncertaintyPropagationGA, UncertaintyPropagation):
+    """What UncertaintyPropagationNumericalHG and UncertaintyPropagationMC share: under x ~ N(u, Sigma_x) the output is the mixture
+    p(y) = sum_s wq_s N(y; mu(x_s), sigma^2(x_s)) over the nodes x_s = u + A z_s of a rule (z [S, d], wq [S]) and a square root A of the
+    input covariance.  The reference evaluates gp(x_s) in S Python calls per expectation; here the nodes of ALL inputs are rows of ONE
+    many-row solve (estimate_many's) and one reduction kernel returns, per input, the mean, the variance and the third and fourth central
+    moments of the mixture, and its density at any number of y.
+
+    Built-in Gaussian and periodic kernels: gpx_propagate_quadrature_many -- nodes, mu and sigma^2 never leave the device.  Every other route
+    (a generic operator, SPGP): the nodes are built on the host, gp.estimate_many evaluates them, gpx_mixture_reduce reduces its output."""
+
+    def _rule(self, d):
+        raise NotImplementedError
+
+    def _root(self, S):
+        raise NotImplementedError
+
+    def _reduce(self, U, Sigma_x, Y=None):
+        """(mom [5, B] = mean WITH meant | var | E[sigma^2] | m3 | m4, dens [B, ny] or None)"""
+        gp = self.gp
+        UU, S = self._many_args(U, Sigma_x)
+        B, d = UU.shape
+        shared = S.ndim == 2
+        A = _gpx.f64(self._root(S) if shared else np.stack([self._root(Si) for Si in S]).reshape(B, d, d))
+        z, wq = self._rule(d)
+        z, wq = _gpx.f64(z), _gpx.f64(wq)
+        ns = len(wq)
+        ny, yshared, YY = 0, 1, None
+        if Y is not None:
+            YY = _gpx.f64(Y)
+            if YY.ndim == 1:
+                ny = len(YY)
+            elif YY.ndim == 2 and YY.shape[0] == B:
+                ny, yshared = YY.shape[1], 0
+            else:
+                raise ValueError("Y must be (ny,) or (%d, ny), got %s" % (B, YY.shape))
+        mom = np.empty((5, B))
+        dens = np.empty((B, ny)) if ny else None
+        yp = _gpx.ptr(YY) if ny else None
+        dp = _gpx.ptr(dens) if ny else None
+        meant = float(gp._get_mean_t())
+        if gp._route() in ("gaussian", "periodic"):
+            st = _gpx.lib.gpx_propagate_quadrature_many(gp._dev().handle, _gpx.ptr(UU), _gpx.ptr(A), int(shared), B, _gpx.ptr(z), _gpx.ptr(wq),
+                                                        ns, yp, ny, yshared, meant, _gpx.ptr(mom), dp)
+            _gpx.check(st, "gpx_propagate_quadrature_many")
+            mom[0] += meant
+        else:
+            # the model's own estimate_many output (its means carry meant: no shift)
+            X = UU[:, None, :] + (z.dot(A.T)[None] if shared else np.einsum("ike,se->isk", A, z))
+            mu, var = gp.estimate_many(X.reshape(B * ns, d))
+            mu, var = _gpx.f64(mu), _gpx.f64(var)
+            st = _gpx.lib.gpx_mixture_reduce(_gpx.ptr(mu), _gpx.ptr(var), _gpx.ptr(wq), ns, B, yp, ny, yshared, 0.0, _gpx.ptr(mom), dp)
+            _gpx.check(st, "gpx_mixture_reduce")
+        return mom, dens
+
+    # ---- the reference's surface ----
+    def propagate_mean(self, u, Sigma_x):
+        """E[mu(x)], meant included (the reference averages gp(x)[0])"""
+        return np.float64(self._reduce(np.atleast_2d(_gpx.f64(u)), Sigma_x)[0][0, 0])
+
+    def propagate_GA(self, u, Sigma_x):
+        mom, _ = self._reduce(np.atleast_2d(_gpx.f64(u)), Sigma_x)
+        return np.float64(mom[0, 0]), np.float64(mom[1, 0])
+
+    def propagate(self, y, u, Sigma_x):
+        return np.float64(self.propagate_many([y], u, Sigma_x)[0])
+
+    def propagate_many(self, yvec, u, Sigma_x):
+        """the density at every y of yvec: one device call (the reference: len(yvec) S calls of gp(x))"""
+        return self._reduce(np.atleast_2d(_gpx.f64(u)), Sigma_x, _gpx.f64(yvec).reshape(-1))[1][0]
+
+    # ---- many inputs in one call ----
+    def propagate_GA_many(self, U, Sigma_x):
+        """(means [B] with meant, variances [B]) for the rows of U (B, d); Sigma_x (d, d) for all of them or (B, d, d)"""
+        mom, _ = self._reduce(U, Sigma_x)
+        return mom[0], mom[1]
+
+    def propagate_moments_many(self, U, Sigma_x):
+        """(mean with meant, variance, third central moment, fourth central moment), each [B]"""
+        mom, _ = self._reduce(U, Sigma_x)
+        return mom[0], mom[1], mom[3], mom[4]
+
+    def propagate_density_many(self, Y, U, Sigma_x):
+        """densities [B, ny] at Y (ny,) -- the same y for every input -- or (B, ny)"""
+        return self._reduce(U, Sigma_x, Y)[1]
+
+
+class UncertaintyPropagationNumericalHG(_MixturePropagation):
+    """Gauss-Hermite quadrature (UncertaintyPropagation.py:135-162, Utilities.py:144-167): the tensor grid of
+    numpy.polynomial.hermite.hermgauss(order) in itertools.product order, wq = prod w / pi^(d/2), order = 4 as the reference fixes it.
+
+    full_sigma=False is the reference's rule EXACTLY: x_s = u + sqrt(2) diag(sqrt(Sigma_kk)) z_s -- it reads the diagonal of Sigma_x and
+    ignores every off-diagonal entry (Utilities.py:157), so correlated inputs are propagated as if independent.  full_sigma=True takes
+    A = sqrt(2) chol(Sigma_x) instead, the rule for the covariance as given.  order^d may not exceed 2^22 nodes."""
+
+    def __init__(self, gp, order=4, full_sigma=False):
+        UncertaintyPropagationGA.__init__(self, gp)
+        self.order = int(order)
+        self.full_sigma = bool(full_sigma)
+        if self.order < 1:
+            raise ValueError("order must be >= 1")
+
+    def _rule(self, d):
+        if self.order ** d > MAX_NODES:
+            raise ValueError("order %d in %d dimensions is %d nodes (more than %d)" % (self.order, d, self.order ** d, MAX_NODES))
+        x, w = np.polynomial.hermite.hermgauss(self.order)
+        # w / sqrt(pi) per axis, with the weights' own sum for sqrt(pi) (they are equal in exact arithmetic; hermgauss's sum is off by up to
+        # 2.5 u, which the d-fold product multiplies): wq then sums to 1 within 4 u for every order <= 8, d <= 4
+        w = w / math.fsum(w)
+        z = np.stack(np.meshgrid(*([x] * d), indexing="ij"), -1).reshape(-1, d)          # itertools.product(x, repeat=d) order
+        ws = np.stack(np.meshgrid(*([w] * d), indexing="ij"), -1).reshape(-1, d)
+        return z, ws.prod(axis=1)
+
+    def _root(self, S):
+        if self.full_sigma:
+            return np.sqrt(2.0) * np.linalg.cholesky(S)
+        return np.diag(np.sqrt(np.diag(S)) * np.sqrt(2.0))
+
+
+class UncertaintyPropagationMC(_MixturePropagation):
+    """Monte-Carlo integration (UncertaintyPropagation.py:90-132, Utilities.py:172-185): z = standard_normal((n, d)) from
+    RandomState(seed), or from numpy's global state when seed is None (as the reference, so numpy.random.seed governs it), wq = 1 / n,
+    x_s = u + A z_s with A = chol(Sigma_x) (the symmetric square root when Sigma_x is singular).
+
+    ONE sample set per call serves the mean, the variance and the density, and every input of a batch.  The reference draws three
+    independent sets inside propagate_GA (and its sampler is SVD-based): results are statistically equivalent, not sample-identical."""
+
+    def __init__(self, gp, n=1000, seed=None):
+        UncertaintyPropagationGA.__init__(self, gp)
+        self.n = int(n)
+        self.seed = seed
+        if self.n < 1:
+            raise ValueError("n must be >= 1")
+
+    def _rule(self, d):
+        if self.n > MAX_NODES:
+            raise ValueError("n = %d is more than %d nodes" % (self.n, MAX_NODES))
+        rng = np.random if self.seed is None else np.random.RandomState(self.seed)
+        return rng.standard_normal((self.n, d)), np.full(self.n, 1.0 / self.n)
+
+    def _root(self, S):
+        try:
+            return np.linalg.cholesky(S)
+        except np.linalg.LinAlgError:
+            lam, V = np.linalg.eigh(0.5 * (S + S.T))
+            return (V * np.sqrt(np.maximum(lam, 0.0))).dot(V.T)

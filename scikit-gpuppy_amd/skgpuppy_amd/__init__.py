@@ -11,6 +11,9 @@ from .UncertaintyPropagation import (  # noqa: F401
     UncertaintyPropagationApprox,
     UncertaintyPropagationExact,
     UncertaintyPropagationGA,
+    UncertaintyPropagation,
+    UncertaintyPropagationMC,
+    UncertaintyPropagationNumericalHG,
 )
 
 from .InverseUncertaintyPropagation import (  # noqa: F401,E402
@@ -22,5 +25,6 @@ from .InverseUncertaintyPropagation import (  # noqa: F401,E402
 __all__ = [
     "Covariance", "GaussianCovariance", "PeriodicCovariance", "SPGPCovariance", "GaussianProcess", "UncertaintyPropagationGA",
     "UncertaintyPropagationApprox", "UncertaintyPropagationExact", "tracedot",
+    "UncertaintyPropagation", "UncertaintyPropagationMC", "UncertaintyPropagationNumericalHG",
     "InverseUncertaintyPropagation", "InverseUncertaintyPropagationApprox", "InverseUncertaintyPropagationNumerical",
 ]

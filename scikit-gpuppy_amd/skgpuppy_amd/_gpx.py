@@ -80,6 +80,9 @@ SIGNATURES = {
     "gpx_propagate_approx_rhs": (_int, [_hp, _dp, _dp, _int, _int, _dp]),
     "gpx_propagate_dvh": (_int, [_hp, _dp, _dp]),
     "gpx_propagate_dvh_many": (_int, [_hp, _dp, _i64, _dp, _dp]),
+    "gpx_propagate_quadrature_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp, _dp, _i64, _dp, _i64, _int, _dbl, _dp, _dp]),
+    "gpx_mixture_reduce": (_int, [_dp, _dp, _dp, _i64, _i64, _dp, _i64, _int, _dbl, _dp, _dp]),
+    "gpx_quadrature_nodes": (_int, [_dp, _dp, _int, _i64, _dp, _i64, _int, _dp]),
     "gpx_propagate_exact": (_int, [_hp, _dp, _dp, ctypes.POINTER(_dbl), ctypes.POINTER(_dbl)]),
     "gpx_propagate_exact_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp, _dp]),
     "gpx_propagate_exact_rows": (_int, [_hp, _dp, _dp, _i64, _i64, _dp]),
