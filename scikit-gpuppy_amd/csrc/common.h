@@ -62,6 +62,13 @@ static __device__ __forceinline__ double exp_nonpos(double x)
     p = fma(p, r, 1.0);
     return ldexp(p, (int)n);
 }
+// ---- the sum over a wave's 64 lanes, in every lane: butterfly, the partner 32 lanes away first ----
+static __device__ __forceinline__ double wave_sum(double s)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    return s;
+}
 // ---- per-kernel-class event profiler ---------------------------------------------------------
 struct Profiler {
     int level = 0;   // 0 off; 1 = only the dominant kernel (128x128-tile GEMM launches); 2 = every kernel class
@@ -116,10 +123,14 @@ struct TriSolver {
 };
 
 // ---- the fitted model held in HBM ------------------------------------------------------------
+// What evaluates a handle's kernel: nothing (the matrix was supplied: gpx_fit_matrix), gram_kernel on xs_w (gpx_fit, gpx_adopt_factor)
+// or periodic_gram_kernel on per->x (gpx_periodic_fit).  Callers ask the handle_* helpers below, not the fields.
+enum class KernelKind { Matrix, Gaussian, Periodic };
 struct gpx_handle {
     int device = 0;
     int64_t n = 0, npad = 0, nblk = 0;
-    int d = 0;
+    KernelKind kind = KernelKind::Matrix;
+    int d = 0;                  // Gaussian: the input dimension (0 otherwise: handle_dim)
     double v = 0, vt = 0, jitter = 0;
     double theta[GPX_MAX_D + 2];
     double w[GPX_MAX_D];
@@ -431,11 +442,26 @@ int launch_exact_many_finish(const double *Y, const double *H, int64_t npad, con
         if (!(h)) { gpx_set_error("null handle"); return GPX_ERR_BAD_ARG; } \
         GPX_HIP(hipSetDevice((h)->device));                         \
     } while (0)
+// ---- the one description of a handle's kernel (KernelKind) ----
+static inline bool handle_has_kernel(const gpx_handle *h) { return h->kind != KernelKind::Matrix; }
+static inline int handle_dim(const gpx_handle *h) { return h->kind == KernelKind::Periodic ? h->per->d : h->d; }   // 0: a supplied matrix
+// the training inputs [n, handle_dim] in the form the handle's Gram kernel reads: scaled by sqrt(w) (Gaussian), raw (periodic)
+static inline const double *handle_train_inputs(const gpx_handle *h) { return h->kind == KernelKind::Periodic ? h->per->x : h->xs_w; }
+// launch_gram / launch_periodic_gram with the handle's parameters; xi, xj in the form of handle_train_inputs
+static inline int handle_gram(const gpx_handle *h, const double *xi, int64_t n1, const double *xj, int64_t n2, double add_diag, int lower_only,
+                              int pad_mode, double *out, int64_t ld, int64_t rows_pad, int64_t cols_pad, hipStream_t s, Profiler *prof)
+{
+    switch (h->kind) {
+    case KernelKind::Gaussian: return launch_gram(xi, n1, xj, n2, h->d, h->v, add_diag, lower_only, pad_mode, out, ld, rows_pad, cols_pad, s, prof);
+    case KernelKind::Periodic: return launch_periodic_gram(xi, n1, xj, n2, h->per, add_diag, lower_only, pad_mode, out, ld, rows_pad, cols_pad, s, prof);
+    default: gpx_set_error("handle_gram: the handle was built from a supplied matrix"); return GPX_ERR_STATE;
+    }
+}
 // entry points that evaluate the GaussianCovariance kernel need the handle's inputs and theta: not a gpx_fit_matrix handle
 #define NEED_KERNEL(h, what)                                                                                             \
     do {                                                                                                                 \
-        if ((h)->per) { gpx_set_error(what ": the handle holds a PeriodicCovariance model (gpx_periodic_fit): use the gpx_periodic_* entry points"); return GPX_ERR_STATE; } \
-        if ((h)->d == 0) { gpx_set_error(what ": the handle was built from a supplied matrix (gpx_fit_matrix): no inputs / theta to evaluate the kernel on"); return GPX_ERR_STATE; } \
+        if ((h)->kind == KernelKind::Periodic) { gpx_set_error(what ": the handle holds a PeriodicCovariance model (gpx_periodic_fit): use the gpx_periodic_* entry points"); return GPX_ERR_STATE; } \
+        if (!handle_has_kernel(h)) { gpx_set_error(what ": the handle was built from a supplied matrix (gpx_fit_matrix): no inputs / theta to evaluate the kernel on"); return GPX_ERR_STATE; } \
     } while (0)
 
 int fetch_small(double *dst, const double *src, size_t n);   // a few doubles from a caller's pointer (host or device) into host memory (runtime.hip)
@@ -468,15 +494,14 @@ int row_solve_run(gpx_handle *h, const RowSolve &rs, int64_t mc, int64_t mp, con
 
 // The predictor's chunk loop on device-resident queries and outputs (predict.hip): begin sizes the chunk as gpx_predict does (bounded rows;
 // a periodic handle: the many-row solver always, and its chunk cap) and takes the query, prior-variance and partial-sum buffers; chunk
-// runs load -> (scale + Gram | periodic Gram) -> guarded solve -> row reduction for one chunk.  gpx_predict, gpx_predict_kv,
+// runs load -> (scale, Gaussian alone) -> handle_gram -> guarded solve -> row reduction for one chunk.  gpx_predict, gpx_predict_kv,
 // gpx_periodic_predict and gpx_propagate_quadrature_many all go through it.
 struct PredictRun {
     RowSolve rs;
-    const PeriodicData *per = nullptr;
-    int d = 0;
     bool from_x = false, fused = false;
+    bool periodic = false;   // from_x on a periodic handle: the rows carry +vt on equality, results independent of the batch (predict.hip)
     int64_t nslots = 0;
-    double *xq = nullptr, *xqw = nullptr, *kd = nullptr, *part = nullptr;   // [chunk, d] queries, the same scaled, [chunk] prior variances, fused row sums
+    double *xq = nullptr, *xqw = nullptr, *kd = nullptr, *part = nullptr;   // [chunk, d] queries, the same scaled (Gaussian), [chunk] prior variances, fused row sums
     explicit PredictRun(hipStream_t s) : rs(s) {}
 };
 int predict_run_begin(gpx_handle *h, bool from_x, int64_t m, PredictRun &pr);

@@ -2,13 +2,6 @@
 // the row sums of a prediction, identity fill, lower-to-upper mirror.
 #include "common.h"
 
-__device__ __forceinline__ double wave_sum(double s)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    return s;
-}
-
 // logdet K = 2 sum_i log L_ii over the n real rows; single block, fixed order -> deterministic
 __global__ __launch_bounds__(256) void logdet_kernel(const double *diagL, long n, double *out)
 {

@@ -10,6 +10,7 @@
 #include <new>
 
 #include "common.h"
+#include "gram_tile.h"
 
 static int parse_theta(const double *theta, int d, double *v, double *vt, double *w)
 {
@@ -235,42 +236,25 @@ static int factor_once(gpx_handle *h, double add_diag, int *info_host)
         }
         return 0;
     };
-    if (h->Ksrc) {
-        // the operator supplied its matrix (gpx_fit_matrix): K (+ jitter on a retry) into the padded factor buffer, then the same schedule
+    // K into the padded factor buffer (lower half, identity in the padding).  A supplied matrix (gpx_fit_matrix) is copied, + jitter on
+    // a retry.  A kernel assembles it there: add_diag = vt + jitter (Gaussian) or the jitter alone (the periodic kernel adds vt itself,
+    // wherever two rows are equal).  Beyond one outer panel, and with a chain stream: the first panel's columns now, the rest of the
+    // lower half underneath the first panel's diagonal chain.
+    const double *x = handle_has_kernel(h) ? handle_train_inputs(h) : nullptr;
+    const bool split = x && h->npad > c1 && h->s_pan;
+    const std::function<int()> rest = [&]() -> int {
+        const double *xr = x + c1 * handle_dim(h);
+        return handle_gram(h, xr, h->n - c1, xr, h->n - c1, add_diag, 1, PAD_IDENT, h->L + c1 * h->npad + c1, h->npad, h->npad - c1, h->npad - c1, s,
+                           &h->prof);
+    };
+    if (!x) {
         hipLaunchKernelGGL(pad_copy_kernel, dim3((unsigned)h->npad), dim3(256), 0, s, (const double *)h->Ksrc, (long)h->n, h->L, (long)h->npad, add_diag);
         GPX_HIP(hipGetLastError());
-        GPX_TRY(chol_factor(h->L, h->npad, h->nblk, h->Dinv, h->diagL, h->info_dev, s, h->s_pan, &h->prof, h->s_top, nullptr, &ride));
-    } else if (h->per) {
-        // PeriodicCovariance (gpx_periodic_fit): K assembled straight into the padded factor buffer, +vt where two rows are equal (the
-        // kernel's own test), add_diag = the retry's jitter alone; the same split as below -- the first panel's columns now, the rest of
-        // the lower half underneath the first panel's diagonal chain
-        const double *px = h->per->x;
-        const int pdim = h->per->d;
-        if (h->npad <= c1 || !h->s_pan) {
-            GPX_TRY(launch_periodic_gram(px, h->n, px, h->n, h->per, add_diag, 1, 2, h->L, h->npad, h->npad, h->npad, s, &h->prof));
-            GPX_TRY(chol_factor(h->L, h->npad, h->nblk, h->Dinv, h->diagL, h->info_dev, s, h->s_pan, &h->prof, h->s_top, nullptr, &ride));
-        } else {
-            GPX_TRY(launch_periodic_gram(px, h->n, px, std::min<int64_t>(h->n, c1), h->per, add_diag, 1, 2, h->L, h->npad, h->npad, c1, s, &h->prof));
-            const std::function<int()> rest = [&]() -> int {
-                const double *xr = px + c1 * pdim;
-                return launch_periodic_gram(xr, h->n - c1, xr, h->n - c1, h->per, add_diag, 1, 2, h->L + c1 * h->npad + c1, h->npad,
-                                            h->npad - c1, h->npad - c1, s, &h->prof);
-            };
-            GPX_TRY(chol_factor(h->L, h->npad, h->nblk, h->Dinv, h->diagL, h->info_dev, s, h->s_pan, &h->prof, h->s_top, &rest, &ride));
-        }
-    } else if (h->npad <= c1 || !h->s_pan) {
-        GPX_TRY(launch_gram(h->xs_w, h->n, h->xs_w, h->n, h->d, h->v, add_diag, 1, 2, h->L, h->npad, h->npad, h->npad, s, &h->prof));
-        GPX_TRY(chol_factor(h->L, h->npad, h->nblk, h->Dinv, h->diagL, h->info_dev, s, h->s_pan, &h->prof, h->s_top, nullptr, &ride));
     } else {
-        // the first panel's columns now; the rest of the (lower) Gram matrix underneath the first panel's diagonal chain
-        GPX_TRY(launch_gram(h->xs_w, h->n, h->xs_w, std::min<int64_t>(h->n, c1), h->d, h->v, add_diag, 1, 2, h->L, h->npad, h->npad, c1, s, &h->prof));
-        const std::function<int()> rest = [&]() -> int {
-            const double *xr = h->xs_w + c1 * h->d;
-            return launch_gram(xr, h->n - c1, xr, h->n - c1, h->d, h->v, add_diag, 1, 2, h->L + c1 * h->npad + c1, h->npad, h->npad - c1,
-                               h->npad - c1, s, &h->prof);
-        };
-        GPX_TRY(chol_factor(h->L, h->npad, h->nblk, h->Dinv, h->diagL, h->info_dev, s, h->s_pan, &h->prof, h->s_top, &rest, &ride));
+        const int64_t cols = split ? c1 : h->npad;
+        GPX_TRY(handle_gram(h, x, h->n, x, std::min<int64_t>(h->n, cols), add_diag, 1, PAD_IDENT, h->L, h->npad, h->npad, cols, s, &h->prof));
     }
+    GPX_TRY(chol_factor(h->L, h->npad, h->nblk, h->Dinv, h->diagL, h->info_dev, s, h->s_pan, &h->prof, h->s_top, split ? &rest : nullptr, &ride));
     GPX_TRY(ride(h->tri.P - 1, 0, true));                      // whatever the factorisation's schedule left over
     GPX_HIP(hipMemcpyAsync(info_host, h->info_dev, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
     GPX_HIP(hipStreamSynchronize(s));
@@ -309,6 +293,7 @@ static int make_handle(const double *x, const double *t_centered, int64_t n, int
         if (rc) { delete h; return rc; }
         memcpy(h->theta, theta, sizeof(double) * (d + 2));
     } else d = 0;
+    h->kind = pspec ? KernelKind::Periodic : Kmat ? KernelKind::Matrix : KernelKind::Gaussian;
     h->n = n;
     h->d = d;
     h->npad = round_up(n, TILE);
@@ -361,7 +346,7 @@ static int make_handle(const double *x, const double *t_centered, int64_t n, int
     FIT_HIP(hipMemcpyAsync(h->t, t_centered, sizeof(double) * n, hipMemcpyDefault, s));
     FIT_HIP(hipStreamSynchronize(s));   // sw is a stack buffer: its copy must be complete before any return path
     if (!ext) chol_probe_streams(s, h->s_pan, h->s_top);   // while every stream of the fit is idle (cached per pair of streams)
-    if (!Kmat && !pspec && (rc = launch_scale_rows(h->x, n, h->npad, d, h->sw, h->xs_w, s))) return fail(rc);
+    if (h->kind == KernelKind::Gaussian && (rc = launch_scale_rows(h->x, n, h->npad, d, h->sw, h->xs_w, s))) return fail(rc);
 
     if (!ext) {
         // A stalled hand-off (an in-kernel wait of the look-ahead schedule expired: streams that were probed as concurrent no longer
@@ -383,7 +368,7 @@ static int make_handle(const double *x, const double *t_centered, int64_t n, int
             return 0;
         };
         int info = 0;
-        const double diag0 = (Kmat || pspec) ? 0.0 : h->vt;   // (a supplied K carries its own diagonal; the periodic Gram adds vt itself)
+        const double diag0 = h->kind == KernelKind::Gaussian ? h->vt : 0.0;   // (a supplied K carries its own diagonal; the periodic Gram adds vt itself)
         if ((rc = factor(diag0, &info))) return fail(rc);
         if (info > 0) {
             // reference fallback: cholesky(K + 1e-5 I)   (skgpuppy/Covariance.py:180-185)
@@ -455,7 +440,7 @@ extern "C" int gpx_n(const gpx_handle *h, int64_t *n, int *d)
 {
     if (!h) { gpx_set_error("null handle"); return GPX_ERR_BAD_ARG; }
     if (n) *n = h->n;
-    if (d) *d = h->per ? h->per->d : h->d;
+    if (d) *d = handle_dim(h);
     return 0;
 }
 
@@ -608,8 +593,8 @@ __global__ __launch_bounds__(256) void trace_quad_rows_kernel(const double *__re
         s1 = fma(Kinv[i * ldk + j], dk, s1);
         s2 = fma(dk, alpha[j], s2);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
+    s1 = wave_sum(s1);
+    s2 = wave_sum(s2);
     if (lane == 0) { part[2 * i] = s1; part[2 * i + 1] = alpha[i] * s2; }
 }
 __global__ __launch_bounds__(256) void sum_pairs_kernel(const double *__restrict__ part, long n, double *__restrict__ out)

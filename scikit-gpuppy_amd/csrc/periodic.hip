@@ -11,20 +11,11 @@
 #include <string.h>
 
 #include "common.h"
+#include "gram_tile.h"
 #include "periodic_math.h"
 
-constexpr int PG_ROWS = 64;    // rows of one block tile (4 waves x 16 rows)
-constexpr int PG_COLS = 128;   // columns of one block tile (64 lanes x 2 adjacent columns)
-enum { PAD_NONE = 0, PAD_ZERO = 1, PAD_IDENT = 2 };
 // what the deriv variant writes (the parameter's group; its coordinate is a second argument)
 enum { PD_V = 0, PD_VT = 1, PD_W = 2, PD_P = 3, PD_W2 = 4 };
-
-__device__ __forceinline__ double wave_sum_q(double s)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    return s;
-}
 
 // one entry of d K / d theta_j from Kf = v exp(-q) and the difference e of the parameter's coordinate (Covariance.py:417-433)
 __device__ __forceinline__ double periodic_deriv_entry(int kind, double e, double kf, bool equal, double vt, double hk, double ih, double il,
@@ -38,148 +29,98 @@ __device__ __forceinline__ double periodic_deriv_entry(int kind, double e, doubl
     return -(hk * sn) * sn * kf;                                      // hk = w2 / 2
 }
 
-// gram_kernel's memory shape: the column tile of xj k-major in LDS, a wave's 16 rows of xi wave-uniform (scalar loads), a lane owns
-// two adjacent columns and stores 16 bytes.  Per k and entry: the difference, max |delta| (the equality test: delta == 0 in EVERY
-// component, not q == 0, which a zero w or an underflowing delta^2 would fool), two products into q and one sin(pi r): 24 fp64
-// operations, so the kernel is bound by the fp64 VALU from d = 2 on, not by its 8 B / entry store.
+// The pair policy of the periodic kernel on the RAW inputs (the frame: gram_tile.h).  Per k and entry: the difference, max |delta| (the
+// equality test: delta == 0 in EVERY component, not q == 0, which a zero w or an underflowing delta^2 would fool), two products into q
+// and one sin(pi r): 24 fp64 operations, so the kernel is bound by the fp64 VALU from d = 2 on, not by its 8 B / entry store.
 // K_ij and K_ji are the same bits: delta changes sign, and every term of q is even in delta operation by operation.
+// The equality term is part of the entry, not of the frame's diagonal: a query may equal a training row anywhere.
 // DERIV: d K / d theta_j instead of K -- kind (PD_*) and coordinate kd select the factor on Kf = v exp(-q); dscale = pi w2 / p (PD_P).
+template <bool DERIV>
+struct PeriodicPair {
+    const double *par;   // [4][d]: w / 2, fl(1 / p), its correction, w2 / 2
+    int d;
+    double v, vt;
+    int kind, kd;
+    double dscale;
+    // q and max |delta| of a lane's 16 rows x 2 columns, each set of 16 as ONE vector value: as arrays inside this struct they are taken
+    // apart into 64 scalars before the frame is inlined into the kernel, and the kernel then needs 172 VGPRs instead of 164 (two waves
+    // per SIMD instead of three).  DERIV alone: the constants hk, ih, il of coordinate kd and the lane's two columns bk of it.
+    struct State { v16d acc0, acc1, m0, m1; double hk, ih, il; v2d bk; };
+
+    __device__ __forceinline__ void accumulate(State &st, const double *const (&arow)[16], const double *b_s, int lane, long, int) const
+    {
+        v16d &acc0 = st.acc0, &acc1 = st.acc1, &m0 = st.m0, &m1 = st.m1;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { acc0[r] = 0.0; acc1[r] = 0.0; m0[r] = 0.0; m1[r] = 0.0; }
+        for (int k = 0; k < d; ++k) {
+            const double hw = par[k], ih = par[d + k], il = par[2 * d + k], hw2 = par[3 * d + k];
+            const v2d b = *reinterpret_cast<const v2d *>(&b_s[k * GT_COLS + 2 * lane]);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const double a = arow[r][k];
+                const double e0 = a - b.x, e1 = a - b.y;
+                m0[r] = fmax(m0[r], fabs(e0));
+                m1[r] = fmax(m1[r], fabs(e1));
+                acc0[r] = fma(hw * e0, e0, acc0[r]);
+                acc1[r] = fma(hw * e1, e1, acc1[r]);
+                const double s0 = sinpi_half(periodic_reduce(e0, ih, il)), s1 = sinpi_half(periodic_reduce(e1, ih, il));
+                acc0[r] = fma(hw2 * s0, s0, acc0[r]);
+                acc1[r] = fma(hw2 * s1, s1, acc1[r]);
+            }
+        }
+        if (DERIV) {
+            st.hk = par[(kind == PD_W2 ? 3 * d : 0) + kd]; st.ih = par[d + kd]; st.il = par[2 * d + kd];
+            st.bk = *reinterpret_cast<const v2d *>(&b_s[kd * GT_COLS + 2 * lane]);
+        }
+    }
+    __device__ __forceinline__ v2d entry(const State &st, const double *const (&arow)[16], int r) const
+    {
+        v2d o;
+        if (DERIV) {
+            const double a = arow[r][kd];
+            o.x = periodic_deriv_entry(kind, a - st.bk.x, v * exp_nonpos(-st.acc0[r]), st.m0[r] == 0.0, vt, st.hk, st.ih, st.il, dscale);
+            o.y = periodic_deriv_entry(kind, a - st.bk.y, v * exp_nonpos(-st.acc1[r]), st.m1[r] == 0.0, vt, st.hk, st.ih, st.il, dscale);
+        } else {
+            o.x = v * exp_nonpos(-st.acc0[r]) + (st.m0[r] == 0.0 ? vt : 0.0);
+            o.y = v * exp_nonpos(-st.acc1[r]) + (st.m1[r] == 0.0 ? vt : 0.0);
+        }
+        return o;
+    }
+};
+
 template <bool DERIV>
 __global__ __launch_bounds__(256) void periodic_gram_kernel(const double *__restrict__ xi, long n1, const double *__restrict__ xj, long n2,
                                                            int d, const double *__restrict__ par, double v, double vt, double add_diag,
                                                            int lower_only, int pad_mode, double *__restrict__ out, long ld, int kind, int kd,
                                                            double dscale)
 {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    double *b_s = smem;               // [d][128] columns of xj, k-major so a lane reads 2 adjacent columns
-
-    long ry = blockIdx.y, cx = blockIdx.x;
-    if (lower_only == 2) {
-        // 1-D grid over the tiles that touch the lower triangle (gram_kernel): row pair m holds m + 1 column tiles per row tile
-        const long lid = blockIdx.x;
-        long m = (long)((sqrt(4.0 * (double)lid + 1.0) - 1.0) * 0.5);
-        while (m * (m + 1) > lid) --m;
-        while ((m + 1) * (m + 2) <= lid) ++m;
-        const long rem = lid - m * (m + 1);
-        ry = 2 * m + (rem > m ? 1 : 0);
-        cx = rem > m ? rem - (m + 1) : rem;
-    }
-    const long row0 = ry * PG_ROWS;
-    const long col0 = cx * PG_COLS;
-    if (lower_only && col0 > row0 + (PG_ROWS - 1)) return;   // tile entirely above the diagonal
-
-    const int t = threadIdx.x;
-    for (int e = t; e < PG_COLS * d; e += 256) {
-        int c = e & (PG_COLS - 1), k = e >> 7;
-        long gc = col0 + c;
-        b_s[k * PG_COLS + c] = (gc < n2) ? xj[gc * d + k] : 0.0;
-    }
-    __syncthreads();
-
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
-    double acc0[16], acc1[16], m0[16], m1[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { acc0[r] = 0.0; acc1[r] = 0.0; m0[r] = 0.0; m1[r] = 0.0; }
-
-    // rows past n1 (padding) read the last real row: their outputs are overwritten below
-    const long rbase = row0 + wave * 16;
-    const double *arow[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) arow[r] = xi + (rbase + r < n1 ? rbase + r : n1 - 1) * d;
-    for (int k = 0; k < d; ++k) {
-        const double hw = par[k], ih = par[d + k], il = par[2 * d + k], hw2 = par[3 * d + k];
-        const v2d b = *reinterpret_cast<const v2d *>(&b_s[k * PG_COLS + 2 * lane]);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const double a = arow[r][k];
-            const double e0 = a - b.x, e1 = a - b.y;
-            m0[r] = fmax(m0[r], fabs(e0));
-            m1[r] = fmax(m1[r], fabs(e1));
-            acc0[r] = fma(hw * e0, e0, acc0[r]);
-            acc1[r] = fma(hw * e1, e1, acc1[r]);
-            const double s0 = sinpi_half(periodic_reduce(e0, ih, il)), s1 = sinpi_half(periodic_reduce(e1, ih, il));
-            acc0[r] = fma(hw2 * s0, s0, acc0[r]);
-            acc1[r] = fma(hw2 * s1, s1, acc1[r]);
-        }
-    }
-
-    const long gc = col0 + 2 * lane;
-    if (DERIV) {
-        const double hk = par[(kind == PD_W2 ? 3 * d : 0) + kd], ih = par[d + kd], il = par[2 * d + kd];
-        const v2d b = *reinterpret_cast<const v2d *>(&b_s[kd * PG_COLS + 2 * lane]);
-        const bool pad = pad_mode != PAD_NONE;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const long gr = rbase + r;
-            const double a = arow[r][kd];
-            v2d o;
-            o.x = periodic_deriv_entry(kind, a - b.x, v * exp_nonpos(-acc0[r]), m0[r] == 0.0, vt, hk, ih, il, dscale);
-            o.y = periodic_deriv_entry(kind, a - b.y, v * exp_nonpos(-acc1[r]), m1[r] == 0.0, vt, hk, ih, il, dscale);
-            if (pad && (gr >= n1 || gc >= n2)) o.x = 0.0;
-            if (pad && (gr >= n1 || gc + 1 >= n2)) o.y = 0.0;
-            *reinterpret_cast<v2d *>(&out[gr * ld + gc]) = o;
-        }
-        return;
-    }
-    // a tile that touches neither the diagonal nor the padding skips the per-entry tests of those two (not the equality test: a query
-    // may equal a training row anywhere)
-    if (row0 + PG_ROWS <= n1 && col0 + PG_COLS <= n2 && (col0 >= row0 + PG_ROWS || col0 + PG_COLS <= row0)) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            v2d o;
-            o.x = v * exp_nonpos(-acc0[r]) + (m0[r] == 0.0 ? vt : 0.0);
-            o.y = v * exp_nonpos(-acc1[r]) + (m1[r] == 0.0 ? vt : 0.0);
-            *reinterpret_cast<v2d *>(&out[(rbase + r) * ld + gc]) = o;
-        }
-        return;
-    }
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const long gr = rbase + r;
-        double k0 = v * exp_nonpos(-acc0[r]) + (m0[r] == 0.0 ? vt : 0.0);
-        double k1 = v * exp_nonpos(-acc1[r]) + (m1[r] == 0.0 ? vt : 0.0);
-        if (gr == gc) k0 += add_diag;
-        if (gr == gc + 1) k1 += add_diag;
-        if (pad_mode != PAD_NONE) {
-            if (gr >= n1 || gc >= n2) k0 = (pad_mode == PAD_IDENT && gr == gc) ? 1.0 : 0.0;
-            if (gr >= n1 || gc + 1 >= n2) k1 = (pad_mode == PAD_IDENT && gr == gc + 1) ? 1.0 : 0.0;
-        }
-        v2d o;
-        o.x = k0;
-        o.y = k1;
-        *reinterpret_cast<v2d *>(&out[gr * ld + gc]) = o;
-    }
+    gram_tile<PeriodicPair<DERIV>, !DERIV>(PeriodicPair<DERIV>{par, d, v, vt, kind, kd, dscale}, xi, n1, xj, n2, d, add_diag, lower_only,
+                                           pad_mode, out, ld);
 }
 
-// out must hold rows_pad x ld doubles with rows_pad % 64 == 0, cols_pad % 128 == 0, ld >= cols_pad, ld even, out 16-byte aligned
+// the padding contract of out: gram_launch_plan (gram_tile.h)
 int launch_periodic_gram(const double *xi, int64_t n1, const double *xj, int64_t n2, const PeriodicData *pd, double add_diag,
                          int lower_only, int pad_mode, double *out, int64_t ld, int64_t rows_pad, int64_t cols_pad, hipStream_t s,
                          Profiler *prof, int deriv)
 {
     const int d = pd->d;
-    if (rows_pad % PG_ROWS || cols_pad % PG_COLS || ld < cols_pad || (ld & 1) || d < 1 || d > GPX_MAX_D || n1 < 1 || n2 < 1 ||
-        n1 > rows_pad || n2 > cols_pad || deriv < -1 || deriv >= 2 + 3 * d) {
+    GramLaunch pl;
+    // (a derivative has no diagonal term: identity padding would have no meaning for it, and no caller asks for it)
+    if (!gram_launch_plan(rows_pad, cols_pad, ld, d, lower_only, &pl) || n1 < 1 || n2 < 1 || n1 > rows_pad || n2 > cols_pad || deriv < -1 ||
+        deriv >= 2 + 3 * d || (deriv >= 0 && pad_mode == PAD_IDENT)) {
         gpx_set_error("launch_periodic_gram: bad shape (n1=%ld n2=%ld rows_pad=%ld cols_pad=%ld ld=%ld d=%d deriv=%d)", (long)n1, (long)n2,
                       (long)rows_pad, (long)cols_pad, (long)ld, d, deriv);
         return GPX_ERR_BAD_ARG;
     }
-    dim3 grid((unsigned)(cols_pad / PG_COLS), (unsigned)(rows_pad / PG_ROWS));
-    const size_t lds = (size_t)PG_COLS * d * sizeof(double);
-    const double stored = lower_only ? 0.5 * (double)rows_pad * (double)cols_pad : (double)rows_pad * (double)cols_pad;
-    ProfScope ps(prof, s, GPX_K_GRAM, 8.0 * stored);
-    if (lower_only && rows_pad == cols_pad && rows_pad % (2 * PG_ROWS) == 0) {
-        const int64_t m = rows_pad / (2 * PG_ROWS);
-        grid = dim3((unsigned)(m * (m + 1)), 1);
-        lower_only = 2;
-    }
+    ProfScope ps(prof, s, GPX_K_GRAM, pl.bytes);
     if (deriv < 0) {
-        hipLaunchKernelGGL(periodic_gram_kernel<false>, grid, dim3(256), lds, s, xi, (long)n1, xj, (long)n2, d, (const double *)pd->par, pd->v,
-                           pd->vt, add_diag, lower_only, pad_mode, out, (long)ld, 0, 0, 0.0);
+        hipLaunchKernelGGL(periodic_gram_kernel<false>, pl.grid, dim3(256), pl.lds, s, xi, (long)n1, xj, (long)n2, d, (const double *)pd->par,
+                           pd->v, pd->vt, add_diag, pl.lower_only, pad_mode, out, (long)ld, 0, 0, 0.0);
     } else {
         const int kind = deriv < 2 ? deriv : 2 + (deriv - 2) / d, kd = deriv < 2 ? 0 : (deriv - 2) % d;
         const double dscale = kind == PD_P ? M_PI * pd->w2[kd] / pd->p[kd] : 0.0;
-        hipLaunchKernelGGL(periodic_gram_kernel<true>, grid, dim3(256), lds, s, xi, (long)n1, xj, (long)n2, d, (const double *)pd->par, pd->v,
-                           pd->vt, 0.0, lower_only, pad_mode, out, (long)ld, kind, kd, dscale);
+        hipLaunchKernelGGL(periodic_gram_kernel<true>, pl.grid, dim3(256), pl.lds, s, xi, (long)n1, xj, (long)n2, d, (const double *)pd->par,
+                           pd->v, pd->vt, 0.0, pl.lower_only, pad_mode, out, (long)ld, kind, kd, dscale);
     }
     GPX_HIP(hipGetLastError());
     return 0;
@@ -268,7 +209,7 @@ __global__ __launch_bounds__(256) void periodic_nll_grad_kernel(const double *__
     }
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-        const double s = wave_sum_q(acc[c]);
+        const double s = wave_sum(acc[c]);
         if (lane == 0) red[wave][c] = s;
     }
     __syncthreads();
@@ -403,7 +344,7 @@ extern "C" int gpx_periodic_gram(const double *xi, int64_t n1, const double *xj,
 extern "C" int gpx_periodic_nll_grad(gpx_handle *h, double *grad_out)
 {
     CHECK_H(h);
-    if (!h->per) { gpx_set_error("gpx_periodic_nll_grad: not a gpx_periodic_fit handle"); return GPX_ERR_STATE; }
+    if (h->kind != KernelKind::Periodic) { gpx_set_error("gpx_periodic_nll_grad: not a gpx_periodic_fit handle"); return GPX_ERR_STATE; }
     if (!grad_out) { gpx_set_error("null argument"); return GPX_ERR_BAD_ARG; }
     GPX_TRY(ensure_kinv(h));
     const PeriodicData *pd = h->per;

@@ -6,6 +6,7 @@
 #include <initializer_list>
 
 #include "common.h"
+#include "gram_tile.h"
 
 int ensure_Z(gpx_handle *h, int64_t rows)
 {
@@ -59,27 +60,27 @@ int row_solve_run(gpx_handle *h, const RowSolve &rs, int64_t mc, int64_t mp, con
 // from_x: the cross-covariance rows come from the Gram kernel on queries that the caller's load leaves on the device in pr.xq; otherwise
 // load fills h->Z with the caller's rows kv [m, n] and pr.kd with the prior variance of each query (the diagonal of cov_matrix(x_star),
 // GaussianProcess.py:75).
-// A periodic handle (from_x with h->per): the rows come from periodic_gram_kernel, +vt on equality included, and the prior variance is
+// A periodic handle (pr.periodic): the rows come from periodic_gram_kernel, +vt on equality included, and the prior variance is
 // v + vt.  That call promises a result that does not depend on the query's place in the batch or on the chunking: always the many-row
 // solver and the stand-alone row reduction (the few-vector solver and the reduction fused into a slab's last product sum in other
 // orders), chunks of at most GPX_PERIODIC_CHUNK rows (read at every call; default: the solver's own cap).
 int predict_run_begin(gpx_handle *h, bool from_x, int64_t m, PredictRun &pr)
 {
     pr.from_x = from_x;
-    pr.per = from_x ? h->per : nullptr;
-    pr.d = pr.per ? pr.per->d : h->d;
+    pr.periodic = from_x && h->kind == KernelKind::Periodic;
+    const int d = handle_dim(h);
     RowSolve &rs = pr.rs;
     // |row of Zs|^2 = k*^T K^-1 k* <= k(x*, x*): sqrt(v) for the built-in kernel, sqrt(kdiag) for the caller's (tsolve.hip, launch_row_bounds)
     int64_t chunk_cap = 0;
-    if (pr.per)
+    if (pr.periodic)
         if (const char *e = getenv("GPX_PERIODIC_CHUNK")) chunk_cap = atoll(e);
-    GPX_TRY(row_solve_begin(h, m, rs, true, !pr.per, chunk_cap));
+    GPX_TRY(row_solve_begin(h, m, rs, true, !pr.periodic, chunk_cap));
     const int64_t chunk = rs.chunk;
     // the row sums |z|^2 and z.y ride in the epilogue of each slab's last product (tsolve.hip): per row one partial pair per 64 columns
     pr.nslots = h->npad / 64;
-    pr.fused = chunk >= 3072 && !pr.per;
-    GPX_TRY(rs.sc.take(&pr.xq, chunk * std::max(pr.d, 1)));
-    GPX_TRY(rs.sc.take(&pr.xqw, chunk * std::max(pr.d, 1)));
+    pr.fused = chunk >= 3072 && !pr.periodic;
+    GPX_TRY(rs.sc.take(&pr.xq, chunk * std::max(d, 1)));
+    GPX_TRY(rs.sc.take(&pr.xqw, chunk * std::max(d, 1)));
     GPX_TRY(rs.sc.take(&pr.kd, chunk));
     if (pr.fused) GPX_TRY(rs.sc.take(&pr.part, 2 * chunk * pr.nslots));
     return 0;
@@ -93,8 +94,6 @@ int predict_run_chunk(gpx_handle *h, PredictRun &pr, int64_t m0, int64_t mc, con
 {
     hipStream_t s = h->stream;
     RowSolve &rs = pr.rs;
-    const PeriodicData *per = pr.per;
-    const int d = pr.d;
     const bool from_x = pr.from_x;
     const int64_t chunk = rs.chunk, nslots = pr.nslots, mp = round_up(mc, TILE);
     double *xq = pr.xq, *xqw = pr.xqw, *kd = pr.kd, *part = pr.part, *Zs = rs.Zs;
@@ -102,10 +101,10 @@ int predict_run_chunk(gpx_handle *h, PredictRun &pr, int64_t m0, int64_t mc, con
     auto fill = [&]() -> int {
         GPX_TRY(load(mc, mp));
         if (!from_x) return 0;   // the operator's own cross-covariance rows, zero padded to the tile grid by load
-        if (per) return launch_periodic_gram(xq, mc, per->x, h->n, per, 0.0, 0, 1, h->Z, h->npad, mp, h->npad, s, &h->prof);
-        GPX_TRY(launch_scale_rows(xq, mc, mp, d, h->sw, xqw, s));
-        // kv = cross-covariance (no vt), zero padded: rows >= mc and columns >= n are 0
-        return launch_gram(xqw, mc, h->xs_w, h->n, d, h->v, 0.0, 0, 1, h->Z, h->npad, mp, h->npad, s, &h->prof);
+        const bool scale = h->kind == KernelKind::Gaussian;   // its Gram kernel reads inputs scaled by sqrt(w)
+        if (scale) GPX_TRY(launch_scale_rows(xq, mc, mp, h->d, h->sw, xqw, s));
+        // kv = cross-covariance (no add_diag), zero padded: rows >= mc and columns >= n are 0
+        return handle_gram(h, scale ? xqw : xq, mc, handle_train_inputs(h), h->n, 0.0, 0, PAD_ZERO, h->Z, h->npad, mp, h->npad, s, &h->prof);
     };
     // Z <- kv L^-T  : row m of Z is (L^-1 kv_m)^T
     // var = k_mm - |z|^2 (k_mm = v + vt for the built-in kernel: k includes vt, GaussianProcess.py:75,78) ; mean = z . y
@@ -125,7 +124,7 @@ int predict_run_chunk(gpx_handle *h, PredictRun &pr, int64_t m0, int64_t mc, con
     return emu_left_guarded(rs.use_left, [&](bool left, int *status) -> int {
         GPX_TRY(fill());
         if (left) {
-            GPX_TRY(launch_row_bounds(from_x ? nullptr : kd, per ? h->v + h->vt : h->v, mc, rs.left.bound, s));
+            GPX_TRY(launch_row_bounds(from_x ? nullptr : kd, pr.periodic ? h->v + h->vt : h->v, mc, rs.left.bound, s));
             GPX_TRY(emu_left_begin(rs.left, rs.left.bound, mc, s));
         }
         GPX_TRY(solve(left));
@@ -146,7 +145,7 @@ static int predict_common(gpx_handle *h, const double *xs, const double *kv, con
     PredictRun pr(s);
     GPX_TRY(predict_run_begin(h, xs != nullptr, m, pr));
     const int64_t chunk = pr.rs.chunk;
-    const int d = pr.d;
+    const int d = handle_dim(h);
     double *mv = nullptr;
     GPX_TRY(pr.rs.sc.take(&mv, 2 * chunk));
     int rc = 0;
@@ -187,7 +186,7 @@ extern "C" int gpx_predict(gpx_handle *h, const double *xs, int64_t m, double *m
 extern "C" int gpx_periodic_predict(gpx_handle *h, const double *xs, int64_t m, double *mean_out, double *var_out)
 {
     CHECK_H(h);
-    if (!h->per) { gpx_set_error("gpx_periodic_predict: not a gpx_periodic_fit handle"); return GPX_ERR_STATE; }
+    if (h->kind != KernelKind::Periodic) { gpx_set_error("gpx_periodic_predict: not a gpx_periodic_fit handle"); return GPX_ERR_STATE; }
     if (m < 0 || (m > 0 && (!xs || !mean_out || !var_out))) { gpx_set_error("gpx_periodic_predict: bad arguments"); return GPX_ERR_BAD_ARG; }
     if (m == 0) return 0;
     return predict_common(h, xs, nullptr, nullptr, m, mean_out, var_out);

@@ -11,13 +11,6 @@
 //          rows; the d^2 inner loop is factorised as exp(e_i + e_j + b_i . a_j), b_i = Lambda^-1 a_i / 4.
 #include "common.h"
 
-__device__ __forceinline__ double wave_sum_p(double s)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    return s;
-}
-
 // ---------------------------------------------------------------------------------------------
 // Approx: per-row quantities for a given u.   VM rows: 0 = C, 1..d = J_k.   AUX rows: 1..d = H_kk
 // c_i = v exp(-1/2 sum w_k delta_k^2), delta = x_i - u          (Covariance.py:660-689)
@@ -96,7 +89,7 @@ __global__ __launch_bounds__(1024) void dot_pairs_kernel(DotPairs pairs, long n,
         }
     } else
         for (long i = threadIdx.x; i < n; i += 1024) s0 = fma(P[i], Q[i], s0);
-    double s = wave_sum_p(s0 + s1);
+    double s = wave_sum(s0 + s1);
     if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -286,7 +279,7 @@ __global__ __launch_bounds__(256) void approx_reduce_many_kernel(const double *_
             y1 = fma(e.x, yy.x, y1); y1 = fma(e.y, yy.y, y1);
             x01 = fma(a.x, e.x, x01); x01 = fma(a.y, e.y, x01);
         }
-        q0 = wave_sum_p(q0); y0 = wave_sum_p(y0); q1 = wave_sum_p(q1); y1 = wave_sum_p(y1); x01 = wave_sum_p(x01);
+        q0 = wave_sum(q0); y0 = wave_sum(y0); q1 = wave_sum(q1); y1 = wave_sum(y1); x01 = wave_sum(x01);
         if (lane == 0) { part[0][wave] = q0; part[1][wave] = y0; part[2][wave] = q1; part[3][wave] = y1; part[2 * (d + 2)][wave] = x01; }
     }
     for (int r = 2; r < d + 2; ++r) {
@@ -298,7 +291,7 @@ __global__ __launch_bounds__(256) void approx_reduce_many_kernel(const double *_
             q = fma(a.x, a.x, q); q = fma(a.y, a.y, q);
             sy = fma(a.x, yy.x, sy); sy = fma(a.y, yy.y, sy);
         }
-        q = wave_sum_p(q); sy = wave_sum_p(sy);
+        q = wave_sum(q); sy = wave_sum(sy);
         if (lane == 0) { part[2 * r][wave] = q; part[2 * r + 1][wave] = sy; }
     }
     __syncthreads();
@@ -476,12 +469,12 @@ __global__ __launch_bounds__(256) void dvh_reduce_many_kernel(const double *__re
                 }
             }
         }
-        qc = wave_sum_p(qc);
+        qc = wave_sum(qc);
         if (lane == 0) part[3 * d][wave] = qc;
 #pragma unroll
         for (int k = 0; k < DR; ++k) {
             if (k < d) {
-                const double q = wave_sum_p(qj[k]), sy = wave_sum_p(yj[k]), sh = wave_sum_p(ch[k]);
+                const double q = wave_sum(qj[k]), sy = wave_sum(yj[k]), sh = wave_sum(ch[k]);
                 if (lane == 0) { part[3 * k][wave] = q; part[3 * k + 1][wave] = sy; part[3 * k + 2][wave] = sh; }
             }
         }
@@ -491,7 +484,7 @@ __global__ __launch_bounds__(256) void dvh_reduce_many_kernel(const double *__re
             const v2d a = *reinterpret_cast<const v2d *>(zc + c);
             qc = fma(a.x, a.x, qc); qc = fma(a.y, a.y, qc);
         }
-        qc = wave_sum_p(qc);
+        qc = wave_sum(qc);
         if (lane == 0) part[3 * d][wave] = qc;
         for (int k = 0; k < d; ++k) {
             const double *zjr = zc + (long)(1 + k) * npad, *zhr = zc + (long)(1 + d + k) * npad;
@@ -504,7 +497,7 @@ __global__ __launch_bounds__(256) void dvh_reduce_many_kernel(const double *__re
                 sy = fma(zj.x, yy.x, sy); sy = fma(zj.y, yy.y, sy);
                 sh = fma(a.x, zh.x, sh); sh = fma(a.y, zh.y, sh);
             }
-            q = wave_sum_p(q); sy = wave_sum_p(sy); sh = wave_sum_p(sh);
+            q = wave_sum(q); sy = wave_sum(sy); sh = wave_sum(sh);
             if (lane == 0) { part[3 * k][wave] = q; part[3 * k + 1][wave] = sy; part[3 * k + 2][wave] = sh; }
         }
     }
@@ -570,7 +563,7 @@ __global__ __launch_bounds__(256) void kinv_pass_kernel(const double *__restrict
     for (int r = 0; r < R; ++r)
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-            const double s = wave_sum_p(acc[r][c]);
+            const double s = wave_sum(acc[r][c]);
             if (lane == 0) red[wave][r * NC + c] = s;
         }
     __syncthreads();
@@ -726,7 +719,7 @@ __global__ __launch_bounds__(256, 2) void exact_sum_kernel(const double *__restr
     double s = 0.0;
 #pragma unroll
     for (int r = 0; r < EXR; ++r) s = fma(acc[r], rs[r][1], s);
-    s = wave_sum_p(s);
+    s = wave_sum(s);
     if ((t & 63) == 0) ws[t >> 6] = s;
     __syncthreads();
     if (t == 0) partial[rb - rb_base] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
@@ -789,7 +782,7 @@ __global__ __launch_bounds__(256, 2) void nll_grad_kernel(const double *__restri
     }
 #pragma unroll
     for (int c = 0; c < DMAX + 2; ++c) {
-        const double s = wave_sum_p(acc[c]);
+        const double s = wave_sum(acc[c]);
         if (lane == 0) red[wave][c] = s;
     }
     __syncthreads();
@@ -803,7 +796,7 @@ __global__ __launch_bounds__(256) void sum_columns_kernel(const double *__restri
     const int c = blockIdx.x;
     double s = 0.0;
     for (long b = threadIdx.x; b < nb; b += 256) s += partial[b * nc + c];
-    s = wave_sum_p(s);
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) out[c] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
@@ -846,7 +839,7 @@ __global__ __launch_bounds__(256) void sum_vector_kernel(const double *__restric
     __shared__ double ws[4];
     double s = 0.0;
     for (long i = threadIdx.x; i < n; i += 256) s += p[i];
-    s = wave_sum_p(s);
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) *out = (ws[0] + ws[1]) + (ws[2] + ws[3]);
@@ -1114,7 +1107,7 @@ __global__ __launch_bounds__(256) void exact_many_build_kernel(const double *__r
         const double Ci = same ? c + vt : c;
         const double lm = inb ? Ci * nc1 * exp(0.5 * qd) : 0.0;
         if constexpr (WANT_H) H[i * npad + j] = inb ? (same ? (v + vt) : v) * exp_nonpos(-qa) : 0.0;
-        const double m = wave_sum_p(bj * lm);
+        const double m = wave_sum(bj * lm);
         if (lane == 0) mpart[i * npart + blockIdx.x] = m;
     }
 }
@@ -1163,8 +1156,8 @@ __global__ __launch_bounds__(256) void exact_many_finish_kernel(const double *__
             s1 = fma(a.y, b.y, s1);
         }
     }
-    m = wave_sum_p(m);
-    const double sv = wave_sum_p(s0 + s1);
+    m = wave_sum(m);
+    const double sv = wave_sum(s0 + s1);
     if (lane == 0) { ws[0][wave] = m; ws[1][wave] = sv; }
     __syncthreads();
     if (t == 0) {

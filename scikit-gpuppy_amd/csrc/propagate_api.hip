@@ -374,7 +374,7 @@ extern "C" int gpx_propagate_quadrature_many(gpx_handle *h, const double *U, con
 {
     CHECK_H(h);
     if (mixture_args_bad(wq, S, b, y, ny, mom, dens) || (b > 0 && (!U || !A || !z))) { gpx_set_error("gpx_propagate_quadrature_many: bad arguments"); return GPX_ERR_BAD_ARG; }
-    if (!h->per && h->d == 0) {
+    if (!handle_has_kernel(h)) {
         gpx_set_error("gpx_propagate_quadrature_many: the handle was built from a supplied matrix (gpx_fit_matrix): no inputs / theta to evaluate the kernel on");
         return GPX_ERR_STATE;
     }
@@ -384,7 +384,7 @@ extern "C" int gpx_propagate_quadrature_many(gpx_handle *h, const double *U, con
     PredictRun pr(s);
     GPX_TRY(predict_run_begin(h, true, rows, pr));
     Scratch &sc = pr.rs.sc;
-    const int d = pr.d;
+    const int d = handle_dim(h);
     const int64_t d2 = (int64_t)d * d;
     double *Ud = nullptr, *Ad = nullptr, *zd = nullptr, *wqd = nullptr, *yd = nullptr, *mv = nullptr, *momd = nullptr, *densd = nullptr;
     GPX_TRY(stage_in(sc, U, b * d, &Ud));

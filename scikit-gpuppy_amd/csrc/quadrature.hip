@@ -4,13 +4,6 @@
 // (Girard 2004, p. 32).  The S reference calls of gp(x) in between are rows of the many-row solver (predict.hip, PredictRun).
 #include "common.h"
 
-__device__ __forceinline__ double wave_sum_q(double s)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    return s;
-}
-
 // ---------------------------------------------------------------------------------------------
 // Nodes.  Query row g = i S + s (input i, node s), component k:
 //   X[g][k] = fma(A_i[k][d-1], z[s][d-1], ... fma(A_i[k][1], z[s][1], fma(A_i[k][0], z[s][0], U[i][k])) ...)
@@ -62,7 +55,7 @@ template <int NQ> __device__ __forceinline__ void block_sum_store(double (&acc)[
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
-        const double w = wave_sum_q(acc[q]);
+        const double w = wave_sum(acc[q]);
         if (lane == 0) slot[q][wave] = w;
     }
     __syncthreads();
@@ -128,7 +121,7 @@ template <int PASS> __global__ __launch_bounds__(256) void mixture_finish_kernel
     for (int q = 0; q < NQ; ++q) {
         acc[q] = 0.0;
         for (long g = t; g < nseg; g += 256) acc[q] += part[q * pstride + i * nseg + g];
-        const double w = wave_sum_q(acc[q]);
+        const double w = wave_sum(acc[q]);
         if (lane == 0) slot[q][wave] = w;
     }
     __syncthreads();

@@ -173,8 +173,7 @@ __global__ __launch_bounds__(256) void sum_kernel(const double *__restrict__ p, 
     __shared__ double ws[4];
     double s = 0.0;
     for (long i = threadIdx.x; i < n; i += 256) s += p[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) *out = (ws[0] + ws[1]) + (ws[2] + ws[3]);

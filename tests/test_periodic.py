@@ -169,6 +169,31 @@ def test_fit_solve_predict(N, d):
     mm.close()
 
 
+def _chol_of(handle, n):
+    out = np.empty((n, n))
+    _gpx.check(_gpx.lib.gpx_chol(handle, _gpx.ptr(out)), "gpx_chol")
+    return out
+
+
+def test_fit_matrix_of_the_device_gram_is_the_fit():
+    """gpx_fit_matrix on gpx_periodic_gram's matrix gives gpx_periodic_fit's factor bit for bit (the periodic twin of
+    test_backward_error.py's test of that name).  N = 1153 pads to 1280, the smallest shape whose assembly is split: the first outer
+    panel's 1024 columns, then the rest with 129 real rows in a 256-row padded grid that starts off the origin of the buffer."""
+    N, d = 1153, 3
+    x, t, theta = pl.make_case(N, d)
+    K = _gram(x, N, x, N, d, theta)
+    gp = sk.GaussianProcess(x, t, sk.PeriodicCovariance(), theta.copy())
+    assert gp._route() == "periodic"
+    L1 = _chol_of(gp._dev().handle, N)
+    assert gp._dev().jitter() == 0.0
+    gp._dev().close()
+    m = _MatrixModel(K, None)
+    L2 = _chol_of(m.handle, N)
+    assert m.jitter() == 0.0
+    m.close()
+    assert np.array_equal(L1, L2), np.abs(L1 - L2).max()
+
+
 def test_batch_place_and_chunking_do_not_change_a_query(monkeypatch):
     """2049 + 3 queries at N = 130 in chunks of 1024 (GPX_PERIODIC_CHUNK, read at call time) against the same queries one at a time and
     reversed, bit for bit"""
