@@ -346,6 +346,10 @@ int gpx_emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t l
 int gpx_emu_rebuild(const int8_t *R, int64_t ldr, int64_t sr, int nmod, const int *sa, const int *sb, double *C, int64_t ldc, int64_t rows,
                     int64_t cols);
 int gpx_emu_i8_gemm(const int8_t *A, const int8_t *B, int64_t rows, int64_t cols, int64_t K, int nmod, int8_t *R);
+/* the same with the kernel's strides: planes A [nmod][rows][lda] (lda >= K, a multiple of 16, 255 lda + K < 2^31) and R [nmod][rows][ldr]
+ * (ldr >= cols); R and ldr need no alignment (the residues are stored byte by byte).
+ * gpx_emu_i8_gemm(A, B, ..., R) is gpx_emu_i8_gemm_ld(A, K, B, ..., R, cols). */
+int gpx_emu_i8_gemm_ld(const int8_t *A, int64_t lda, const int8_t *B, int64_t rows, int64_t cols, int64_t K, int nmod, int8_t *R, int64_t ldr);
 /* The two splits of the emulated update alone, on device buffers (tests).  Synchronous; GPX_ERR_BAD_ARG before anything is queued.
  * Both store, for every row < rows_pad and l < nmod (1 .. 16), the balanced residue modulo the l-th modulus of a' = rint(x 2^s) as one
  * byte (128 mod 256 stored as -128); rows >= rows are padding (zero residues).  bits is 1 .. 59; X is 16-byte aligned, ldx even.

@@ -27,6 +27,10 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v16i __attribute__((ext_vector_type(16)));
 typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
+#ifndef EMU_MFMA_16   // the product loop's MFMA shape, compile time only: 1 v_mfma_i32_16x16x64_i8, 0 v_mfma_i32_32x32x32_i8 (same LDS
+#define EMU_MFMA_16 1 // image, staging, barriers and epilogue).  16 x 16 x 64 takes 8-11 % more cycles and holds a clock 13-18 % higher
+#endif                // on random residues: 4-5 % less wall (profiles/r20_emu_product.txt; -DEMU_MFMA_16=0 repeats the A/B)
+
 constexpr int EMU_MAXL = 16;
 constexpr int EMU_BT = 256;   // int8 block tile: 256 x 256, 2 x 4 waves of 128 x 64 (4 x 2 MFMAs of 32 x 32), two waves per SIMD
 constexpr int EMU_SLAB = 1024; // columns of one slab of the left-looking solve (tsolve.hip: PB)
@@ -74,12 +78,16 @@ constexpr EmuCrtAll emu_crt_tables()
 }
 static constexpr EmuCrtAll emu_crt = emu_crt_tables();
 
-#ifdef EMU_STAMP   // diagnostic build only (never the shipped library): s_memtime / s_memrealtime around the k loop of every workgroup
-constexpr int EMU_STAMP_SLOTS = 1 << 16;
-__device__ unsigned long emu_stamps[EMU_STAMP_SLOTS][4];
+#ifdef EMU_STAMP   // diagnostic build only (never the shipped library): s_memtime / s_memrealtime of every workgroup before its k loop,
+// after it, and at kernel exit once its stores have landed: {cycles, 100 MHz} x {loop start, loop end, exit}
+constexpr int EMU_STAMP_SLOTS = 1 << 16, EMU_STAMP_WIDTH = 6;
+__device__ unsigned long emu_stamps[EMU_STAMP_SLOTS][EMU_STAMP_WIDTH];
+extern "C" int gpx_emu_stamp_width() { return EMU_STAMP_WIDTH; }
 extern "C" int gpx_emu_stamps(unsigned long *out, int n)
 {
-    return hipMemcpyFromSymbol(out, HIP_SYMBOL(emu_stamps), sizeof(unsigned long) * 4 * std::min(n, EMU_STAMP_SLOTS)) == hipSuccess ? 0 : GPX_ERR_HIP;
+    return hipMemcpyFromSymbol(out, HIP_SYMBOL(emu_stamps), sizeof(unsigned long) * EMU_STAMP_WIDTH * std::min(n, EMU_STAMP_SLOTS)) == hipSuccess
+               ? 0
+               : GPX_ERR_HIP;
 }
 #endif
 
@@ -313,6 +321,19 @@ __global__ __launch_bounds__(256) void emu_scale_from_bound_kernel(const double 
 // A, B: planes of [tm 256][lda] and [tn 256][K] bytes (B packed: ldb = K; lda >= K is the row stride of A's planes, so that a product
 // reads columns 0 .. K of a wider residue image: a panel's byte offsets stay below 256 lda < 2^25, its 64-bit base comes from the
 // host's row tile and from z, by); R: planes of [tm 256][ldr] bytes.
+//
+// EMU_MFMA_16: the wave tile (128 x 64) as 8 x 4 MFMAs of 16 x 16 x 64.  A fragment is one ds_read_b128 per lane: row fr = lane & 15 of a
+// 16-row tile, k-bytes 16 fq .. +15 (fq = lane >> 4) of the 64-byte slice kk, at granule (4 kk + fq) ^ ((fr >> 1) & 7) of its 128-byte
+// row.  Banks are (a / 4) % 64: a 256-byte bank row holds LDS rows 2n and 2n + 1, so a lane's 16-byte slot is 8 (fr & 1) + granule.
+// ds_read_b128 is served in the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same + 32.  The first holds rows 0-3 and
+// 12-15 at fq = 0 and rows 4-11 at fq = 1: of either parity that is fr >> 1 in {0, 1, 6, 7} at granule c ^ (fr >> 1) and fr >> 1 in
+// {2, 3, 4, 5} at granule c ^ 1 ^ (fr >> 1) (c = 4 kk): c ^ {0, 1, 6, 7, 3, 2, 5, 4}, eight distinct granules per parity, sixteen distinct
+// slots.  The second group swaps the two fq, the other two XOR every granule with 2: all conflict-free, as the 32-row read is.
+//
+// Epilogue (either shape): registers 4 g .. 4 g + 3 of an accumulator are four consecutive rows of one column; |v| < 2^31 is exact in fp64
+// and v / p is never within 1 / (2p) of a half-integer for odd p (256: a tie wraps to the same byte).  One byte store per residue: the
+// stores cost nothing that shows (profiles/r20_emu_product.txt, which also has the integer reduction and the 16-byte stores through an
+// LDS image that were tried in their place: tools/native/rejected/r20_emu_epilogue_int_wide.patch).
 __global__ __launch_bounds__(512, 1) void emu_i8_gemm_kernel(const int8_t *__restrict__ A, const int8_t *__restrict__ B, long sa, long sb, int K,
                                                              int8_t *__restrict__ R, long ldr, long sr, int tm, int tn, int lda)
 {
@@ -353,24 +374,82 @@ __global__ __launch_bounds__(512, 1) void emu_i8_gemm_kernel(const int8_t *__res
     }
     const int nk = K / EMU_BK;
     EMU_DMA_STAGE(0, 0)
+#if EMU_MFMA_16
+    v4i acc[8][4];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = (v4i){};
+#else
     v16i acc[4][2];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int j = 0; j < 2; ++j) acc[i][j] = (v16i){};
+#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 #ifdef EMU_STAMP
     const unsigned long stamp_c0 = __builtin_amdgcn_s_memtime(), stamp_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
 
+    typedef const __attribute__((address_space(3))) v4i lds_v4i;
+    const __attribute__((address_space(3))) int8_t *lsm = (const __attribute__((address_space(3))) int8_t *)smem;
+#if EMU_MFMA_16
+    // a stage is four sub-steps (slice kk, half h of the wave's eight A tiles) of 4 x 4 MFMAs: the A fragments alternate between two sets
+    // per sub-step, the B fragments per kk, so the loads of a sub-step ride under the MFMAs of the one before, as in the 32 x 32 x 32 loop
+    const int fr = lane & 15, fq = lane >> 4, sw = (fr >> 1) & 7;
+    int koff[2];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) koff[kk] = 16 * ((4 * kk + fq) ^ sw);
+    const int a_row = (wr * 128 + fr) * EMU_BK, b_row = EMU_BT * EMU_BK + (wc * 64 + fr) * EMU_BK;
+    v4i fa[2][4], fb[2][4];
+#define EMU_LOAD_A(SET, BUFOFF, KK, H)                                                               \
+    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                 \
+        fa[SET][i_] = *(lds_v4i *)(lsm + (BUFOFF) + a_row + (4 * (H) + i_) * 16 * EMU_BK + koff[KK]);
+#define EMU_LOAD_B(SET, BUFOFF, KK)                                                                  \
+    _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                                 \
+        fb[SET][j_] = *(lds_v4i *)(lsm + (BUFOFF) + b_row + j_ * 16 * EMU_BK + koff[KK]);
+#define EMU_MMA(ASET, BSET, H)                                                                       \
+    _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                 \
+        _Pragma("unroll") for (int j_ = 0; j_ < 4; ++j_)                                             \
+            acc[4 * (H) + i_][j_] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[ASET][i_], fb[BSET][j_], acc[4 * (H) + i_][j_], 0, 0, 0);
+    EMU_LOAD_A(0, 0, 0, 0)
+    EMU_LOAD_B(0, 0, 0)
+#define EMU_KSTEP(CUR_OFF, NXT_OFF, NXT_BUF, KT)                   \
+    {                                                             \
+        const bool has_next_ = (KT) + 1 < nk;                     \
+        if (has_next_) EMU_DMA_STAGE(NXT_BUF, (KT) + 1)           \
+        EMU_LOAD_A(1, CUR_OFF, 0, 1)                              \
+        EMU_MMA(0, 0, 0)                                          \
+        __builtin_amdgcn_sched_barrier(0);                        \
+        EMU_LOAD_A(0, CUR_OFF, 1, 0)                              \
+        EMU_LOAD_B(1, CUR_OFF, 1)                                 \
+        EMU_MMA(1, 0, 1)                                          \
+        __builtin_amdgcn_sched_barrier(0);                        \
+        EMU_LOAD_A(1, CUR_OFF, 1, 1)                              \
+        EMU_MMA(0, 1, 0)                                          \
+        __builtin_amdgcn_sched_barrier(0);                        \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          \
+        __syncthreads();                                          \
+        if (has_next_) { EMU_LOAD_A(0, NXT_OFF, 0, 0) EMU_LOAD_B(0, NXT_OFF, 0) } \
+        EMU_MMA(1, 1, 1)                                          \
+        __builtin_amdgcn_sched_barrier(0);                        \
+    }
+    for (int kt = 0; kt < nk; kt += 2) {
+        EMU_KSTEP(0, STAGE, 1, kt)
+        if (kt + 1 < nk) EMU_KSTEP(STAGE, 0, 0, kt + 1)
+    }
+#undef EMU_KSTEP
+#undef EMU_LOAD_A
+#undef EMU_LOAD_B
+#undef EMU_MMA
+#else
     const int fr = lane & 31, sw = (fr >> 1) & 7;
     int koff[4];
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) koff[kk] = 16 * ((2 * kk + (lane >> 5)) ^ sw);
     const int a_row = (wr * 128 + fr) * EMU_BK, b_row = EMU_BT * EMU_BK + (wc * 64 + fr) * EMU_BK;
-    typedef const __attribute__((address_space(3))) v4i lds_v4i;
-    const __attribute__((address_space(3))) int8_t *lsm = (const __attribute__((address_space(3))) int8_t *)smem;
     v4i fa[2][4], fb[2][2];
 #define EMU_LOAD_FRAGS(SET, BUFOFF, KK)                                                              \
     _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                 \
@@ -408,28 +487,42 @@ __global__ __launch_bounds__(512, 1) void emu_i8_gemm_kernel(const int8_t *__res
 #undef EMU_KSTEP
 #undef EMU_LOAD_FRAGS
 #undef EMU_MMA
+#endif
 #undef EMU_DMA_STAGE
 #undef EMU_DMA_ONE
 #ifdef EMU_STAMP
-    if (t == 0 && orig < EMU_STAMP_SLOTS) {
-        unsigned long *st = emu_stamps[orig];
-        st[0] = stamp_c0; st[1] = __builtin_amdgcn_s_memtime(); st[2] = stamp_r0; st[3] = __builtin_amdgcn_s_memrealtime();
-    }
+    const unsigned long stamp_c1 = __builtin_amdgcn_s_memtime(), stamp_r1 = __builtin_amdgcn_s_memrealtime();
 #endif
 
-    // epilogue: accumulator register r of tile (i, j) is row (r & 3) + 8 (r >> 2) + 4 (lane >> 5), column lane & 31; |v| < 2^31 is exact
-    // in fp64 and v / p is never within 1 / (2p) of a half-integer for odd p (256: a tie wraps to the same byte)
+    // epilogue
+#if EMU_MFMA_16
+    constexpr int TI = 8, TJ = 4, TG = 1, TW = 16;   // accumulator register r of tile (i, j): row 16 i + 4 fq + r, column 16 j + fr
+    const int row0 = 4 * fq;
+#else
+    constexpr int TI = 4, TJ = 2, TG = 4, TW = 32;   // row 32 i + 8 (r >> 2) + 4 (lane >> 5) + (r & 3), column 32 j + fr
+    const int row0 = 4 * (lane >> 5);
+#endif
     const double p = (double)emu_p[z], pinv = 1.0 / p;
-    int8_t *Rw = R + z * sr + ((long)by * EMU_BT + wr * 128 + 4 * (lane >> 5)) * ldr + (long)bx * EMU_BT + wc * 64 + fr;
+    int8_t *Rw = R + z * sr + ((long)by * EMU_BT + wr * 128 + row0) * ldr + (long)bx * EMU_BT + wc * 64 + fr;
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < TI; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+        for (int j = 0; j < TJ; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const double v = (double)acc[i][j][r];
-                Rw[(long)(i * 32 + (r & 3) + 8 * (r >> 2)) * ldr + j * 32] = (int8_t)(int)fma(-rint(v * pinv), p, v);
-            }
+            for (int g = 0; g < TG; ++g)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) {
+                    const double v = (double)acc[i][j][4 * g + b];
+                    Rw[(long)(i * TW + 8 * g + b) * ldr + j * TW] = (int8_t)(int)fma(-rint(v * pinv), p, v);
+                }
+#ifdef EMU_STAMP
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (t == 0 && orig < EMU_STAMP_SLOTS) {
+        unsigned long *st = emu_stamps[orig];
+        st[0] = stamp_c0; st[1] = stamp_c1; st[2] = stamp_r0; st[3] = stamp_r1;
+        st[4] = __builtin_amdgcn_s_memtime(); st[5] = __builtin_amdgcn_s_memrealtime();
+    }
+#endif
 }
 
 // ---- rebuild: C_ij -= X_ij 2^-(sig_i + tau_j), four consecutive columns per thread ----------------------------------------------
@@ -756,20 +849,29 @@ extern "C" int gpx_emu_split_fixed(const double *X, int64_t ldx, int64_t rows, i
     return 0;
 }
 
-extern "C" int gpx_emu_i8_gemm(const int8_t *A, const int8_t *B, int64_t rows, int64_t cols, int64_t K, int nmod, int8_t *R)
+// A: planes of [rows][lda] bytes (lda >= K, a multiple of 16; 256 lda < 2^31: a panel's 32-bit byte offsets), B: dense planes of [cols][K],
+// R: planes of [rows][ldr] bytes (ldr >= cols; any R and ldr: byte stores)
+extern "C" int gpx_emu_i8_gemm_ld(const int8_t *A, int64_t lda, const int8_t *B, int64_t rows, int64_t cols, int64_t K, int nmod, int8_t *R,
+                                  int64_t ldr)
 {
     GPX_TRY(gpx_require_device());
     if (!A || !B || !R || rows <= 0 || cols <= 0 || rows % EMU_BT || cols % EMU_BT || K <= 0 || K % EMU_BK || K >= (1 << 17) || nmod < 1 ||
-        nmod > EMU_MAXL || ((uintptr_t)A | (uintptr_t)B) & 15 || rows / EMU_BT * (cols / EMU_BT) * nmod > INT32_MAX) {
+        nmod > EMU_MAXL || ((uintptr_t)A | (uintptr_t)B) & 15 || rows / EMU_BT * (cols / EMU_BT) * nmod > INT32_MAX || lda < K || lda & 15 ||
+        (EMU_BT - 1) * lda + K >= ((int64_t)1 << 31) || ldr < cols) {
         gpx_set_error("gpx_emu_i8_gemm: bad arguments");
         return GPX_ERR_BAD_ARG;
     }
     const int tm = (int)(rows / EMU_BT), tn = (int)(cols / EMU_BT);
-    hipLaunchKernelGGL(emu_i8_gemm_kernel, dim3((unsigned)(tm * tn * nmod)), dim3(512), 0, 0, A, B, (long)(rows * K), (long)(cols * K), (int)K, R,
-                       (long)cols, (long)(rows * cols), tm, tn, (int)K);
+    hipLaunchKernelGGL(emu_i8_gemm_kernel, dim3((unsigned)(tm * tn * nmod)), dim3(512), 0, 0, A, B, (long)(rows * lda), (long)(cols * K), (int)K, R,
+                       (long)ldr, (long)(rows * ldr), tm, tn, (int)lda);
     GPX_HIP(hipGetLastError());
     GPX_HIP(hipStreamSynchronize(0));
     return 0;
+}
+
+extern "C" int gpx_emu_i8_gemm(const int8_t *A, const int8_t *B, int64_t rows, int64_t cols, int64_t K, int nmod, int8_t *R)
+{
+    return gpx_emu_i8_gemm_ld(A, K, B, rows, cols, K, nmod, R, cols);
 }
 
 __global__ void emu_fill_kernel(int8_t *p, long n, unsigned seed)

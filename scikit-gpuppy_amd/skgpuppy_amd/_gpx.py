@@ -113,6 +113,7 @@ SIGNATURES = {
     "gpx_emu_gemm_nt_sub": (_int, [_dp, _i64, _dp, _i64, _dp, _i64, _i64, _i64, _i64]),
     "gpx_emu_rebuild": (_int, [_dp, _i64, _i64, _int, _dp, _dp, _dp, _i64, _i64, _i64]),
     "gpx_emu_i8_gemm": (_int, [_dp, _dp, _i64, _i64, _i64, _int, _dp]),
+    "gpx_emu_i8_gemm_ld": (_int, [_dp, _i64, _dp, _i64, _i64, _i64, _int, _dp, _i64]),
     "gpx_emu_split": (_int, [_dp, _i64, _i64, _i64, _i64, _int, _int, _dp, _i64, _dp]),
     "gpx_emu_split_fixed": (_int, [_dp, _i64, _i64, _i64, _i64, _int, _int, _dp, _i64, _i64, _dp, _dp]),
     "gpx_emu_trsm_left": (_int, [_hp, _dp, _i64, _i64, _dp, _dp, _i64, ctypes.POINTER(_int)]),
