@@ -272,6 +272,33 @@ int gpx_periodic_predict(gpx_handle *h, const double *xs, int64_t m, double *mea
  * reduction: two calls give the same bits. */
 int gpx_periodic_nll_grad(gpx_handle *h, double *grad_out);
 
+/* ---- MaternCovariance: ARD Matern kernel with nu = 3/2 or 5/2 (nu2 = 2 nu = 3 or 5; anything else: GPX_ERR_BAD_ARG) ----
+ * theta = (log v, log vt, log w_1..d), GaussianCovariance's layout, a host pointer.  With delta = xi - xj, q = sum_k w_k delta_k^2 and
+ * s = sqrt(2 nu q):   nu = 5/2: Kf = v (1 + s + s^2 / 3) exp(-s),   nu = 3/2: Kf = v (1 + s) exp(-s),
+ *   k(xi, xj) = Kf + (vt iff xi == xj in every component, decided on the raw inputs)
+ * in cov_matrix AND cov_matrix_ij, as for every kernel built on the base class -- also a query row that equals a training row; the
+ * prior variance of a query is v + vt.  delta = 0 gives exactly v (+ vt).
+ * gpx_matern_gram: out [n1, n2] = K (deriv = -1) or d K / d theta_deriv (0 <= deriv < 2 + d: Kf | vt on equality | -1/2 w_k delta_k^2 G
+ * with G = (5/3) v (1 + s) exp(-s) resp. 3 v exp(-s)); xj may alias xi.  K_ij and K_ji are the same bits.  n1, n2 >= 1. */
+int gpx_matern_gram(const double *xi, int64_t n1, const double *xj, int64_t n2, int d, const double *theta, int nu2, int deriv, double *out);
+/* GaussianProcess.__init__ with cov = MaternCovariance: K is assembled on the device straight into the factor's buffer, then factored with
+ * gpx_fit's schedule and its single +1e-5 I retry.  The handle answers whatever a gpx_fit_matrix handle answers, gpx_propagate_quadrature_many
+ * and the gpx_matern_* calls below; the entry points that evaluate the GaussianCovariance kernel and the gpx_periodic_* ones return
+ * GPX_ERR_STATE on it, as the gpx_matern_* ones do on every other handle.  gpx_n reports its d. */
+int gpx_matern_fit(const double *x, const double *t_centered, int64_t n, int d, const double *theta, int nu2, void *stream, gpx_handle **out);
+/* estimate_many / estimate: mean_out[m] = kv alpha (WITHOUT meant), var_out[m] = v + vt - kv K^-1 kv^T, kv the cross-covariance with the
+ * +vt on equality, through the routes of gpx_predict.  Host or device pointers; m = 0 is a no-op. */
+int gpx_matern_predict(gpx_handle *h, const double *xs, int64_t m, double *mean_out, double *var_out);
+/* Covariance._d_nll_d_theta: grad_out [2 + d] from ONE pass over the lower half of K^-1 with the kernel recomputed on the fly.
+ * Fixed-order reduction: two calls give the same bits. */
+int gpx_matern_nll_grad(gpx_handle *h, double *grad_out);
+/* gpx_propagate_approx_many / gpx_propagate_dvh_many (same arguments, same results) for a nu = 5/2 handle, whose kernel is twice
+ * differentiable with J_k = -w_k diff_k G and H_kl = (5/3) v exp(-s) [5 (w_k diff_k)(w_l diff_l) - delta_kl w_k (1 + s)], diff = x_i - u.
+ * A nu = 3/2 handle (no Hessian at the origin): GPX_ERR_STATE. */
+int gpx_matern_propagate_approx_many(gpx_handle *h, const double *U, const double *Sigma, int sigma_shared, int64_t b,
+                                     double *mean, double *var, double *sigma2, double *rest);
+int gpx_matern_propagate_dvh_many(gpx_handle *h, const double *U, int64_t b, double *dvh_out /* [b, d] */, double *sigma2_out /* [b], may be NULL */);
+
 /* ---- "next" row f3: Snelson sparse pseudo-input GP (SPGPCovariance, skgpuppy/Covariance.py:692-1019) ----
  * theta = [log v, log vt, log w_1..d] (the GaussianCovariance part of the reference's theta), xb = the m x d
  * pseudo-inputs (the tail of the reference's theta, reshaped).  The fit keeps K_NM, chol(K_M + 1e-5 I),

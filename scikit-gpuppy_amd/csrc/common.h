@@ -124,8 +124,9 @@ struct TriSolver {
 
 // ---- the fitted model held in HBM ------------------------------------------------------------
 // What evaluates a handle's kernel: nothing (the matrix was supplied: gpx_fit_matrix), gram_kernel on xs_w (gpx_fit, gpx_adopt_factor)
-// or periodic_gram_kernel on per->x (gpx_periodic_fit).  Callers ask the handle_* helpers below, not the fields.
-enum class KernelKind { Matrix, Gaussian, Periodic };
+// periodic_gram_kernel on per->x (gpx_periodic_fit) or matern_gram_kernel on mat->x (gpx_matern_fit).  Callers ask the handle_* helpers
+// below, not the fields.
+enum class KernelKind { Matrix, Gaussian, Periodic, Matern };
 struct gpx_handle {
     int device = 0;
     int64_t n = 0, npad = 0, nblk = 0;
@@ -172,6 +173,7 @@ struct gpx_handle {
     double *V = nullptr;        // [ncolV, npad] column-major block of C, J_k, hh_k, tr
     double *KV = nullptr;       // [ncolV, npad] Kinv * V
     struct PeriodicData *per = nullptr;   // gpx_periodic_fit only (periodic.hip): inputs and parameters of the periodic kernel; d stays 0
+    struct MaternData *mat = nullptr;     // gpx_matern_fit only (matern.hip): the same for the Matern kernel, with its nu
     Profiler prof;
 };
 
@@ -200,6 +202,27 @@ constexpr int PER_NC = 3 * PER_KC + 2;           // sums per sweep: S_0, (A_k, B
 // partial [sweeps, npad / 8, PER_NC] scratch, out_dev [sweeps, PER_NC]; sweeps = ceil(d / PER_KC)
 int launch_periodic_nll_grad(const double *Kinv, int64_t ld, int64_t n, int64_t npad, const PeriodicData *pd, const double *alpha,
                              double *partial, double *out_dev, hipStream_t s, Profiler *prof);
+
+// ---- MaternCovariance (matern.hip): ARD Matern with nu = 3/2 or 5/2 -------------------------------------------------------
+// theta = (log v, log vt, log w_1..d).  A Matern handle is, like a periodic one, a matrix handle (d == 0) that keeps what
+// gpx_matern_predict / gpx_matern_nll_grad / gpx_matern_propagate_* evaluate the kernel on.
+struct MaternData {
+    int d = 0, nu2 = 5;       // nu2 = 2 nu: 3 or 5
+    double v = 0, vt = 0;
+    double w[GPX_MAX_D];      // exp(theta)
+    double *x = nullptr;      // [n, d] raw inputs
+    double *xT = nullptr;     // [d, npad] the same k-major (the gradient pass reads a column of K^-1 per lane)
+    double *wdev = nullptr;   // [d] w on the device
+};
+int matern_parse(const double *theta, int d, int nu2, MaternData *out);    // host; GPX_ERR_BAD_ARG with text
+int matern_upload(MaternData *md, const double *x, int64_t n, int64_t npad, hipStream_t s);   // x (host or device) -> md->x, xT, wdev; synchronises
+void matern_release(MaternData *md);
+// out[i][j] = Kf(q_ij) (+ vt where x_i == x_j in every component) (+ add_diag where row == col), q = sum_k w_k delta_k^2, from the raw
+// inputs; lower_only / pad_mode / padding contract as launch_gram.  deriv >= 0: d K / d theta_deriv instead (no add_diag)
+int launch_matern_gram(const double *xi, int64_t n1, const double *xj, int64_t n2, const MaternData *md, double add_diag, int lower_only,
+                       int pad_mode, double *out, int64_t ld, int64_t rows_pad, int64_t cols_pad, hipStream_t s, Profiler *prof, int deriv = -1);
+constexpr int MAT_KC = 8;                        // coordinates per sweep of the gradient pass
+constexpr int MAT_NC = MAT_KC + 2;               // sums per sweep: S_0, A_k of the sweep's k, T
 
 // ---- kernels / host launchers implemented across the .hip files -------------------------------
 int launch_gram(const double *xi_w, int64_t n1, const double *xj_w, int64_t n2, int d, double v, double add_diag,
@@ -444,16 +467,25 @@ int launch_exact_many_finish(const double *Y, const double *H, int64_t npad, con
     } while (0)
 // ---- the one description of a handle's kernel (KernelKind) ----
 static inline bool handle_has_kernel(const gpx_handle *h) { return h->kind != KernelKind::Matrix; }
-static inline int handle_dim(const gpx_handle *h) { return h->kind == KernelKind::Periodic ? h->per->d : h->d; }   // 0: a supplied matrix
-// the training inputs [n, handle_dim] in the form the handle's Gram kernel reads: scaled by sqrt(w) (Gaussian), raw (periodic)
-static inline const double *handle_train_inputs(const gpx_handle *h) { return h->kind == KernelKind::Periodic ? h->per->x : h->xs_w; }
-// launch_gram / launch_periodic_gram with the handle's parameters; xi, xj in the form of handle_train_inputs
+static inline int handle_dim(const gpx_handle *h)   // 0: a supplied matrix
+{
+    return h->kind == KernelKind::Periodic ? h->per->d : h->kind == KernelKind::Matern ? h->mat->d : h->d;
+}
+// the training inputs [n, handle_dim] in the form the handle's Gram kernel reads: scaled by sqrt(w) (Gaussian), raw (periodic, Matern)
+static inline const double *handle_train_inputs(const gpx_handle *h)
+{
+    return h->kind == KernelKind::Periodic ? h->per->x : h->kind == KernelKind::Matern ? h->mat->x : h->xs_w;
+}
+// does the handle's Gram kernel add vt wherever two rows are equal (the prior variance of a query is then v + vt also for its bound)
+static inline bool handle_gram_has_vt(const gpx_handle *h) { return h->kind == KernelKind::Periodic || h->kind == KernelKind::Matern; }
+// launch_gram / launch_periodic_gram / launch_matern_gram with the handle's parameters; xi, xj in the form of handle_train_inputs
 static inline int handle_gram(const gpx_handle *h, const double *xi, int64_t n1, const double *xj, int64_t n2, double add_diag, int lower_only,
                               int pad_mode, double *out, int64_t ld, int64_t rows_pad, int64_t cols_pad, hipStream_t s, Profiler *prof)
 {
     switch (h->kind) {
     case KernelKind::Gaussian: return launch_gram(xi, n1, xj, n2, h->d, h->v, add_diag, lower_only, pad_mode, out, ld, rows_pad, cols_pad, s, prof);
     case KernelKind::Periodic: return launch_periodic_gram(xi, n1, xj, n2, h->per, add_diag, lower_only, pad_mode, out, ld, rows_pad, cols_pad, s, prof);
+    case KernelKind::Matern: return launch_matern_gram(xi, n1, xj, n2, h->mat, add_diag, lower_only, pad_mode, out, ld, rows_pad, cols_pad, s, prof);
     default: gpx_set_error("handle_gram: the handle was built from a supplied matrix"); return GPX_ERR_STATE;
     }
 }
@@ -461,6 +493,7 @@ static inline int handle_gram(const gpx_handle *h, const double *xi, int64_t n1,
 #define NEED_KERNEL(h, what)                                                                                             \
     do {                                                                                                                 \
         if ((h)->kind == KernelKind::Periodic) { gpx_set_error(what ": the handle holds a PeriodicCovariance model (gpx_periodic_fit): use the gpx_periodic_* entry points"); return GPX_ERR_STATE; } \
+        if ((h)->kind == KernelKind::Matern) { gpx_set_error(what ": the handle holds a MaternCovariance model (gpx_matern_fit): use the gpx_matern_* entry points"); return GPX_ERR_STATE; } \
         if (!handle_has_kernel(h)) { gpx_set_error(what ": the handle was built from a supplied matrix (gpx_fit_matrix): no inputs / theta to evaluate the kernel on"); return GPX_ERR_STATE; } \
     } while (0)
 
@@ -491,6 +524,14 @@ struct RowSolve {
 int row_solve_begin(gpx_handle *h, int64_t m, RowSolve &rs, bool bounded = false, bool allow_few = true, int64_t chunk_cap = 0);
 // Zs[0 : mp) <- Z[0 : mp) L^-T (mc real rows, mp = mc rounded up to the tile); red: the fused row sums of tsolve.hip (many rows only)
 int row_solve_run(gpx_handle *h, const RowSolve &rs, int64_t mc, int64_t mp, const GemmReduce *red, bool left = false);
+
+// The chunk loops of gpx_propagate_approx_many and gpx_propagate_dvh_many (propagate_api.hip) for any kernel that has the right-hand
+// sides: build(U_dev, Sigma_dev, sigma_stride, bc, mp) writes the rows of bc inputs into h->Z [mp, npad] (d + 2 rows an input:
+// [C, tr, J_1..J_d]; 2 d + 1: [C, J_1..J_d, H_11..H_dd], no Sigma); the solve, the row reductions and the copies are the loops' own.
+using RowsBuild = std::function<int(const double *, const double *, int64_t, int64_t, int64_t)>;
+int approx_many_run(gpx_handle *h, int d, const double *U, const double *Sigma, int sigma_shared, int64_t b, double *mean, double *var, double *sigma2,
+                    double *rest, const char *what, const RowsBuild &build);
+int dvh_many_run(gpx_handle *h, int d, const double *U, int64_t b, double *dvh_out, double *sigma2_out, const char *what, const RowsBuild &build);
 
 // The predictor's chunk loop on device-resident queries and outputs (predict.hip): begin sizes the chunk as gpx_predict does (bounded rows;
 // a periodic handle: the many-row solver always, and its chunk cap) and takes the query, prior-variance and partial-sum buffers; chunk

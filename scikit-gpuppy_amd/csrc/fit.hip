@@ -179,6 +179,8 @@ extern "C" void gpx_free(gpx_handle *h)
     h->tri.release();
     periodic_release(h->per);
     h->per = nullptr;
+    matern_release(h->mat);
+    h->mat = nullptr;
     if (h->external_factor) { h->L = nullptr; h->Dinv = nullptr; h->diagL = nullptr; }
     double *bufs[] = {h->Ksrc, h->x, h->xs_w, h->sw, h->wdev, h->L, h->Dinv, h->diagL, h->t, h->y, h->alpha, h->Kinv, h->KinvRows, h->Z, h->small, h->V, h->KV};
     for (double *p : bufs)
@@ -237,7 +239,7 @@ static int factor_once(gpx_handle *h, double add_diag, int *info_host)
         return 0;
     };
     // K into the padded factor buffer (lower half, identity in the padding).  A supplied matrix (gpx_fit_matrix) is copied, + jitter on
-    // a retry.  A kernel assembles it there: add_diag = vt + jitter (Gaussian) or the jitter alone (the periodic kernel adds vt itself,
+    // a retry.  A kernel assembles it there: add_diag = vt + jitter (Gaussian) or the jitter alone (the periodic and Matern kernels add vt themselves,
     // wherever two rows are equal).  Beyond one outer panel, and with a chain stream: the first panel's columns now, the rest of the
     // lower half underneath the first panel's diagonal chain.
     const double *x = handle_has_kernel(h) ? handle_train_inputs(h) : nullptr;
@@ -276,24 +278,25 @@ static void setup_lookahead_streams(gpx_handle *h)
 // Kmat != nullptr: the handle of a SUPPLIED covariance matrix (gpx_fit_matrix; n x n, host or device): no inputs, no kernel
 // parameters (d = 0) -- the factor, alpha, K^-1 and the solves work as for any handle, everything that evaluates the kernel does not.
 // pspec != nullptr: a PeriodicCovariance model (gpx_periodic_fit): as a matrix handle (d = 0), but K is assembled on the device from x
-// and the parsed parameters, which the handle keeps (h->per)
+// and the parsed parameters, which the handle keeps (h->per); mspec != nullptr: the same for a MaternCovariance model (h->mat)
 static int make_handle(const double *x, const double *t_centered, int64_t n, int d, const double *theta, void *stream,
-                       const ExternalFactor *ext, gpx_handle **out, const double *Kmat = nullptr, const PeriodicData *pspec = nullptr)
+                       const ExternalFactor *ext, gpx_handle **out, const double *Kmat = nullptr, const PeriodicData *pspec = nullptr,
+                       const MaternData *mspec = nullptr)
 {
     gpx_handle *h = new (std::nothrow) gpx_handle();
     if (!h) { gpx_set_error("out of host memory"); return GPX_ERR_HIP; }
     h->device = gpx_thread_device();
     int rc = 0;
-    if (pspec) {
-        h->v = pspec->v;
-        h->vt = pspec->vt;
+    if (pspec || mspec) {
+        h->v = pspec ? pspec->v : mspec->v;
+        h->vt = pspec ? pspec->vt : mspec->vt;
         d = 0;
     } else if (!Kmat) {
         rc = parse_theta(theta, d, &h->v, &h->vt, h->w);
         if (rc) { delete h; return rc; }
         memcpy(h->theta, theta, sizeof(double) * (d + 2));
     } else d = 0;
-    h->kind = pspec ? KernelKind::Periodic : Kmat ? KernelKind::Matrix : KernelKind::Gaussian;
+    h->kind = pspec ? KernelKind::Periodic : mspec ? KernelKind::Matern : Kmat ? KernelKind::Matrix : KernelKind::Gaussian;
     h->n = n;
     h->d = d;
     h->npad = round_up(n, TILE);
@@ -334,6 +337,10 @@ static int make_handle(const double *x, const double *t_centered, int64_t n, int
         h->per = new (std::nothrow) PeriodicData(*pspec);
         if (!h->per) { gpx_set_error("out of host memory"); return fail(GPX_ERR_HIP); }
         if ((rc = periodic_upload(h->per, x, n, h->npad, s))) return fail(rc);
+    } else if (mspec) {
+        h->mat = new (std::nothrow) MaternData(*mspec);
+        if (!h->mat) { gpx_set_error("out of host memory"); return fail(GPX_ERR_HIP); }
+        if ((rc = matern_upload(h->mat, x, n, h->npad, s))) return fail(rc);
     } else if (Kmat) {
         if ((rc = dalloc(&h->Ksrc, n * n))) return fail(rc);
         FIT_HIP(hipMemcpyAsync(h->Ksrc, Kmat, sizeof(double) * n * n, hipMemcpyDefault, s));
@@ -368,7 +375,7 @@ static int make_handle(const double *x, const double *t_centered, int64_t n, int
             return 0;
         };
         int info = 0;
-        const double diag0 = h->kind == KernelKind::Gaussian ? h->vt : 0.0;   // (a supplied K carries its own diagonal; the periodic Gram adds vt itself)
+        const double diag0 = h->kind == KernelKind::Gaussian ? h->vt : 0.0;   // (a supplied K carries its own diagonal; the periodic and Matern Grams add vt themselves)
         if ((rc = factor(diag0, &info))) return fail(rc);
         if (info > 0) {
             // reference fallback: cholesky(K + 1e-5 I)   (skgpuppy/Covariance.py:180-185)
@@ -434,6 +441,18 @@ extern "C" int gpx_periodic_fit(const double *x, const double *t_centered, int64
     PeriodicData pd;
     GPX_TRY(periodic_parse(theta, d, &pd));
     return make_handle(x, t_centered, n, 0, nullptr, stream, nullptr, out, nullptr, &pd);
+}
+
+// ---- MaternCovariance (nu2 = 2 nu: 3 or 5): K assembled on the device by matern_gram_kernel, everything after it as for every handle ----
+extern "C" int gpx_matern_fit(const double *x, const double *t_centered, int64_t n, int d, const double *theta, int nu2, void *stream,
+                              gpx_handle **out)
+{
+    if (out) *out = nullptr;
+    GPX_TRY(gpx_require_device());
+    if (!x || !t_centered || !out || n < 1) { gpx_set_error("gpx_matern_fit: null pointer or n < 1"); return GPX_ERR_BAD_ARG; }
+    MaternData md;
+    GPX_TRY(matern_parse(theta, d, nu2, &md));
+    return make_handle(x, t_centered, n, 0, nullptr, stream, nullptr, out, nullptr, nullptr, &md);
 }
 
 extern "C" int gpx_n(const gpx_handle *h, int64_t *n, int *d)

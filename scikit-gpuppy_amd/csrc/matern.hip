@@ -1,0 +1,550 @@
+// matern.hip -- MaternCovariance (ARD Matern, nu = 3/2 or 5/2) on the device: Gram / cross-covariance assembly, the one-pass likelihood
+// gradient, and for nu = 5/2 the right-hand-side blocks of the batched Approx and inverse propagation.
+//
+// theta = (log v, log vt, log w_1..d), GaussianCovariance's layout.  With delta = xi - xj, q = sum_k w_k delta_k^2 and s = sqrt(2 nu q)
+//   nu = 5/2: Kf = v (1 + s + s^2 / 3) exp(-s)      nu = 3/2: Kf = v (1 + s) exp(-s)      K = Kf + (vt iff delta == 0 in every component).
+// Every derivative is a polynomial in s times exp(-s) -- with G = (5/3) v (1 + s) exp(-s) (5/2) or 3 v exp(-s) (3/2)
+//   d K / d log w_k = -1/2 w_k delta_k^2 G,      d Kf / d xi_k = -w_k delta_k G       (5/2: d^2 Kf / d xi_k d xi_l below)
+// so nothing divides by s and delta = 0 gives exactly v: sqrt(0) = 0, exp_nonpos(0) = 1.  nu enters as NU2 = 2 nu (3 or 5), a template
+// parameter.  The inputs are read RAW: equality is decided on max |delta|, which scaling by sqrt(w) would not preserve.
+#include <math.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "common.h"
+#include "gram_tile.h"
+
+// the radial factors at q = sum_k w_k delta_k^2: one sqrt and one exp serve all of them
+template <int NU2>
+struct MaternRadial {
+    double s, e;   // sqrt(2 nu q), v exp(-s)
+    __device__ __forceinline__ MaternRadial(double v, double q) : s(sqrt((double)NU2 * q)), e(v * exp_nonpos(-s)) {}
+    __device__ __forceinline__ double kf() const { return NU2 == 5 ? e * fma(s, fma(s, 1.0 / 3.0, 1.0), 1.0) : e * (1.0 + s); }
+    __device__ __forceinline__ double g() const { return NU2 == 5 ? (5.0 / 3.0) * e * (1.0 + s) : 3.0 * e; }
+};
+
+// what the deriv variant writes (the parameter's group; MD_W: its coordinate is a second argument)
+enum { MD_V = 0, MD_VT = 1, MD_W = 2 };
+
+// The pair policy of the Matern kernel on the raw inputs (the frame: gram_tile.h).  Per k and entry: the difference, max |delta| (the
+// equality test) and one product into q with the wave-uniform w_k -- the Gaussian kernel's arithmetic plus one multiply; per entry one
+// sqrt, one exp and the polynomial.  K_ij and K_ji are the same bits: delta changes sign and q is even in it operation by operation.
+// The equality term is part of the entry, not of the frame's diagonal: a query may equal a training row anywhere.
+// DERIV: d K / d theta_j instead of K -- kind (MD_*) and coordinate kd.
+template <int NU2, bool DERIV>
+struct MaternPair {
+    const double *w;   // [d]
+    int d;
+    double v, vt;
+    int kind, kd;
+    // (q and max |delta| of a lane's 16 rows x 2 columns as vector values: PeriodicPair's State explains why)
+    struct State { v16d acc0, acc1, m0, m1; double wk; v2d bk; };
+
+    __device__ __forceinline__ void accumulate(State &st, const double *const (&arow)[16], const double *b_s, int lane, long, int) const
+    {
+        v16d &acc0 = st.acc0, &acc1 = st.acc1, &m0 = st.m0, &m1 = st.m1;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) { acc0[r] = 0.0; acc1[r] = 0.0; m0[r] = 0.0; m1[r] = 0.0; }
+        for (int k = 0; k < d; ++k) {
+            const double wk = w[k];
+            const v2d b = *reinterpret_cast<const v2d *>(&b_s[k * GT_COLS + 2 * lane]);
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const double a = arow[r][k];
+                const double e0 = a - b.x, e1 = a - b.y;
+                m0[r] = fmax(m0[r], fabs(e0));
+                m1[r] = fmax(m1[r], fabs(e1));
+                acc0[r] = fma(wk * e0, e0, acc0[r]);
+                acc1[r] = fma(wk * e1, e1, acc1[r]);
+            }
+        }
+        if (DERIV) {
+            st.wk = w[kd];
+            st.bk = *reinterpret_cast<const v2d *>(&b_s[kd * GT_COLS + 2 * lane]);
+        }
+    }
+    __device__ __forceinline__ double deriv_entry(double q, bool equal, double e, double wk) const
+    {
+        if (kind == MD_VT) return equal ? vt : 0.0;
+        const MaternRadial<NU2> rad(v, q);
+        if (kind == MD_V) return rad.kf();
+        return -(0.5 * wk * e) * e * rad.g();
+    }
+    __device__ __forceinline__ v2d entry(const State &st, const double *const (&arow)[16], int r) const
+    {
+        v2d o;
+        if (DERIV) {
+            const double a = arow[r][kd];
+            o.x = deriv_entry(st.acc0[r], st.m0[r] == 0.0, a - st.bk.x, st.wk);
+            o.y = deriv_entry(st.acc1[r], st.m1[r] == 0.0, a - st.bk.y, st.wk);
+        } else {
+            o.x = MaternRadial<NU2>(v, st.acc0[r]).kf() + (st.m0[r] == 0.0 ? vt : 0.0);
+            o.y = MaternRadial<NU2>(v, st.acc1[r]).kf() + (st.m1[r] == 0.0 ? vt : 0.0);
+        }
+        return o;
+    }
+};
+
+template <int NU2, bool DERIV>
+__global__ __launch_bounds__(256) void matern_gram_kernel(const double *__restrict__ xi, long n1, const double *__restrict__ xj, long n2, int d,
+                                                         const double *__restrict__ w, double v, double vt, double add_diag, int lower_only,
+                                                         int pad_mode, double *__restrict__ out, long ld, int kind, int kd)
+{
+    gram_tile<MaternPair<NU2, DERIV>, !DERIV>(MaternPair<NU2, DERIV>{w, d, v, vt, kind, kd}, xi, n1, xj, n2, d, add_diag, lower_only, pad_mode, out,
+                                              ld);
+}
+
+// the padding contract of out: gram_launch_plan (gram_tile.h)
+int launch_matern_gram(const double *xi, int64_t n1, const double *xj, int64_t n2, const MaternData *md, double add_diag, int lower_only,
+                       int pad_mode, double *out, int64_t ld, int64_t rows_pad, int64_t cols_pad, hipStream_t s, Profiler *prof, int deriv)
+{
+    const int d = md->d;
+    GramLaunch pl;
+    // (a derivative has no diagonal term: identity padding would have no meaning for it, and no caller asks for it)
+    if (!gram_launch_plan(rows_pad, cols_pad, ld, d, lower_only, &pl) || n1 < 1 || n2 < 1 || n1 > rows_pad || n2 > cols_pad || deriv < -1 ||
+        deriv >= 2 + d || (deriv >= 0 && pad_mode == PAD_IDENT) || (md->nu2 != 3 && md->nu2 != 5)) {
+        gpx_set_error("launch_matern_gram: bad shape (n1=%ld n2=%ld rows_pad=%ld cols_pad=%ld ld=%ld d=%d deriv=%d nu2=%d)", (long)n1, (long)n2,
+                      (long)rows_pad, (long)cols_pad, (long)ld, d, deriv, md->nu2);
+        return GPX_ERR_BAD_ARG;
+    }
+    ProfScope ps(prof, s, GPX_K_GRAM, pl.bytes);
+    const double *w = md->wdev;
+    const int kind = deriv < 2 ? deriv : MD_W, kd = deriv < 2 ? 0 : deriv - 2;
+#define MATERN_GRAM(NU2, DERIV, diag)                                                                                                       \
+    hipLaunchKernelGGL((matern_gram_kernel<NU2, DERIV>), pl.grid, dim3(256), pl.lds, s, xi, (long)n1, xj, (long)n2, d, w, md->v, md->vt, diag, \
+                       pl.lower_only, pad_mode, out, (long)ld, kind, kd)
+    if (deriv < 0) {
+        if (md->nu2 == 5) MATERN_GRAM(5, false, add_diag);
+        else MATERN_GRAM(3, false, add_diag);
+    } else {
+        if (md->nu2 == 5) MATERN_GRAM(5, true, 0.0);
+        else MATERN_GRAM(3, true, 0.0);
+    }
+#undef MATERN_GRAM
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Gradient of the negative log likelihood: ONE pass over the j <= i half of K^-1 recomputes the radial factors on the fly and
+// accumulates, with M_ij = Kinv_ij - a_i a_j,
+//   S_0 = sum M Kf,   A_k = sum M G delta_k^2,   T = sum over the pairs with x_i == x_j of M     (T = tr Kinv - a.a without duplicate rows)
+// so that  g_0 = S_0 / 2,  g_1 = vt T / 2,  g_{2+k} = -w_k A_k / 4.
+// The frame is periodic_nll_grad_kernel's: grid.y sweeps of MAT_KC coordinates each (d + 2 accumulators do not fit in registers at
+// d = 64); a sweep forms q over ALL d coordinates in a runtime loop, then the weighted squares of its own coordinates.  A lane owns a
+// column j and reads it from the k-major copy of the inputs (coalesced); the block's 8 rows sit in LDS.
+// partial[sweep][block][MAT_NC]: [0] = S_0, [1 + kk] = A of coordinate sweep MAT_KC + kk, [MAT_KC + 1] = T.
+// ---------------------------------------------------------------------------------------------
+template <int NU2>
+__global__ __launch_bounds__(256) void matern_nll_grad_kernel(const double *__restrict__ Kinv, long ld, long n, long npad, int d,
+                                                             const double *__restrict__ alpha, const double *__restrict__ x,
+                                                             const double *__restrict__ xT, const double *__restrict__ w, double v,
+                                                             double *__restrict__ partial)
+{
+    constexpr int R = 8, KC = MAT_KC, NC = MAT_NC;
+    __shared__ double xs[R][GPX_MAX_D];
+    __shared__ double as[R];
+    __shared__ double red[4][NC];
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const int rb = gridDim.x - 1 - blockIdx.x;
+    const long i0 = (long)rb * R;
+    const int k0 = blockIdx.y * KC;
+    for (int q = t; q < R * GPX_MAX_D; q += 256) {
+        const int r = q / GPX_MAX_D, k = q - r * GPX_MAX_D;
+        xs[r][k] = (k < d && i0 + r < n) ? x[(i0 + r) * d + k] : 0.0;
+    }
+    if (t < R) as[t] = alpha[i0 + t];
+    __syncthreads();
+    double acc[NC];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) acc[c] = 0.0;
+    for (long j = t; j < i0 + R && j < n; j += 256) {
+        const double aj = alpha[j];
+        double q[R], mx[R], wq[R];
+#pragma unroll
+        for (int r = 0; r < R; ++r) { q[r] = 0.0; mx[r] = 0.0; }
+        for (int k = 0; k < d; ++k) {
+            const double wk = w[k];
+            const double xjk = xT[(long)k * npad + j];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const double e = xs[r][k] - xjk;
+                mx[r] = fmax(mx[r], fabs(e));
+                q[r] = fma(wk * e, e, q[r]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const long i = i0 + r;
+            const bool live = i < n && j <= i;
+            const double mij = live ? Kinv[i * ld + j] - as[r] * aj : 0.0;
+            const double m = mij * ((j < i) ? 2.0 : 1.0);
+            const MaternRadial<NU2> rad(v, q[r]);
+            acc[0] = fma(m, rad.kf(), acc[0]);
+            if (live && mx[r] == 0.0) acc[NC - 1] += m;
+            wq[r] = m * rad.g();
+        }
+#pragma unroll
+        for (int kk = 0; kk < KC; ++kk) {
+            const int k = k0 + kk;
+            if (k < d) {
+                const double xjk = xT[(long)k * npad + j];
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    const double e = xs[r][k] - xjk;
+                    acc[1 + kk] = fma(wq[r], e * e, acc[1 + kk]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+        const double s = wave_sum(acc[c]);
+        if (lane == 0) red[wave][c] = s;
+    }
+    __syncthreads();
+    if (t < NC) partial[((long)blockIdx.y * gridDim.x + rb) * NC + t] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+}
+
+// partial [sweeps, npad / 8, MAT_NC] scratch, out_dev [sweeps, MAT_NC]; sweeps = ceil(d / MAT_KC)
+static int launch_matern_nll_grad(const double *Kinv, int64_t ld, int64_t n, int64_t npad, const MaternData *md, const double *alpha, double *partial,
+                                  double *out_dev, hipStream_t s, Profiler *prof)
+{
+    const unsigned nblk = (unsigned)(npad / 8);
+    const int sweeps = (md->d + MAT_KC - 1) / MAT_KC;
+    {
+        ProfScope ps(prof, s, GPX_K_QUAD, 4.0 * (double)npad * (double)npad * sweeps);
+        const dim3 grid(nblk, (unsigned)sweeps);
+        if (md->nu2 == 5)
+            hipLaunchKernelGGL(matern_nll_grad_kernel<5>, grid, dim3(256), 0, s, Kinv, (long)ld, (long)n, (long)npad, md->d, alpha,
+                               (const double *)md->x, (const double *)md->xT, (const double *)md->wdev, md->v, partial);
+        else
+            hipLaunchKernelGGL(matern_nll_grad_kernel<3>, grid, dim3(256), 0, s, Kinv, (long)ld, (long)n, (long)npad, md->d, alpha,
+                               (const double *)md->x, (const double *)md->xT, (const double *)md->wdev, md->v, partial);
+        GPX_HIP(hipGetLastError());
+    }
+    for (int y = 0; y < sweeps; ++y) GPX_TRY(launch_sum_columns(partial + (int64_t)y * nblk * MAT_NC, nblk, MAT_NC, out_dev + y * MAT_NC, s));
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Batched Approx and inverse propagation, nu = 5/2: the build kernels of approx_build_many_kernel / dvh_build_many_kernel (propagate.hip)
+// with the Matern kernel's three radial factors in place of the Gaussian kernel's single c.  With diff = x_i - u, a = w . diff,
+// q = a . diff, s = sqrt(5 q), e = v exp(-s):
+//   C = e (1 + s + s^2 / 3) (+vt iff x_i == u elementwise)     J_k = -a_k G,  G = (5/3) e (1 + s)
+//   H_kl = (5/3) e [5 a_k a_l - delta_kl w_k (1 + s)],   tr(H Sigma) = (5/3) e [5 a^T Sigma a - (1 + s) sum_k w_k Sigma_kk]
+// DVH = false: row b (d + 2) + r of Z is [C, tr, J_1..J_d]; DVH = true: row b (2 d + 1) + r is [C, J_1..J_d, H_11..H_dd] (no Sigma).
+// Same workgroup (128 columns of x k-major in LDS, AB_INPUTS inputs, four per wave, u / w / Sigma wave-uniform), 16-byte stores, one
+// exp and one sqrt per (input, column).  DR > 0: d <= DR and a stays in registers; DR = 0: any d, recomputed from the LDS tile.
+// ---------------------------------------------------------------------------------------------
+constexpr int MB_COLS = 128;
+constexpr int MB_INPUTS = 16;
+
+template <int DR, bool DVH>
+__global__ __launch_bounds__(256) void matern52_build_many_kernel(const double *__restrict__ x, long n, long npad, int d,
+                                                                 const double *__restrict__ U, const double *__restrict__ Sigma,
+                                                                 long sigma_stride, long nb, const double *__restrict__ w, double v, double vt,
+                                                                 double *__restrict__ Z)
+{
+    extern __shared__ __attribute__((aligned(16))) double mb_smem[];
+    double *x_s = mb_smem;   // [d][128] raw inputs of the tile's columns, k-major
+    const int t = threadIdx.x;
+    const long col0 = (long)blockIdx.x * MB_COLS;
+    for (int e = t; e < MB_COLS * d; e += 256) {
+        const int c = e & (MB_COLS - 1), k = e >> 7;
+        const long gc = col0 + c;
+        x_s[k * MB_COLS + c] = (gc < n) ? x[gc * d + k] : 0.0;
+    }
+    __syncthreads();
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
+    const long c = col0 + 2 * lane;
+    const bool in0 = c < n, in1 = c + 1 < n;
+    const long nrow = DVH ? 2 * d + 1 : d + 2;
+    const int jrow = DVH ? 1 : 2;   // first row of J
+    for (int j = 0; j < MB_INPUTS / 4; ++j) {
+        const long b = (long)blockIdx.y * MB_INPUTS + 4 * j + wave;   // wave-uniform
+        if (b >= nb) break;
+        const double *u = U + b * d;
+        double *zrow = Z + b * nrow * npad + c;
+        double wd0[DR > 0 ? DR : 1], wd1[DR > 0 ? DR : 1];
+        double q0 = 0.0, q1 = 0.0;
+        bool same0 = true, same1 = true;
+        if constexpr (DR > 0) {
+#pragma unroll
+            for (int k = 0; k < DR; ++k) {
+                wd0[k] = 0.0; wd1[k] = 0.0;
+                if (k < d) {
+                    const v2d xv = *reinterpret_cast<const v2d *>(&x_s[k * MB_COLS + 2 * lane]);
+                    const double uk = u[k], wk = w[k];
+                    const double d0 = xv.x - uk, d1 = xv.y - uk;
+                    same0 = same0 && (xv.x == uk);
+                    same1 = same1 && (xv.y == uk);
+                    wd0[k] = wk * d0; wd1[k] = wk * d1;
+                    q0 = fma(wd0[k], d0, q0);
+                    q1 = fma(wd1[k], d1, q1);
+                }
+            }
+        } else {
+            for (int k = 0; k < d; ++k) {
+                const v2d xv = *reinterpret_cast<const v2d *>(&x_s[k * MB_COLS + 2 * lane]);
+                const double uk = u[k], wk = w[k];
+                const double d0 = xv.x - uk, d1 = xv.y - uk;
+                same0 = same0 && (xv.x == uk);
+                same1 = same1 && (xv.y == uk);
+                q0 = fma(wk * d0, d0, q0);
+                q1 = fma(wk * d1, d1, q1);
+            }
+        }
+        // columns past n: every row of the block is zero there
+        const MaternRadial<5> r0(in0 ? v : 0.0, q0), r1(in1 ? v : 0.0, q1);
+        const double c0 = r0.kf(), c1 = r1.kf(), g0 = r0.g(), g1 = r1.g();
+        const double f0 = (5.0 / 3.0) * r0.e, f1 = (5.0 / 3.0) * r1.e;   // H = f [5 a a^T - diag(w) (1 + s)]
+        const double p0 = 1.0 + r0.s, p1 = 1.0 + r1.s;
+        v2d o;
+        o.x = (in0 && same0) ? c0 + vt : c0;
+        o.y = (in1 && same1) ? c1 + vt : c1;
+        *reinterpret_cast<v2d *>(zrow) = o;
+        double s0 = 0.0, s1 = 0.0, wdiag = 0.0;
+        if constexpr (DR > 0) {
+#pragma unroll
+            for (int a = 0; a < DR; ++a) {
+                if (a < d) {
+                    v2d jk;
+                    jk.x = -wd0[a] * g0; jk.y = -wd1[a] * g1;
+                    *reinterpret_cast<v2d *>(zrow + (long)(jrow + a) * npad) = jk;
+                    if constexpr (DVH) {
+                        const double wa = w[a];
+                        v2d hk;
+                        hk.x = f0 * fma(5.0 * wd0[a], wd0[a], -wa * p0); hk.y = f1 * fma(5.0 * wd1[a], wd1[a], -wa * p1);
+                        *reinterpret_cast<v2d *>(zrow + (long)(1 + d + a) * npad) = hk;
+                    } else {
+                        const double *S = Sigma + b * sigma_stride;
+                        double t0 = 0.0, t1 = 0.0;
+#pragma unroll
+                        for (int e = 0; e < DR; ++e)
+                            if (e < d) {
+                                const double sg = S[a * d + e];
+                                t0 = fma(sg, wd0[e], t0);
+                                t1 = fma(sg, wd1[e], t1);
+                            }
+                        s0 = fma(wd0[a], t0, s0);
+                        s1 = fma(wd1[a], t1, s1);
+                        wdiag = fma(w[a], S[a * d + a], wdiag);
+                    }
+                }
+            }
+        } else {
+            for (int a = 0; a < d; ++a) {
+                const v2d xa = *reinterpret_cast<const v2d *>(&x_s[a * MB_COLS + 2 * lane]);
+                const double wa = w[a], ua = u[a];
+                const double a0 = wa * (xa.x - ua), a1 = wa * (xa.y - ua);
+                v2d jk;
+                jk.x = -a0 * g0; jk.y = -a1 * g1;
+                *reinterpret_cast<v2d *>(zrow + (long)(jrow + a) * npad) = jk;
+                if constexpr (DVH) {
+                    v2d hk;
+                    hk.x = f0 * fma(5.0 * a0, a0, -wa * p0); hk.y = f1 * fma(5.0 * a1, a1, -wa * p1);
+                    *reinterpret_cast<v2d *>(zrow + (long)(1 + d + a) * npad) = hk;
+                } else {
+                    const double *S = Sigma + b * sigma_stride;
+                    double t0 = 0.0, t1 = 0.0;
+                    for (int e = 0; e < d; ++e) {
+                        const v2d xv = *reinterpret_cast<const v2d *>(&x_s[e * MB_COLS + 2 * lane]);
+                        const double sg = S[a * d + e], ue = u[e], we = w[e];
+                        t0 = fma(sg, we * (xv.x - ue), t0);
+                        t1 = fma(sg, we * (xv.y - ue), t1);
+                    }
+                    s0 = fma(a0, t0, s0);
+                    s1 = fma(a1, t1, s1);
+                    wdiag = fma(wa, S[a * d + a], wdiag);
+                }
+            }
+        }
+        if constexpr (!DVH) {
+            o.x = f0 * fma(5.0, s0, -p0 * wdiag);
+            o.y = f1 * fma(5.0, s1, -p1 * wdiag);
+            *reinterpret_cast<v2d *>(zrow + npad) = o;
+        }
+    }
+}
+
+// Z [rows_pad, npad]: rows [0, nb nrow) written by the kernel (every column, zeros from n on), the rest of the last 128-row tile cleared
+static int launch_matern52_build_many(bool dvh, const double *x, int64_t n, int64_t npad, int d, const double *U_dev, const double *Sigma_dev,
+                                      int64_t sigma_stride, int64_t nb, int64_t rows_pad, const double *w_dev, double v, double vt, double *Z,
+                                      hipStream_t s, Profiler *prof)
+{
+    if (nb <= 0) return 0;
+    const int64_t rows = nb * (dvh ? 2 * d + 1 : d + 2);
+    if (npad % MB_COLS || rows > rows_pad || d < 1 || d > GPX_MAX_D) { gpx_set_error("matern52_build_many: bad block shape"); return GPX_ERR_BAD_ARG; }
+    ProfScope ps(prof, s, GPX_K_GRAM, 8.0 * (double)rows_pad * (double)npad);
+    if (rows_pad > rows) GPX_HIP(hipMemsetAsync(Z + rows * npad, 0, sizeof(double) * (rows_pad - rows) * npad, s));
+    const dim3 grid((unsigned)(npad / MB_COLS), (unsigned)((nb + MB_INPUTS - 1) / MB_INPUTS));
+    const size_t lds = sizeof(double) * MB_COLS * d;
+#define MATERN_BUILD(DR, DVH)                                                                                                                  \
+    hipLaunchKernelGGL((matern52_build_many_kernel<DR, DVH>), grid, dim3(256), lds, s, x, (long)n, (long)npad, d, U_dev, Sigma_dev, (long)sigma_stride, \
+                       (long)nb, w_dev, v, vt, Z)
+    if (dvh) {
+        if (d <= 8) MATERN_BUILD(8, true);
+        else MATERN_BUILD(0, true);
+    } else {
+        if (d <= 8) MATERN_BUILD(8, false);
+        else MATERN_BUILD(0, false);
+    }
+#undef MATERN_BUILD
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// ---- parameters and inputs of a Matern model ----------------------------------------------------------------------
+int matern_parse(const double *theta, int d, int nu2, MaternData *out)
+{
+    if (nu2 != 3 && nu2 != 5) {
+        gpx_set_error("matern kernel: nu2 = 2 nu = %d (3 or 5 supported)", nu2);
+        return GPX_ERR_BAD_ARG;
+    }
+    if (!theta || d < 1 || d > GPX_MAX_D) {
+        gpx_set_error("matern kernel: bad theta / d=%d (1..%d supported)", d, GPX_MAX_D);
+        return GPX_ERR_BAD_ARG;
+    }
+    out->d = d;
+    out->nu2 = nu2;
+    out->v = exp(theta[0]);
+    out->vt = exp(theta[1]);   // theta[1] = -inf gives vt = 0
+    if (!(out->v > 0.0) || !isfinite(out->v) || !isfinite(out->vt)) {
+        gpx_set_error("matern kernel: theta gives v=%g vt=%g", out->v, out->vt);
+        return GPX_ERR_BAD_ARG;
+    }
+    for (int k = 0; k < d; ++k) {
+        out->w[k] = exp(theta[2 + k]);
+        if (!(out->w[k] >= 0.0) || !isfinite(out->w[k])) {
+            gpx_set_error("matern kernel: theta gives w[%d]=%g", k, out->w[k]);
+            return GPX_ERR_BAD_ARG;
+        }
+    }
+    return 0;
+}
+
+__global__ __launch_bounds__(256) void matern_transpose_kernel(const double *__restrict__ x, long n, long npad, int d, double *__restrict__ xT)
+{
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= npad * d) return;
+    const long k = e / npad, j = e - k * npad;
+    xT[e] = j < n ? x[j * d + k] : 0.0;
+}
+
+int matern_upload(MaternData *md, const double *x, int64_t n, int64_t npad, hipStream_t s)
+{
+    const int d = md->d;
+    GPX_TRY(dalloc(&md->wdev, d));
+    GPX_TRY(dalloc(&md->x, n * d));
+    GPX_TRY(dalloc(&md->xT, npad * d));
+    GPX_HIP(hipMemcpyAsync(md->wdev, md->w, sizeof(double) * d, hipMemcpyHostToDevice, s));
+    GPX_HIP(hipMemcpyAsync(md->x, x, sizeof(double) * n * d, hipMemcpyDefault, s));
+    hipLaunchKernelGGL(matern_transpose_kernel, dim3((unsigned)((npad * d + 255) / 256)), dim3(256), 0, s, (const double *)md->x, (long)n, (long)npad,
+                       d, md->xT);
+    GPX_HIP(hipGetLastError());
+    GPX_HIP(hipStreamSynchronize(s));   // md->w may be a caller's stack object
+    return 0;
+}
+
+void matern_release(MaternData *md)
+{
+    if (!md) return;
+    for (double *p : {md->x, md->xT, md->wdev})
+        if (p) dfree(p);
+    delete md;
+}
+
+// ---- C-ABI ---------------------------------------------------------------------------------------------------------
+#define NEED_MATERN(h, what)                                                                                   \
+    do {                                                                                                       \
+        if ((h)->kind != KernelKind::Matern) { gpx_set_error(what ": not a gpx_matern_fit handle"); return GPX_ERR_STATE; } \
+    } while (0)
+
+extern "C" int gpx_matern_gram(const double *xi, int64_t n1, const double *xj, int64_t n2, int d, const double *theta, int nu2, int deriv,
+                               double *out)
+{
+    GPX_TRY(gpx_require_device());
+    if (!xi || !xj || !out || n1 < 1 || n2 < 1) { gpx_set_error("gpx_matern_gram: null pointer or n < 1"); return GPX_ERR_BAD_ARG; }
+    MaternData md;
+    GPX_TRY(matern_parse(theta, d, nu2, &md));
+    if (deriv < -1 || deriv >= 2 + d) { gpx_set_error("gpx_matern_gram: deriv=%d (-1 .. %d)", deriv, 1 + d); return GPX_ERR_BAD_ARG; }
+    const int64_t rp = round_up(n1, TILE), cp = round_up(n2, TILE);
+    hipStream_t s = nullptr;
+    Scratch sc(s);
+    double *a = nullptr, *b = nullptr, *o = nullptr, *w = nullptr;
+    // (the parameters through the call's own scratch: nothing of md outlives the call)
+    GPX_TRY(sc.take(&w, d));
+    GPX_HIP(hipMemcpy(w, md.w, sizeof(double) * d, hipMemcpyHostToDevice));
+    md.wdev = w;
+    GPX_TRY(sc.take(&a, n1 * d));
+    GPX_HIP(hipMemcpy(a, xi, sizeof(double) * n1 * d, hipMemcpyDefault));
+    if (xj == xi && n1 == n2) b = a;
+    else {
+        GPX_TRY(sc.take(&b, n2 * d));
+        GPX_HIP(hipMemcpy(b, xj, sizeof(double) * n2 * d, hipMemcpyDefault));
+    }
+    GPX_TRY(sc.take(&o, rp * cp));
+    GPX_TRY(launch_matern_gram(a, n1, b, n2, &md, 0.0, 0, PAD_ZERO, o, cp, rp, cp, s, nullptr, deriv));
+    GPX_HIP(hipMemcpy2D(out, sizeof(double) * n2, o, sizeof(double) * cp, sizeof(double) * n2, n1, hipMemcpyDefault));
+    return 0;
+}
+
+// d nll / d theta [2 + d] at the handle's theta
+extern "C" int gpx_matern_nll_grad(gpx_handle *h, double *grad_out)
+{
+    CHECK_H(h);
+    NEED_MATERN(h, "gpx_matern_nll_grad");
+    if (!grad_out) { gpx_set_error("null argument"); return GPX_ERR_BAD_ARG; }
+    GPX_TRY(ensure_kinv(h));
+    const MaternData *md = h->mat;
+    const int d = md->d, sweeps = (d + MAT_KC - 1) / MAT_KC;
+    Scratch sc(h->stream);
+    double *buf = nullptr;
+    const int64_t nb = h->npad / 8;
+    GPX_TRY(sc.take(&buf, (nb + 1) * sweeps * MAT_NC));
+    double *outd = buf + nb * sweeps * MAT_NC;
+    GPX_TRY(launch_matern_nll_grad(h->Kinv, h->npad, h->n, h->npad, md, h->alpha, buf, outd, h->stream, &h->prof));
+    double o[(GPX_MAX_D / MAT_KC) * MAT_NC];
+    GPX_HIP(hipMemcpyAsync(o, outd, sizeof(double) * sweeps * MAT_NC, hipMemcpyDeviceToHost, h->stream));
+    GPX_HIP(hipStreamSynchronize(h->stream));
+    std::vector<double> g(2 + d);
+    g[0] = 0.5 * o[0];                       // d K / d theta_0 = Kf
+    g[1] = 0.5 * md->vt * o[MAT_NC - 1];     // vt on equality
+    for (int k = 0; k < d; ++k) g[2 + k] = -0.25 * md->w[k] * o[(k / MAT_KC) * MAT_NC + 1 + k % MAT_KC];   // -1/2 w_k delta_k^2 G
+    GPX_HIP(hipMemcpy(grad_out, g.data(), sizeof(double) * (2 + d), hipMemcpyDefault));
+    return 0;
+}
+
+#define NEED_MATERN52(h, what)                                                                                                              \
+    do {                                                                                                                                    \
+        NEED_MATERN(h, what);                                                                                                               \
+        if ((h)->mat->nu2 != 5) { gpx_set_error(what ": nu = 3/2 has no Hessian at the origin: the fused propagation serves nu = 5/2 alone"); return GPX_ERR_STATE; } \
+    } while (0)
+
+// propagate_GA_many with cov = MaternCovariance(2.5): gpx_propagate_approx_many's loop on this kernel's right-hand sides
+extern "C" int gpx_matern_propagate_approx_many(gpx_handle *h, const double *U, const double *Sigma, int sigma_shared, int64_t b, double *mean,
+                                                double *var, double *sigma2, double *rest)
+{
+    CHECK_H(h);
+    NEED_MATERN52(h, "gpx_matern_propagate_approx_many");
+    const MaternData *md = h->mat;
+    return approx_many_run(h, md->d, U, Sigma, sigma_shared, b, mean, var, sigma2, rest, "gpx_matern_propagate_approx_many",
+                           [&](const double *ud, const double *sd, int64_t sstride, int64_t bc, int64_t mp) -> int {
+                               return launch_matern52_build_many(false, md->x, h->n, h->npad, md->d, ud, sd, sstride, bc, mp, md->wdev, md->v, md->vt, h->Z,
+                                                                 h->stream, &h->prof);
+                           });
+}
+
+// get_best_solution_many's dvh (and sigma2) with cov = MaternCovariance(2.5): gpx_propagate_dvh_many's loop
+extern "C" int gpx_matern_propagate_dvh_many(gpx_handle *h, const double *U, int64_t b, double *dvh_out, double *sigma2_out)
+{
+    CHECK_H(h);
+    NEED_MATERN52(h, "gpx_matern_propagate_dvh_many");
+    const MaternData *md = h->mat;
+    return dvh_many_run(h, md->d, U, b, dvh_out, sigma2_out, "gpx_matern_propagate_dvh_many",
+                        [&](const double *ud, const double *, int64_t, int64_t bc, int64_t mp) -> int {
+                            return launch_matern52_build_many(true, md->x, h->n, h->npad, md->d, ud, nullptr, 0, bc, mp, md->wdev, md->v, md->vt, h->Z,
+                                                              h->stream, &h->prof);
+                        });
+}

@@ -56,7 +56,8 @@ int row_solve_run(gpx_handle *h, const RowSolve &rs, int64_t mc, int64_t mp, con
     return trsm_right_lt_squares(h->Z, rs.Zs, h->npad, mp, &h->tri, 0, h->tri.P, h->stream, &h->prof, red, rs.emu);
 }
 
-// The chunk loop behind gpx_predict / gpx_predict_kv / gpx_periodic_predict and gpx_propagate_quadrature_many (PredictRun: common.h).
+// The chunk loop behind gpx_predict / gpx_predict_kv / gpx_periodic_predict / gpx_matern_predict and gpx_propagate_quadrature_many
+// (PredictRun: common.h).
 // from_x: the cross-covariance rows come from the Gram kernel on queries that the caller's load leaves on the device in pr.xq; otherwise
 // load fills h->Z with the caller's rows kv [m, n] and pr.kd with the prior variance of each query (the diagonal of cov_matrix(x_star),
 // GaussianProcess.py:75).
@@ -64,6 +65,8 @@ int row_solve_run(gpx_handle *h, const RowSolve &rs, int64_t mc, int64_t mp, con
 // v + vt.  That call promises a result that does not depend on the query's place in the batch or on the chunking: always the many-row
 // solver and the stand-alone row reduction (the few-vector solver and the reduction fused into a slab's last product sum in other
 // orders), chunks of at most GPX_PERIODIC_CHUNK rows (read at every call; default: the solver's own cap).
+// A Matern handle: the rows come from matern_gram_kernel, +vt on equality included, through the routes of a Gaussian handle; the
+// row bound of the left-looking solve is sqrt(v + vt) for both kinds whose Gram adds vt itself (handle_gram_has_vt).
 int predict_run_begin(gpx_handle *h, bool from_x, int64_t m, PredictRun &pr)
 {
     pr.from_x = from_x;
@@ -124,7 +127,7 @@ int predict_run_chunk(gpx_handle *h, PredictRun &pr, int64_t m0, int64_t mc, con
     return emu_left_guarded(rs.use_left, [&](bool left, int *status) -> int {
         GPX_TRY(fill());
         if (left) {
-            GPX_TRY(launch_row_bounds(from_x ? nullptr : kd, pr.periodic ? h->v + h->vt : h->v, mc, rs.left.bound, s));
+            GPX_TRY(launch_row_bounds(from_x ? nullptr : kd, handle_gram_has_vt(h) ? h->v + h->vt : h->v, mc, rs.left.bound, s));
             GPX_TRY(emu_left_begin(rs.left, rs.left.bound, mc, s));
         }
         GPX_TRY(solve(left));
@@ -188,6 +191,17 @@ extern "C" int gpx_periodic_predict(gpx_handle *h, const double *xs, int64_t m, 
     CHECK_H(h);
     if (h->kind != KernelKind::Periodic) { gpx_set_error("gpx_periodic_predict: not a gpx_periodic_fit handle"); return GPX_ERR_STATE; }
     if (m < 0 || (m > 0 && (!xs || !mean_out || !var_out))) { gpx_set_error("gpx_periodic_predict: bad arguments"); return GPX_ERR_BAD_ARG; }
+    if (m == 0) return 0;
+    return predict_common(h, xs, nullptr, nullptr, m, mean_out, var_out);
+}
+
+// estimate_many / estimate with cov = MaternCovariance: the rows come from matern_gram_kernel with the +vt on equality, k = v + vt for
+// every query (also as the row bound of the left-looking solve); the routes are gpx_predict's; mean WITHOUT meant
+extern "C" int gpx_matern_predict(gpx_handle *h, const double *xs, int64_t m, double *mean_out, double *var_out)
+{
+    CHECK_H(h);
+    if (h->kind != KernelKind::Matern) { gpx_set_error("gpx_matern_predict: not a gpx_matern_fit handle"); return GPX_ERR_STATE; }
+    if (m < 0 || (m > 0 && (!xs || !mean_out || !var_out))) { gpx_set_error("gpx_matern_predict: bad arguments"); return GPX_ERR_BAD_ARG; }
     if (m == 0) return 0;
     return predict_common(h, xs, nullptr, nullptr, m, mean_out, var_out);
 }

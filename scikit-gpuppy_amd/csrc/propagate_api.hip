@@ -169,15 +169,13 @@ extern "C" int gpx_propagate_approx(gpx_handle *h, const double *u, const double
 // gpx_predict.  With K = L L^T, y = L^-1 t and z_v = L^-1 v every sum of gpx_propagate_approx is a row product of the solved block:
 // beta.v = z_v.y, v.Kinv v = |z_v|^2, tr.Kinv C = z_tr.z_C.  No K^-1, no use of the handle's single-u cache, one synchronisation
 // per chunk; an input never straddles two chunks.
-extern "C" int gpx_propagate_approx_many(gpx_handle *h, const double *U, const double *Sigma, int sigma_shared, int64_t b,
-                                         double *mean, double *var, double *sigma2, double *rest)
+int approx_many_run(gpx_handle *h, int d, const double *U, const double *Sigma, int sigma_shared, int64_t b, double *mean, double *var, double *sigma2,
+                    double *rest, const char *what, const RowsBuild &build)
 {
-    CHECK_H(h);
-    NEED_KERNEL(h, "gpx_propagate_approx_many");
-    if (b < 0 || (b > 0 && (!U || !Sigma || !mean || !var))) { gpx_set_error("gpx_propagate_approx_many: bad arguments"); return GPX_ERR_BAD_ARG; }
+    if (b < 0 || (b > 0 && (!U || !Sigma || !mean || !var))) { gpx_set_error("%s: bad arguments", what); return GPX_ERR_BAD_ARG; }
     if (b == 0) return 0;
     hipStream_t s = h->stream;
-    const int d = h->d, nrow = d + 2;
+    const int nrow = d + 2;
     RowSolve rs(s);
     GPX_TRY(row_solve_begin(h, b * nrow, rs));
     const int64_t bchunk = rs.chunk / nrow;           // inputs per chunk (chunk >= 128 > d + 2)
@@ -196,7 +194,7 @@ extern "C" int gpx_propagate_approx_many(gpx_handle *h, const double *U, const d
         e = hipMemcpyAsync(ud, U + b0 * d, sizeof(double) * bc * d, hipMemcpyDefault, s);
         if (e == hipSuccess && !sigma_shared) e = hipMemcpyAsync(sd, Sigma + b0 * d * d, sizeof(double) * bc * d * d, hipMemcpyDefault, s);
         if (e != hipSuccess) { gpx_set_error("copy U / Sigma failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
-        if ((rc = launch_approx_build_many(h->x, h->n, h->npad, d, ud, sd, sstride, bc, mp, h->wdev, h->v, h->vt, h->Z, s, &h->prof))) break;
+        if ((rc = build(ud, sd, sstride, bc, mp))) break;
         if ((rc = row_solve_run(h, rs, mc, mp, nullptr))) break;
         if ((rc = launch_approx_reduce_many(rs.Zs, h->npad, d, h->y, sd, sstride, bc, h->v + h->vt, od, bchunk, s, &h->prof))) break;
         e = hipMemcpyAsync(mean + b0, od, sizeof(double) * bc, hipMemcpyDefault, s);
@@ -207,6 +205,18 @@ extern "C" int gpx_propagate_approx_many(gpx_handle *h, const double *U, const d
         if (e != hipSuccess) { gpx_set_error("propagate copy-out failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
     }
     return rc;
+}
+
+extern "C" int gpx_propagate_approx_many(gpx_handle *h, const double *U, const double *Sigma, int sigma_shared, int64_t b,
+                                         double *mean, double *var, double *sigma2, double *rest)
+{
+    CHECK_H(h);
+    NEED_KERNEL(h, "gpx_propagate_approx_many");
+    return approx_many_run(h, h->d, U, Sigma, sigma_shared, b, mean, var, sigma2, rest, "gpx_propagate_approx_many",
+                           [&](const double *ud, const double *sd, int64_t sstride, int64_t bc, int64_t mp) -> int {
+                               return launch_approx_build_many(h->x, h->n, h->npad, h->d, ud, sd, sstride, bc, mp, h->wdev, h->v, h->vt, h->Z, h->stream,
+                                                               &h->prof);
+                           });
 }
 
 // Row-sharded form of the Approx propagation (last row): the 4 + 2 d sums of gpx_propagate_approx restricted to
@@ -318,18 +328,16 @@ extern "C" int gpx_propagate_dvh(gpx_handle *h, const double *u, double *dvh_out
 // loop of gpx_propagate_approx_many.  With y = L^-1 t and z_v = L^-1 v the three sums of gpx_propagate_dvh are row products of the solved
 // block: J_k.Kinv J_k = |z_Jk|^2, beta.J_k = z_Jk.y, (Kinv C).H_kk = z_C.z_Hkk; sigma2 = (v + vt) - |z_C|^2.  No K^-1, no use of the handle's
 // single-u cache (have_u, V, KV), one synchronisation per chunk; an input never straddles two chunks.
-extern "C" int gpx_propagate_dvh_many(gpx_handle *h, const double *U, int64_t b, double *dvh_out, double *sigma2_out)
+int dvh_many_run(gpx_handle *h, int d, const double *U, int64_t b, double *dvh_out, double *sigma2_out, const char *what, const RowsBuild &build)
 {
-    CHECK_H(h);
-    NEED_KERNEL(h, "gpx_propagate_dvh_many");
-    if (b < 0 || (b > 0 && (!U || !dvh_out))) { gpx_set_error("gpx_propagate_dvh_many: bad arguments"); return GPX_ERR_BAD_ARG; }
+    if (b < 0 || (b > 0 && (!U || !dvh_out))) { gpx_set_error("%s: bad arguments", what); return GPX_ERR_BAD_ARG; }
     if (b == 0) return 0;
     hipStream_t s = h->stream;
-    const int d = h->d, nrow = 2 * d + 1;
+    const int nrow = 2 * d + 1;
     RowSolve rs(s);
     GPX_TRY(row_solve_begin(h, b * nrow, rs));
     const int64_t bchunk = rs.chunk / nrow;           // inputs per chunk
-    if (bchunk < 1) { gpx_set_error("gpx_propagate_dvh_many: a chunk of %ld rows holds no input of %d rows", (long)rs.chunk, nrow); return GPX_ERR_STATE; }
+    if (bchunk < 1) { gpx_set_error("%s: a chunk of %ld rows holds no input of %d rows", what, (long)rs.chunk, nrow); return GPX_ERR_STATE; }
     double *ud = nullptr, *od = nullptr;
     int rc = 0;
     GPX_TRY(rs.sc.take(&ud, bchunk * d));
@@ -339,7 +347,7 @@ extern "C" int gpx_propagate_dvh_many(gpx_handle *h, const double *U, int64_t b,
         const int64_t bc = std::min<int64_t>(bchunk, b - b0), mc = bc * nrow, mp = round_up(mc, TILE);
         hipError_t e = hipMemcpyAsync(ud, U + b0 * d, sizeof(double) * bc * d, hipMemcpyDefault, s);
         if (e != hipSuccess) { gpx_set_error("copy U failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
-        if ((rc = launch_dvh_build_many(h->x, h->n, h->npad, d, ud, bc, mp, h->wdev, h->v, h->vt, h->Z, s, &h->prof))) break;
+        if ((rc = build(ud, nullptr, 0, bc, mp))) break;
         if ((rc = row_solve_run(h, rs, mc, mp, nullptr))) break;
         if ((rc = launch_dvh_reduce_many(rs.Zs, h->npad, d, h->y, bc, h->v + h->vt, od, s2d, s, &h->prof))) break;
         e = hipMemcpyAsync(dvh_out + b0 * d, od, sizeof(double) * bc * d, hipMemcpyDefault, s);
@@ -348,6 +356,16 @@ extern "C" int gpx_propagate_dvh_many(gpx_handle *h, const double *U, int64_t b,
         if (e != hipSuccess) { gpx_set_error("propagate copy-out failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
     }
     return rc;
+}
+
+extern "C" int gpx_propagate_dvh_many(gpx_handle *h, const double *U, int64_t b, double *dvh_out, double *sigma2_out)
+{
+    CHECK_H(h);
+    NEED_KERNEL(h, "gpx_propagate_dvh_many");
+    return dvh_many_run(h, h->d, U, b, dvh_out, sigma2_out, "gpx_propagate_dvh_many",
+                        [&](const double *ud, const double *, int64_t, int64_t bc, int64_t mp) -> int {
+                            return launch_dvh_build_many(h->x, h->n, h->npad, h->d, ud, bc, mp, h->wdev, h->v, h->vt, h->Z, h->stream, &h->prof);
+                        });
 }
 
 // ---- numerical propagation (UncertaintyPropagation.py:90-162; kernels: quadrature.hip) -----------------------------------------------

@@ -635,6 +635,212 @@ class PeriodicCovariance(Covariance):
         return state
 
 
+class _MaternModel(_MatrixModel):
+    """Owner of one gpx_matern_fit handle: K of the Matern kernel assembled and factored on the device.  Everything a matrix
+    model answers, plus the kernel's own prediction and likelihood gradient (and, for nu = 5/2, the batched propagation calls
+    that UncertaintyPropagationApprox makes on the handle)."""
+
+    def __init__(self, x, t_centered, theta, nu2):
+        x = _gpx.f64(x)
+        if x.ndim != 2:
+            raise ValueError("x must be an (n, d) array")
+        self.n, self.d = x.shape
+        self.nu2 = int(nu2)
+        theta = _theta(theta, self.d)
+        t = np.zeros(self.n) if t_centered is None else _gpx.f64(t_centered)
+        if t.shape != (self.n,):
+            raise ValueError("t must have %d entries" % self.n)
+        self._h = ctypes.c_void_p()
+        _gpx.check(_gpx.lib.gpx_matern_fit(_gpx.ptr(x), _gpx.ptr(t), self.n, self.d, _gpx.ptr(theta), self.nu2, None, ctypes.byref(self._h)),
+                   "gpx_matern_fit")
+
+    def predict(self, xs):
+        m = xs.shape[0]
+        mean = np.empty(m)
+        var = np.empty(m)
+        _gpx.check(_gpx.lib.gpx_matern_predict(self.handle, _gpx.ptr(xs), m, _gpx.ptr(mean), _gpx.ptr(var)), "gpx_matern_predict")
+        return mean, var
+
+    def nll_grad(self):
+        g = np.empty(2 + self.d)
+        _gpx.check(_gpx.lib.gpx_matern_nll_grad(self.handle, _gpx.ptr(g)), "gpx_matern_nll_grad")
+        return g
+
+
+class MaternCovariance(Covariance):
+    """ARD Matern kernel with nu = 3/2 or 5/2, theta = (log v, log vt, log w_1..d) as for GaussianCovariance.  With delta = xi - xj,
+    q = sum_k w_k delta_k^2 and s = sqrt(2 nu q):
+        nu = 5/2:  k = v (1 + s + s^2 / 3) exp(-s)        nu = 3/2:  k = v (1 + s) exp(-s)        (+ vt iff xi == xj elementwise).
+
+    Built on the base class's conventions, like PeriodicCovariance: cov_matrix AND cov_matrix_ij carry the +vt on exact equality (also
+    for a query that equals a training row) and duplicate training rows make K singular.  The matrix methods are the fused HIP path
+    (matern_gram_kernel, Cholesky on the Gram tiles, one-pass likelihood gradient); a subclass that overrides one of the matrix
+    builders falls back to the generic device route of `Covariance` (`_fused()`).  nu = 5/2 is twice differentiable and offers
+    get_Jacobian / get_Hessian, so UncertaintyPropagationApprox and the inverse propagation run fused on the device for it; nu = 3/2
+    (no Hessian at the origin) is propagated as any generic operator without derivatives."""
+
+    _MATRIX_METHODS = GaussianCovariance._MATRIX_METHODS
+
+    def __init__(self, nu=2.5):
+        Covariance.__init__(self)
+        if nu not in (1.5, 2.5):
+            raise ValueError("nu must be 1.5 or 2.5, got %r" % (nu,))
+        self.nu = float(nu)
+
+    @property
+    def _nu2(self):
+        return int(round(2 * self.nu))
+
+    def _fused(self):
+        """True when every matrix-defining method of this instance is MaternCovariance's own"""
+        cls = type(self)
+        return cls is MaternCovariance or all(getattr(cls, m) is getattr(MaternCovariance, m) for m in self._MATRIX_METHODS)
+
+    def _radial(self, diff, theta):
+        """(s, v exp(-s), w) at the difference diff"""
+        with np.errstate(divide="ignore"):
+            v = np.exp(theta[0])
+            w = np.exp(np.asarray(theta[2:], dtype=float))
+        s = np.sqrt(self._nu2 * np.dot(diff, w * diff))
+        return s, v * np.exp(-s), w
+
+    def _kf_g(self, s, e):
+        """the noise-free kernel and the factor G of its first derivatives"""
+        if self._nu2 == 5:
+            return e * (1.0 + s + s * s / 3.0), (5.0 / 3.0) * e * (1.0 + s)
+        return e * (1.0 + s), 3.0 * e
+
+    def __call__(self, xi, xj, theta):
+        xi = np.asarray(xi)
+        xj = np.asarray(xj)
+        with np.errstate(divide="ignore"):
+            vt = np.exp(theta[1])
+        s, e, _w = self._radial(xi - xj, theta)
+        return self._kf_g(s, e)[0] + (vt if (xi == xj).all() else 0)
+
+    get_theta = GaussianCovariance.get_theta
+
+    def _d_cov_d_theta(self, xi, xj, theta, j):
+        """d k(xi, xj) / d theta_j in closed form; theta is the LOG of (v, vt, w): j = 0 -> the noise-free kernel, j = 1 -> vt iff
+        xi == xj elementwise, j = 2 + k -> -1/2 w_k delta_k^2 G (no division by s)"""
+        xi = np.asarray(xi, dtype=float)
+        xj = np.asarray(xj, dtype=float)
+        if j == 1:
+            with np.errstate(divide="ignore"):
+                return np.exp(theta[1]) if (xi == xj).all() else 0
+        diff = xi - xj
+        s, e, w = self._radial(diff, theta)
+        kf, g = self._kf_g(s, e)
+        if j == 0:
+            return kf
+        return -0.5 * w[j - 2] * diff[j - 2] ** 2 * g
+
+    def get_Jacobian(self, u, xi, theta):
+        """nu = 5/2: -(xi - u) w G as a (d, 1) column, GaussianCovariance.get_Jacobian's convention"""
+        if self._nu2 != 5:
+            return Covariance.get_Jacobian(self, u, xi, theta)
+        diff = np.asarray(xi, dtype=float) - np.asarray(u, dtype=float)
+        s, e, w = self._radial(diff, theta)
+        return np.atleast_2d(-diff * w * self._kf_g(s, e)[1]).T
+
+    def get_Hessian(self, u, xi, theta):
+        """nu = 5/2: (5/3) v exp(-s) [5 (w diff)(w diff)^T - diag(w) (1 + s)]"""
+        if self._nu2 != 5:
+            return Covariance.get_Hessian(self, u, xi, theta)
+        diff = np.asarray(xi, dtype=float) - np.asarray(u, dtype=float)
+        s, e, w = self._radial(diff, theta)
+        wd = diff * w
+        return (5.0 / 3.0) * e * (5.0 * np.outer(wd, wd) - np.diag(w) * (1.0 + s))
+
+    def _gram(self, xi, xj, theta, deriv):
+        a = _gpx.f64(xi)
+        b = a if xj is xi else _gpx.f64(xj)
+        if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1]:
+            raise ValueError("inputs must be (n, d) arrays with equal d")
+        th = _theta(theta, a.shape[1])
+        K = np.empty((a.shape[0], b.shape[0]), dtype=np.float64)
+        if K.size:
+            _gpx.check(_gpx.lib.gpx_matern_gram(_gpx.ptr(a), a.shape[0], _gpx.ptr(b), b.shape[0], a.shape[1], _gpx.ptr(th), self._nu2,
+                                                int(deriv), _gpx.ptr(K)), "gpx_matern_gram")
+        return K
+
+    def cov_matrix_ij(self, xi, xj, theta):
+        """N1 x N2 matrix of the kernel, +vt wherever two rows are equal -- HIP Gram kernel."""
+        return self._gram(xi, xj, theta, -1)
+
+    def cov_matrix(self, x, theta):
+        # cov_matrix_ij(x, x) -- a subclass's own cross-covariance if it has one
+        return self.cov_matrix_ij(x, x, theta)
+
+    def _d_cov_matrix_d_theta_ij(self, xi, xj, theta, j):
+        """d K / d theta_j entry-wise from the kernel's derivative variant.  An accessor: the likelihood gradient never forms these
+        matrices (matern_nll_grad_kernel)."""
+        if not 0 <= j < len(theta):
+            raise ValueError("j must be in [0, %d)" % len(theta))
+        return self._gram(xi, xj, theta, j)
+
+    def _d_cov_matrix_d_theta(self, x, theta, j):
+        return self._d_cov_matrix_d_theta_ij(x, x, theta, j)
+
+    def inv_cov_matrix(self, x, theta, cov_matrix=None):
+        """K^-1 from a device fit: K never leaves the device"""
+        if cov_matrix is not None or not self._fused():
+            return Covariance.inv_cov_matrix(self, x, theta, cov_matrix)
+        model = _MaternModel(x, None, theta, self._nu2)
+        try:
+            return model.kinv()
+        finally:
+            model.close()
+
+    def _log_det_cov_matrix(self, x, theta):
+        """log det K from the Cholesky factor of a device fit"""
+        if not self._fused():
+            return Covariance._log_det_cov_matrix(self, x, theta)
+        model = _MaternModel(x, None, theta, self._nu2)
+        try:
+            return model.logdet()
+        finally:
+            model.close()
+
+    def _model_at(self, x, t, theta):
+        """device model fitted at theta, cached on (x, t, theta) identity/bytes: L-BFGS-B asks for the value and the
+        gradient at the same theta in two separate calls."""
+        xa = _gpx.f64(x)
+        ta = _gpx.f64(t)
+        th = _theta(theta, xa.shape[1]).copy()
+        key = (xa.ctypes.data if xa is x else id(x), xa.shape, ta.tobytes(), th.tobytes())
+        cached = getattr(self, "_ml_cache", None)
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        if cached is not None:
+            cached[1].close()
+        self._ml_cache = None
+        model = _MaternModel(xa, ta, th, self._nu2)
+        self._ml_cache = (key, model)
+        return model
+
+    def _negativeloglikelihood(self, x, t, theta):
+        """N/2 log 2pi + 1/2 log det K + 1/2 t^T K^-1 t on the GPU; 1e20 when K cannot be factored, like the base class's."""
+        if not self._fused():
+            return Covariance._negativeloglikelihood(self, x, t, theta)
+        try:
+            return self._model_at(x, t, theta).nll()
+        except (np.linalg.LinAlgError, ValueError, ZeroDivisionError):
+            return 1.0e+20
+
+    def _d_nll_d_theta(self, x, t, theta):
+        """gradient of the NLL: one fused pass over K^-1 on the GPU instead of 2 + d derivative matrices evaluated entry by entry in
+        Python."""
+        if not self._fused():
+            return Covariance._d_nll_d_theta(self, x, t, theta)
+        return self._model_at(x, t, theta).nll_grad()
+
+    def __getstate__(self):
+        state = Covariance.__getstate__(self)
+        state.pop("_ml_cache", None)     # device handles never enter a pickle
+        return state
+
+
 class _SPGPDeviceModel(object):
     """Owner of one gpx_spgp handle: K_NM, chol(K_M + 1e-5 I), Lambda and chol(B + 1e-5 I) resident in HBM."""
 

@@ -10,7 +10,8 @@ import ctypes
 import numpy as np
 
 from . import _gpx
-from .Covariance import GaussianCovariance, PeriodicCovariance, SPGPCovariance, _MatrixModel, _PeriodicModel
+from .Covariance import (GaussianCovariance, MaternCovariance, PeriodicCovariance, SPGPCovariance, _MaternModel, _MatrixModel,
+                         _PeriodicModel)
 
 
 class _DeviceModel(object):
@@ -122,7 +123,7 @@ class GaussianProcess(object):
     # ---- device model management -----------------------------------------------------------
     def _route(self):
         """which device path serves this operator.  The reference's GaussianProcess talks to `cov` only through its interface
-        (GaussianProcess.py:39-41, :75-78); here the three built-in kernels have fused paths and EVERY other operator -- a
+        (GaussianProcess.py:39-41, :75-78); here the four built-in kernels have fused paths and EVERY other operator -- a
         from-scratch Covariance, or a subclass of a built-in one that overrides a matrix builder -- takes the generic route:
         its own cov_matrix / cov_matrix_ij, factored and solved on the GPU (gpx_fit_matrix / gpx_predict_kv)."""
         cov = self.cov
@@ -132,6 +133,8 @@ class GaussianProcess(object):
             return "gaussian"
         if isinstance(cov, PeriodicCovariance) and cov._fused():
             return "periodic"
+        if isinstance(cov, MaternCovariance) and cov._fused():
+            return "matern"
         return "generic"
 
     def _fit(self):
@@ -144,6 +147,9 @@ class GaussianProcess(object):
         elif route == "periodic":
             # K assembled on the device straight into the factor's buffer (gpx_periodic_fit): no N x N transfer
             self._model = _PeriodicModel(self.x, self.t, self.theta_min)
+        elif route == "matern":
+            # the same for the Matern kernel (gpx_matern_fit)
+            self._model = _MaternModel(self.x, self.t, self.theta_min, self.cov._nu2)
         else:
             self._model = _MatrixModel(np.array(self.cov.cov_matrix(self.x, self.theta_min)), self.t)
 

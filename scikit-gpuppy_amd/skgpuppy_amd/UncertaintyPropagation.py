@@ -53,7 +53,8 @@ class UncertaintyPropagationApprox(UncertaintyPropagationGA):
     UncertaintyPropagation2.pyx:189-380).
 
     With the built-in GaussianCovariance everything runs fused on the device handle (C / J / tr built by a kernel, one pass
-    K^-1 [C, J_1..J_d] or two sweeps over the factor, dot products).  With any other operator (the generic route of
+    K^-1 [C, J_1..J_d] or two sweeps over the factor, dot products); with MaternCovariance(2.5) every sum comes from the batched
+    gpx_matern_propagate_* calls, a single input as a batch of one.  With any other operator (the generic route of
     GaussianProcess) C_ux / J_ux / H_ux come from the operator's own __call__ / get_Jacobian / get_Hessian -- 3N host calls,
     as in the reference (:504-510) -- and the reference's N^2 double loops become two device sweeps over the factor
     (gpx_solve) plus O(N d) dot products."""
@@ -69,6 +70,11 @@ class UncertaintyPropagationApprox(UncertaintyPropagationGA):
     def _generic(self):
         return self.gp._route() != "gaussian"
 
+    def _matern52(self):
+        """MaternCovariance(2.5) on its fused route: every sum comes from the gpx_matern_propagate_* calls (a single input is a batch
+        of one); C_ux / J_ux / H_ux stay host attributes built from the scalar methods.  nu = 3/2 has no Hessian: generic."""
+        return self.gp._route() == "matern" and self.gp.cov._nu2 == 5
+
     def _new_u(self, u, uu):
         if self.u is None or (np.asarray(self.u) != uu).any():
             self.u = u               # stored by reference like UncertaintyPropagation.py:500
@@ -78,6 +84,8 @@ class UncertaintyPropagationApprox(UncertaintyPropagationGA):
     def _parts(self, u, Sigma_x):
         uu, S = _u_sigma(self.gp, u, Sigma_x)
         self._new_u(u, uu)
+        if self._matern52():
+            return tuple(float(o[0]) for o in self._parts_many(uu[None, :], S))
         if self._generic():
             return self._parts_generic(S)
         out = [ctypes.c_double() for _ in range(4)]
@@ -168,6 +176,11 @@ class UncertaintyPropagationApprox(UncertaintyPropagationGA):
         B = len(UU)
         shared = S.ndim == 2
         out = [np.empty(B) for _ in range(4)]
+        if self._matern52():
+            st = _gpx.lib.gpx_matern_propagate_approx_many(self.gp._dev().handle, _gpx.ptr(UU), _gpx.ptr(S), int(shared), B,
+                                                           *[_gpx.ptr(o) for o in out])
+            _gpx.check(st, "gpx_matern_propagate_approx_many")
+            return out
         if self._generic():
             one = type(self)(self.gp)
             for i in range(B):
@@ -250,6 +263,8 @@ class UncertaintyPropagationApprox(UncertaintyPropagationGA):
         # (UncertaintyPropagation.py:564-630); all d values come out of one device call
         uu = _gpx.f64(u)
         self._new_u(u, uu)
+        if self._matern52():
+            return self._get_variance_dv_many(uu[None, :])[0][0, h]
         if self._generic():
             C, J, H = self._fetch_cjh()
             kv = self._kinv_rows()
@@ -271,6 +286,10 @@ class UncertaintyPropagationApprox(UncertaintyPropagationGA):
         UU, _S = self._many_args(U, np.zeros((d, d)))
         B = len(UU)
         dvh, sigma2 = np.empty((B, d)), np.empty(B)
+        if self._matern52():
+            st = _gpx.lib.gpx_matern_propagate_dvh_many(self.gp._dev().handle, _gpx.ptr(UU), B, _gpx.ptr(dvh), _gpx.ptr(sigma2))
+            _gpx.check(st, "gpx_matern_propagate_dvh_many")
+            return dvh, sigma2
         if self._generic():
             one = type(self)(self.gp)
             for i in range(B):
@@ -353,9 +372,9 @@ class UncertaintyPropagationExact(UncertaintyPropagationGA):
         cuu = float(gp._covariance(u, u)) if want_var else 0.0
         mean, var = ctypes.c_double(), ctypes.c_double()
         pvar = ctypes.byref(var) if want_var else None      # mean only: the library neither builds nor reads K^-1
-        if gp._route() in ("generic", "gaussian", "periodic"):
+        if gp._route() in ("generic", "gaussian", "periodic", "matern"):
             # (any fitted handle: a gpx_fit_matrix one, a gpx_periodic_fit one -- the reference has no input derivatives for that kernel,
-            # it is propagated as any generic operator --, or -- a caller-supplied C_ux on the built-in route -- the gpx_fit one)
+            # it is propagated as any generic operator --, a gpx_matern_fit one likewise, or -- a caller-supplied C_ux on the built-in route -- the gpx_fit one)
             st = _gpx.lib.gpx_propagate_exact_matrix(gp._dev().handle, None, None, _gpx.ptr(x), gp.n, gp.d, _gpx.ptr(w), _gpx.ptr(C),
                                                      _gpx.ptr(uu), _gpx.ptr(S), cuu, ctypes.byref(mean), pvar)
         else:
@@ -470,7 +489,7 @@ class _MixturePropagation(UncertaintyPropagationGA, UncertaintyPropagation):
     many-row solve (estimate_many's) and one reduction kernel returns, per input, the mean, the variance and the third and fourth central
     moments of the mixture, and its density at any number of y.
 
-    Built-in Gaussian and periodic kernels: gpx_propagate_quadrature_many -- nodes, mu and sigma^2 never leave the device.  Every other route
+    Built-in Gaussian, periodic and Matern kernels: gpx_propagate_quadrature_many -- nodes, mu and sigma^2 never leave the device.  Every other route
     (a generic operator, SPGP): the nodes are built on the host, gp.estimate_many evaluates them, gpx_mixture_reduce reduces its output."""
 
     def _rule(self, d):
@@ -503,7 +522,7 @@ class _MixturePropagation(UncertaintyPropagationGA, UncertaintyPropagation):
         yp = _gpx.ptr(YY) if ny else None
         dp = _gpx.ptr(dens) if ny else None
         meant = float(gp._get_mean_t())
-        if gp._route() in ("gaussian", "periodic"):
+        if gp._route() in ("gaussian", "periodic", "matern"):
             st = _gpx.lib.gpx_propagate_quadrature_many(gp._dev().handle, _gpx.ptr(UU), _gpx.ptr(A), int(shared), B, _gpx.ptr(z), _gpx.ptr(wq),
                                                         ns, yp, ny, yshared, meant, _gpx.ptr(mom), dp)
             _gpx.check(st, "gpx_propagate_quadrature_many")

@@ -5,7 +5,7 @@ and skgpuppy.UncertaintyPropagation; the arithmetic runs in hand-written HIP ker
 behind a ctypes C-ABI (include/gpx.h).  Importing this package without the built library fails.
 """
 from . import _gpx  # noqa: F401  (fails loudly when libgpx.so is missing)
-from .Covariance import Covariance, GaussianCovariance, PeriodicCovariance, SPGPCovariance, tracedot  # noqa: F401
+from .Covariance import Covariance, GaussianCovariance, MaternCovariance, PeriodicCovariance, SPGPCovariance, tracedot  # noqa: F401
 from .GaussianProcess import GaussianProcess  # noqa: F401
 from .UncertaintyPropagation import (  # noqa: F401
     UncertaintyPropagationApprox,
@@ -23,7 +23,8 @@ from .InverseUncertaintyPropagation import (  # noqa: F401,E402
 )
 
 __all__ = [
-    "Covariance", "GaussianCovariance", "PeriodicCovariance", "SPGPCovariance", "GaussianProcess", "UncertaintyPropagationGA",
+    "Covariance", "GaussianCovariance", "MaternCovariance", "PeriodicCovariance", "SPGPCovariance", "GaussianProcess",
+    "UncertaintyPropagationGA",
     "UncertaintyPropagationApprox", "UncertaintyPropagationExact", "tracedot",
     "UncertaintyPropagation", "UncertaintyPropagationMC", "UncertaintyPropagationNumericalHG",
     "InverseUncertaintyPropagation", "InverseUncertaintyPropagationApprox", "InverseUncertaintyPropagationNumerical",

@@ -97,6 +97,12 @@ SIGNATURES = {
     "gpx_periodic_fit": (_int, [_dp, _dp, _i64, _int, _dp, ctypes.c_void_p, ctypes.POINTER(_hp)]),
     "gpx_periodic_predict": (_int, [_hp, _dp, _i64, _dp, _dp]),
     "gpx_periodic_nll_grad": (_int, [_hp, _dp]),
+    "gpx_matern_gram": (_int, [_dp, _i64, _dp, _i64, _int, _dp, _int, _int, _dp]),
+    "gpx_matern_fit": (_int, [_dp, _dp, _i64, _int, _dp, _int, ctypes.c_void_p, ctypes.POINTER(_hp)]),
+    "gpx_matern_predict": (_int, [_hp, _dp, _i64, _dp, _dp]),
+    "gpx_matern_nll_grad": (_int, [_hp, _dp]),
+    "gpx_matern_propagate_approx_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp, _dp, _dp, _dp]),
+    "gpx_matern_propagate_dvh_many": (_int, [_hp, _dp, _i64, _dp, _dp]),
     "gpx_spgp_fit": (_int, [_dp, _dp, _i64, _int, _dp, _dp, _i64, ctypes.POINTER(_hp)]),
     "gpx_spgp_free": (None, [_hp]),
     "gpx_spgp_predict": (_int, [_hp, _dp, _i64, _dp, _dp]),
