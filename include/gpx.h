@@ -99,6 +99,22 @@ int gpx_predict_kv(gpx_handle *h, const double *kv, int64_t m, const double *kdi
  * Never forms the M x M matrices of the reference. */
 int gpx_predict(gpx_handle *h, const double *xs, int64_t m, double *mean_out, double *var_out);
 
+/* ---- the predictor's input gradients: d mu / d x* and d sigma^2 / d x* at m queries xs [m, d] ----
+ * The reference has no such method: its UncertaintyPropagationLinear differentiates gp(x)[0] by central differences, 2 d calls of
+ * estimate per point (skgpuppy/UncertaintyPropagation.py:214-227), and propagates var = sum_k g_k^2 Sigma_kk + vt (:233-242).  Both
+ * gradients are closed-form sums: with delta = x_i - x*, c_i the noise-free kernel and d c_i / d x*_k = +w_k delta_k g_i (g = c for
+ * GaussianCovariance, skgpuppy/Covariance.py:660-689 -- whose get_Jacobian returns the NEGATIVE of it, as its comment at :687 says --, and
+ * G of gpx_matern_* for MaternCovariance, either nu),
+ *   d mu / d x*_k = sum_i alpha_i d_k c_i          d sigma^2 / d x*_k = -2 (L^-1 C).(L^-1 d_k c).
+ * mean and var are the handle's own predictor's at every query: on a gpx_matern_fit handle they carry the +vt of a query that equals a
+ * training row elementwise (Covariance.py:440-451, as gpx_matern_predict), on a gpx_fit handle they do not (as gpx_predict, whose rows
+ * are GaussianCovariance.cov_matrix_ij's, :466-483).  No derivative carries that term.  One entry point each for gpx_fit handles and gpx_matern_fit handles of both nu; a periodic or a
+ * gpx_fit_matrix handle: GPX_ERR_STATE.  Results do not depend on a query's place in the batch.  m == 0 returns 0. */
+/* mean (WITHOUT meant) [m] and its gradient [m, d] from alpha alone: no solve.  Either output may be NULL, not both. */
+int gpx_predict_mean_grad(gpx_handle *h, const double *xs, int64_t m, double *mean_out, double *dmean_out);
+/* gpx_predict's mean and variance plus both gradients [m, d]; d + 1 solved rows per query.  dmean_out may be NULL. */
+int gpx_predict_grad(gpx_handle *h, const double *xs, int64_t m, double *mean_out, double *var_out, double *dmean_out, double *dvar_out);
+
 /* ---- a8: accessors ---- */
 int gpx_alpha(gpx_handle *h, double *beta_out);     /* beta = K^-1 t  [n]   (GaussianProcess.py:114-119) */
 /* Kinv . B for a few vectors without forming K^-1 (every `numpy.dot(Kinv, v)` of the reference: GaussianProcess.py:77,

@@ -221,6 +221,9 @@ void matern_release(MaternData *md);
 // inputs; lower_only / pad_mode / padding contract as launch_gram.  deriv >= 0: d K / d theta_deriv instead (no add_diag)
 int launch_matern_gram(const double *xi, int64_t n1, const double *xj, int64_t n2, const MaternData *md, double add_diag, int lower_only,
                        int pad_mode, double *out, int64_t ld, int64_t rows_pad, int64_t cols_pad, hipStream_t s, Profiler *prof, int deriv = -1);
+// rows [C, J_1..J_d] of nb queries (gpx_predict_grad), nu = 3/2 or 5/2: Z [rows_pad, npad], the rest of the last 128-row tile cleared
+int launch_matern_grad_build_many(const MaternData *md, int64_t n, int64_t npad, const double *U_dev, int64_t nb, int64_t rows_pad, double *Z,
+                                  hipStream_t s, Profiler *prof);
 constexpr int MAT_KC = 8;                        // coordinates per sweep of the gradient pass
 constexpr int MAT_NC = MAT_KC + 2;               // sums per sweep: S_0, A_k of the sweep's k, T
 
@@ -433,6 +436,19 @@ int launch_approx_build_many(const double *x, int64_t n, int64_t npad, int d, co
                              hipStream_t s, Profiler *prof);
 int launch_approx_reduce_many(const double *Zs, int64_t npad, int d, const double *y, const double *Sigma_dev, int64_t sigma_stride,
                               int64_t nb, double vplusvt, double *out, int64_t ldo, hipStream_t s, Profiler *prof);
+// the same kernel's rows [C, J_1..J_d] per query (gpx_predict_grad)
+int launch_grad_build_many(const double *x, int64_t n, int64_t npad, int d, const double *U_dev, int64_t nb, int64_t rows_pad, const double *w_dev,
+                           double v, double vt, double *Z, hipStream_t s, Profiler *prof);
+// ---- launchers of predict_grad.hip: the predictor's input gradients ----
+// mean [nb] and dmean [nb, d] from alpha alone (nu2 = 0: the Gaussian kernel, 3 / 5: Matern; x raw); partial [S, nb, 1 + d] scratch with
+// S = predict_mean_grad_splits(nb, npad); either output may be null
+int predict_mean_grad_splits(int64_t nb, int64_t npad);
+int launch_predict_mean_grad(const double *x, int64_t n, int64_t npad, int d, int nu2, const double *U_dev, int64_t nb, const double *w_dev,
+                             const double *alpha, double v, double vt, int S, double *partial, double *mean_dev, double *dmean_dev, hipStream_t s,
+                             Profiler *prof);
+// the row products of the solved block [C, J_1..J_d] per query: mean, var [nb], dmean (or null), dvar [nb, d]
+int launch_grad_reduce_many(const double *Zs, int64_t npad, int d, const double *y, int64_t nb, double vplusvt, double *mean, double *var,
+                            double *dmean, double *dvar, hipStream_t s, Profiler *prof);
 // batched inverse propagation (gpx_propagate_dvh_many): rows [C, J_1..J_d, H_11..H_dd] per input; dvh [nb, d], sigma2 [nb] or null
 int launch_dvh_build_many(const double *x, int64_t n, int64_t npad, int d, const double *U_dev, int64_t nb, int64_t rows_pad,
                           const double *w_dev, double v, double vt, double *Z, hipStream_t s, Profiler *prof);
@@ -532,6 +548,9 @@ using RowsBuild = std::function<int(const double *, const double *, int64_t, int
 int approx_many_run(gpx_handle *h, int d, const double *U, const double *Sigma, int sigma_shared, int64_t b, double *mean, double *var, double *sigma2,
                     double *rest, const char *what, const RowsBuild &build);
 int dvh_many_run(gpx_handle *h, int d, const double *U, int64_t b, double *dvh_out, double *sigma2_out, const char *what, const RowsBuild &build);
+// the same loop on d + 1 rows a query, [C, J_1..J_d] (no Sigma): gpx_predict_grad's mean, var [b], dmean (or null), dvar [b, d]
+int grad_many_run(gpx_handle *h, int d, const double *U, int64_t b, double *mean, double *var, double *dmean, double *dvar, const char *what,
+                  const RowsBuild &build);
 
 // The predictor's chunk loop on device-resident queries and outputs (predict.hip): begin sizes the chunk as gpx_predict does (bounded rows;
 // a periodic handle: the many-row solver always, and its chunk cap) and takes the query, prior-variance and partial-sum buffers; chunk

@@ -1,5 +1,6 @@
 // matern.hip -- MaternCovariance (ARD Matern, nu = 3/2 or 5/2) on the device: Gram / cross-covariance assembly, the one-pass likelihood
-// gradient, and for nu = 5/2 the right-hand-side blocks of the batched Approx and inverse propagation.
+// gradient, for nu = 5/2 the right-hand-side blocks of the batched Approx and inverse propagation, and for either nu the rows [C, J_1..J_d]
+// of the predictor's input gradients (gpx_predict_grad).
 //
 // theta = (log v, log vt, log w_1..d), GaussianCovariance's layout.  With delta = xi - xj, q = sum_k w_k delta_k^2 and s = sqrt(2 nu q)
 //   nu = 5/2: Kf = v (1 + s + s^2 / 3) exp(-s)      nu = 3/2: Kf = v (1 + s) exp(-s)      K = Kf + (vt iff delta == 0 in every component).
@@ -13,15 +14,7 @@
 
 #include "common.h"
 #include "gram_tile.h"
-
-// the radial factors at q = sum_k w_k delta_k^2: one sqrt and one exp serve all of them
-template <int NU2>
-struct MaternRadial {
-    double s, e;   // sqrt(2 nu q), v exp(-s)
-    __device__ __forceinline__ MaternRadial(double v, double q) : s(sqrt((double)NU2 * q)), e(v * exp_nonpos(-s)) {}
-    __device__ __forceinline__ double kf() const { return NU2 == 5 ? e * fma(s, fma(s, 1.0 / 3.0, 1.0), 1.0) : e * (1.0 + s); }
-    __device__ __forceinline__ double g() const { return NU2 == 5 ? (5.0 / 3.0) * e * (1.0 + s) : 3.0 * e; }
-};
+#include "radial.h"   // MaternRadial: the radial factors at q, one sqrt and one exp for all of them
 
 // what the deriv variant writes (the parameter's group; MD_W: its coordinate is a second argument)
 enum { MD_V = 0, MD_VT = 1, MD_W = 2 };
@@ -234,18 +227,24 @@ static int launch_matern_nll_grad(const double *Kinv, int64_t ld, int64_t n, int
 //   C = e (1 + s + s^2 / 3) (+vt iff x_i == u elementwise)     J_k = -a_k G,  G = (5/3) e (1 + s)
 //   H_kl = (5/3) e [5 a_k a_l - delta_kl w_k (1 + s)],   tr(H Sigma) = (5/3) e [5 a^T Sigma a - (1 + s) sum_k w_k Sigma_kk]
 // DVH = false: row b (d + 2) + r of Z is [C, tr, J_1..J_d]; DVH = true: row b (2 d + 1) + r is [C, J_1..J_d, H_11..H_dd] (no Sigma).
+// The body is one function over a compile-time row layout (MB_APPROX, MB_DVH, and MB_GRAD: row b (d + 1) + r is [C, J_1..J_d], the rows of
+// gpx_predict_grad, which needs one derivative only and therefore serves nu = 3/2 as well: NU2 selects the radial factors).
 // Same workgroup (128 columns of x k-major in LDS, AB_INPUTS inputs, four per wave, u / w / Sigma wave-uniform), 16-byte stores, one
 // exp and one sqrt per (input, column).  DR > 0: d <= DR and a stays in registers; DR = 0: any d, recomputed from the LDS tile.
 // ---------------------------------------------------------------------------------------------
 constexpr int MB_COLS = 128;
 constexpr int MB_INPUTS = 16;
 
-template <int DR, bool DVH>
-__global__ __launch_bounds__(256) void matern52_build_many_kernel(const double *__restrict__ x, long n, long npad, int d,
-                                                                 const double *__restrict__ U, const double *__restrict__ Sigma,
-                                                                 long sigma_stride, long nb, const double *__restrict__ w, double v, double vt,
-                                                                 double *__restrict__ Z)
+enum { MB_APPROX = 0, MB_DVH = 1, MB_GRAD = 2 };
+
+template <int DR, int ROWS, int NU2>
+__device__ __forceinline__ void matern_build_many(const double *__restrict__ x, long n, long npad, int d, const double *__restrict__ U,
+                                                  const double *__restrict__ Sigma, long sigma_stride, long nb, const double *__restrict__ w_in,
+                                                  double v, double vt, double *__restrict__ Z)
 {
+    const double *w = w_in;
+    constexpr bool DVH = ROWS == MB_DVH, TR = ROWS == MB_APPROX;
+    static_assert(NU2 == 5 || ROWS == MB_GRAD, "nu = 3/2 has no Hessian at the origin");
     extern __shared__ __attribute__((aligned(16))) double mb_smem[];
     double *x_s = mb_smem;   // [d][128] raw inputs of the tile's columns, k-major
     const int t = threadIdx.x;
@@ -259,11 +258,14 @@ __global__ __launch_bounds__(256) void matern52_build_many_kernel(const double *
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
     const long c = col0 + 2 * lane;
     const bool in0 = c < n, in1 = c + 1 < n;
-    const long nrow = DVH ? 2 * d + 1 : d + 2;
-    const int jrow = DVH ? 1 : 2;   // first row of J
+    const long nrow = DVH ? 2 * d + 1 : TR ? d + 2 : d + 1;
+    const int jrow = TR ? 2 : 1;   // first row of J
     for (int j = 0; j < MB_INPUTS / 4; ++j) {
         const long b = (long)blockIdx.y * MB_INPUTS + 4 * j + wave;   // wave-uniform
         if (b >= nb) break;
+        // (the new layout alone, so that the older instantiations stay the code they were: w and the tests k < d are formed per input --
+        // held across the inputs they spill scalar registers, as predict_grad.hip explains)
+        if constexpr (ROWS == MB_GRAD) asm volatile("" : "+s"(w), "+s"(d));
         const double *u = U + b * d;
         double *zrow = Z + b * nrow * npad + c;
         double wd0[DR > 0 ? DR : 1], wd1[DR > 0 ? DR : 1];
@@ -296,7 +298,7 @@ __global__ __launch_bounds__(256) void matern52_build_many_kernel(const double *
             }
         }
         // columns past n: every row of the block is zero there
-        const MaternRadial<5> r0(in0 ? v : 0.0, q0), r1(in1 ? v : 0.0, q1);
+        const MaternRadial<NU2> r0(in0 ? v : 0.0, q0), r1(in1 ? v : 0.0, q1);
         const double c0 = r0.kf(), c1 = r1.kf(), g0 = r0.g(), g1 = r1.g();
         const double f0 = (5.0 / 3.0) * r0.e, f1 = (5.0 / 3.0) * r1.e;   // H = f [5 a a^T - diag(w) (1 + s)]
         const double p0 = 1.0 + r0.s, p1 = 1.0 + r1.s;
@@ -317,7 +319,7 @@ __global__ __launch_bounds__(256) void matern52_build_many_kernel(const double *
                         v2d hk;
                         hk.x = f0 * fma(5.0 * wd0[a], wd0[a], -wa * p0); hk.y = f1 * fma(5.0 * wd1[a], wd1[a], -wa * p1);
                         *reinterpret_cast<v2d *>(zrow + (long)(1 + d + a) * npad) = hk;
-                    } else {
+                    } else if constexpr (TR) {
                         const double *S = Sigma + b * sigma_stride;
                         double t0 = 0.0, t1 = 0.0;
 #pragma unroll
@@ -334,6 +336,7 @@ __global__ __launch_bounds__(256) void matern52_build_many_kernel(const double *
                 }
             }
         } else {
+            if constexpr (ROWS == MB_GRAD) asm volatile("" : "+s"(w), "+s"(d), "+s"(u));
             for (int a = 0; a < d; ++a) {
                 const v2d xa = *reinterpret_cast<const v2d *>(&x_s[a * MB_COLS + 2 * lane]);
                 const double wa = w[a], ua = u[a];
@@ -345,7 +348,7 @@ __global__ __launch_bounds__(256) void matern52_build_many_kernel(const double *
                     v2d hk;
                     hk.x = f0 * fma(5.0 * a0, a0, -wa * p0); hk.y = f1 * fma(5.0 * a1, a1, -wa * p1);
                     *reinterpret_cast<v2d *>(zrow + (long)(1 + d + a) * npad) = hk;
-                } else {
+                } else if constexpr (TR) {
                     const double *S = Sigma + b * sigma_stride;
                     double t0 = 0.0, t1 = 0.0;
                     for (int e = 0; e < d; ++e) {
@@ -360,7 +363,7 @@ __global__ __launch_bounds__(256) void matern52_build_many_kernel(const double *
                 }
             }
         }
-        if constexpr (!DVH) {
+        if constexpr (TR) {
             o.x = f0 * fma(5.0, s0, -p0 * wdiag);
             o.y = f1 * fma(5.0, s1, -p1 * wdiag);
             *reinterpret_cast<v2d *>(zrow + npad) = o;
@@ -368,14 +371,32 @@ __global__ __launch_bounds__(256) void matern52_build_many_kernel(const double *
     }
 }
 
+template <int DR, bool DVH>
+__global__ __launch_bounds__(256) void matern52_build_many_kernel(const double *__restrict__ x, long n, long npad, int d,
+                                                                 const double *__restrict__ U, const double *__restrict__ Sigma,
+                                                                 long sigma_stride, long nb, const double *__restrict__ w, double v, double vt,
+                                                                 double *__restrict__ Z)
+{
+    matern_build_many<DR, DVH ? MB_DVH : MB_APPROX, 5>(x, n, npad, d, U, Sigma, sigma_stride, nb, w, v, vt, Z);
+}
+
+template <int DR, int NU2>
+__global__ __launch_bounds__(256) void matern_grad_build_many_kernel(const double *__restrict__ x, long n, long npad, int d,
+                                                                    const double *__restrict__ U, long nb, const double *__restrict__ w, double v,
+                                                                    double vt, double *__restrict__ Z)
+{
+    matern_build_many<DR, MB_GRAD, NU2>(x, n, npad, d, U, nullptr, 0, nb, w, v, vt, Z);
+}
+
 // Z [rows_pad, npad]: rows [0, nb nrow) written by the kernel (every column, zeros from n on), the rest of the last 128-row tile cleared
-static int launch_matern52_build_many(bool dvh, const double *x, int64_t n, int64_t npad, int d, const double *U_dev, const double *Sigma_dev,
-                                      int64_t sigma_stride, int64_t nb, int64_t rows_pad, const double *w_dev, double v, double vt, double *Z,
-                                      hipStream_t s, Profiler *prof)
+static int launch_matern_build_many(int layout, int nu2, const double *x, int64_t n, int64_t npad, int d, const double *U_dev, const double *Sigma_dev,
+                                    int64_t sigma_stride, int64_t nb, int64_t rows_pad, const double *w_dev, double v, double vt, double *Z,
+                                    hipStream_t s, Profiler *prof)
 {
     if (nb <= 0) return 0;
-    const int64_t rows = nb * (dvh ? 2 * d + 1 : d + 2);
-    if (npad % MB_COLS || rows > rows_pad || d < 1 || d > GPX_MAX_D) { gpx_set_error("matern52_build_many: bad block shape"); return GPX_ERR_BAD_ARG; }
+    const bool dvh = layout == MB_DVH;
+    const int64_t rows = nb * (dvh ? 2 * d + 1 : layout == MB_GRAD ? d + 1 : d + 2);
+    if (npad % MB_COLS || rows > rows_pad || d < 1 || d > GPX_MAX_D || (nu2 != 5 && layout != MB_GRAD)) { gpx_set_error("matern_build_many: bad block shape"); return GPX_ERR_BAD_ARG; }
     ProfScope ps(prof, s, GPX_K_GRAM, 8.0 * (double)rows_pad * (double)npad);
     if (rows_pad > rows) GPX_HIP(hipMemsetAsync(Z + rows * npad, 0, sizeof(double) * (rows_pad - rows) * npad, s));
     const dim3 grid((unsigned)(npad / MB_COLS), (unsigned)((nb + MB_INPUTS - 1) / MB_INPUTS));
@@ -383,7 +404,12 @@ static int launch_matern52_build_many(bool dvh, const double *x, int64_t n, int6
 #define MATERN_BUILD(DR, DVH)                                                                                                                  \
     hipLaunchKernelGGL((matern52_build_many_kernel<DR, DVH>), grid, dim3(256), lds, s, x, (long)n, (long)npad, d, U_dev, Sigma_dev, (long)sigma_stride, \
                        (long)nb, w_dev, v, vt, Z)
-    if (dvh) {
+#define MATERN_GRAD_BUILD(DR, NU2)                                                                                                              \
+    hipLaunchKernelGGL((matern_grad_build_many_kernel<DR, NU2>), grid, dim3(256), lds, s, x, (long)n, (long)npad, d, U_dev, (long)nb, w_dev, v, vt, Z)
+    if (layout == MB_GRAD) {
+        if (nu2 == 5) { if (d <= 8) MATERN_GRAD_BUILD(8, 5); else MATERN_GRAD_BUILD(0, 5); }
+        else { if (d <= 8) MATERN_GRAD_BUILD(8, 3); else MATERN_GRAD_BUILD(0, 3); }
+    } else if (dvh) {
         if (d <= 8) MATERN_BUILD(8, true);
         else MATERN_BUILD(0, true);
     } else {
@@ -391,8 +417,16 @@ static int launch_matern52_build_many(bool dvh, const double *x, int64_t n, int6
         else MATERN_BUILD(0, false);
     }
 #undef MATERN_BUILD
+#undef MATERN_GRAD_BUILD
     GPX_HIP(hipGetLastError());
     return 0;
+}
+
+// rows [C, J_1..J_d] of nb queries for gpx_predict_grad (propagate_api.hip), either nu
+int launch_matern_grad_build_many(const MaternData *md, int64_t n, int64_t npad, const double *U_dev, int64_t nb, int64_t rows_pad, double *Z,
+                                  hipStream_t s, Profiler *prof)
+{
+    return launch_matern_build_many(MB_GRAD, md->nu2, md->x, n, npad, md->d, U_dev, nullptr, 0, nb, rows_pad, md->wdev, md->v, md->vt, Z, s, prof);
 }
 
 // ---- parameters and inputs of a Matern model ----------------------------------------------------------------------
@@ -531,8 +565,8 @@ extern "C" int gpx_matern_propagate_approx_many(gpx_handle *h, const double *U, 
     const MaternData *md = h->mat;
     return approx_many_run(h, md->d, U, Sigma, sigma_shared, b, mean, var, sigma2, rest, "gpx_matern_propagate_approx_many",
                            [&](const double *ud, const double *sd, int64_t sstride, int64_t bc, int64_t mp) -> int {
-                               return launch_matern52_build_many(false, md->x, h->n, h->npad, md->d, ud, sd, sstride, bc, mp, md->wdev, md->v, md->vt, h->Z,
-                                                                 h->stream, &h->prof);
+                               return launch_matern_build_many(MB_APPROX, 5, md->x, h->n, h->npad, md->d, ud, sd, sstride, bc, mp, md->wdev, md->v, md->vt,
+                                                               h->Z, h->stream, &h->prof);
                            });
 }
 
@@ -544,7 +578,7 @@ extern "C" int gpx_matern_propagate_dvh_many(gpx_handle *h, const double *U, int
     const MaternData *md = h->mat;
     return dvh_many_run(h, md->d, U, b, dvh_out, sigma2_out, "gpx_matern_propagate_dvh_many",
                         [&](const double *ud, const double *, int64_t, int64_t bc, int64_t mp) -> int {
-                            return launch_matern52_build_many(true, md->x, h->n, h->npad, md->d, ud, nullptr, 0, bc, mp, md->wdev, md->v, md->vt, h->Z,
-                                                              h->stream, &h->prof);
+                            return launch_matern_build_many(MB_DVH, 5, md->x, h->n, h->npad, md->d, ud, nullptr, 0, bc, mp, md->wdev, md->v, md->vt,
+                                                            h->Z, h->stream, &h->prof);
                         });
 }

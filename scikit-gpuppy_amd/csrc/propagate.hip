@@ -123,11 +123,12 @@ int launch_dot_pairs(const std::vector<std::pair<const double *, const double *>
 // wave; the x tile sits in LDS k-major as in gram_kernel, and the input's u, w, Sigma are wave-uniform: they come through the
 // scalar cache (loads only).  One exp per (input, column).  DR > 0: d <= DR and the scaled differences w_k (x_ik - u_k) stay
 // in registers; DR = 0: any d, they are recomputed from the LDS tile.
+// GRAD: the row layout of gpx_predict_grad instead -- row b (d + 1) + r is [C, J_1..J_d]: no tr row, Sigma is not read.
 // ---------------------------------------------------------------------------------------------
 constexpr int AB_COLS = 128;
 constexpr int AB_INPUTS = 16;
 
-template <int DR>
+template <int DR, bool GRAD = false>
 __global__ __launch_bounds__(256) void approx_build_many_kernel(const double *__restrict__ x, long n, long npad, int d,
                                                                const double *__restrict__ U, const double *__restrict__ Sigma,
                                                                long sigma_stride, long nb, const double *__restrict__ w, double v,
@@ -146,11 +147,11 @@ __global__ __launch_bounds__(256) void approx_build_many_kernel(const double *__
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
     const long c = col0 + 2 * lane;
     const bool in0 = c < n, in1 = c + 1 < n;
-    const int nrow = d + 2;
+    const int nrow = GRAD ? d + 1 : d + 2, jrow = GRAD ? 1 : 2;   // jrow: first row of J
     for (int j = 0; j < AB_INPUTS / 4; ++j) {
         const long b = (long)blockIdx.y * AB_INPUTS + 4 * j + wave;   // wave-uniform
         if (b >= nb) break;
-        const double *u = U + b * d, *S = Sigma + b * sigma_stride;
+        const double *u = U + b * d, *S = GRAD ? nullptr : Sigma + b * sigma_stride;
         double *zrow = Z + b * nrow * npad + c;
         double wd0[DR > 0 ? DR : 1], wd1[DR > 0 ? DR : 1];
         double q0 = 0.0, q1 = 0.0;
@@ -192,44 +193,50 @@ __global__ __launch_bounds__(256) void approx_build_many_kernel(const double *__
 #pragma unroll
             for (int a = 0; a < DR; ++a) {
                 if (a < d) {
-                    double r0 = 0.0, r1 = 0.0;
+                    if constexpr (!GRAD) {
+                        double r0 = 0.0, r1 = 0.0;
 #pragma unroll
-                    for (int e = 0; e < DR; ++e)
-                        if (e < d) {
-                            const double sg = S[a * d + e];
-                            r0 = fma(sg, wd0[e], r0);
-                            r1 = fma(sg, wd1[e], r1);
-                        }
-                    s0 = fma(wd0[a], r0, s0);
-                    s1 = fma(wd1[a], r1, s1);
-                    wdiag = fma(w[a], S[a * d + a], wdiag);
+                        for (int e = 0; e < DR; ++e)
+                            if (e < d) {
+                                const double sg = S[a * d + e];
+                                r0 = fma(sg, wd0[e], r0);
+                                r1 = fma(sg, wd1[e], r1);
+                            }
+                        s0 = fma(wd0[a], r0, s0);
+                        s1 = fma(wd1[a], r1, s1);
+                        wdiag = fma(w[a], S[a * d + a], wdiag);
+                    }
                     v2d jk;
                     jk.x = -wd0[a] * c0; jk.y = -wd1[a] * c1;
-                    *reinterpret_cast<v2d *>(zrow + (long)(2 + a) * npad) = jk;
+                    *reinterpret_cast<v2d *>(zrow + (long)(jrow + a) * npad) = jk;
                 }
             }
         } else {
             for (int a = 0; a < d; ++a) {
-                double r0 = 0.0, r1 = 0.0;
-                for (int e = 0; e < d; ++e) {
-                    const v2d xv = *reinterpret_cast<const v2d *>(&x_s[e * AB_COLS + 2 * lane]);
-                    const double sg = S[a * d + e], ue = u[e], we = w[e];
-                    r0 = fma(sg, we * (xv.x - ue), r0);
-                    r1 = fma(sg, we * (xv.y - ue), r1);
-                }
                 const v2d xa = *reinterpret_cast<const v2d *>(&x_s[a * AB_COLS + 2 * lane]);
                 const double a0 = w[a] * (xa.x - u[a]), a1 = w[a] * (xa.y - u[a]);
-                s0 = fma(a0, r0, s0);
-                s1 = fma(a1, r1, s1);
-                wdiag = fma(w[a], S[a * d + a], wdiag);
+                if constexpr (!GRAD) {
+                    double r0 = 0.0, r1 = 0.0;
+                    for (int e = 0; e < d; ++e) {
+                        const v2d xv = *reinterpret_cast<const v2d *>(&x_s[e * AB_COLS + 2 * lane]);
+                        const double sg = S[a * d + e], ue = u[e], we = w[e];
+                        r0 = fma(sg, we * (xv.x - ue), r0);
+                        r1 = fma(sg, we * (xv.y - ue), r1);
+                    }
+                    s0 = fma(a0, r0, s0);
+                    s1 = fma(a1, r1, s1);
+                    wdiag = fma(w[a], S[a * d + a], wdiag);
+                }
                 v2d jk;
                 jk.x = -a0 * c0; jk.y = -a1 * c1;
-                *reinterpret_cast<v2d *>(zrow + (long)(2 + a) * npad) = jk;
+                *reinterpret_cast<v2d *>(zrow + (long)(jrow + a) * npad) = jk;
             }
         }
-        o.x = c0 * (s0 - wdiag);
-        o.y = c1 * (s1 - wdiag);
-        *reinterpret_cast<v2d *>(zrow + npad) = o;
+        if constexpr (!GRAD) {
+            o.x = c0 * (s0 - wdiag);
+            o.y = c1 * (s1 - wdiag);
+            *reinterpret_cast<v2d *>(zrow + npad) = o;
+        }
     }
 }
 
@@ -251,6 +258,27 @@ int launch_approx_build_many(const double *x, int64_t n, int64_t npad, int d, co
     else
         hipLaunchKernelGGL(approx_build_many_kernel<0>, grid, dim3(256), lds, s, x, (long)n, (long)npad, d, U_dev, Sigma_dev,
                            (long)sigma_stride, (long)nb, w_dev, v, vt, Z);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// the rows of gpx_predict_grad: Z [rows_pad, npad], rows [0, nb (d + 1)) = [C, J_1..J_d] per query, the rest of the last tile cleared
+int launch_grad_build_many(const double *x, int64_t n, int64_t npad, int d, const double *U_dev, int64_t nb, int64_t rows_pad, const double *w_dev,
+                           double v, double vt, double *Z, hipStream_t s, Profiler *prof)
+{
+    if (nb <= 0) return 0;
+    const int64_t rows = nb * (d + 1);
+    if (npad % AB_COLS || rows > rows_pad || d < 1 || d > GPX_MAX_D) { gpx_set_error("grad_build_many: bad block shape"); return GPX_ERR_BAD_ARG; }
+    ProfScope ps(prof, s, GPX_K_GRAM, 8.0 * (double)rows_pad * (double)npad);
+    if (rows_pad > rows) GPX_HIP(hipMemsetAsync(Z + rows * npad, 0, sizeof(double) * (rows_pad - rows) * npad, s));
+    const dim3 grid((unsigned)(npad / AB_COLS), (unsigned)((nb + AB_INPUTS - 1) / AB_INPUTS));
+    const size_t lds = sizeof(double) * AB_COLS * d;
+    if (d <= 8)
+        hipLaunchKernelGGL((approx_build_many_kernel<8, true>), grid, dim3(256), lds, s, x, (long)n, (long)npad, d, U_dev, (const double *)nullptr, 0L,
+                           (long)nb, w_dev, v, vt, Z);
+    else
+        hipLaunchKernelGGL((approx_build_many_kernel<0, true>), grid, dim3(256), lds, s, x, (long)n, (long)npad, d, U_dev, (const double *)nullptr, 0L,
+                           (long)nb, w_dev, v, vt, Z);
     GPX_HIP(hipGetLastError());
     return 0;
 }

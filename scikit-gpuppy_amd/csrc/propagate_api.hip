@@ -368,6 +368,105 @@ extern "C" int gpx_propagate_dvh_many(gpx_handle *h, const double *U, int64_t b,
                         });
 }
 
+// ---- the predictor's input gradients (kernels: predict_grad.hip) -----------------------------------------------------------------------
+// b queries as b (d + 1) right-hand sides [C, J_1..J_d] of the many-right-hand-side solver, the loop of gpx_propagate_approx_many with one row
+// fewer: mean = z_C.y, var = (v + vt) - |z_C|^2, dmean_k = -z_Jk.y, dvar_k = 2 z_C.z_Jk.  One synchronisation per chunk; a query never
+// straddles two chunks.
+int grad_many_run(gpx_handle *h, int d, const double *U, int64_t b, double *mean, double *var, double *dmean, double *dvar, const char *what,
+                  const RowsBuild &build)
+{
+    if (b < 0 || (b > 0 && (!U || !mean || !var || !dvar))) { gpx_set_error("%s: bad arguments", what); return GPX_ERR_BAD_ARG; }
+    if (b == 0) return 0;
+    hipStream_t s = h->stream;
+    const int nrow = d + 1;
+    RowSolve rs(s);
+    GPX_TRY(row_solve_begin(h, b * nrow, rs));
+    const int64_t bchunk = rs.chunk / nrow;           // queries per chunk (chunk >= 128 > d + 1)
+    double *ud = nullptr, *od = nullptr;
+    int rc = 0;
+    GPX_TRY(rs.sc.take(&ud, bchunk * d));
+    GPX_TRY(rs.sc.take(&od, bchunk * (2 + 2 * d)));   // mean [bchunk] | var [bchunk] | dmean [bchunk, d] | dvar [bchunk, d]
+    double *vd = od + bchunk, *dmd = vd + bchunk, *dvd = dmd + bchunk * d;
+    for (int64_t b0 = 0; b0 < b && rc == 0; b0 += bchunk) {
+        const int64_t bc = std::min<int64_t>(bchunk, b - b0), mc = bc * nrow, mp = round_up(mc, TILE);
+        hipError_t e = hipMemcpyAsync(ud, U + b0 * d, sizeof(double) * bc * d, hipMemcpyDefault, s);
+        if (e != hipSuccess) { gpx_set_error("copy xs failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
+        if ((rc = build(ud, nullptr, 0, bc, mp))) break;
+        if ((rc = row_solve_run(h, rs, mc, mp, nullptr))) break;
+        if ((rc = launch_grad_reduce_many(rs.Zs, h->npad, d, h->y, bc, h->v + h->vt, od, vd, dmean ? dmd : nullptr, dvd, s, &h->prof))) break;
+        e = hipMemcpyAsync(mean + b0, od, sizeof(double) * bc, hipMemcpyDefault, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(var + b0, vd, sizeof(double) * bc, hipMemcpyDefault, s);
+        if (e == hipSuccess && dmean) e = hipMemcpyAsync(dmean + b0 * d, dmd, sizeof(double) * bc * d, hipMemcpyDefault, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(dvar + b0 * d, dvd, sizeof(double) * bc * d, hipMemcpyDefault, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) { gpx_set_error("gradient copy-out failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
+    }
+    return rc;
+}
+
+// The value differentiated is the handle's own predictor.  gpx_matern_predict's cross-covariance rows carry +vt where a query equals a training
+// row elementwise (handle_gram_has_vt), gpx_predict's on a Gaussian handle do not (GaussianCovariance.cov_matrix_ij is the vectorised Gram
+// without it, Covariance.py:466-483): the C row of a Gaussian handle is therefore built with vt = 0 here, so that mean and variance are
+// gpx_predict's at every query.  No derivative carries the term on either kind.
+static inline double grad_row_vt(const gpx_handle *h) { return handle_gram_has_vt(h) ? h->mat->vt : 0.0; }
+
+// the kinds that have a closed-form input gradient: gpx_fit (Gaussian) and gpx_matern_fit (either nu) handles
+static int need_grad_kernel(const gpx_handle *h, const char *what)
+{
+    if (h->kind == KernelKind::Gaussian || h->kind == KernelKind::Matern) return 0;
+    if (h->kind == KernelKind::Periodic)
+        gpx_set_error("%s: the handle holds a PeriodicCovariance model (gpx_periodic_fit): no closed-form input gradient of that kernel is built", what);
+    else
+        gpx_set_error("%s: the handle was built from a supplied matrix (gpx_fit_matrix): no inputs / theta to differentiate the kernel on", what);
+    return GPX_ERR_STATE;
+}
+
+extern "C" int gpx_predict_mean_grad(gpx_handle *h, const double *xs, int64_t m, double *mean_out, double *dmean_out)
+{
+    CHECK_H(h);
+    if (m < 0 || (m > 0 && (!xs || (!mean_out && !dmean_out)))) { gpx_set_error("gpx_predict_mean_grad: bad arguments"); return GPX_ERR_BAD_ARG; }
+    GPX_TRY(need_grad_kernel(h, "gpx_predict_mean_grad"));
+    if (m == 0) return 0;
+    const bool matern = h->kind == KernelKind::Matern;
+    const MaternData *md = h->mat;
+    const int d = handle_dim(h);
+    const int S = predict_mean_grad_splits(m, h->npad);
+    hipStream_t s = h->stream;
+    Scratch sc(s);
+    double *ud = nullptr, *part = nullptr, *od = nullptr;
+    GPX_TRY(sc.take(&ud, m * d));
+    GPX_TRY(sc.take(&part, (int64_t)S * m * (1 + d)));
+    GPX_TRY(sc.take(&od, m * (1 + d)));
+    double *dmd = od + m;
+    GPX_HIP(hipMemcpyAsync(ud, xs, sizeof(double) * m * d, hipMemcpyDefault, s));
+    GPX_TRY(launch_predict_mean_grad(matern ? md->x : h->x, h->n, h->npad, d, matern ? md->nu2 : 0, ud, m, matern ? md->wdev : h->wdev, h->alpha,
+                                     matern ? md->v : h->v, grad_row_vt(h), S, part, mean_out ? od : nullptr, dmean_out ? dmd : nullptr, s,
+                                     &h->prof));
+    if (mean_out) GPX_HIP(hipMemcpyAsync(mean_out, od, sizeof(double) * m, hipMemcpyDefault, s));
+    if (dmean_out) GPX_HIP(hipMemcpyAsync(dmean_out, dmd, sizeof(double) * m * d, hipMemcpyDefault, s));
+    const hipError_t e = sc.wait_and_free();
+    if (e != hipSuccess) { gpx_set_error("gpx_predict_mean_grad: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
+    return 0;
+}
+
+extern "C" int gpx_predict_grad(gpx_handle *h, const double *xs, int64_t m, double *mean_out, double *var_out, double *dmean_out, double *dvar_out)
+{
+    CHECK_H(h);
+    if (m < 0 || (m > 0 && (!xs || !mean_out || !var_out || !dvar_out))) { gpx_set_error("gpx_predict_grad: bad arguments"); return GPX_ERR_BAD_ARG; }
+    GPX_TRY(need_grad_kernel(h, "gpx_predict_grad"));
+    if (h->kind == KernelKind::Matern) {
+        const MaternData *md = h->mat;
+        return grad_many_run(h, md->d, xs, m, mean_out, var_out, dmean_out, dvar_out, "gpx_predict_grad",
+                             [&](const double *ud, const double *, int64_t, int64_t bc, int64_t mp) -> int {
+                                 return launch_matern_grad_build_many(md, h->n, h->npad, ud, bc, mp, h->Z, h->stream, &h->prof);
+                             });
+    }
+    return grad_many_run(h, h->d, xs, m, mean_out, var_out, dmean_out, dvar_out, "gpx_predict_grad",
+                         [&](const double *ud, const double *, int64_t, int64_t bc, int64_t mp) -> int {
+                             return launch_grad_build_many(h->x, h->n, h->npad, h->d, ud, bc, mp, h->wdev, h->v, grad_row_vt(h), h->Z, h->stream, &h->prof);
+                         });
+}
+
 // ---- numerical propagation (UncertaintyPropagation.py:90-162; kernels: quadrature.hip) -----------------------------------------------
 // a caller's array (host or device pointer) into a block of the call's scratch, queued on its stream
 static int stage_in(Scratch &sc, const double *src, int64_t count, double **dst)

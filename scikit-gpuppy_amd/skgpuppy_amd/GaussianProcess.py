@@ -252,6 +252,43 @@ class GaussianProcess(object):
         mean, var = self._dev().predict(xs)
         return mean[0] + self.meant, var[0]
 
+    # ---- input gradients of the predictor (no reference counterpart: UncertaintyPropagation.py:214-227 takes central differences) ----
+    def estimate_many_gradient(self, x_stars, variance=True, h=1e-5):
+        """(mean + meant [M], var [M], d mean / d x* [M, d], d var / d x* [M, d]) at M query points; variance=False: (mean + meant,
+        d mean / d x*) alone.
+
+        Routes "gaussian" and "matern" (either nu) are fused: both gradients are closed-form sums over what the handle holds --
+        gpx_predict_grad solves d + 1 rows per query, and variance=False (gpx_predict_mean_grad) needs alpha alone: no solve.  Every other
+        route (periodic, a generic operator, SPGP) takes central differences of step h through ONE estimate_many call on the 2 d M
+        perturbed points -- the reference's _derivative, batched.  The operator's get_Jacobian is not consulted: its sign is the
+        reference's convention (Covariance.py:687), which a user subclass need not share."""
+        xs = _gpx.f64(np.array(x_stars))
+        if xs.ndim != 2 or xs.shape[1] != self.d:
+            raise ValueError("x_stars must be (m, %d)" % self.d)
+        m, d = xs.shape
+        if self._route() in ("gaussian", "matern"):
+            handle = self._dev().handle
+            mean, dmean = np.empty(m), np.empty((m, d))
+            if not variance:
+                _gpx.check(_gpx.lib.gpx_predict_mean_grad(handle, _gpx.ptr(xs), m, _gpx.ptr(mean), _gpx.ptr(dmean)), "gpx_predict_mean_grad")
+                return mean + self.meant, dmean
+            var, dvar = np.empty(m), np.empty((m, d))
+            _gpx.check(_gpx.lib.gpx_predict_grad(handle, _gpx.ptr(xs), m, _gpx.ptr(mean), _gpx.ptr(var), _gpx.ptr(dmean), _gpx.ptr(dvar)),
+                       "gpx_predict_grad")
+            return mean + self.meant, var, dmean, dvar
+        # rows [0, M): the points; then per k the M points moved by -h and the M moved by +h along k
+        pts = np.concatenate([xs[None]] + [xs[None] + s * h * np.eye(d)[k] for k in range(d) for s in (-1.0, 1.0)]).reshape(-1, d)
+        mu, var = self.estimate_many(pts)
+        mu, var = np.asarray(mu).reshape(2 * d + 1, m), np.asarray(var).reshape(2 * d + 1, m)
+        dmean = ((mu[2::2] - mu[1::2]) / (2.0 * h)).T
+        if not variance:
+            return mu[0], dmean
+        return mu[0], var[0], dmean, ((var[2::2] - var[1::2]) / (2.0 * h)).T
+
+    def estimate_gradient(self, x_star, variance=True, h=1e-5):
+        """single-point twin of estimate_many_gradient: scalars for mean and var, [d] for the gradients"""
+        return tuple(o[0] for o in self.estimate_many_gradient(np.atleast_2d(np.array(x_star)), variance, h))
+
     def _get_beta(self):
         # beta = K^-1 t (GaussianProcess.py:114-119)
         if self._route() == "spgp":

@@ -302,6 +302,59 @@ class UncertaintyPropagationApprox(UncertaintyPropagationGA):
         return dvh, sigma2
 
 
+class UncertaintyPropagationLinear(UncertaintyPropagationGA):
+    """First-order (delta-method) propagation (UncertaintyPropagation.py:213-242): mean = mu(u), variance = sum_k g_k^2 Sigma_kk + vt with
+    g = d mu / d u -- the DIAGONAL of Sigma_x only, plus vt, as the reference has it.
+
+    The reference takes g by central differences of gp(x)[0], 2 d calls of estimate per input.  With the built-in Gaussian and Matern
+    kernels g is the closed-form sum over alpha (GaussianProcess.estimate_many_gradient(variance=False), gpx_predict_mean_grad): one
+    fused pass over the B x N pairs for a whole batch and no solve at all.  Every other route takes the reference's differences, batched
+    into one estimate_many call."""
+
+    def _mean_grad(self, U):
+        """(mean WITHOUT meant [B], g [B, d])"""
+        gp = self.gp
+        if gp._route() in ("gaussian", "matern"):
+            UU = _gpx.f64(U)
+            mean, g = np.empty(len(UU)), np.empty(UU.shape)
+            _gpx.check(_gpx.lib.gpx_predict_mean_grad(gp._dev().handle, _gpx.ptr(UU), len(UU), _gpx.ptr(mean), _gpx.ptr(g)), "gpx_predict_mean_grad")
+            return mean, g
+        mean, g = gp.estimate_many_gradient(U, variance=False)
+        return mean - gp._get_mean_t(), g
+
+    def _derivative(self, x, i, d=1e-5):
+        """d mu / d x_i at x (UncertaintyPropagation.py:214-227): analytic on the fused routes (d is not used there), the reference's
+        central difference of step d otherwise"""
+        return np.float64(self.gp.estimate_many_gradient(np.atleast_2d(_gpx.f64(x)), variance=False, h=d)[1][0, i])
+
+    def propagate_mean(self, u, Sigma_x):
+        # (UncertaintyPropagation.py:229-231): gp(u)[0], meant included
+        uu, _S = _u_sigma(self.gp, u, Sigma_x)
+        return np.float64(self._mean_grad(uu[None, :])[0][0] + self.gp._get_mean_t())
+
+    def propagate_GA(self, u, Sigma_x):
+        # (UncertaintyPropagation.py:233-242)
+        uu, S = _u_sigma(self.gp, u, Sigma_x)
+        mean, var = self.propagate_GA_many(uu[None, :], S)
+        return np.float64(mean[0]), np.float64(var[0])
+
+    # ---- many inputs in one call ----
+    def propagate_mean_many(self, U, Sigma_x):
+        """propagate_mean for the rows of U (B, d); Sigma_x (d, d) for all of them or (B, d, d): means [B] WITHOUT meant"""
+        UU, _S = self._many_args(U, Sigma_x)
+        return self._mean_grad(UU)[0]
+
+    def propagate_GA_many(self, U, Sigma_x):
+        """propagate_GA for the rows of U (B, d); Sigma_x (d, d) for all of them or (B, d, d): (means [B] with meant, variances [B])"""
+        UU, S = self._many_args(U, Sigma_x)
+        mean, g = self._mean_grad(UU)
+        sd = np.diagonal(S, axis1=-2, axis2=-1)             # (d,) or (B, d)
+        var = np.zeros(len(UU))
+        for k in range(UU.shape[1]):                        # the reference's order of the sum (:236-238), then + vt (:240)
+            var = var + g[:, k] ** 2 * (sd[k] if S.ndim == 2 else sd[:, k])
+        return mean + self.gp._get_mean_t(), var + self.gp._get_vt()
+
+
 class _ExplicitInverse(object):
     """Owner of one gpx_kinv_model: an explicit K^-1 / beta resident in HBM (gpx.h)."""
 

@@ -11,6 +11,7 @@ from .UncertaintyPropagation import (  # noqa: F401
     UncertaintyPropagationApprox,
     UncertaintyPropagationExact,
     UncertaintyPropagationGA,
+    UncertaintyPropagationLinear,
     UncertaintyPropagation,
     UncertaintyPropagationMC,
     UncertaintyPropagationNumericalHG,
@@ -25,7 +26,7 @@ from .InverseUncertaintyPropagation import (  # noqa: F401,E402
 __all__ = [
     "Covariance", "GaussianCovariance", "MaternCovariance", "PeriodicCovariance", "SPGPCovariance", "GaussianProcess",
     "UncertaintyPropagationGA",
-    "UncertaintyPropagationApprox", "UncertaintyPropagationExact", "tracedot",
+    "UncertaintyPropagationApprox", "UncertaintyPropagationExact", "UncertaintyPropagationLinear", "tracedot",
     "UncertaintyPropagation", "UncertaintyPropagationMC", "UncertaintyPropagationNumericalHG",
     "InverseUncertaintyPropagation", "InverseUncertaintyPropagationApprox", "InverseUncertaintyPropagationNumerical",
 ]

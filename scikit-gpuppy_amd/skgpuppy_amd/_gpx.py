@@ -66,6 +66,8 @@ SIGNATURES = {
     "gpx_logdet": (_int, [_hp, ctypes.POINTER(_dbl)]),
     "gpx_spd_inverse": (_int, [_dp, _i64, _dp, ctypes.POINTER(_dbl)]),
     "gpx_predict": (_int, [_hp, _dp, _i64, _dp, _dp]),
+    "gpx_predict_mean_grad": (_int, [_hp, _dp, _i64, _dp, _dp]),
+    "gpx_predict_grad": (_int, [_hp, _dp, _i64, _dp, _dp, _dp, _dp]),
     "gpx_alpha": (_int, [_hp, _dp]),
     "gpx_solve": (_int, [_hp, _dp, _int, _dp, _dp]),
     "gpx_chol_mul": (_int, [_hp, _dp, _int, _dp]),
