@@ -315,6 +315,26 @@ int gpx_matern_propagate_approx_many(gpx_handle *h, const double *U, const doubl
                                      double *mean, double *var, double *sigma2, double *rest);
 int gpx_matern_propagate_dvh_many(gpx_handle *h, const double *U, int64_t b, double *dvh_out /* [b, d] */, double *sigma2_out /* [b], may be NULL */);
 
+/* ---- test / tool access: the two kernel stages at the ends of the batched calls (gpx_propagate_approx_many, gpx_propagate_dvh_many,
+ * gpx_predict_grad, gpx_matern_propagate_*_many), each alone: no solve in either ---- */
+#define GPX_ROWS_APPROX 0   /* d + 2 rows an input: [C, tr, J_1..J_d]          */
+#define GPX_ROWS_DVH    1   /* 2 d + 1 rows:        [C, J_1..J_d, H_11..H_dd]  */
+#define GPX_ROWS_GRAD   2   /* d + 1 rows:          [C, J_1..J_d]              */
+/* or-ed into gpx_rows_reduce's layout: the kernel is launched with its nullable output null (sigma2 of DVH, dmean of GRAD), as
+ * gpx_propagate_dvh_many with sigma2_out = NULL and gpx_predict_grad with dmean_out = NULL launch it; that part of out is left as it was */
+#define GPX_ROWS_SKIP_NULLABLE 0x100
+/* the right-hand-side rows of b inputs as the batched call of this handle's kind would build them (the same launch, from the same
+ * dispatch), before any solve: rows_out [round_up(b * nrow, 128), npad], host.  U [b, d]; Sigma [b, d, d], or ONE [d, d] when
+ * sigma_shared != 0, read for GPX_ROWS_APPROX alone (may be NULL otherwise).  gpx_fit handles: every layout; gpx_matern_fit with nu = 5/2:
+ * every layout, with nu = 3/2: GPX_ROWS_GRAD; every other combination GPX_ERR_STATE.  A batch of more rows than one chunk of the batched
+ * calls (32768 rows, fewer from npad = 32768 on), a NULL handle or pointer: GPX_ERR_BAD_ARG before anything is written.  b = 0 is a no-op. */
+int gpx_rows_build(gpx_handle *h, int layout, const double *U, const double *Sigma, int sigma_shared, int64_t b, double *rows_out);
+/* the row reduction alone on caller arrays (host or device pointers): Zs [b * nrow, npad] (npad a multiple of 128), y [npad]; Sigma as
+ * above, read for GPX_ROWS_APPROX alone; out in the layout of the batched calls' device buffer:
+ *   APPROX [4, b] = mean | var | sigma2 | rest;   DVH dvh [b, d] then sigma2 [b];   GRAD mean [b] | var [b] | dmean [b, d] | dvar [b, d] */
+int gpx_rows_reduce(int layout, int d, int64_t npad, const double *Zs, const double *y, const double *Sigma, int sigma_shared,
+                    int64_t b, double vplusvt, double *out);
+
 /* ---- "next" row f3: Snelson sparse pseudo-input GP (SPGPCovariance, skgpuppy/Covariance.py:692-1019) ----
  * theta = [log v, log vt, log w_1..d] (the GaussianCovariance part of the reference's theta), xb = the m x d
  * pseudo-inputs (the tail of the reference's theta, reshaped).  The fit keeps K_NM, chol(K_M + 1e-5 I),

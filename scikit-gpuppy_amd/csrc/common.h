@@ -221,9 +221,11 @@ void matern_release(MaternData *md);
 // inputs; lower_only / pad_mode / padding contract as launch_gram.  deriv >= 0: d K / d theta_deriv instead (no add_diag)
 int launch_matern_gram(const double *xi, int64_t n1, const double *xj, int64_t n2, const MaternData *md, double add_diag, int lower_only,
                        int pad_mode, double *out, int64_t ld, int64_t rows_pad, int64_t cols_pad, hipStream_t s, Profiler *prof, int deriv = -1);
-// rows [C, J_1..J_d] of nb queries (gpx_predict_grad), nu = 3/2 or 5/2: Z [rows_pad, npad], the rest of the last 128-row tile cleared
-int launch_matern_grad_build_many(const MaternData *md, int64_t n, int64_t npad, const double *U_dev, int64_t nb, int64_t rows_pad, double *Z,
-                                  hipStream_t s, Profiler *prof);
+// the right-hand-side rows of nb inputs in the row layout `layout` (GPX_ROWS_*; nu2 = 3: GPX_ROWS_GRAD alone; Sigma read for GPX_ROWS_APPROX
+// alone): Z [rows_pad, npad], the rest of the last 128-row tile cleared
+int launch_matern_build_many(int layout, int nu2, const double *x, int64_t n, int64_t npad, int d, const double *U_dev, const double *Sigma_dev,
+                             int64_t sigma_stride, int64_t nb, int64_t rows_pad, const double *w_dev, double v, double vt, double *Z, hipStream_t s,
+                             Profiler *prof);
 constexpr int MAT_KC = 8;                        // coordinates per sweep of the gradient pass
 constexpr int MAT_NC = MAT_KC + 2;               // sums per sweep: S_0, A_k of the sweep's k, T
 
@@ -538,6 +540,7 @@ struct RowSolve {
 // allow_few = false: the many-row solver whatever m is (a caller that promises results independent of the batch); chunk_cap > 0: at
 // most that many rows a chunk (a multiple of 128)
 int row_solve_begin(gpx_handle *h, int64_t m, RowSolve &rs, bool bounded = false, bool allow_few = true, int64_t chunk_cap = 0);
+int64_t row_solve_chunk_cap(const gpx_handle *h, int64_t chunk_cap = 0);   // the most rows of a chunk (a multiple of 128)
 // Zs[0 : mp) <- Z[0 : mp) L^-T (mc real rows, mp = mc rounded up to the tile); red: the fused row sums of tsolve.hip (many rows only)
 int row_solve_run(gpx_handle *h, const RowSolve &rs, int64_t mc, int64_t mp, const GemmReduce *red, bool left = false);
 
@@ -545,6 +548,9 @@ int row_solve_run(gpx_handle *h, const RowSolve &rs, int64_t mc, int64_t mp, con
 // sides: build(U_dev, Sigma_dev, sigma_stride, bc, mp) writes the rows of bc inputs into h->Z [mp, npad] (d + 2 rows an input:
 // [C, tr, J_1..J_d]; 2 d + 1: [C, J_1..J_d, H_11..H_dd], no Sigma); the solve, the row reductions and the copies are the loops' own.
 using RowsBuild = std::function<int(const double *, const double *, int64_t, int64_t, int64_t)>;
+// The build of the handle's kind for a row layout (GPX_ROWS_*): the ONE place that launches the build kernels, for the five batched entry
+// points and for gpx_rows_build alike.  The caller has checked that the kind has the layout (Gaussian: all; Matern 5/2: all; 3/2: GRAD).
+RowsBuild rows_build_of(gpx_handle *h, int layout);
 int approx_many_run(gpx_handle *h, int d, const double *U, const double *Sigma, int sigma_shared, int64_t b, double *mean, double *var, double *sigma2,
                     double *rest, const char *what, const RowsBuild &build);
 int dvh_many_run(gpx_handle *h, int d, const double *U, int64_t b, double *dvh_out, double *sigma2_out, const char *what, const RowsBuild &build);

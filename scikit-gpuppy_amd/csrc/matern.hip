@@ -235,7 +235,7 @@ static int launch_matern_nll_grad(const double *Kinv, int64_t ld, int64_t n, int
 constexpr int MB_COLS = 128;
 constexpr int MB_INPUTS = 16;
 
-enum { MB_APPROX = 0, MB_DVH = 1, MB_GRAD = 2 };
+enum { MB_APPROX = GPX_ROWS_APPROX, MB_DVH = GPX_ROWS_DVH, MB_GRAD = GPX_ROWS_GRAD };   // the public row layouts (include/gpx.h)
 
 template <int DR, int ROWS, int NU2>
 __device__ __forceinline__ void matern_build_many(const double *__restrict__ x, long n, long npad, int d, const double *__restrict__ U,
@@ -389,9 +389,9 @@ __global__ __launch_bounds__(256) void matern_grad_build_many_kernel(const doubl
 }
 
 // Z [rows_pad, npad]: rows [0, nb nrow) written by the kernel (every column, zeros from n on), the rest of the last 128-row tile cleared
-static int launch_matern_build_many(int layout, int nu2, const double *x, int64_t n, int64_t npad, int d, const double *U_dev, const double *Sigma_dev,
-                                    int64_t sigma_stride, int64_t nb, int64_t rows_pad, const double *w_dev, double v, double vt, double *Z,
-                                    hipStream_t s, Profiler *prof)
+int launch_matern_build_many(int layout, int nu2, const double *x, int64_t n, int64_t npad, int d, const double *U_dev, const double *Sigma_dev,
+                             int64_t sigma_stride, int64_t nb, int64_t rows_pad, const double *w_dev, double v, double vt, double *Z, hipStream_t s,
+                             Profiler *prof)
 {
     if (nb <= 0) return 0;
     const bool dvh = layout == MB_DVH;
@@ -420,13 +420,6 @@ static int launch_matern_build_many(int layout, int nu2, const double *x, int64_
 #undef MATERN_GRAD_BUILD
     GPX_HIP(hipGetLastError());
     return 0;
-}
-
-// rows [C, J_1..J_d] of nb queries for gpx_predict_grad (propagate_api.hip), either nu
-int launch_matern_grad_build_many(const MaternData *md, int64_t n, int64_t npad, const double *U_dev, int64_t nb, int64_t rows_pad, double *Z,
-                                  hipStream_t s, Profiler *prof)
-{
-    return launch_matern_build_many(MB_GRAD, md->nu2, md->x, n, npad, md->d, U_dev, nullptr, 0, nb, rows_pad, md->wdev, md->v, md->vt, Z, s, prof);
 }
 
 // ---- parameters and inputs of a Matern model ----------------------------------------------------------------------
@@ -562,12 +555,8 @@ extern "C" int gpx_matern_propagate_approx_many(gpx_handle *h, const double *U, 
 {
     CHECK_H(h);
     NEED_MATERN52(h, "gpx_matern_propagate_approx_many");
-    const MaternData *md = h->mat;
-    return approx_many_run(h, md->d, U, Sigma, sigma_shared, b, mean, var, sigma2, rest, "gpx_matern_propagate_approx_many",
-                           [&](const double *ud, const double *sd, int64_t sstride, int64_t bc, int64_t mp) -> int {
-                               return launch_matern_build_many(MB_APPROX, 5, md->x, h->n, h->npad, md->d, ud, sd, sstride, bc, mp, md->wdev, md->v, md->vt,
-                                                               h->Z, h->stream, &h->prof);
-                           });
+    return approx_many_run(h, h->mat->d, U, Sigma, sigma_shared, b, mean, var, sigma2, rest, "gpx_matern_propagate_approx_many",
+                           rows_build_of(h, GPX_ROWS_APPROX));
 }
 
 // get_best_solution_many's dvh (and sigma2) with cov = MaternCovariance(2.5): gpx_propagate_dvh_many's loop
@@ -575,10 +564,5 @@ extern "C" int gpx_matern_propagate_dvh_many(gpx_handle *h, const double *U, int
 {
     CHECK_H(h);
     NEED_MATERN52(h, "gpx_matern_propagate_dvh_many");
-    const MaternData *md = h->mat;
-    return dvh_many_run(h, md->d, U, b, dvh_out, sigma2_out, "gpx_matern_propagate_dvh_many",
-                        [&](const double *ud, const double *, int64_t, int64_t bc, int64_t mp) -> int {
-                            return launch_matern_build_many(MB_DVH, 5, md->x, h->n, h->npad, md->d, ud, nullptr, 0, bc, mp, md->wdev, md->v, md->vt,
-                                                            h->Z, h->stream, &h->prof);
-                        });
+    return dvh_many_run(h, h->mat->d, U, b, dvh_out, sigma2_out, "gpx_matern_propagate_dvh_many", rows_build_of(h, GPX_ROWS_DVH));
 }

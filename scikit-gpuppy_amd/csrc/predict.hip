@@ -18,13 +18,18 @@ int ensure_Z(gpx_handle *h, int64_t rows)
 }
 
 // ---- predict (RowSolve: common.h) ----------------------------------------------------------------
-int row_solve_begin(gpx_handle *h, int64_t m, RowSolve &rs, bool bounded, bool allow_few, int64_t chunk_cap)
+int64_t row_solve_chunk_cap(const gpx_handle *h, int64_t chunk_cap)
 {
     int64_t cap = ((int64_t)8 << 30) / (h->npad * (int64_t)sizeof(double));   // rows per 8 GB buffer (two of them: Z and Zs)
     cap = std::max<int64_t>(TILE, cap / TILE * TILE);
     cap = std::min<int64_t>(cap, 32768);
     if (chunk_cap > 0) cap = std::min<int64_t>(cap, std::max<int64_t>(TILE, chunk_cap / TILE * TILE));
-    rs.chunk = std::min<int64_t>(round_up(m, TILE), cap);
+    return cap;
+}
+
+int row_solve_begin(gpx_handle *h, int64_t m, RowSolve &rs, bool bounded, bool allow_few, int64_t chunk_cap)
+{
+    rs.chunk = std::min<int64_t>(round_up(m, TILE), row_solve_chunk_cap(h, chunk_cap));
     GPX_TRY(ensure_Z(h, rs.chunk));
     // the triangular solve runs out of place against the inverted diagonal squares (tsolve.hip): second slab-major buffer
     GPX_TRY(rs.sc.take(&rs.Zs, rs.chunk * h->npad));

@@ -212,11 +212,7 @@ extern "C" int gpx_propagate_approx_many(gpx_handle *h, const double *U, const d
 {
     CHECK_H(h);
     NEED_KERNEL(h, "gpx_propagate_approx_many");
-    return approx_many_run(h, h->d, U, Sigma, sigma_shared, b, mean, var, sigma2, rest, "gpx_propagate_approx_many",
-                           [&](const double *ud, const double *sd, int64_t sstride, int64_t bc, int64_t mp) -> int {
-                               return launch_approx_build_many(h->x, h->n, h->npad, h->d, ud, sd, sstride, bc, mp, h->wdev, h->v, h->vt, h->Z, h->stream,
-                                                               &h->prof);
-                           });
+    return approx_many_run(h, h->d, U, Sigma, sigma_shared, b, mean, var, sigma2, rest, "gpx_propagate_approx_many", rows_build_of(h, GPX_ROWS_APPROX));
 }
 
 // Row-sharded form of the Approx propagation (last row): the 4 + 2 d sums of gpx_propagate_approx restricted to
@@ -362,10 +358,7 @@ extern "C" int gpx_propagate_dvh_many(gpx_handle *h, const double *U, int64_t b,
 {
     CHECK_H(h);
     NEED_KERNEL(h, "gpx_propagate_dvh_many");
-    return dvh_many_run(h, h->d, U, b, dvh_out, sigma2_out, "gpx_propagate_dvh_many",
-                        [&](const double *ud, const double *, int64_t, int64_t bc, int64_t mp) -> int {
-                            return launch_dvh_build_many(h->x, h->n, h->npad, h->d, ud, bc, mp, h->wdev, h->v, h->vt, h->Z, h->stream, &h->prof);
-                        });
+    return dvh_many_run(h, h->d, U, b, dvh_out, sigma2_out, "gpx_propagate_dvh_many", rows_build_of(h, GPX_ROWS_DVH));
 }
 
 // ---- the predictor's input gradients (kernels: predict_grad.hip) -----------------------------------------------------------------------
@@ -454,17 +447,123 @@ extern "C" int gpx_predict_grad(gpx_handle *h, const double *xs, int64_t m, doub
     CHECK_H(h);
     if (m < 0 || (m > 0 && (!xs || !mean_out || !var_out || !dvar_out))) { gpx_set_error("gpx_predict_grad: bad arguments"); return GPX_ERR_BAD_ARG; }
     GPX_TRY(need_grad_kernel(h, "gpx_predict_grad"));
-    if (h->kind == KernelKind::Matern) {
-        const MaternData *md = h->mat;
-        return grad_many_run(h, md->d, xs, m, mean_out, var_out, dmean_out, dvar_out, "gpx_predict_grad",
-                             [&](const double *ud, const double *, int64_t, int64_t bc, int64_t mp) -> int {
-                                 return launch_matern_grad_build_many(md, h->n, h->npad, ud, bc, mp, h->Z, h->stream, &h->prof);
-                             });
+    return grad_many_run(h, handle_dim(h), xs, m, mean_out, var_out, dmean_out, dvar_out, "gpx_predict_grad", rows_build_of(h, GPX_ROWS_GRAD));
+}
+
+// ---- the build of every batched call, and the two stages alone (test / tool access) ----------------------------------------------------
+// Each lambda writes the rows of bc inputs into h->Z [mp, npad] on the handle's stream; h->Z is read when the build runs (the chunk loop
+// has sized it by then).  Sigma reaches the APPROX layout alone.
+RowsBuild rows_build_of(gpx_handle *h, int layout)
+{
+    if (h->kind == KernelKind::Matern)
+        return [h, layout](const double *ud, const double *sd, int64_t sstride, int64_t bc, int64_t mp) -> int {
+            const MaternData *md = h->mat;
+            const bool tr = layout == GPX_ROWS_APPROX;
+            return launch_matern_build_many(layout, md->nu2, md->x, h->n, h->npad, md->d, ud, tr ? sd : nullptr, tr ? sstride : 0, bc, mp, md->wdev, md->v,
+                                            md->vt, h->Z, h->stream, &h->prof);
+        };
+    switch (layout) {
+    case GPX_ROWS_APPROX:
+        return [h](const double *ud, const double *sd, int64_t sstride, int64_t bc, int64_t mp) -> int {
+            return launch_approx_build_many(h->x, h->n, h->npad, h->d, ud, sd, sstride, bc, mp, h->wdev, h->v, h->vt, h->Z, h->stream, &h->prof);
+        };
+    case GPX_ROWS_DVH:
+        return [h](const double *ud, const double *, int64_t, int64_t bc, int64_t mp) -> int {
+            return launch_dvh_build_many(h->x, h->n, h->npad, h->d, ud, bc, mp, h->wdev, h->v, h->vt, h->Z, h->stream, &h->prof);
+        };
+    default:
+        return [h](const double *ud, const double *, int64_t, int64_t bc, int64_t mp) -> int {
+            return launch_grad_build_many(h->x, h->n, h->npad, h->d, ud, bc, mp, h->wdev, h->v, grad_row_vt(h), h->Z, h->stream, &h->prof);
+        };
     }
-    return grad_many_run(h, h->d, xs, m, mean_out, var_out, dmean_out, dvar_out, "gpx_predict_grad",
-                         [&](const double *ud, const double *, int64_t, int64_t bc, int64_t mp) -> int {
-                             return launch_grad_build_many(h->x, h->n, h->npad, h->d, ud, bc, mp, h->wdev, h->v, grad_row_vt(h), h->Z, h->stream, &h->prof);
-                         });
+}
+
+static inline int rows_per_input(int layout, int d) { return layout == GPX_ROWS_DVH ? 2 * d + 1 : layout == GPX_ROWS_APPROX ? d + 2 : d + 1; }
+
+extern "C" int gpx_rows_build(gpx_handle *h, int layout, const double *U, const double *Sigma, int sigma_shared, int64_t b, double *rows_out)
+{
+    CHECK_H(h);
+    const bool approx = layout == GPX_ROWS_APPROX;
+    if ((layout != GPX_ROWS_APPROX && layout != GPX_ROWS_DVH && layout != GPX_ROWS_GRAD) || b < 0 || !U || !rows_out || (approx && !Sigma)) {
+        gpx_set_error("gpx_rows_build: bad arguments (layout %d, b = %ld, or a null pointer)", layout, (long)b);
+        return GPX_ERR_BAD_ARG;
+    }
+    if (h->kind == KernelKind::Periodic || h->kind == KernelKind::Matrix) {
+        gpx_set_error("gpx_rows_build: %s", h->kind == KernelKind::Periodic
+                                                ? "the handle holds a PeriodicCovariance model (gpx_periodic_fit): no batched call builds rows of that kernel"
+                                                : "the handle was built from a supplied matrix (gpx_fit_matrix): no inputs / theta to evaluate the kernel on");
+        return GPX_ERR_STATE;
+    }
+    if (h->kind == KernelKind::Matern && h->mat->nu2 != 5 && layout != GPX_ROWS_GRAD) {
+        gpx_set_error("gpx_rows_build: the handle holds a MaternCovariance model with nu = 3/2 (gpx_matern_fit), which has no Hessian at the origin: "
+                      "GPX_ROWS_GRAD is its only layout");
+        return GPX_ERR_STATE;
+    }
+    if (b == 0) return 0;
+    const int d = handle_dim(h), nrow = rows_per_input(layout, d);
+    const int64_t cap = row_solve_chunk_cap(h);
+    if (b > cap / nrow) {
+        gpx_set_error("gpx_rows_build: %ld inputs of %d rows are more than one chunk of %ld rows", (long)b, nrow, (long)cap);
+        return GPX_ERR_BAD_ARG;
+    }
+    const int64_t mp = round_up(b * nrow, TILE), nsig = sigma_shared ? 1 : b, d2 = (int64_t)d * d;
+    hipStream_t s = h->stream;
+    GPX_TRY(ensure_Z(h, mp));
+    Scratch sc(s);
+    double *ud = nullptr, *sd = nullptr;
+    GPX_TRY(sc.take(&ud, b * d));
+    GPX_HIP(hipMemcpyAsync(ud, U, sizeof(double) * b * d, hipMemcpyDefault, s));
+    if (approx) {
+        GPX_TRY(sc.take(&sd, nsig * d2));
+        GPX_HIP(hipMemcpyAsync(sd, Sigma, sizeof(double) * nsig * d2, hipMemcpyDefault, s));
+    }
+    GPX_TRY(rows_build_of(h, layout)(ud, sd, sigma_shared ? 0 : d2, b, mp));
+    GPX_HIP(hipMemcpyAsync(rows_out, h->Z, sizeof(double) * mp * h->npad, hipMemcpyDefault, s));
+    const hipError_t e = sc.wait_and_free();
+    if (e != hipSuccess) { gpx_set_error("gpx_rows_build: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
+    return 0;
+}
+
+extern "C" int gpx_rows_reduce(int layout_flags, int d, int64_t npad, const double *Zs, const double *y, const double *Sigma, int sigma_shared,
+                               int64_t b, double vplusvt, double *out)
+{
+    const int layout = layout_flags & ~GPX_ROWS_SKIP_NULLABLE;
+    const bool skip = (layout_flags & GPX_ROWS_SKIP_NULLABLE) != 0, approx = layout == GPX_ROWS_APPROX;
+    if ((layout != GPX_ROWS_APPROX && layout != GPX_ROWS_DVH && layout != GPX_ROWS_GRAD) || d < 1 || d > GPX_MAX_D || npad < TILE || npad % TILE ||
+        b < 0 || !Zs || !y || !out || (approx && !Sigma) || (b > 0 && npad > ((int64_t)1 << 31) / (b * rows_per_input(layout, d)))) {
+        gpx_set_error("gpx_rows_reduce: bad arguments");
+        return GPX_ERR_BAD_ARG;
+    }
+    GPX_TRY(gpx_require_device());
+    if (b == 0) return 0;
+    const int64_t rows = b * rows_per_input(layout, d), nsig = sigma_shared ? 1 : b, d2 = (int64_t)d * d;
+    Scratch sc(nullptr);
+    double *zd = nullptr, *yd = nullptr, *sd = nullptr, *od = nullptr;
+    GPX_TRY(sc.take(&zd, rows * npad));
+    GPX_TRY(sc.take(&yd, npad));
+    GPX_HIP(hipMemcpyAsync(zd, Zs, sizeof(double) * rows * npad, hipMemcpyDefault, sc.s));
+    GPX_HIP(hipMemcpyAsync(yd, y, sizeof(double) * npad, hipMemcpyDefault, sc.s));
+    if (approx) {
+        GPX_TRY(sc.take(&sd, nsig * d2));
+        GPX_HIP(hipMemcpyAsync(sd, Sigma, sizeof(double) * nsig * d2, hipMemcpyDefault, sc.s));
+        GPX_TRY(sc.take(&od, 4 * b));
+        GPX_TRY(launch_approx_reduce_many(zd, npad, d, yd, sd, sigma_shared ? 0 : d2, b, vplusvt, od, b, sc.s, nullptr));
+        GPX_HIP(hipMemcpyAsync(out, od, sizeof(double) * 4 * b, hipMemcpyDefault, sc.s));
+    } else if (layout == GPX_ROWS_DVH) {
+        GPX_TRY(sc.take(&od, b * (d + 1)));            // dvh [b, d] | sigma2 [b]
+        GPX_TRY(launch_dvh_reduce_many(zd, npad, d, yd, b, vplusvt, od, skip ? nullptr : od + b * d, sc.s, nullptr));
+        GPX_HIP(hipMemcpyAsync(out, od, sizeof(double) * b * (skip ? d : d + 1), hipMemcpyDefault, sc.s));
+    } else {
+        GPX_TRY(sc.take(&od, b * (2 + 2 * d)));        // mean [b] | var [b] | dmean [b, d] | dvar [b, d]
+        double *vd = od + b, *dmd = vd + b, *dvd = dmd + b * d;
+        GPX_TRY(launch_grad_reduce_many(zd, npad, d, yd, b, vplusvt, od, vd, skip ? nullptr : dmd, dvd, sc.s, nullptr));
+        GPX_HIP(hipMemcpyAsync(out, od, sizeof(double) * 2 * b, hipMemcpyDefault, sc.s));
+        if (!skip) GPX_HIP(hipMemcpyAsync(out + 2 * b, dmd, sizeof(double) * b * d, hipMemcpyDefault, sc.s));
+        GPX_HIP(hipMemcpyAsync(out + 2 * b + b * d, dvd, sizeof(double) * b * d, hipMemcpyDefault, sc.s));
+    }
+    const hipError_t e = sc.wait_and_free();
+    if (e != hipSuccess) { gpx_set_error("gpx_rows_reduce: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
+    return 0;
 }
 
 // ---- numerical propagation (UncertaintyPropagation.py:90-162; kernels: quadrature.hip) -----------------------------------------------

@@ -19,6 +19,7 @@ KERNEL_CLASS_NAMES = ["gram", "gemm_f64_mfma", "potrf_leaf", "trsv", "predict_re
                       "gemm_f64_mfma_small_tiles", "trsv_under_factorisation", "gemm_f64_emulated_int8"]
 
 # GPX_GEMM_TRI_* and GPX_GEMM_V_* of include/gpx.h (gpx_dev_gemm_nt_ex; tests/test_gemm_exact_helpers.py holds the two copies together)
+ROWS_APPROX, ROWS_DVH, ROWS_GRAD, ROWS_SKIP_NULLABLE = 0, 1, 2, 0x100     # GPX_ROWS_* of include/gpx.h (gpx_rows_build, gpx_rows_reduce)
 GEMM_TRI_NONE, GEMM_TRI_A_UPPER, GEMM_TRI_A_LOWER, GEMM_TRI_B_LOWER, GEMM_TRI_B_UPPER = 0, 1, 2, 3, 5
 
 
@@ -105,6 +106,8 @@ SIGNATURES = {
     "gpx_matern_nll_grad": (_int, [_hp, _dp]),
     "gpx_matern_propagate_approx_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp, _dp, _dp, _dp]),
     "gpx_matern_propagate_dvh_many": (_int, [_hp, _dp, _i64, _dp, _dp]),
+    "gpx_rows_build": (_int, [_hp, _int, _dp, _dp, _int, _i64, _dp]),
+    "gpx_rows_reduce": (_int, [_int, _int, _i64, _dp, _dp, _dp, _int, _i64, _dbl, _dp]),
     "gpx_spgp_fit": (_int, [_dp, _dp, _i64, _int, _dp, _dp, _i64, ctypes.POINTER(_hp)]),
     "gpx_spgp_free": (None, [_hp]),
     "gpx_spgp_predict": (_int, [_hp, _dp, _i64, _dp, _dp]),
