@@ -363,6 +363,25 @@ int gpx_spgp_cross(gpx_spgp *h, const double *xi, int64_t n1, const double *xj, 
 /* *chunks = the number of K-chunks the fit chose for this model's rank-N products (K_MN Lambda^-1 K_NM, A, the gradient's Qb), 0 when each
  * runs as one plain launch.  GPX_SPGP_SPLIT (read at every fit) overrides the choice; a value that does not divide npad / 128 gives 0. */
 int gpx_spgp_split(const gpx_spgp *h, int *chunks);
+/* The fitted SPGP model as a dense predictor over its m pseudo-inputs: gpx_spgp_predict's mean(x*) = k(x*)^T beta and
+ * var(x*) = v + vt - k(x*)^T P k(x*), k(x*) = K(x*, xbar) the plain ARD squared-exponential kernel and
+ * P = (K_M + 1e-5 I)^-1 - (B + 1e-5 I)^-1 (m x m), are those of a GP with training inputs xbar, alpha = beta and K^-1 = P.  *out is a
+ * gpx_handle of the Gaussian kind with n = m that OWNS copies of xbar, beta and P (built here from the two resident inverse factors:
+ * symmetric to the bit, zero in the padding) and has its own stream: it outlives gpx_spgp_free and is released by gpx_free.
+ * It has NO factor and no targets.  P is positive semi-definite in exact arithmetic only: it is never factored.  What reads nothing but
+ * (xbar, beta, P, v, vt, w) serves it, with the arithmetic and kernels of a gpx_fit handle:
+ *   gpx_n, gpx_alpha (beta), gpx_kinv / gpx_kinv_rows (P), gpx_cjh, gpx_exact_mean, gpx_propagate_exact / _exact_rows / _exact_many,
+ *   gpx_propagate_approx, gpx_propagate_dvh, gpx_predict_mean_grad, gpx_profile_*;
+ *   gpx_propagate_approx_many and gpx_predict_grad in their K^-1 form: the same rows R, Y = R P as one fp64 product per chunk, and the row
+ *   reductions on (R, Y, beta): r.y for |L^-1 r|^2, r.beta for (L^-1 r).(L^-1 t).  One synchronisation per chunk, no atomics, results
+ *   independent of an input's place in the batch.
+ * These are the Gaussian-approximation moments and input gradients of the SPGP predictive distribution itself, at O(m^2) an input; no
+ * N x N matrix is formed.  One difference to a gpx_fit handle: a pseudo-input is no observation, so C(u, xbar_i) carries NO +vt where u
+ * equals a pseudo-input elementwise (the prior variance stays v + vt).
+ * EVERY other entry point that takes a gpx_handle returns GPX_ERR_STATE on it, with a text that names the pseudo-input model: the solves,
+ * the factor and likelihood accessors, gpx_predict (use gpx_spgp_predict), gpx_propagate_dvh_many, gpx_propagate_quadrature_many,
+ * gpx_propagate_approx_rows / _rhs, gpx_rows_build, gpx_propagate_exact_matrix, gpx_emu_trsm_left. */
+int gpx_spgp_pseudo_handle(gpx_spgp *h, gpx_handle **out);
 
 /* ---- measurement: per-kernel-class GPU timings taken with HIP events on the handle's stream ----
  * gpx_profile_enable(h,1) brackets every launch of the listed kernel classes with an event pair;

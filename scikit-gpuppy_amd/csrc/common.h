@@ -138,6 +138,10 @@ struct gpx_handle {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     bool external_factor = false;   // L / Dinv / diagL belong to the caller (gpx_adopt_factor)
+    // A pseudo-input model (gpx_spgp_pseudo_handle, spgp.hip): x = the m pseudo-inputs, alpha = beta, Kinv = P resident from the start, and
+    // NO factor -- L, Dinv, diagL, tri, t and y stay null.  CHECK_H refuses such a handle; the entry points that read nothing but
+    // (x, alpha, Kinv, v, vt, w) take it through CHECK_H_PSEUDO_OK.
+    bool no_factor = false;
     hipStream_t s_pan = nullptr;   // side stream (high priority) for the latency-bound diagonal chain
     hipStream_t s_top = nullptr;   // pipelined panel solves of the factorisation (chol.hip, TopPipe)
 
@@ -438,6 +442,10 @@ int launch_approx_build_many(const double *x, int64_t n, int64_t npad, int d, co
                              hipStream_t s, Profiler *prof);
 int launch_approx_reduce_many(const double *Zs, int64_t npad, int d, const double *y, const double *Sigma_dev, int64_t sigma_stride,
                               int64_t nb, double vplusvt, double *out, int64_t ldo, hipStream_t s, Profiler *prof);
+// the pair form (a model held as K^-1, not as a factor): R = the built rows, Y = R K^-1, alpha = K^-1 t; v.Kinv v = r_v.y_v, beta.v = r_v.alpha,
+// tr.Kinv C = y_C.r_tr
+int launch_approx_reduce_many_pair(const double *R, const double *Y, int64_t npad, int d, const double *alpha, const double *Sigma_dev,
+                                   int64_t sigma_stride, int64_t nb, double vplusvt, double *out, int64_t ldo, hipStream_t s, Profiler *prof);
 // the same kernel's rows [C, J_1..J_d] per query (gpx_predict_grad)
 int launch_grad_build_many(const double *x, int64_t n, int64_t npad, int d, const double *U_dev, int64_t nb, int64_t rows_pad, const double *w_dev,
                            double v, double vt, double *Z, hipStream_t s, Profiler *prof);
@@ -451,6 +459,9 @@ int launch_predict_mean_grad(const double *x, int64_t n, int64_t npad, int d, in
 // the row products of the solved block [C, J_1..J_d] per query: mean, var [nb], dmean (or null), dvar [nb, d]
 int launch_grad_reduce_many(const double *Zs, int64_t npad, int d, const double *y, int64_t nb, double vplusvt, double *mean, double *var,
                             double *dmean, double *dvar, hipStream_t s, Profiler *prof);
+// the pair form: R = the built rows [C, J_1..J_d], Y = R K^-1, alpha = K^-1 t
+int launch_grad_reduce_many_pair(const double *R, const double *Y, int64_t npad, int d, const double *alpha, int64_t nb, double vplusvt, double *mean,
+                                 double *var, double *dmean, double *dvar, hipStream_t s, Profiler *prof);
 // batched inverse propagation (gpx_propagate_dvh_many): rows [C, J_1..J_d, H_11..H_dd] per input; dvh [nb, d], sigma2 [nb] or null
 int launch_dvh_build_many(const double *x, int64_t n, int64_t npad, int d, const double *U_dev, int64_t nb, int64_t rows_pad,
                           const double *w_dev, double v, double vt, double *Z, hipStream_t s, Profiler *prof);
@@ -478,10 +489,21 @@ int launch_exact_many_finish(const double *Y, const double *H, int64_t npad, con
 // ---- host orchestration shared by fit.hip, predict.hip and propagate_api.hip ---------------------
 // (helpers, not interface: they stay out of the library's dynamic symbol table)
 #pragma GCC visibility push(hidden)
-#define CHECK_H(h)                                                  \
+// Every entry point that takes a gpx_handle begins with one of the two.  CHECK_H refuses a pseudo-input model (no_factor): whatever the
+// entry point goes on to read -- L, Dinv, tri, y, t -- is null there, so refusal is the default and serving it is the exception that an
+// entry point states by name (CHECK_H_PSEUDO_OK), after its body has been read for uses of the factor.
+#define CHECK_H_PSEUDO_OK(h)                                        \
     do {                                                            \
         if (!(h)) { gpx_set_error("null handle"); return GPX_ERR_BAD_ARG; } \
         GPX_HIP(hipSetDevice((h)->device));                         \
+    } while (0)
+#define CHECK_H(h)                                                  \
+    do {                                                            \
+        CHECK_H_PSEUDO_OK(h);                                       \
+        if ((h)->no_factor) {                                       \
+            gpx_set_error("%s: the handle is a pseudo-input model (gpx_spgp_pseudo_handle): it holds beta and P, no factor, no targets", __func__); \
+            return GPX_ERR_STATE;                                   \
+        }                                                           \
     } while (0)
 // ---- the one description of a handle's kernel (KernelKind) ----
 static inline bool handle_has_kernel(const gpx_handle *h) { return h->kind != KernelKind::Matrix; }
@@ -496,6 +518,10 @@ static inline const double *handle_train_inputs(const gpx_handle *h)
 }
 // does the handle's Gram kernel add vt wherever two rows are equal (the prior variance of a query is then v + vt also for its bound)
 static inline bool handle_gram_has_vt(const gpx_handle *h) { return h->kind == KernelKind::Periodic || h->kind == KernelKind::Matern; }
+// what the builders of C(u, x_i) add where u equals row i elementwise (the reference's scalar kernel, Covariance.py:440-451): vt on a fitted
+// model, whose rows are observations; 0 on a pseudo-input model -- a pseudo-input is no observation and SPGP's k(x*) = K(x*, xbar) never
+// carries vt.  The prior variance v + vt is not affected.
+static inline double handle_vt_on_equal(const gpx_handle *h) { return h->no_factor ? 0.0 : h->vt; }
 // launch_gram / launch_periodic_gram / launch_matern_gram with the handle's parameters; xi, xj in the form of handle_train_inputs
 static inline int handle_gram(const gpx_handle *h, const double *xi, int64_t n1, const double *xj, int64_t n2, double add_diag, int lower_only,
                               int pad_mode, double *out, int64_t ld, int64_t rows_pad, int64_t cols_pad, hipStream_t s, Profiler *prof)

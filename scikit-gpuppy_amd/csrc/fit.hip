@@ -487,7 +487,7 @@ extern "C" int gpx_logdet(gpx_handle *h, double *logdet)
 // ---- accessors -----------------------------------------------------------------------------------
 extern "C" int gpx_alpha(gpx_handle *h, double *beta_out)
 {
-    CHECK_H(h);
+    CHECK_H_PSEUDO_OK(h);
     if (!beta_out) { gpx_set_error("null argument"); return GPX_ERR_BAD_ARG; }
     GPX_HIP(hipMemcpyAsync(beta_out, h->alpha, sizeof(double) * h->n, hipMemcpyDefault, h->stream));
     GPX_HIP(hipStreamSynchronize(h->stream));

@@ -359,7 +359,7 @@ int check_row_range(const gpx_handle *h, int64_t row0, int64_t row1, const char 
 // row-sharded propagation builds them
 extern "C" int gpx_kinv_rows(gpx_handle *h, int64_t row0, int64_t row1, double *out)
 {
-    CHECK_H(h);
+    CHECK_H_PSEUDO_OK(h);
     // (an empty range is an error here alone; with it excluded, row0 == n cannot pass and the shared test is the test of old)
     if (!out || row1 <= row0) { gpx_set_error("gpx_kinv_rows: bad arguments (rows [%ld, %ld) of %ld)", (long)row0, (long)row1, (long)h->n); return GPX_ERR_BAD_ARG; }
     GPX_TRY(check_row_range(h, row0, row1, "gpx_kinv_rows"));
@@ -373,7 +373,7 @@ extern "C" int gpx_kinv_rows(gpx_handle *h, int64_t row0, int64_t row1, double *
 
 extern "C" int gpx_kinv(gpx_handle *h, double *Kinv_out)
 {
-    CHECK_H(h);
+    CHECK_H_PSEUDO_OK(h);
     if (!Kinv_out) { gpx_set_error("null argument"); return GPX_ERR_BAD_ARG; }
     GPX_TRY(ensure_kinv(h));
     GPX_HIP(hipMemcpy2DAsync(Kinv_out, sizeof(double) * h->n, h->Kinv, sizeof(double) * h->npad, sizeof(double) * h->n, h->n,

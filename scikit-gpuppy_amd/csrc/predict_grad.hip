@@ -215,15 +215,20 @@ int launch_predict_mean_grad(const double *x, int64_t n, int64_t npad, int d, in
 // DR > 0 (d <= DR): columns outside, k inside, every solved row read once; DR = 0 (any d): rows outside, the z_C row (it stays in L2) read
 // again for every k.  No atomics; thread -> column, wave -> LDS slot and the final sum are fixed.
 // ---------------------------------------------------------------------------------------------
-template <int DR>
-__global__ __launch_bounds__(256) void grad_reduce_many_kernel(const double *__restrict__ Zs, long npad, int d, const double *__restrict__ y,
-                                                              double vplusvt, double *__restrict__ mean, double *__restrict__ var,
-                                                              double *__restrict__ dmean, double *__restrict__ dvar)
+// PAIR: the model is held as K^-1 (a pseudo-input model), not as a factor.  Zs = R, the rows as built, Ys = R K^-1 and y = alpha: z_C.y becomes
+// r_C.alpha, |z_C|^2 becomes r_C.y_C, z_Jk.y becomes r_Jk.alpha and z_C.z_Jk becomes y_C.r_Jk (the row of R K^-1 that a query needs is y_C
+// alone); thread -> column, the order of the terms and the finish are the same.  PAIR = false does not touch Ys.  One body, two kernels:
+// grad_reduce_many_kernel<DR> keeps its signature and its code, grad_reduce_pair_kernel<DR> is the K^-1 form.
+template <int DR, bool PAIR>
+static __device__ __forceinline__ void grad_reduce_body(const double *__restrict__ Zs, const double *__restrict__ Ys, long npad, int d,
+                                                        const double *__restrict__ y, double vplusvt, double *__restrict__ mean,
+                                                        double *__restrict__ var, double *__restrict__ dmean, double *__restrict__ dvar)
 {
     __shared__ double part[2 * GPX_MAX_D + 2][4];   // 2 k: z_Jk.y   2 k + 1: z_C.z_Jk   2 d: z_C.y   2 d + 1: |z_C|^2
     const long b = blockIdx.x;
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
     const double *zc = Zs + b * (d + 1) * npad;
+    const double *pc = PAIR ? Ys + b * (d + 1) * npad : zc;   // the C row's second factor: y_C (pair form), z_C itself otherwise
     if constexpr (DR > 0) {
         double yj[DR], cj[DR], yc = 0.0, qc = 0.0;
 #pragma unroll
@@ -231,14 +236,16 @@ __global__ __launch_bounds__(256) void grad_reduce_many_kernel(const double *__r
         for (long c = 2 * t; c < npad; c += 512) {
             const v2d a = *reinterpret_cast<const v2d *>(zc + c);
             const v2d yy = *reinterpret_cast<const v2d *>(y + c);
+            v2d p = a;
+            if constexpr (PAIR) p = *reinterpret_cast<const v2d *>(pc + c);
             yc = fma(a.x, yy.x, yc); yc = fma(a.y, yy.y, yc);
-            qc = fma(a.x, a.x, qc); qc = fma(a.y, a.y, qc);
+            qc = fma(a.x, p.x, qc); qc = fma(a.y, p.y, qc);
 #pragma unroll
             for (int k = 0; k < DR; ++k) {
                 if (k < d) {
                     const v2d zj = *reinterpret_cast<const v2d *>(zc + (long)(1 + k) * npad + c);
                     yj[k] = fma(zj.x, yy.x, yj[k]); yj[k] = fma(zj.y, yy.y, yj[k]);
-                    cj[k] = fma(a.x, zj.x, cj[k]); cj[k] = fma(a.y, zj.y, cj[k]);
+                    cj[k] = fma(p.x, zj.x, cj[k]); cj[k] = fma(p.y, zj.y, cj[k]);
                 }
             }
         }
@@ -256,8 +263,10 @@ __global__ __launch_bounds__(256) void grad_reduce_many_kernel(const double *__r
         for (long c = 2 * t; c < npad; c += 512) {
             const v2d a = *reinterpret_cast<const v2d *>(zc + c);
             const v2d yy = *reinterpret_cast<const v2d *>(y + c);
+            v2d p = a;
+            if constexpr (PAIR) p = *reinterpret_cast<const v2d *>(pc + c);
             yc = fma(a.x, yy.x, yc); yc = fma(a.y, yy.y, yc);
-            qc = fma(a.x, a.x, qc); qc = fma(a.y, a.y, qc);
+            qc = fma(a.x, p.x, qc); qc = fma(a.y, p.y, qc);
         }
         yc = wave_sum(yc); qc = wave_sum(qc);
         if (lane == 0) { part[2 * d][wave] = yc; part[2 * d + 1][wave] = qc; }
@@ -265,7 +274,7 @@ __global__ __launch_bounds__(256) void grad_reduce_many_kernel(const double *__r
             const double *zjr = zc + (long)(1 + k) * npad;
             double sy = 0.0, sc = 0.0;
             for (long c = 2 * t; c < npad; c += 512) {
-                const v2d a = *reinterpret_cast<const v2d *>(zc + c);
+                const v2d a = *reinterpret_cast<const v2d *>(pc + c);
                 const v2d yy = *reinterpret_cast<const v2d *>(y + c);
                 const v2d zj = *reinterpret_cast<const v2d *>(zjr + c);
                 sy = fma(zj.x, yy.x, sy); sy = fma(zj.y, yy.y, sy);
@@ -284,6 +293,22 @@ __global__ __launch_bounds__(256) void grad_reduce_many_kernel(const double *__r
     if (t == 64) { mean[b] = tot(2 * d); var[b] = vplusvt - tot(2 * d + 1); }
 }
 
+template <int DR>
+__global__ __launch_bounds__(256) void grad_reduce_many_kernel(const double *__restrict__ Zs, long npad, int d, const double *__restrict__ y,
+                                                              double vplusvt, double *__restrict__ mean, double *__restrict__ var,
+                                                              double *__restrict__ dmean, double *__restrict__ dvar)
+{
+    grad_reduce_body<DR, false>(Zs, nullptr, npad, d, y, vplusvt, mean, var, dmean, dvar);
+}
+
+template <int DR>
+__global__ __launch_bounds__(256) void grad_reduce_pair_kernel(const double *__restrict__ R, const double *__restrict__ Y, long npad, int d,
+                                                              const double *__restrict__ alpha, double vplusvt, double *__restrict__ mean,
+                                                              double *__restrict__ var, double *__restrict__ dmean, double *__restrict__ dvar)
+{
+    grad_reduce_body<DR, true>(R, Y, npad, d, alpha, vplusvt, mean, var, dmean, dvar);
+}
+
 int launch_grad_reduce_many(const double *Zs, int64_t npad, int d, const double *y, int64_t nb, double vplusvt, double *mean, double *var,
                             double *dmean, double *dvar, hipStream_t s, Profiler *prof)
 {
@@ -294,6 +319,20 @@ int launch_grad_reduce_many(const double *Zs, int64_t npad, int d, const double 
         hipLaunchKernelGGL(grad_reduce_many_kernel<8>, dim3((unsigned)nb), dim3(256), 0, s, Zs, (long)npad, d, y, vplusvt, mean, var, dmean, dvar);
     else
         hipLaunchKernelGGL(grad_reduce_many_kernel<0>, dim3((unsigned)nb), dim3(256), 0, s, Zs, (long)npad, d, y, vplusvt, mean, var, dmean, dvar);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_grad_reduce_many_pair(const double *R, const double *Y, int64_t npad, int d, const double *alpha, int64_t nb, double vplusvt, double *mean,
+                                 double *var, double *dmean, double *dvar, hipStream_t s, Profiler *prof)
+{
+    if (nb <= 0) return 0;
+    if (!R || !Y || !alpha || npad % 2 || d < 1 || d > GPX_MAX_D) { gpx_set_error("grad_reduce_many_pair: bad block shape"); return GPX_ERR_BAD_ARG; }
+    ProfScope ps(prof, s, GPX_K_REDUCE, 8.0 * (double)nb * (double)(d + 2) * (double)npad);
+    if (d <= 8)
+        hipLaunchKernelGGL(grad_reduce_pair_kernel<8>, dim3((unsigned)nb), dim3(256), 0, s, R, Y, (long)npad, d, alpha, vplusvt, mean, var, dmean, dvar);
+    else
+        hipLaunchKernelGGL(grad_reduce_pair_kernel<0>, dim3((unsigned)nb), dim3(256), 0, s, R, Y, (long)npad, d, alpha, vplusvt, mean, var, dmean, dvar);
     GPX_HIP(hipGetLastError());
     return 0;
 }

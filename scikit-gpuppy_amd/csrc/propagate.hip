@@ -288,24 +288,38 @@ int launch_grad_build_many(const double *x, int64_t n, int64_t npad, int d, cons
 //   mean = z_C.y + 1/2 z_tr.y   sigma2 = (v + vt) - |z_C|^2   rest = -sum_k Sigma_kk (|z_Jk|^2 - (z_Jk.y)^2) - z_C.z_tr
 // No atomics; thread -> column, wave -> LDS slot and the final sum are fixed, so an input's result does not depend on its
 // place in the batch.  out: [4][ldo] = mean | var | sigma2 | rest.
-__global__ __launch_bounds__(256) void approx_reduce_many_kernel(const double *__restrict__ Zs, long npad, int d,
-                                                                const double *__restrict__ y, const double *__restrict__ Sigma,
-                                                                long sigma_stride, double vplusvt, double *__restrict__ out, long ldo)
+// PAIR: the model is held as K^-1 (a pseudo-input model), not as a factor.  Zs = R, the rows as built, Ys = R K^-1 and y = alpha = K^-1 t: every
+// |z_r|^2 becomes r_r.y_r, every z_r.y becomes r_r.alpha and z_C.z_tr becomes y_C.r_tr; the thread -> column map, the order of the terms
+// and everything after the sums are the same.  PAIR = false reads Zs alone (Ys is not touched).  One body, two kernels:
+// approx_reduce_many_kernel keeps its signature and its code, approx_reduce_pair_kernel is the K^-1 form.
+template <bool PAIR>
+static __device__ __forceinline__ void approx_reduce_body(const double *__restrict__ Zs, const double *__restrict__ Ys, long npad, int d,
+                                                          const double *__restrict__ y, const double *__restrict__ Sigma, long sigma_stride,
+                                                          double vplusvt, double *__restrict__ out, long ldo)
 {
     __shared__ double part[(GPX_MAX_D + 2) * 2 + 1][4];
     const long b = blockIdx.x;
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
     const double *z0 = Zs + b * (d + 2) * npad, *z1 = z0 + npad;
+    const double *p0 = PAIR ? Ys + b * (d + 2) * npad : z0;   // the second factor of every square
     {
         double q0 = 0.0, y0 = 0.0, q1 = 0.0, y1 = 0.0, x01 = 0.0;
         for (long c = 2 * t; c < npad; c += 512) {
             const v2d a = *reinterpret_cast<const v2d *>(z0 + c), e = *reinterpret_cast<const v2d *>(z1 + c);
             const v2d yy = *reinterpret_cast<const v2d *>(y + c);
-            q0 = fma(a.x, a.x, q0); q0 = fma(a.y, a.y, q0);
-            y0 = fma(a.x, yy.x, y0); y0 = fma(a.y, yy.y, y0);
-            q1 = fma(e.x, e.x, q1); q1 = fma(e.y, e.y, q1);
-            y1 = fma(e.x, yy.x, y1); y1 = fma(e.y, yy.y, y1);
-            x01 = fma(a.x, e.x, x01); x01 = fma(a.y, e.y, x01);
+            if constexpr (PAIR) {
+                const v2d pa = *reinterpret_cast<const v2d *>(p0 + c);
+                q0 = fma(a.x, pa.x, q0); q0 = fma(a.y, pa.y, q0);
+                y0 = fma(a.x, yy.x, y0); y0 = fma(a.y, yy.y, y0);
+                y1 = fma(e.x, yy.x, y1); y1 = fma(e.y, yy.y, y1);
+                x01 = fma(pa.x, e.x, x01); x01 = fma(pa.y, e.y, x01);   // (tr.Kinv tr is no output: q1 stays 0)
+            } else {
+                q0 = fma(a.x, a.x, q0); q0 = fma(a.y, a.y, q0);
+                y0 = fma(a.x, yy.x, y0); y0 = fma(a.y, yy.y, y0);
+                q1 = fma(e.x, e.x, q1); q1 = fma(e.y, e.y, q1);
+                y1 = fma(e.x, yy.x, y1); y1 = fma(e.y, yy.y, y1);
+                x01 = fma(a.x, e.x, x01); x01 = fma(a.y, e.y, x01);
+            }
         }
         q0 = wave_sum(q0); y0 = wave_sum(y0); q1 = wave_sum(q1); y1 = wave_sum(y1); x01 = wave_sum(x01);
         if (lane == 0) { part[0][wave] = q0; part[1][wave] = y0; part[2][wave] = q1; part[3][wave] = y1; part[2 * (d + 2)][wave] = x01; }
@@ -316,7 +330,12 @@ __global__ __launch_bounds__(256) void approx_reduce_many_kernel(const double *_
         for (long c = 2 * t; c < npad; c += 512) {
             const v2d a = *reinterpret_cast<const v2d *>(zr + c);
             const v2d yy = *reinterpret_cast<const v2d *>(y + c);
-            q = fma(a.x, a.x, q); q = fma(a.y, a.y, q);
+            if constexpr (PAIR) {
+                const v2d pa = *reinterpret_cast<const v2d *>(p0 + (long)r * npad + c);
+                q = fma(a.x, pa.x, q); q = fma(a.y, pa.y, q);
+            } else {
+                q = fma(a.x, a.x, q); q = fma(a.y, a.y, q);
+            }
             sy = fma(a.x, yy.x, sy); sy = fma(a.y, yy.y, sy);
         }
         q = wave_sum(q); sy = wave_sum(sy);
@@ -341,12 +360,38 @@ __global__ __launch_bounds__(256) void approx_reduce_many_kernel(const double *_
     }
 }
 
+__global__ __launch_bounds__(256) void approx_reduce_many_kernel(const double *__restrict__ Zs, long npad, int d,
+                                                                const double *__restrict__ y, const double *__restrict__ Sigma,
+                                                                long sigma_stride, double vplusvt, double *__restrict__ out, long ldo)
+{
+    approx_reduce_body<false>(Zs, nullptr, npad, d, y, Sigma, sigma_stride, vplusvt, out, ldo);
+}
+
+__global__ __launch_bounds__(256) void approx_reduce_pair_kernel(const double *__restrict__ R, const double *__restrict__ Y, long npad, int d,
+                                                                const double *__restrict__ alpha, const double *__restrict__ Sigma,
+                                                                long sigma_stride, double vplusvt, double *__restrict__ out, long ldo)
+{
+    approx_reduce_body<true>(R, Y, npad, d, alpha, Sigma, sigma_stride, vplusvt, out, ldo);
+}
+
 int launch_approx_reduce_many(const double *Zs, int64_t npad, int d, const double *y, const double *Sigma_dev, int64_t sigma_stride,
                               int64_t nb, double vplusvt, double *out, int64_t ldo, hipStream_t s, Profiler *prof)
 {
     if (nb <= 0) return 0;
     ProfScope ps(prof, s, GPX_K_REDUCE, 8.0 * (double)nb * (double)(d + 2) * (double)npad);
     hipLaunchKernelGGL(approx_reduce_many_kernel, dim3((unsigned)nb), dim3(256), 0, s, Zs, (long)npad, d, y, Sigma_dev,
+                       (long)sigma_stride, vplusvt, out, (long)ldo);
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_approx_reduce_many_pair(const double *R, const double *Y, int64_t npad, int d, const double *alpha, const double *Sigma_dev,
+                                   int64_t sigma_stride, int64_t nb, double vplusvt, double *out, int64_t ldo, hipStream_t s, Profiler *prof)
+{
+    if (nb <= 0) return 0;
+    if (!R || !Y || !alpha || npad % 2 || d < 1 || d > GPX_MAX_D) { gpx_set_error("approx_reduce_many_pair: bad block shape"); return GPX_ERR_BAD_ARG; }
+    ProfScope ps(prof, s, GPX_K_REDUCE, 16.0 * (double)nb * (double)(d + 2) * (double)npad);
+    hipLaunchKernelGGL(approx_reduce_pair_kernel, dim3((unsigned)nb), dim3(256), 0, s, R, Y, (long)npad, d, alpha, Sigma_dev,
                        (long)sigma_stride, vplusvt, out, (long)ldo);
     GPX_HIP(hipGetLastError());
     return 0;

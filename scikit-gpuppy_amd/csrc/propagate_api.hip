@@ -71,7 +71,7 @@ static int prepare_u(gpx_handle *h)
     if (h->have_u && memcmp(uh, h->u, sizeof(double) * h->d) == 0) return 0;
     hipStream_t s = h->stream;
     h->have_u = false;
-    GPX_TRY(launch_approx_build(h->x, h->n, h->npad, h->d, udev_ptr(h), h->wdev, h->v, h->vt, h->V, aux_ptr(h), cplain_ptr(h), s));
+    GPX_TRY(launch_approx_build(h->x, h->n, h->npad, h->d, udev_ptr(h), h->wdev, h->v, handle_vt_on_equal(h), h->V, aux_ptr(h), cplain_ptr(h), s));
     if (by_solves) {
         // KV = V K^-1 row by row: K^-1 v = L^-T (L^-1 v) as two sweeps of the few-right-hand-side triangular solver
         // (tsolve.hip) that read the triangle of L once each -- no K^-1, no transposed copy of the factor
@@ -90,7 +90,7 @@ static int prepare_u(gpx_handle *h)
 
 extern "C" int gpx_cjh(gpx_handle *h, const double *u, double *C, double *J, double *H)
 {
-    CHECK_H(h);
+    CHECK_H_PSEUDO_OK(h);
     NEED_KERNEL(h, "gpx_cjh");
     if (!u) { gpx_set_error("null u"); return GPX_ERR_BAD_ARG; }
     const int64_t n = h->n;
@@ -102,7 +102,7 @@ extern "C" int gpx_cjh(gpx_handle *h, const double *u, double *C, double *J, dou
     GPX_TRY(sc.take(&buf, n * (1 + d + (int64_t)d * d)));
     GPX_HIP(hipMemcpy(ud, u, sizeof(double) * d, hipMemcpyDefault));
     double *Cd = buf, *Jd = buf + n, *Hd = Jd + n * d;
-    GPX_TRY(launch_cjh(h->x, n, d, ud, h->wdev, h->v, h->vt, C ? Cd : nullptr, J ? Jd : nullptr, H ? Hd : nullptr, s));
+    GPX_TRY(launch_cjh(h->x, n, d, ud, h->wdev, h->v, handle_vt_on_equal(h), C ? Cd : nullptr, J ? Jd : nullptr, H ? Hd : nullptr, s));
     if (C) GPX_HIP(hipMemcpyAsync(C, Cd, sizeof(double) * n, hipMemcpyDefault, s));
     if (J) GPX_HIP(hipMemcpyAsync(J, Jd, sizeof(double) * n * d, hipMemcpyDefault, s));
     if (H) GPX_HIP(hipMemcpyAsync(H, Hd, sizeof(double) * n * d * d, hipMemcpyDefault, s));
@@ -137,7 +137,7 @@ static DotPairs approx_pairs(gpx_handle *h, int64_t row0, int k0, int k1, int *s
 extern "C" int gpx_propagate_approx(gpx_handle *h, const double *u, const double *Sigma, double *mean, double *var,
                                     double *sigma2, double *rest)
 {
-    CHECK_H(h);
+    CHECK_H_PSEUDO_OK(h);
     NEED_KERNEL(h, "gpx_propagate_approx");
     if (!u || !Sigma) { gpx_set_error("null u / Sigma"); return GPX_ERR_BAD_ARG; }
     const int d = h->d;
@@ -169,11 +169,91 @@ extern "C" int gpx_propagate_approx(gpx_handle *h, const double *u, const double
 // gpx_predict.  With K = L L^T, y = L^-1 t and z_v = L^-1 v every sum of gpx_propagate_approx is a row product of the solved block:
 // beta.v = z_v.y, v.Kinv v = |z_v|^2, tr.Kinv C = z_tr.z_C.  No K^-1, no use of the handle's single-u cache, one synchronisation
 // per chunk; an input never straddles two chunks.
+// The batched row calls on a model held as K^-1 (a pseudo-input model: no factor to solve against): the chunk's rows R are built into h->Z as
+// for the solve, then Y = R K^-1 is ONE fp64 product per chunk (K^-1 symmetric, so R Kinv^T of launch_gemm_nt is it) and the row reductions
+// run in their pair form on (R, Y, alpha).  Chunks are cut as row_solve_begin cuts them; an element of Y is one contraction over npad in the
+// order of the k-tiles whatever tile shape the launch takes, so a row's sums do not depend on the batch.
+struct PairRows {
+    Scratch sc;
+    int64_t chunk = 0;
+    double *Y = nullptr;   // [chunk, npad]
+    explicit PairRows(hipStream_t s) : sc(s) {}
+};
+static int pair_rows_begin(gpx_handle *h, int64_t m, PairRows &pr)
+{
+    if (!h->Kinv || !h->alpha) { gpx_set_error("pair rows: the handle holds no K^-1"); return GPX_ERR_STATE; }
+    pr.chunk = std::min<int64_t>(round_up(m, TILE), row_solve_chunk_cap(h));
+    GPX_TRY(ensure_Z(h, pr.chunk));
+    return pr.sc.take(&pr.Y, pr.chunk * h->npad);
+}
+static int pair_rows_product(gpx_handle *h, const PairRows &pr, int64_t mp)
+{
+    return launch_gemm_nt(h->Z, h->npad, h->Kinv, h->npad, pr.Y, h->npad, mp, h->npad, h->npad, 1.0, 0.0, 0, h->stream, &h->prof);
+}
+
+static int approx_many_run_pair(gpx_handle *h, int d, const double *U, const double *Sigma, int sigma_shared, int64_t b, double *mean, double *var,
+                                double *sigma2, double *rest, const RowsBuild &build)
+{
+    hipStream_t s = h->stream;
+    const int nrow = d + 2;
+    PairRows pr(s);
+    GPX_TRY(pair_rows_begin(h, b * nrow, pr));
+    const int64_t bchunk = pr.chunk / nrow;           // inputs per chunk (chunk >= 128 > d + 2)
+    const int64_t nsig = sigma_shared ? 1 : bchunk, sstride = sigma_shared ? 0 : (int64_t)d * d;
+    double *ud = nullptr, *sd = nullptr, *od = nullptr;
+    GPX_TRY(pr.sc.take(&ud, bchunk * d));
+    GPX_TRY(pr.sc.take(&sd, nsig * d * d));
+    GPX_TRY(pr.sc.take(&od, 4 * bchunk));
+    if (sigma_shared) GPX_HIP(hipMemcpyAsync(sd, Sigma, sizeof(double) * d * d, hipMemcpyDefault, s));
+    for (int64_t b0 = 0; b0 < b; b0 += bchunk) {
+        const int64_t bc = std::min<int64_t>(bchunk, b - b0), mp = round_up(bc * nrow, TILE);
+        GPX_HIP(hipMemcpyAsync(ud, U + b0 * d, sizeof(double) * bc * d, hipMemcpyDefault, s));
+        if (!sigma_shared) GPX_HIP(hipMemcpyAsync(sd, Sigma + b0 * d * d, sizeof(double) * bc * d * d, hipMemcpyDefault, s));
+        GPX_TRY(build(ud, sd, sstride, bc, mp));
+        GPX_TRY(pair_rows_product(h, pr, mp));
+        GPX_TRY(launch_approx_reduce_many_pair(h->Z, pr.Y, h->npad, d, h->alpha, sd, sstride, bc, h->v + h->vt, od, bchunk, s, &h->prof));
+        GPX_HIP(hipMemcpyAsync(mean + b0, od, sizeof(double) * bc, hipMemcpyDefault, s));
+        GPX_HIP(hipMemcpyAsync(var + b0, od + bchunk, sizeof(double) * bc, hipMemcpyDefault, s));
+        if (sigma2) GPX_HIP(hipMemcpyAsync(sigma2 + b0, od + 2 * bchunk, sizeof(double) * bc, hipMemcpyDefault, s));
+        if (rest) GPX_HIP(hipMemcpyAsync(rest + b0, od + 3 * bchunk, sizeof(double) * bc, hipMemcpyDefault, s));
+        GPX_HIP(hipStreamSynchronize(s));             // the chunk's one synchronisation
+    }
+    return 0;
+}
+
+static int grad_many_run_pair(gpx_handle *h, int d, const double *U, int64_t b, double *mean, double *var, double *dmean, double *dvar,
+                              const RowsBuild &build)
+{
+    hipStream_t s = h->stream;
+    const int nrow = d + 1;
+    PairRows pr(s);
+    GPX_TRY(pair_rows_begin(h, b * nrow, pr));
+    const int64_t bchunk = pr.chunk / nrow;           // queries per chunk (chunk >= 128 > d + 1)
+    double *ud = nullptr, *od = nullptr;
+    GPX_TRY(pr.sc.take(&ud, bchunk * d));
+    GPX_TRY(pr.sc.take(&od, bchunk * (2 + 2 * d)));   // mean [bchunk] | var [bchunk] | dmean [bchunk, d] | dvar [bchunk, d]
+    double *vd = od + bchunk, *dmd = vd + bchunk, *dvd = dmd + bchunk * d;
+    for (int64_t b0 = 0; b0 < b; b0 += bchunk) {
+        const int64_t bc = std::min<int64_t>(bchunk, b - b0), mp = round_up(bc * nrow, TILE);
+        GPX_HIP(hipMemcpyAsync(ud, U + b0 * d, sizeof(double) * bc * d, hipMemcpyDefault, s));
+        GPX_TRY(build(ud, nullptr, 0, bc, mp));
+        GPX_TRY(pair_rows_product(h, pr, mp));
+        GPX_TRY(launch_grad_reduce_many_pair(h->Z, pr.Y, h->npad, d, h->alpha, bc, h->v + h->vt, od, vd, dmean ? dmd : nullptr, dvd, s, &h->prof));
+        GPX_HIP(hipMemcpyAsync(mean + b0, od, sizeof(double) * bc, hipMemcpyDefault, s));
+        GPX_HIP(hipMemcpyAsync(var + b0, vd, sizeof(double) * bc, hipMemcpyDefault, s));
+        if (dmean) GPX_HIP(hipMemcpyAsync(dmean + b0 * d, dmd, sizeof(double) * bc * d, hipMemcpyDefault, s));
+        GPX_HIP(hipMemcpyAsync(dvar + b0 * d, dvd, sizeof(double) * bc * d, hipMemcpyDefault, s));
+        GPX_HIP(hipStreamSynchronize(s));             // the chunk's one synchronisation
+    }
+    return 0;
+}
+
 int approx_many_run(gpx_handle *h, int d, const double *U, const double *Sigma, int sigma_shared, int64_t b, double *mean, double *var, double *sigma2,
                     double *rest, const char *what, const RowsBuild &build)
 {
     if (b < 0 || (b > 0 && (!U || !Sigma || !mean || !var))) { gpx_set_error("%s: bad arguments", what); return GPX_ERR_BAD_ARG; }
     if (b == 0) return 0;
+    if (h->no_factor) return approx_many_run_pair(h, d, U, Sigma, sigma_shared, b, mean, var, sigma2, rest, build);
     hipStream_t s = h->stream;
     const int nrow = d + 2;
     RowSolve rs(s);
@@ -210,7 +290,7 @@ int approx_many_run(gpx_handle *h, int d, const double *U, const double *Sigma, 
 extern "C" int gpx_propagate_approx_many(gpx_handle *h, const double *U, const double *Sigma, int sigma_shared, int64_t b,
                                          double *mean, double *var, double *sigma2, double *rest)
 {
-    CHECK_H(h);
+    CHECK_H_PSEUDO_OK(h);
     NEED_KERNEL(h, "gpx_propagate_approx_many");
     return approx_many_run(h, h->d, U, Sigma, sigma_shared, b, mean, var, sigma2, rest, "gpx_propagate_approx_many", rows_build_of(h, GPX_ROWS_APPROX));
 }
@@ -234,7 +314,7 @@ extern "C" int gpx_propagate_approx_rows(gpx_handle *h, const double *u, const d
     if (row1 > row0) GPX_TRY(ensure_kinv_rows(h, row0, round_up(row1, TILE), &kbase));
     h->have_u = false;   // KV is about to hold a row panel only
     GPX_TRY(stage_u_sigma(h, u, Sigma));
-    GPX_TRY(launch_approx_build(h->x, h->n, np, d, udev_ptr(h), h->wdev, h->v, h->vt, h->V, aux_ptr(h), cplain_ptr(h), s));
+    GPX_TRY(launch_approx_build(h->x, h->n, np, d, udev_ptr(h), h->wdev, h->v, handle_vt_on_equal(h), h->V, aux_ptr(h), cplain_ptr(h), s));
     double *tr = aux_ptr(h);
     GPX_TRY(launch_trace(h->x, h->n, np, d, udev_ptr(h), h->wdev, sigma_ptr(h), cplain_ptr(h), tr, s));
     const int64_t r1p = round_up(row1, TILE), len = row1 > row0 ? r1p - row0 : 0;   // rows past n are padding: V and tr are zero there
@@ -273,7 +353,7 @@ extern "C" int gpx_propagate_approx_rhs(gpx_handle *h, const double *u, const do
     double o[4 + 2 * GPX_MAX_D];
     for (int i = 0; i < npair; ++i) o[i] = 0.0;
     if (k1 > k0) {
-        GPX_TRY(launch_approx_build(h->x, h->n, np, d, udev_ptr(h), h->wdev, h->v, h->vt, h->V, aux_ptr(h), cplain_ptr(h), s));
+        GPX_TRY(launch_approx_build(h->x, h->n, np, d, udev_ptr(h), h->wdev, h->v, handle_vt_on_equal(h), h->V, aux_ptr(h), cplain_ptr(h), s));
         double *tr = aux_ptr(h);
         GPX_TRY(launch_trace(h->x, h->n, np, d, udev_ptr(h), h->wdev, sigma_ptr(h), cplain_ptr(h), tr, s));
         for (int c0 = k0; c0 < k1; c0 += 32)
@@ -292,7 +372,7 @@ extern "C" int gpx_propagate_approx_rhs(gpx_handle *h, const double *u, const do
 
 extern "C" int gpx_propagate_dvh(gpx_handle *h, const double *u, double *dvh_out)
 {
-    CHECK_H(h);
+    CHECK_H_PSEUDO_OK(h);
     NEED_KERNEL(h, "gpx_propagate_dvh");
     if (!u || !dvh_out) { gpx_set_error("null argument"); return GPX_ERR_BAD_ARG; }
     const int d = h->d;
@@ -370,6 +450,7 @@ int grad_many_run(gpx_handle *h, int d, const double *U, int64_t b, double *mean
 {
     if (b < 0 || (b > 0 && (!U || !mean || !var || !dvar))) { gpx_set_error("%s: bad arguments", what); return GPX_ERR_BAD_ARG; }
     if (b == 0) return 0;
+    if (h->no_factor) return grad_many_run_pair(h, d, U, b, mean, var, dmean, dvar, build);
     hipStream_t s = h->stream;
     const int nrow = d + 1;
     RowSolve rs(s);
@@ -416,7 +497,7 @@ static int need_grad_kernel(const gpx_handle *h, const char *what)
 
 extern "C" int gpx_predict_mean_grad(gpx_handle *h, const double *xs, int64_t m, double *mean_out, double *dmean_out)
 {
-    CHECK_H(h);
+    CHECK_H_PSEUDO_OK(h);
     if (m < 0 || (m > 0 && (!xs || (!mean_out && !dmean_out)))) { gpx_set_error("gpx_predict_mean_grad: bad arguments"); return GPX_ERR_BAD_ARG; }
     GPX_TRY(need_grad_kernel(h, "gpx_predict_mean_grad"));
     if (m == 0) return 0;
@@ -444,7 +525,7 @@ extern "C" int gpx_predict_mean_grad(gpx_handle *h, const double *xs, int64_t m,
 
 extern "C" int gpx_predict_grad(gpx_handle *h, const double *xs, int64_t m, double *mean_out, double *var_out, double *dmean_out, double *dvar_out)
 {
-    CHECK_H(h);
+    CHECK_H_PSEUDO_OK(h);
     if (m < 0 || (m > 0 && (!xs || !mean_out || !var_out || !dvar_out))) { gpx_set_error("gpx_predict_grad: bad arguments"); return GPX_ERR_BAD_ARG; }
     GPX_TRY(need_grad_kernel(h, "gpx_predict_grad"));
     return grad_many_run(h, handle_dim(h), xs, m, mean_out, var_out, dmean_out, dvar_out, "gpx_predict_grad", rows_build_of(h, GPX_ROWS_GRAD));
@@ -465,11 +546,11 @@ RowsBuild rows_build_of(gpx_handle *h, int layout)
     switch (layout) {
     case GPX_ROWS_APPROX:
         return [h](const double *ud, const double *sd, int64_t sstride, int64_t bc, int64_t mp) -> int {
-            return launch_approx_build_many(h->x, h->n, h->npad, h->d, ud, sd, sstride, bc, mp, h->wdev, h->v, h->vt, h->Z, h->stream, &h->prof);
+            return launch_approx_build_many(h->x, h->n, h->npad, h->d, ud, sd, sstride, bc, mp, h->wdev, h->v, handle_vt_on_equal(h), h->Z, h->stream, &h->prof);
         };
     case GPX_ROWS_DVH:
         return [h](const double *ud, const double *, int64_t, int64_t bc, int64_t mp) -> int {
-            return launch_dvh_build_many(h->x, h->n, h->npad, h->d, ud, bc, mp, h->wdev, h->v, h->vt, h->Z, h->stream, &h->prof);
+            return launch_dvh_build_many(h->x, h->n, h->npad, h->d, ud, bc, mp, h->wdev, h->v, handle_vt_on_equal(h), h->Z, h->stream, &h->prof);
         };
     default:
         return [h](const double *ud, const double *, int64_t, int64_t bc, int64_t mp) -> int {
@@ -756,7 +837,7 @@ static int exact_common(gpx_handle *h, const double *u, const double *Sigma, boo
     double *Lsd = partial + np, *ddd = Lsd + (int64_t)d * d, *outd = ddd + d;
     GPX_HIP(hipMemcpyAsync(Lsd, c.Ls.data(), sizeof(double) * d * d, hipMemcpyHostToDevice, s));
     GPX_HIP(hipMemcpyAsync(ddd, c.dd.data(), sizeof(double) * d, hipMemcpyHostToDevice, s));
-    GPX_TRY(launch_exact_build(h->x, h->n, np, d, udev_ptr(h), h->wdev, Lsd, ddd, h->v, h->vt, c.nc1, aT, bT, e, F, lm, s));
+    GPX_TRY(launch_exact_build(h->x, h->n, np, d, udev_ptr(h), h->wdev, Lsd, ddd, h->v, handle_vt_on_equal(h), c.nc1, aT, bT, e, F, lm, s));
     const bool ranged = row1 > 0;
     const int64_t r0 = ranged ? row0 : 0, r1 = ranged ? round_up(row1, TILE) : np;   // rows past n are padding (l, F are zero there)
     if (r1 > r0) GPX_TRY(launch_dot_pairs({{h->alpha + r0, lm + r0}}, r1 - r0, outd, s));
@@ -784,7 +865,7 @@ static int exact_common(gpx_handle *h, const double *u, const double *Sigma, boo
 extern "C" int gpx_propagate_exact_rows(gpx_handle *h, const double *u, const double *Sigma, int64_t row0, int64_t row1,
                                         double *partial_out)
 {
-    CHECK_H(h);
+    CHECK_H_PSEUDO_OK(h);
     NEED_KERNEL(h, "gpx_propagate_exact_rows");
     if (!u || !Sigma || !partial_out) { gpx_set_error("gpx_propagate_exact_rows: null argument"); return GPX_ERR_BAD_ARG; }
     GPX_TRY(check_row_range(h, row0, row1, "gpx_propagate_exact_rows"));
@@ -798,7 +879,7 @@ extern "C" int gpx_propagate_exact_rows(gpx_handle *h, const double *u, const do
 
 extern "C" int gpx_propagate_exact(gpx_handle *h, const double *u, const double *Sigma, double *mean, double *var)
 {
-    CHECK_H(h);
+    CHECK_H_PSEUDO_OK(h);
     NEED_KERNEL(h, "gpx_propagate_exact");
     if (!u || !Sigma) { gpx_set_error("null u / Sigma"); return GPX_ERR_BAD_ARG; }
     return exact_common(h, u, Sigma, true, mean, var);
@@ -806,7 +887,7 @@ extern "C" int gpx_propagate_exact(gpx_handle *h, const double *u, const double 
 
 extern "C" int gpx_exact_mean(gpx_handle *h, const double *u, const double *Sigma, double *mean)
 {
-    CHECK_H(h);
+    CHECK_H_PSEUDO_OK(h);
     NEED_KERNEL(h, "gpx_exact_mean");
     if (!u || !Sigma || !mean) { gpx_set_error("null argument"); return GPX_ERR_BAD_ARG; }
     return exact_common(h, u, Sigma, false, mean, nullptr);
@@ -833,7 +914,7 @@ static int64_t env_count(const char *name, int64_t dflt)
 extern "C" int gpx_propagate_exact_many(gpx_handle *h, const double *U, const double *Sigma, int sigma_shared, int64_t b, double *mean,
                                         double *var)
 {
-    CHECK_H(h);
+    CHECK_H_PSEUDO_OK(h);
     NEED_KERNEL(h, "gpx_propagate_exact_many");
     if (b < 0 || (b > 0 && (!U || !Sigma || !mean))) { gpx_set_error("gpx_propagate_exact_many: bad arguments"); return GPX_ERR_BAD_ARG; }
     if (b == 0) return 0;
@@ -916,7 +997,7 @@ extern "C" int gpx_propagate_exact_many(gpx_handle *h, const double *U, const do
         if (!r.matrix) {
             double *aT = pb, *bT = aT + (int64_t)d * np, *e = bT + (int64_t)d * np, *F = e + np, *lm = F + np, *partial = lm + np;
             for (int64_t i = r.i0; i < r.i0 + r.cnt; ++i) {   // exact_common's launches; od[i] = beta . l, od[b + i] = the double sum / nc2
-                GPX_TRY(launch_exact_build(h->x, n, np, d, Ud + i * d, h->wdev, Lsd, ddd, h->v, h->vt, r.nc1, aT, bT, e, F, lm, s));
+                GPX_TRY(launch_exact_build(h->x, n, np, d, Ud + i * d, h->wdev, Lsd, ddd, h->v, handle_vt_on_equal(h), r.nc1, aT, bT, e, F, lm, s));
                 GPX_TRY(launch_dot_pairs({{h->alpha, lm}}, np, od + i, s));
                 if (want_var) GPX_TRY(launch_exact_sum(h->Kinv, np, np, d, h->alpha, aT, bT, e, F, partial, od + b + i, s, &h->prof));
             }
@@ -931,7 +1012,7 @@ extern "C" int gpx_propagate_exact_many(gpx_handle *h, const double *U, const do
         for (int64_t b0 = 0; b0 < r.cnt; b0 += rows) {
             const int64_t bc = std::min(rows, r.cnt - b0), bp = round_up(bc, TILE), i0 = r.i0 + b0;
             if (want_var) GPX_TRY(launch_exact_many_transform(Ud + i0 * d, bc, bc, d, h->x, T2, Uh, s));
-            GPX_TRY(launch_exact_many_build(h->x, xh, n, np, d, Ud + i0 * d, Uh, bc, bp, h->wdev, ddd, s2, h->alpha, h->v, h->vt, r.nc1,
+            GPX_TRY(launch_exact_many_build(h->x, xh, n, np, d, Ud + i0 * d, Uh, bc, bp, h->wdev, ddd, s2, h->alpha, h->v, handle_vt_on_equal(h), r.nc1,
                                             want_var ? Hd : nullptr, mpart, s, prof));
             if (want_var) GPX_TRY(launch_gemm_nt(Hd, np, Lo, np, Yd, np, bp, np, np, 1.0, 0.0, 0, s, &h->prof, 0, GEMM_TRI_B_LOWER));
             GPX_TRY(launch_exact_many_finish(want_var ? Yd : nullptr, Hd, np, mpart, bc, vpv, r.nc2, od + i0, b, s, prof));
@@ -1038,7 +1119,7 @@ extern "C" int gpx_propagate_exact_matrix(gpx_handle *h, const double *Kinv, con
                                           double *mean, double *var)
 {
     GPX_TRY(gpx_require_device());
-    if (h) GPX_HIP(hipSetDevice(h->device));
+    if (h) CHECK_H(h);   // (a pseudo-input model is served by the fused entry points, not by this one: refused like everywhere else)
     if (!x || !w || !C_ux || !u || !Sigma || n < 1 || d < 1 || d > GPX_MAX_D || (!h && (!beta || (var && !Kinv))) || (h && h->n != n)) {
         gpx_set_error("gpx_propagate_exact_matrix: bad arguments (n=%ld d=%d%s)", (long)n, d, (h && h->n != n) ? ": the handle holds another n" : "");
         return GPX_ERR_BAD_ARG;

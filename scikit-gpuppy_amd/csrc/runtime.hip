@@ -267,7 +267,7 @@ extern "C" int gpx_profile_reset(gpx_handle *h)
 }
 extern "C" int gpx_profile_read(gpx_handle *h, int cls, int64_t *launches, double *total_ms, double *total_work)
 {
-    CHECK_H(h);
+    CHECK_H_PSEUDO_OK(h);
     if (cls < 0 || cls >= GPX_K_COUNT) { gpx_set_error("bad kernel class"); return GPX_ERR_BAD_ARG; }
     GPX_TRY(h->prof.collect(h->stream));
     if (launches) *launches = h->prof.launches[cls];

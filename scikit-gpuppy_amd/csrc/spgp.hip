@@ -23,8 +23,10 @@ struct gpx_spgp {
     int64_t n = 0, npad = 0, m = 0, mpad = 0, mblk = 0;
     int d = 0;
     double v = 0, vt = 0;
+    double theta[GPX_MAX_D + 2];   // (log v, log vt, log w_1..d) as given to the fit
     hipStream_t stream = nullptr;
     double *xw = nullptr, *xbw = nullptr, *sw = nullptr, *t = nullptr;
+    double *xb = nullptr;    // [m, d] the pseudo-inputs as given: what a pseudo-input model (gpx_spgp_pseudo_handle) evaluates the kernel on
     double *org = nullptr;   // [d] the origin every input is taken from before the sqrt(w) scaling: the first training row (spgp_fit_body)
     double *Knm = nullptr;   // [npad, mpad] K_NM, zero padded
     double *Z = nullptr;     // [npad, mpad] scratch (K_NM L^-T for whichever L was applied last)
@@ -198,7 +200,7 @@ extern "C" void gpx_spgp_free(gpx_spgp *h)
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    void *bufs[] = {h->xw, h->xbw, h->sw, h->org, h->t, h->Knm, h->Z, h->Wt, h->LM, h->DinvM, h->diagM, h->LB, h->DinvB, h->diagB, h->scrA, h->scrB, h->LinvM, h->LinvB, h->lam,
+    void *bufs[] = {h->xw, h->xbw, h->xb, h->sw, h->org, h->t, h->Knm, h->Z, h->Wt, h->LM, h->DinvM, h->diagM, h->LB, h->DinvB, h->diagB, h->scrA, h->scrB, h->LinvM, h->LinvB, h->lam,
                     h->ilam, h->va, h->vb, h->vc, h->ma, h->mb, h->mzero, h->beta, h->mscr, h->outd};
     for (void *p : bufs) dfree(p);
     if (h->info) dfree(h->info);
@@ -265,7 +267,7 @@ static int spgp_fit_body(gpx_spgp *h, const double *x, const double *t_centered,
     if (!(h->stream = stream_acquire(0))) { gpx_set_error("stream creation failed"); return GPX_ERR_HIP; }
     hipStream_t s = h->stream;
     const int64_t tt = h->mblk * (int64_t)TILE * TILE;
-    GPX_TRY(dalloc(&h->xw, np * d)); GPX_TRY(dalloc(&h->xbw, mp * d)); GPX_TRY(dalloc(&h->sw, d)); GPX_TRY(dalloc(&h->org, d)); GPX_TRY(dalloc(&h->t, np));
+    GPX_TRY(dalloc(&h->xw, np * d)); GPX_TRY(dalloc(&h->xbw, mp * d)); GPX_TRY(dalloc(&h->xb, m * d)); GPX_TRY(dalloc(&h->sw, d)); GPX_TRY(dalloc(&h->org, d)); GPX_TRY(dalloc(&h->t, np));
     GPX_TRY(dalloc(&h->Knm, np * mp)); GPX_TRY(dalloc(&h->Z, np * mp)); GPX_TRY(dalloc(&h->Wt, mp * np));
     GPX_TRY(dalloc(&h->LM, mp * mp)); GPX_TRY(dalloc(&h->DinvM, tt)); GPX_TRY(dalloc(&h->diagM, mp));
     GPX_TRY(dalloc(&h->LB, mp * mp)); GPX_TRY(dalloc(&h->DinvB, tt)); GPX_TRY(dalloc(&h->diagB, mp));
@@ -290,6 +292,7 @@ static int spgp_fit_body(gpx_spgp *h, const double *x, const double *t_centered,
     // raw inputs are staged through Z / LB (both overwritten below)
     GPX_HIP(hipMemcpyAsync(h->Z, x, sizeof(double) * n * d, hipMemcpyDefault, s));
     GPX_HIP(hipMemcpyAsync(h->LB, xb, sizeof(double) * m * d, hipMemcpyDefault, s));
+    GPX_HIP(hipMemcpyAsync(h->xb, xb, sizeof(double) * m * d, hipMemcpyDefault, s));
     GPX_HIP(hipMemcpyAsync(h->sw, sw, sizeof(double) * d, hipMemcpyHostToDevice, s));
     // The Gram kernel takes direct differences, but the gradient assembles sum E (xb - x)^2 from the moments sum E, sum E x, sum E x^2
     // (spgp_epass_kernel), which lose (|x| / |xb - x|)^2 digits for data far from zero.  So every input -- x, xb, and later the queries of
@@ -355,6 +358,7 @@ extern "C" int gpx_spgp_fit(const double *x, const double *t_centered, int64_t n
     h->n = n; h->m = m; h->d = d;
     h->npad = round_up(n, TILE); h->mpad = round_up(m, TILE); h->mblk = h->mpad / TILE;
     h->v = exp(theta[0]); h->vt = exp(theta[1]);
+    for (int k = 0; k < d + 2; ++k) h->theta[k] = theta[k];
     const int rc = spgp_fit_body(h, x, t_centered, theta, xb);
     if (rc) { gpx_spgp_free(h); return rc; }
     *out = h;
@@ -401,6 +405,85 @@ extern "C" int gpx_spgp_predict(gpx_spgp *h, const double *xs, int64_t ms, doubl
         GPX_HIP(hipMemcpyAsync(var_out + q0, var, sizeof(double) * qc, hipMemcpyDefault, s));
         GPX_HIP(hipStreamSynchronize(s));
     }
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The fitted model as a dense predictor over the m pseudo-inputs.  gpx_spgp_predict evaluates
+//     mean(x*) = k(x*)^T beta ,   var(x*) = v + vt - |k(x*) L_M^-T|^2 + |k(x*) L_B^-T|^2 ,   k(x*) = K(x*, xbar) (plain ARD SE),
+// which is the predictor of a GP with "training inputs" xbar, alpha = beta and
+//     "K^-1" = P = (K_M + 1e-5 I)^-1 - B~^-1 = LinvM^T LinvM - LinvB^T LinvB     (m x m).
+// Girard's exact moments, the Approx sums, the predictor's input gradients and the linear propagation read a model through
+// (x, alpha, K^-1, v, vt, w) alone, so on (xbar, beta, P) they are those of the SPGP predictive distribution itself at O(m^2) an input.
+// P is positive semi-definite in exact arithmetic and NOT numerically (its smallest computed eigenvalue has either sign): it is never
+// factored; the handle has no factor at all (gpx_handle::no_factor, common.h).
+// ------------------------------------------------------------------------------------------------------------------
+
+// P[i][j] = P[j][i] = A[i][j] - B[i][j] from the LOWER triangles (i >= j) of A = LinvM^T LinvM and B = LinvB^T LinvB, both triangles of P
+// written by the one thread that formed the difference: symmetric to the bit; rows and columns from m on are zero.  A workgroup per
+// (row, 256 columns) of the [mp, mp] square, the threads right of the diagonal idle; every element has exactly one writer.
+__global__ __launch_bounds__(256) void spgp_pseudo_p_kernel(const double *__restrict__ A, const double *__restrict__ B, long m, long mp,
+                                                           double *__restrict__ P)
+{
+    const long i = blockIdx.x, j = (long)blockIdx.y * 256 + threadIdx.x;
+    if (j >= mp || i >= mp || j > i) return;
+    const double p = (i < m) ? A[i * mp + j] - B[i * mp + j] : 0.0;   // (j <= i < m: both real)
+    P[i * mp + j] = p;
+    P[j * mp + i] = p;
+}
+
+extern "C" int gpx_spgp_pseudo_handle(gpx_spgp *h, gpx_handle **out)
+{
+    if (out) *out = nullptr;
+    GPX_TRY(spgp_require(h));
+    if (!out) { gpx_set_error("gpx_spgp_pseudo_handle: null argument"); return GPX_ERR_BAD_ARG; }
+    const int64_t m = h->m, mp = h->mpad;
+    const int d = h->d;
+    gpx_handle *g = new (std::nothrow) gpx_handle();
+    if (!g) { gpx_set_error("out of host memory"); return GPX_ERR_HIP; }
+    g->device = h->device;
+    g->kind = KernelKind::Gaussian;
+    g->no_factor = true;
+    g->n = m; g->npad = mp; g->nblk = h->mblk; g->d = d;
+    g->v = h->v; g->vt = h->vt;
+    double sw[GPX_MAX_D];
+    for (int k = 0; k < d + 2; ++k) g->theta[k] = h->theta[k];
+    for (int k = 0; k < d; ++k) { g->w[k] = exp(h->theta[2 + k]); sw[k] = sqrt(g->w[k]); }
+    auto body = [&]() -> int {
+        if (!(g->stream = stream_acquire(0))) { gpx_set_error("stream creation failed"); return GPX_ERR_HIP; }
+        g->own_stream = true;
+        GPX_TRY(dalloc(&g->x, m * d)); GPX_TRY(dalloc(&g->xs_w, mp * d)); GPX_TRY(dalloc(&g->sw, d)); GPX_TRY(dalloc(&g->wdev, d));
+        GPX_TRY(dalloc(&g->alpha, mp)); GPX_TRY(dalloc(&g->Kinv, mp * mp));
+        // everything is queued on the SPGP model's stream, behind whatever last wrote its factors; the handle's own stream starts idle
+        hipStream_t s = h->stream;
+        double *T = nullptr, *A = nullptr, *B = nullptr;
+        Scratch sc(s);
+        GPX_TRY(sc.take(&T, mp * mp)); GPX_TRY(sc.take(&A, mp * mp)); GPX_TRY(sc.take(&B, mp * mp));
+        GPX_HIP(hipMemcpyAsync(g->x, h->xb, sizeof(double) * m * d, hipMemcpyDeviceToDevice, s));
+        GPX_HIP(hipMemcpyAsync(g->sw, sw, sizeof(double) * d, hipMemcpyHostToDevice, s));
+        GPX_HIP(hipMemcpyAsync(g->wdev, g->w, sizeof(double) * d, hipMemcpyHostToDevice, s));
+        GPX_HIP(hipMemcpyAsync(g->alpha, h->beta, sizeof(double) * mp, hipMemcpyDeviceToDevice, s));
+        if (mp > m) GPX_HIP(hipMemsetAsync(g->alpha + m, 0, sizeof(double) * (mp - m), s));   // (the solve leaves zeros there already: by contract, not by accident)
+        GPX_TRY(launch_scale_rows(g->x, m, mp, d, g->sw, g->xs_w, s));
+        // inv(L)^T inv(L), lower tiles, for both factors: the transpose of the resident inverse is the A operand of C = A A^T
+        const dim3 tg((unsigned)((mp + 31) / 32), (unsigned)((mp + 31) / 32));
+        const double *linv[2] = {h->LinvM, h->LinvB};
+        double *prod[2] = {A, B};
+        for (int f = 0; f < 2; ++f) {
+            hipLaunchKernelGGL(scale_transpose_kernel, tg, dim3(256), 0, s, linv[f], (long)mp, (long)mp, (long)mp, (const double *)nullptr, T, (long)mp);
+            GPX_HIP(hipGetLastError());
+            GPX_TRY(launch_gemm_nt(T, mp, T, mp, prod[f], mp, mp, mp, mp, 1.0, 0.0, 1, s, nullptr));
+        }
+        hipLaunchKernelGGL(spgp_pseudo_p_kernel, dim3((unsigned)mp, (unsigned)((mp + 255) / 256)), dim3(256), 0, s, (const double *)A, (const double *)B,
+                           (long)m, (long)mp, g->Kinv);
+        GPX_HIP(hipGetLastError());
+        const hipError_t e = sc.wait_and_free();   // sw (a stack buffer) has been copied, P is complete
+        if (e != hipSuccess) { gpx_set_error("gpx_spgp_pseudo_handle: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
+        return 0;
+    };
+    const int rc = body();
+    if (rc) { (void)hipStreamSynchronize(h->stream); gpx_free(g); return rc; }
+    *out = g;
     return 0;
 }
 

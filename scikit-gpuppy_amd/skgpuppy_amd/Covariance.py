@@ -908,7 +908,8 @@ class SPGPCovariance(Covariance):
     """Snelson's sparse pseudo-input covariance ("next" row f3; skgpuppy/Covariance.py:692-1019).
 
     theta = (log v, log vt, log w_1..w_d, the m pseudo-inputs flattened row-major).  Like the reference's it offers no
-    Jacobian/Hessian (no uncertainty propagation).  Fit, prediction and Snelson's likelihood are O(N m^2) on the GPU;
+    Jacobian/Hessian; uncertainty propagation of the fitted model goes through GaussianProcess.pseudo_gp(), the model as a dense GP over
+    its m pseudo-inputs (O(m^2) per input, no N x N matrix).  Fit, prediction and Snelson's likelihood are O(N m^2) on the GPU;
     cov_matrix / inv_cov_matrix materialise the reference's N x N matrices for small N only."""
 
     def __init__(self, m):

@@ -102,6 +102,192 @@ class _DeviceModel(object):
         return v.value
 
 
+class _PseudoModel(object):
+    """Owner of one pseudo-input gpx_handle (gpx_spgp_pseudo_handle): copies of the m pseudo-inputs, beta and P = (K_M + 1e-5 I)^-1 - B~^-1
+    of a fitted SPGP model, resident in HBM.  It has no factor; it outlives the SPGP device model it was built from."""
+
+    def __init__(self, spgp_model):
+        self._h = ctypes.c_void_p()
+        _gpx.check(_gpx.lib.gpx_spgp_pseudo_handle(spgp_model.handle, ctypes.byref(self._h)), "gpx_spgp_pseudo_handle")
+        n, d = ctypes.c_int64(), ctypes.c_int()
+        _gpx.check(_gpx.lib.gpx_n(self._h, ctypes.byref(n), ctypes.byref(d)), "gpx_n")
+        self.n, self.d = n.value, d.value
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise RuntimeError("device model already released")
+        return self._h
+
+    def close(self, _free=_gpx.lib.gpx_free, _null=ctypes.c_void_p):
+        if getattr(self, "_h", None):
+            _free(self._h)
+            self._h = _null()
+
+    __del__ = close
+
+    def alpha(self):
+        out = np.empty(self.n)
+        _gpx.check(_gpx.lib.gpx_alpha(self.handle, _gpx.ptr(out)), "gpx_alpha")
+        return out
+
+    def kinv(self):
+        out = np.empty((self.n, self.n))
+        _gpx.check(_gpx.lib.gpx_kinv(self.handle, _gpx.ptr(out)), "gpx_kinv")
+        return out
+
+    def kinv_rows(self, r0, r1):
+        out = np.empty((r1 - r0, self.n))
+        _gpx.check(_gpx.lib.gpx_kinv_rows(self.handle, r0, r1, _gpx.ptr(out)), "gpx_kinv_rows")
+        return out
+
+    def solve(self, B):
+        """P B^T for the rows of B: there is no factor to sweep over, P itself multiplies (gpx_symv on the device)"""
+        B = _gpx.f64(np.atleast_2d(B))
+        if B.shape[1] != self.n:
+            raise ValueError("right-hand sides must be rows of length %d" % self.n)
+        P = self.kinv()
+        out = np.empty_like(B)
+        _gpx.check(_gpx.lib.gpx_symv(_gpx.ptr(P), self.n, _gpx.ptr(B), B.shape[0], _gpx.ptr(out)), "gpx_symv")
+        return out
+
+
+class PseudoInputGP(object):
+    """A fitted SPGP model seen as a dense GP over its m pseudo-inputs (GaussianProcess.pseudo_gp()).
+
+    gpx_spgp_predict evaluates mean(x*) = k(x*)^T beta and var(x*) = v + vt - k(x*)^T P k(x*) with k(x*) = K(x*, xbar) the plain ARD
+    squared-exponential kernel against the m pseudo-inputs and P = (K_M + 1e-5 I)^-1 - B~^-1: the predictor of a GP with training inputs
+    xbar, alpha = beta and K^-1 = P.  The propagation classes read a GP only through (x, beta, K^-1, v, vt, w), so on this object
+    UncertaintyPropagationExact / Approx / Linear and InverseUncertaintyPropagationApprox give the Gaussian-approximation moments of the
+    SPGP predictive distribution itself, on the fused device calls, at O(m^2) per input and without any N x N matrix.  (On the SPGP
+    GaussianProcess itself the classes keep the reference's dense route: Girard's correction factors applied to the low-rank kernel
+    Q(u, x_i) through the N x N Woodbury inverse -- another quantity, for small N only.)
+
+    x = xbar, n = m, theta_min = a copy of theta[:2 + d], cov = GaussianCovariance().  A pseudo-input is no observation: _covariance is the
+    plain kernel, without the +vt of the reference's scalar kernel on equal arguments; the prior variance of a query is v + vt.  P is
+    positive semi-definite in exact arithmetic only -- do not factor Kinv.  estimate / estimate_many / __call__ are the parent's.  The
+    device handle owns copies: it survives the parent's cov.clear_cache() and device model; a pickle drops it and it is rebuilt, from the
+    parent (refitted if need be), on first use."""
+
+    _pseudo = True
+
+    def __init__(self, parent):
+        if not isinstance(parent, GaussianProcess) or parent._route() != "spgp":
+            raise TypeError("PseudoInputGP needs a GaussianProcess whose cov is an SPGPCovariance")
+        self.parent = parent
+        self.d = parent.d
+        theta = _gpx.f64(parent.theta_min)
+        self.theta_min = np.array(theta[:2 + self.d])
+        self.x = np.array(theta[2 + self.d:]).reshape(-1, self.d)
+        self.n = self.x.shape[0]
+        self.meant = parent.meant
+        self.cov = GaussianCovariance()
+        self._model = None
+        self._Kinv = None
+
+    def _route(self):
+        # the propagation classes take their fused built-in path: the handle is of the Gaussian kind
+        return "gaussian"
+
+    def _dev(self):
+        if self._model is None:
+            self._model = _PseudoModel(self.parent._dev())
+        return self._model
+
+    def close(self):
+        if self._model is not None:
+            self._model.close()
+            self._model = None
+
+    @property
+    def Kinv(self):
+        """P [m, m] as a NumPy array, fetched on first access (symmetric to the bit; not numerically definite)"""
+        if self._Kinv is None:
+            self._Kinv = self._dev().kinv()
+        return self._Kinv
+
+    @Kinv.setter
+    def Kinv(self, value):
+        self._Kinv = value
+
+    def __getstate__(self):
+        state = dict(self.__dict__)
+        state["_model"] = None          # raw device handles never enter the pickle
+        return state
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        self._model = None
+
+    # ---- the predictor: the parent's, bit for bit ----
+    def __call__(self, x_star):
+        return self.parent.estimate(x_star)
+
+    def estimate(self, x_star):
+        return self.parent.estimate(x_star)
+
+    def estimate_many(self, x_stars):
+        return self.parent.estimate_many(x_stars)
+
+    def estimate_many_gradient(self, x_stars, variance=True, h=1e-5):
+        """GaussianProcess.estimate_many_gradient in closed form on (xbar, beta, P): gpx_predict_mean_grad (variance=False: beta alone) and
+        gpx_predict_grad in its K^-1 form (d + 1 rows per query times P).  mean and var are the SPGP predictor's to rounding; h is not used."""
+        xs = _gpx.f64(np.array(x_stars))
+        if xs.ndim != 2 or xs.shape[1] != self.d:
+            raise ValueError("x_stars must be (m, %d)" % self.d)
+        m, d = xs.shape
+        handle = self._dev().handle
+        mean, dmean = np.empty(m), np.empty((m, d))
+        if not variance:
+            _gpx.check(_gpx.lib.gpx_predict_mean_grad(handle, _gpx.ptr(xs), m, _gpx.ptr(mean), _gpx.ptr(dmean)), "gpx_predict_mean_grad")
+            return mean + self.meant, dmean
+        var, dvar = np.empty(m), np.empty((m, d))
+        _gpx.check(_gpx.lib.gpx_predict_grad(handle, _gpx.ptr(xs), m, _gpx.ptr(mean), _gpx.ptr(var), _gpx.ptr(dmean), _gpx.ptr(dvar)),
+                   "gpx_predict_grad")
+        return mean + self.meant, var, dmean, dvar
+
+    def estimate_gradient(self, x_star, variance=True, h=1e-5):
+        return tuple(o[0] for o in self.estimate_many_gradient(np.atleast_2d(np.array(x_star)), variance, h))
+
+    # ---- what the propagation classes read ----
+    def _get_beta(self):
+        return self._dev().alpha()
+
+    def _get_W_inv(self):
+        return np.diag(np.exp(self.theta_min[2:self.d + 2]))
+
+    def _get_v(self):
+        return np.exp(self.theta_min[0])
+
+    def _get_vt(self):
+        return np.exp(self.theta_min[1])
+
+    def _prior_variance(self, u=None):
+        return self._get_v() + self._get_vt()
+
+    def _covariance(self, xi, xj, v=None, w=None):
+        # the plain kernel (no +vt on equal arguments); v / w mutate theta in place as GaussianProcess._covariance does
+        theta = self.theta_min
+        if v is not None:
+            theta[0] = np.log(v)
+        if w is not None:
+            theta[2:] = np.log(w)
+        diff = np.asarray(xi, dtype=float) - np.asarray(xj, dtype=float)
+        return np.exp(theta[0]) * np.exp(-0.5 * np.dot(diff, np.exp(theta[2:2 + self.d]) * diff))
+
+    def _inv_cov_matrix(self):
+        return self.Kinv
+
+    def _get_mean_t(self):
+        return self.meant
+
+    def _get_Hessian(self, u, xi):
+        return self.cov.get_Hessian(u, xi, self.theta_min)
+
+    def _get_Jacobian(self, u, xi):
+        return self.cov.get_Jacobian(u, xi, self.theta_min)
+
+
 class GaussianProcess(object):
     """GP regression object (skgpuppy/GaussianProcess.py:11-191)."""
 
@@ -178,6 +364,14 @@ class GaussianProcess(object):
     def __setstate__(self, state):
         self.__dict__.update(state)
         self._model = None
+
+    def pseudo_gp(self):
+        """The fitted SPGP model as a dense GP over its m pseudo-inputs (PseudoInputGP): what to hand to UncertaintyPropagationExact /
+        Approx / Linear and InverseUncertaintyPropagationApprox for the moments of the SPGP predictive distribution at O(m^2) per input.
+        SPGPCovariance only: TypeError otherwise."""
+        if self._route() != "spgp":
+            raise TypeError("pseudo_gp() exists for cov = SPGPCovariance only (this GP's route is %r)" % self._route())
+        return PseudoInputGP(self)
 
     # ---- reference API -------------------------------------------------------------------------
     @staticmethod

@@ -135,7 +135,9 @@ class InverseUncertaintyPropagationApprox(InverseUncertaintyPropagation):
 
     def get_best_solution_many(self, U, output_variance=None):
         """get_best_solution for the rows of U (B, d) in one call: optimal input variances [B, d], NaN rows where the problem has no
-        solution (_closed_form).  output_variance: [B] or scalar, default self.output_variance.  self.u is not used."""
+        solution (_closed_form).  output_variance: [B] or scalar, default self.output_variance.  self.u is not used.
+        On a PseudoInputGP (GaussianProcess.pseudo_gp()) the derivatives come from a loop over the single-input device call, one point
+        after the other: the batched inverse propagation has no K^-1 form yet."""
         upga = self.upga_class(self.gp)
         dvh, sigma2 = upga._get_variance_dv_many(U)
         target = self.output_variance if output_variance is None else output_variance

@@ -231,7 +231,9 @@ class UncertaintyPropagationApprox(UncertaintyPropagationGA):
                 raise ValueError("Kinv must be (%d, %d)" % (gp.n, gp.n))
             KV = np.empty_like(V)
             _gpx.check(_gpx.lib.gpx_symv(_gpx.ptr(M), gp.n, _gpx.ptr(V), V.shape[0], _gpx.ptr(KV)), "gpx_symv")
-        return self._quadratic_parts(gp._covariance(u, u), b, C, J, H, S, KV[0], KV[2:], KV[1])
+        # (a pseudo-input model's _covariance is the plain kernel: its prior variance v + vt is stated apart)
+        cuu = gp._prior_variance(u) if getattr(gp, "_pseudo", False) else gp._covariance(u, u)
+        return self._quadratic_parts(cuu, b, C, J, H, S, KV[0], KV[2:], KV[1])
 
     def _get_sigma2(self, u, Kinv=None, x=None, C_ux=None, J_ux=None, H_ux=None):
         """C(u,u) - C^T K^-1 C  (UncertaintyPropagation.py:412-433); needs no Sigma_x"""
@@ -290,7 +292,8 @@ class UncertaintyPropagationApprox(UncertaintyPropagationGA):
             st = _gpx.lib.gpx_matern_propagate_dvh_many(self.gp._dev().handle, _gpx.ptr(UU), B, _gpx.ptr(dvh), _gpx.ptr(sigma2))
             _gpx.check(st, "gpx_matern_propagate_dvh_many")
             return dvh, sigma2
-        if self._generic():
+        if self._generic() or getattr(self.gp, "_pseudo", False):
+            # (a PseudoInputGP: the batched call has no K^-1 form -- the single-input device call, one input after the other)
             one = type(self)(self.gp)
             for i in range(B):
                 for h in range(d):
@@ -422,10 +425,11 @@ class UncertaintyPropagationExact(UncertaintyPropagationGA):
             C_ux = np.array([gp._covariance(u, gp.x[i]) for i in range(gp.n)])
         C = _gpx.f64(C_ux).reshape(gp.n)
         w = _gpx.f64(np.diag(self.Winv))
-        cuu = float(gp._covariance(u, u)) if want_var else 0.0
+        pseudo = getattr(gp, "_pseudo", False)              # (a PseudoInputGP with a caller's C_ux: its P and beta as an explicit model)
+        cuu = float(gp._prior_variance(u) if pseudo else gp._covariance(u, u)) if want_var else 0.0
         mean, var = ctypes.c_double(), ctypes.c_double()
         pvar = ctypes.byref(var) if want_var else None      # mean only: the library neither builds nor reads K^-1
-        if gp._route() in ("generic", "gaussian", "periodic", "matern"):
+        if gp._route() in ("generic", "gaussian", "periodic", "matern") and not pseudo:
             # (any fitted handle: a gpx_fit_matrix one, a gpx_periodic_fit one -- the reference has no input derivatives for that kernel,
             # it is propagated as any generic operator --, a gpx_matern_fit one likewise, or -- a caller-supplied C_ux on the built-in route -- the gpx_fit one)
             st = _gpx.lib.gpx_propagate_exact_matrix(gp._dev().handle, None, None, _gpx.ptr(x), gp.n, gp.d, _gpx.ptr(w), _gpx.ptr(C),
@@ -545,6 +549,12 @@ class _MixturePropagation(UncertaintyPropagationGA, UncertaintyPropagation):
     Built-in Gaussian, periodic and Matern kernels: gpx_propagate_quadrature_many -- nodes, mu and sigma^2 never leave the device.  Every other route
     (a generic operator, SPGP): the nodes are built on the host, gp.estimate_many evaluates them, gpx_mixture_reduce reduces its output."""
 
+    def __init__(self, gp):
+        if getattr(gp, "_pseudo", False):
+            raise TypeError("%s evaluates the predictor at its nodes: pass the SPGP GaussianProcess itself (the PseudoInputGP's parent), "
+                            "whose estimate_many serves it" % type(self).__name__)
+        UncertaintyPropagationGA.__init__(self, gp)
+
     def _rule(self, d):
         raise NotImplementedError
 
@@ -630,7 +640,7 @@ class UncertaintyPropagationNumericalHG(_MixturePropagation):
     A = sqrt(2) chol(Sigma_x) instead, the rule for the covariance as given.  order^d may not exceed 2^22 nodes."""
 
     def __init__(self, gp, order=4, full_sigma=False):
-        UncertaintyPropagationGA.__init__(self, gp)
+        _MixturePropagation.__init__(self, gp)
         self.order = int(order)
         self.full_sigma = bool(full_sigma)
         if self.order < 1:
@@ -662,7 +672,7 @@ class UncertaintyPropagationMC(_MixturePropagation):
     independent sets inside propagate_GA (and its sampler is SVD-based): results are statistically equivalent, not sample-identical."""
 
     def __init__(self, gp, n=1000, seed=None):
-        UncertaintyPropagationGA.__init__(self, gp)
+        _MixturePropagation.__init__(self, gp)
         self.n = int(n)
         self.seed = seed
         if self.n < 1:

@@ -6,7 +6,7 @@ behind a ctypes C-ABI (include/gpx.h).  Importing this package without the built
 """
 from . import _gpx  # noqa: F401  (fails loudly when libgpx.so is missing)
 from .Covariance import Covariance, GaussianCovariance, MaternCovariance, PeriodicCovariance, SPGPCovariance, tracedot  # noqa: F401
-from .GaussianProcess import GaussianProcess  # noqa: F401
+from .GaussianProcess import GaussianProcess, PseudoInputGP  # noqa: F401
 from .UncertaintyPropagation import (  # noqa: F401
     UncertaintyPropagationApprox,
     UncertaintyPropagationExact,
@@ -24,7 +24,7 @@ from .InverseUncertaintyPropagation import (  # noqa: F401,E402
 )
 
 __all__ = [
-    "Covariance", "GaussianCovariance", "MaternCovariance", "PeriodicCovariance", "SPGPCovariance", "GaussianProcess",
+    "Covariance", "GaussianCovariance", "MaternCovariance", "PeriodicCovariance", "SPGPCovariance", "GaussianProcess", "PseudoInputGP",
     "UncertaintyPropagationGA",
     "UncertaintyPropagationApprox", "UncertaintyPropagationExact", "UncertaintyPropagationLinear", "tracedot",
     "UncertaintyPropagation", "UncertaintyPropagationMC", "UncertaintyPropagationNumericalHG",

@@ -116,6 +116,7 @@ SIGNATURES = {
     "gpx_spgp_dense": (_int, [_hp, _int, _dp]),
     "gpx_spgp_cross": (_int, [_hp, _dp, _i64, _dp, _i64, _dp]),
     "gpx_spgp_split": (_int, [_hp, ctypes.POINTER(_int)]),
+    "gpx_spgp_pseudo_handle": (_int, [_hp, ctypes.POINTER(_hp)]),
     "gpx_profile_enable": (_int, [_hp, _int]),
     "gpx_profile_reset": (_int, [_hp]),
     "gpx_profile_read": (_int, [_hp, _int, ctypes.POINTER(_i64), ctypes.POINTER(_dbl), ctypes.POINTER(_dbl)]),
