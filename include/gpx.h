@@ -250,6 +250,33 @@ void gpx_kinv_model_free(gpx_kinv_model *m);
 int  gpx_propagate_exact_model(gpx_kinv_model *m, const double *x, int d, const double *w, const double *C_ux, const double *u,
                                const double *Sigma, double cuu, double *mean, double *var);
 
+/* ---- Variance decomposition of the predictor mean under independent Gaussian inputs: first-order and total-effect Sobol indices ----
+ * No reference counterpart; the closest reference code is the nquad / Hermite-Gauss cross-checks of
+ * skgpuppy/UncertaintyPropagation.py:135-210.  x_k ~ N(u_k, s_k) independent, s_k >= 0; mu(x) = sum_i beta_i c_i(x), beta = the handle's
+ * alpha, c_i(x) = v exp(-1/2 sum_k w_k (x_k - x_ik)^2) the PLAIN kernel: the +vt of the scalar kernel on elementwise equality is a
+ * measure-zero event under a continuous input and does not enter.  Per coordinate k, a_i = u_k - x_ik, om = w_k, sg = s_k:
+ *   lm_ik     = -1/2 log1p(om sg) - 1/2 om a_i^2 / (1 + om sg)                                          log E[factor k of c_i]
+ *   lE_k(i,j) = -1/2 log1p(2 om sg) - 1/2 om (1 + om sg) / (1 + 2 om sg) (a_i^2 + a_j^2) + om^2 sg / (1 + 2 om sg) a_i a_j
+ *             = -1/2 log1p(2 om sg) - 1/4 om (a_i - a_j)^2 - 1/4 om (a_i + a_j)^2 / (1 + 2 om sg)       log E[factor k of c_i c_j] (v-free)
+ *   m_k = exp(lm_ik + lm_jk),  E_k = exp(lE_k(i,j)),  b_ij = v^2 beta_i beta_j
+ *   mean    = v sum_i beta_i exp(sum_k lm_ik)
+ *   V       = sum_ij b_ij (prod_k E_k - prod_k m_k)                    the variance of mu(x)
+ *   first_k = sum_ij b_ij (prod_{l != k} m_l) (E_k - m_k)              Var_{x_k}(E[mu | x_k])
+ *   total_k = sum_ij b_ij (prod_{l != k} E_l) (E_k - m_k)              E[Var_{x_k}(mu | x_{~k})]
+ * Every factor is an expectation of kernel factors in (0, 1]: no exponent is positive (the second way of writing lE_k is the one
+ * evaluated).  s_k = 0 gives E_k = m_k: first_k and total_k are then exactly 0.0 (the coordinate is skipped).  sum_k first_k <= V <=
+ * sum_k total_k.  It reads (x, beta, v, w) alone -- no K^-1, no factor, no solve -- so it serves gpx_fit handles and pseudo-input handles
+ * (gpx_spgp_pseudo_handle) alike, at d exponentials per pair of training points and sweep of 8 coordinates; a Matern, periodic or
+ * gpx_fit_matrix handle: GPX_ERR_STATE, the text names the handle's kernel.
+ * U [b, d]; S [b, d] variances, or ONE [d] for every input when s_shared != 0; mean [b] (WITHOUT meant), var_mean [b] = V, first [b, d];
+ * total [b, d] may be NULL: its sums are then not formed, the other outputs keep their bits.  Host or device pointers.  A negative or
+ * non-finite s_k or a null required pointer: GPX_ERR_BAD_ARG before the first launch, nothing written.  b = 0 is a no-op.  Inputs run in
+ * chunks sized from the pooled scratch (GPX_SENS_CHUNK, read at every call: at most that many inputs a chunk); no atomics, fixed
+ * summation order: an input's result depends neither on its place in the batch nor on the chunking.  A far input (every c_i ~ 1e-130)
+ * gives finite, tiny or zero outputs. */
+int gpx_sensitivity_many(gpx_handle *h, const double *U, const double *S, int s_shared, int64_t b, double *mean, double *var_mean,
+                         double *first, double *total);
+
 /* ---- "next" row f1: hyper-parameter likelihood at the handle's theta
  * (Covariance._negativeloglikelihood / _d_nll_d_theta, skgpuppy/Covariance.py:197-216, :266-282, :605-657) ----
  * nll = N/2 log 2pi + 1/2 log det K + 1/2 t^T K^-1 t ;  grad_out[2+d] = d nll / d theta. */

@@ -23,7 +23,10 @@ from .InverseUncertaintyPropagation import (  # noqa: F401,E402
     InverseUncertaintyPropagationNumerical,
 )
 
+from .SensitivityAnalysis import SensitivityAnalysis  # noqa: F401,E402
+
 __all__ = [
+    "SensitivityAnalysis",
     "Covariance", "GaussianCovariance", "MaternCovariance", "PeriodicCovariance", "SPGPCovariance", "GaussianProcess", "PseudoInputGP",
     "UncertaintyPropagationGA",
     "UncertaintyPropagationApprox", "UncertaintyPropagationExact", "UncertaintyPropagationLinear", "tracedot",

@@ -94,6 +94,7 @@ SIGNATURES = {
     "gpx_kinv_model_create": (_int, [_dp, _dp, _i64, ctypes.POINTER(_hp)]),
     "gpx_kinv_model_free": (None, [_hp]),
     "gpx_propagate_exact_model": (_int, [_hp, _dp, _int, _dp, _dp, _dp, _dp, _dbl, ctypes.POINTER(_dbl), ctypes.POINTER(_dbl)]),
+    "gpx_sensitivity_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp, _dp, _dp, _dp]),
     "gpx_nll": (_int, [_hp, ctypes.POINTER(_dbl)]),
     "gpx_nll_grad": (_int, [_hp, _dp]),
     "gpx_periodic_gram": (_int, [_dp, _i64, _dp, _i64, _int, _dp, _int, _dp]),
