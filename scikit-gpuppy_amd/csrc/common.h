@@ -1,6 +1,7 @@
 // common.h -- shared declarations of libgpx (gfx950 only; no other target is supported)
 #pragma once
 #include <hip/hip_runtime.h>
+#include <assert.h>
 #include <stdint.h>
 #include <algorithm>
 #include <functional>
@@ -124,8 +125,8 @@ struct TriSolver {
 
 // ---- the fitted model held in HBM ------------------------------------------------------------
 // What evaluates a handle's kernel: nothing (the matrix was supplied: gpx_fit_matrix), gram_kernel on xs_w (gpx_fit, gpx_adopt_factor)
-// periodic_gram_kernel on per->x (gpx_periodic_fit) or matern_gram_kernel on mat->x (gpx_matern_fit).  Callers ask the handle_* helpers
-// below, not the fields.
+// periodic_gram_kernel (gpx_periodic_fit) or matern_gram_kernel (gpx_matern_fit) on raw->x.  Callers ask the handle_* helpers below, not
+// the fields.
 enum class KernelKind { Matrix, Gaussian, Periodic, Matern };
 struct gpx_handle {
     int device = 0;
@@ -176,25 +177,45 @@ struct gpx_handle {
     double u[GPX_MAX_D];
     double *V = nullptr;        // [ncolV, npad] column-major block of C, J_k, hh_k, tr
     double *KV = nullptr;       // [ncolV, npad] Kinv * V
-    struct PeriodicData *per = nullptr;   // gpx_periodic_fit only (periodic.hip): inputs and parameters of the periodic kernel; d stays 0
-    struct MaternData *mat = nullptr;     // gpx_matern_fit only (matern.hip): the same for the Matern kernel, with its nu
+    struct RawModel *raw = nullptr;   // gpx_periodic_fit / gpx_matern_fit only (rawmodel.hip): inputs and parameters of a raw-input kernel; d stays 0
     Profiler prof;
 };
 
-// ---- PeriodicCovariance (periodic.hip; skgpuppy/Covariance.py:361-433) -------------------------------------------------
-// theta = (log v, log vt, log w_1..d, log p_1..d, log w2_1..d).  A periodic handle is a matrix handle (d == 0: K was assembled on the
-// device instead of supplied) that keeps what gpx_periodic_predict / gpx_periodic_nll_grad evaluate the kernel on.
-struct PeriodicData {
+// ---- the raw-input kernels (rawmodel.hip): what PeriodicCovariance and MaternCovariance share ----------------------------------
+// Their Gram kernels read the inputs RAW (the periodic factor needs delta itself; equality is decided on max |delta|).  A handle of such
+// a kind is a matrix handle (d == 0: K was assembled on the device instead of supplied) that owns ONE RawModel -- a PeriodicData or a
+// MaternData, as `kind` says -- with what its predict / nll_grad / propagation entry points evaluate the kernel on.
+struct RawModel {
+    KernelKind kind;
     int d = 0;
     double v = 0, vt = 0;
-    double w[GPX_MAX_D], p[GPX_MAX_D], w2[GPX_MAX_D];   // exp(theta)
     double *x = nullptr;      // [n, d] raw inputs
     double *xT = nullptr;     // [d, npad] the same k-major (the gradient pass reads a column of K^-1 per lane)
-    double *par = nullptr;    // [4, d]: w / 2, fl(1 / p), its correction (periodic_math.h), w2 / 2
+    double *par = nullptr;    // the kernels' wave-uniform constants: [4, d] periodic, [d] Matern (raw_pack)
+    explicit RawModel(KernelKind k) : kind(k) {}
+};
+int raw_pack(const RawModel *m, double *host);    // host [<= 4 GPX_MAX_D] <- the content of par; returns its length
+// the preamble of both parsers: d in range, v, vt (checked) and w_k = exp(theta[2 + k]) (the kind checks them); `name` opens the texts
+int raw_parse_head(const char *name, const double *theta, int d, RawModel *out, double *w);
+RawModel *raw_clone(const RawModel *spec);        // a parsed spec's host part on the heap (null: out of host memory)
+int raw_upload(RawModel *m, const double *x, int64_t n, int64_t npad, hipStream_t s);   // x (host or device) -> m->x, xT, par; synchronises
+void raw_release(RawModel *m);
+// out[i][j] of the model's kernel from the raw inputs (launch_periodic_gram / launch_matern_gram by kind)
+int launch_raw_gram(const double *xi, int64_t n1, const double *xj, int64_t n2, const RawModel *m, double add_diag, int lower_only,
+                    int pad_mode, double *out, int64_t ld, int64_t rows_pad, int64_t cols_pad, hipStream_t s, Profiler *prof, int deriv = -1);
+// the stand-alone Gram of a parsed model (gpx_periodic_gram / gpx_matern_gram): raw_gram_args before the parse, raw_gram after it
+int raw_gram_args(const char *what, const double *xi, int64_t n1, const double *xj, int64_t n2, const double *out);
+int raw_gram(RawModel *m, const double *xi, int64_t n1, const double *xj, int64_t n2, int deriv, double *out);
+// the gradient pass of a handle's model and its column sums: o [sweeps * nc] on the host, sweeps = ceil(d / kc)
+int raw_nll_grad_sums(gpx_handle *h, int kc, int nc, double *o);
+
+// ---- PeriodicCovariance (periodic.hip; skgpuppy/Covariance.py:361-433) -------------------------------------------------
+// theta = (log v, log vt, log w_1..d, log p_1..d, log w2_1..d).  par [4, d]: w / 2, fl(1 / p), its correction (periodic_math.h), w2 / 2.
+struct PeriodicData : RawModel {
+    double w[GPX_MAX_D], p[GPX_MAX_D], w2[GPX_MAX_D];   // exp(theta)
+    PeriodicData() : RawModel(KernelKind::Periodic) {}
 };
 int periodic_parse(const double *theta, int d, PeriodicData *out);          // host; GPX_ERR_BAD_ARG with text
-int periodic_upload(PeriodicData *pd, const double *x, int64_t n, int64_t npad, hipStream_t s);   // x (host or device) -> pd->x, xT, par; synchronises
-void periodic_release(PeriodicData *pd);
 // out[i][j] = v exp(-q_ij) (+ vt where x_i == x_j in every component) (+ add_diag where row == col), q = 1/2 sum_k w_k delta_k^2 +
 // w2_k sin^2(pi delta_k / p_k), from the raw inputs; lower_only / pad_mode / padding contract as launch_gram.
 // deriv >= 0: d K / d theta_deriv instead (no add_diag; pd carries the parameters the factor is made of)
@@ -203,24 +224,18 @@ int launch_periodic_gram(const double *xi, int64_t n1, const double *xj, int64_t
                          Profiler *prof, int deriv = -1);
 constexpr int PER_KC = 8;                        // parameters per sweep of the gradient pass
 constexpr int PER_NC = 3 * PER_KC + 2;           // sums per sweep: S_0, (A_k, B_k, C_k) of the sweep's k, T
-// partial [sweeps, npad / 8, PER_NC] scratch, out_dev [sweeps, PER_NC]; sweeps = ceil(d / PER_KC)
+// the gradient pass alone (raw_nll_grad_sums): partial [sweeps, npad / 8, PER_NC]; sweeps = ceil(d / PER_KC)
 int launch_periodic_nll_grad(const double *Kinv, int64_t ld, int64_t n, int64_t npad, const PeriodicData *pd, const double *alpha,
-                             double *partial, double *out_dev, hipStream_t s, Profiler *prof);
+                             double *partial, hipStream_t s);
 
 // ---- MaternCovariance (matern.hip): ARD Matern with nu = 3/2 or 5/2 -------------------------------------------------------
-// theta = (log v, log vt, log w_1..d).  A Matern handle is, like a periodic one, a matrix handle (d == 0) that keeps what
-// gpx_matern_predict / gpx_matern_nll_grad / gpx_matern_propagate_* evaluate the kernel on.
-struct MaternData {
-    int d = 0, nu2 = 5;       // nu2 = 2 nu: 3 or 5
-    double v = 0, vt = 0;
+// theta = (log v, log vt, log w_1..d).  par [d]: w.
+struct MaternData : RawModel {
+    int nu2 = 5;              // 2 nu: 3 or 5
     double w[GPX_MAX_D];      // exp(theta)
-    double *x = nullptr;      // [n, d] raw inputs
-    double *xT = nullptr;     // [d, npad] the same k-major (the gradient pass reads a column of K^-1 per lane)
-    double *wdev = nullptr;   // [d] w on the device
+    MaternData() : RawModel(KernelKind::Matern) {}
 };
 int matern_parse(const double *theta, int d, int nu2, MaternData *out);    // host; GPX_ERR_BAD_ARG with text
-int matern_upload(MaternData *md, const double *x, int64_t n, int64_t npad, hipStream_t s);   // x (host or device) -> md->x, xT, wdev; synchronises
-void matern_release(MaternData *md);
 // out[i][j] = Kf(q_ij) (+ vt where x_i == x_j in every component) (+ add_diag where row == col), q = sum_k w_k delta_k^2, from the raw
 // inputs; lower_only / pad_mode / padding contract as launch_gram.  deriv >= 0: d K / d theta_deriv instead (no add_diag)
 int launch_matern_gram(const double *xi, int64_t n1, const double *xj, int64_t n2, const MaternData *md, double add_diag, int lower_only,
@@ -232,6 +247,9 @@ int launch_matern_build_many(int layout, int nu2, const double *x, int64_t n, in
                              Profiler *prof);
 constexpr int MAT_KC = 8;                        // coordinates per sweep of the gradient pass
 constexpr int MAT_NC = MAT_KC + 2;               // sums per sweep: S_0, A_k of the sweep's k, T
+// the gradient pass alone (raw_nll_grad_sums): partial [sweeps, npad / 8, MAT_NC]; sweeps = ceil(d / MAT_KC)
+int launch_matern_nll_grad(const double *Kinv, int64_t ld, int64_t n, int64_t npad, const MaternData *md, const double *alpha, double *partial,
+                           hipStream_t s);
 
 // ---- kernels / host launchers implemented across the .hip files -------------------------------
 int launch_gram(const double *xi_w, int64_t n1, const double *xj_w, int64_t n2, int d, double v, double add_diag,
@@ -507,39 +525,55 @@ int launch_exact_many_finish(const double *Y, const double *H, int64_t npad, con
     } while (0)
 // ---- the one description of a handle's kernel (KernelKind) ----
 static inline bool handle_has_kernel(const gpx_handle *h) { return h->kind != KernelKind::Matrix; }
-static inline int handle_dim(const gpx_handle *h)   // 0: a supplied matrix
-{
-    return h->kind == KernelKind::Periodic ? h->per->d : h->kind == KernelKind::Matern ? h->mat->d : h->d;
-}
+static inline int handle_dim(const gpx_handle *h) { return h->raw ? h->raw->d : h->d; }   // 0: a supplied matrix
 // the training inputs [n, handle_dim] in the form the handle's Gram kernel reads: scaled by sqrt(w) (Gaussian), raw (periodic, Matern)
-static inline const double *handle_train_inputs(const gpx_handle *h)
-{
-    return h->kind == KernelKind::Periodic ? h->per->x : h->kind == KernelKind::Matern ? h->mat->x : h->xs_w;
-}
+static inline const double *handle_train_inputs(const gpx_handle *h) { return h->raw ? h->raw->x : h->xs_w; }
 // does the handle's Gram kernel add vt wherever two rows are equal (the prior variance of a query is then v + vt also for its bound)
-static inline bool handle_gram_has_vt(const gpx_handle *h) { return h->kind == KernelKind::Periodic || h->kind == KernelKind::Matern; }
+static inline bool handle_gram_has_vt(const gpx_handle *h) { return h->raw != nullptr; }
+// the kind's own host fields (w / p / w2; nu2) of a handle of that kind
+static inline const PeriodicData *handle_periodic(const gpx_handle *h)
+{
+    assert(h->kind == KernelKind::Periodic && h->raw && h->raw->kind == h->kind);
+    return static_cast<const PeriodicData *>(h->raw);
+}
+static inline const MaternData *handle_matern(const gpx_handle *h)
+{
+    assert(h->kind == KernelKind::Matern && h->raw && h->raw->kind == h->kind);
+    return static_cast<const MaternData *>(h->raw);
+}
 // what the builders of C(u, x_i) add where u equals row i elementwise (the reference's scalar kernel, Covariance.py:440-451): vt on a fitted
 // model, whose rows are observations; 0 on a pseudo-input model -- a pseudo-input is no observation and SPGP's k(x*) = K(x*, xbar) never
 // carries vt.  The prior variance v + vt is not affected.
 static inline double handle_vt_on_equal(const gpx_handle *h) { return h->no_factor ? 0.0 : h->vt; }
-// launch_gram / launch_periodic_gram / launch_matern_gram with the handle's parameters; xi, xj in the form of handle_train_inputs
+// launch_gram / launch_raw_gram with the handle's parameters; xi, xj in the form of handle_train_inputs
 static inline int handle_gram(const gpx_handle *h, const double *xi, int64_t n1, const double *xj, int64_t n2, double add_diag, int lower_only,
                               int pad_mode, double *out, int64_t ld, int64_t rows_pad, int64_t cols_pad, hipStream_t s, Profiler *prof)
 {
-    switch (h->kind) {
-    case KernelKind::Gaussian: return launch_gram(xi, n1, xj, n2, h->d, h->v, add_diag, lower_only, pad_mode, out, ld, rows_pad, cols_pad, s, prof);
-    case KernelKind::Periodic: return launch_periodic_gram(xi, n1, xj, n2, h->per, add_diag, lower_only, pad_mode, out, ld, rows_pad, cols_pad, s, prof);
-    case KernelKind::Matern: return launch_matern_gram(xi, n1, xj, n2, h->mat, add_diag, lower_only, pad_mode, out, ld, rows_pad, cols_pad, s, prof);
-    default: gpx_set_error("handle_gram: the handle was built from a supplied matrix"); return GPX_ERR_STATE;
-    }
+    if (h->raw) return launch_raw_gram(xi, n1, xj, n2, h->raw, add_diag, lower_only, pad_mode, out, ld, rows_pad, cols_pad, s, prof);
+    if (h->kind == KernelKind::Gaussian) return launch_gram(xi, n1, xj, n2, h->d, h->v, add_diag, lower_only, pad_mode, out, ld, rows_pad, cols_pad, s, prof);
+    gpx_set_error("handle_gram: the handle was built from a supplied matrix");
+    return GPX_ERR_STATE;
 }
-// entry points that evaluate the GaussianCovariance kernel need the handle's inputs and theta: not a gpx_fit_matrix handle
-#define NEED_KERNEL(h, what)                                                                                             \
-    do {                                                                                                                 \
-        if ((h)->kind == KernelKind::Periodic) { gpx_set_error(what ": the handle holds a PeriodicCovariance model (gpx_periodic_fit): use the gpx_periodic_* entry points"); return GPX_ERR_STATE; } \
-        if ((h)->kind == KernelKind::Matern) { gpx_set_error(what ": the handle holds a MaternCovariance model (gpx_matern_fit): use the gpx_matern_* entry points"); return GPX_ERR_STATE; } \
-        if (!handle_has_kernel(h)) { gpx_set_error(what ": the handle was built from a supplied matrix (gpx_fit_matrix): no inputs / theta to evaluate the kernel on"); return GPX_ERR_STATE; } \
-    } while (0)
+// The refusals of a handle of the wrong kind, once, from the names of a raw-input kind: its class <cls>Covariance, its entry points gpx_<fn>_*.
+struct KindName { const char *cls, *fn; };
+static inline KindName kind_name(KernelKind k) { return k == KernelKind::Periodic ? KindName{"Periodic", "periodic"} : KindName{"Matern", "matern"}; }
+// an entry point of one raw-input kind (what) on a handle of another
+static inline int need_kind(const gpx_handle *h, KernelKind kind, const char *what)
+{
+    if (h->kind == kind) return 0;
+    gpx_set_error("%s: not a gpx_%s_fit handle", what, kind_name(kind).fn);
+    return GPX_ERR_STATE;
+}
+// entry points that evaluate the GaussianCovariance kernel need the handle's inputs and theta: not a raw-input or gpx_fit_matrix handle
+static inline int need_kernel(const gpx_handle *h, const char *what)
+{
+    if (h->kind == KernelKind::Gaussian) return 0;
+    const KindName nm = kind_name(h->kind);
+    if (h->raw) gpx_set_error("%s: the handle holds a %sCovariance model (gpx_%s_fit): use the gpx_%s_* entry points", what, nm.cls, nm.fn, nm.fn);
+    else gpx_set_error("%s: the handle was built from a supplied matrix (gpx_fit_matrix): no inputs / theta to evaluate the kernel on", what);
+    return GPX_ERR_STATE;
+}
+#define NEED_KERNEL(h, what) GPX_TRY(need_kernel(h, what))
 
 int fetch_small(double *dst, const double *src, size_t n);   // a few doubles from a caller's pointer (host or device) into host memory (runtime.hip)
 int ensure_Z(gpx_handle *h, int64_t rows);

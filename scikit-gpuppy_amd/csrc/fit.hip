@@ -177,10 +177,8 @@ extern "C" void gpx_free(gpx_handle *h)
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     h->prof.destroy();
     h->tri.release();
-    periodic_release(h->per);
-    h->per = nullptr;
-    matern_release(h->mat);
-    h->mat = nullptr;
+    raw_release(h->raw);
+    h->raw = nullptr;
     if (h->external_factor) { h->L = nullptr; h->Dinv = nullptr; h->diagL = nullptr; }
     double *bufs[] = {h->Ksrc, h->x, h->xs_w, h->sw, h->wdev, h->L, h->Dinv, h->diagL, h->t, h->y, h->alpha, h->Kinv, h->KinvRows, h->Z, h->small, h->V, h->KV};
     for (double *p : bufs)
@@ -277,26 +275,25 @@ static void setup_lookahead_streams(gpx_handle *h)
 
 // Kmat != nullptr: the handle of a SUPPLIED covariance matrix (gpx_fit_matrix; n x n, host or device): no inputs, no kernel
 // parameters (d = 0) -- the factor, alpha, K^-1 and the solves work as for any handle, everything that evaluates the kernel does not.
-// pspec != nullptr: a PeriodicCovariance model (gpx_periodic_fit): as a matrix handle (d = 0), but K is assembled on the device from x
-// and the parsed parameters, which the handle keeps (h->per); mspec != nullptr: the same for a MaternCovariance model (h->mat)
+// spec != nullptr: a PeriodicCovariance or MaternCovariance model (gpx_periodic_fit, gpx_matern_fit): as a matrix handle (d = 0), but K is
+// assembled on the device from x and the parsed parameters, which the handle keeps (h->raw)
 static int make_handle(const double *x, const double *t_centered, int64_t n, int d, const double *theta, void *stream,
-                       const ExternalFactor *ext, gpx_handle **out, const double *Kmat = nullptr, const PeriodicData *pspec = nullptr,
-                       const MaternData *mspec = nullptr)
+                       const ExternalFactor *ext, gpx_handle **out, const double *Kmat = nullptr, const RawModel *spec = nullptr)
 {
     gpx_handle *h = new (std::nothrow) gpx_handle();
     if (!h) { gpx_set_error("out of host memory"); return GPX_ERR_HIP; }
     h->device = gpx_thread_device();
     int rc = 0;
-    if (pspec || mspec) {
-        h->v = pspec ? pspec->v : mspec->v;
-        h->vt = pspec ? pspec->vt : mspec->vt;
+    if (spec) {
+        h->v = spec->v;
+        h->vt = spec->vt;
         d = 0;
     } else if (!Kmat) {
         rc = parse_theta(theta, d, &h->v, &h->vt, h->w);
         if (rc) { delete h; return rc; }
         memcpy(h->theta, theta, sizeof(double) * (d + 2));
     } else d = 0;
-    h->kind = pspec ? KernelKind::Periodic : mspec ? KernelKind::Matern : Kmat ? KernelKind::Matrix : KernelKind::Gaussian;
+    h->kind = spec ? spec->kind : Kmat ? KernelKind::Matrix : KernelKind::Gaussian;
     h->n = n;
     h->d = d;
     h->npad = round_up(n, TILE);
@@ -333,14 +330,9 @@ static int make_handle(const double *x, const double *t_centered, int64_t n, int
     }
 #define FIT_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { gpx_set_error("%s failed: %s", #call, hipGetErrorString(e_)); return fail(GPX_ERR_HIP); } } while (0)
     FIT_HIP(hipMemsetAsync(h->info_dev, 0, sizeof(int) * (16 + 2 * h->nblk), s));
-    if (pspec) {
-        h->per = new (std::nothrow) PeriodicData(*pspec);
-        if (!h->per) { gpx_set_error("out of host memory"); return fail(GPX_ERR_HIP); }
-        if ((rc = periodic_upload(h->per, x, n, h->npad, s))) return fail(rc);
-    } else if (mspec) {
-        h->mat = new (std::nothrow) MaternData(*mspec);
-        if (!h->mat) { gpx_set_error("out of host memory"); return fail(GPX_ERR_HIP); }
-        if ((rc = matern_upload(h->mat, x, n, h->npad, s))) return fail(rc);
+    if (spec) {
+        if (!(h->raw = raw_clone(spec))) { gpx_set_error("out of host memory"); return fail(GPX_ERR_HIP); }
+        if ((rc = raw_upload(h->raw, x, n, h->npad, s))) return fail(rc);
     } else if (Kmat) {
         if ((rc = dalloc(&h->Ksrc, n * n))) return fail(rc);
         FIT_HIP(hipMemcpyAsync(h->Ksrc, Kmat, sizeof(double) * n * n, hipMemcpyDefault, s));
@@ -452,7 +444,7 @@ extern "C" int gpx_matern_fit(const double *x, const double *t_centered, int64_t
     if (!x || !t_centered || !out || n < 1) { gpx_set_error("gpx_matern_fit: null pointer or n < 1"); return GPX_ERR_BAD_ARG; }
     MaternData md;
     GPX_TRY(matern_parse(theta, d, nu2, &md));
-    return make_handle(x, t_centered, n, 0, nullptr, stream, nullptr, out, nullptr, nullptr, &md);
+    return make_handle(x, t_centered, n, 0, nullptr, stream, nullptr, out, nullptr, &md);
 }
 
 extern "C" int gpx_n(const gpx_handle *h, int64_t *n, int *d)

@@ -1,4 +1,4 @@
-// gram_tile.h -- the block-tile frame of every Gram / cross-covariance kernel (gram.hip, periodic.hip), once.
+// gram_tile.h -- the block-tile frame of every Gram / cross-covariance kernel (gram.hip, periodic.hip, matern.hip), once.
 //
 // A block of 256 threads owns a 64 x 128 tile of out: the column tile of xj sits k-major in LDS, a wave's 16 rows of xi are wave-uniform
 // (scalar loads), a lane owns two adjacent columns and stores 16 bytes.  The frame owns the tile decode, the staging, the row pointers,
@@ -107,4 +107,12 @@ static inline bool gram_launch_plan(int64_t rows_pad, int64_t cols_pad, int64_t 
         pl->lower_only = 2;
     }
     return true;
+}
+// the plan of a raw-input kernel's launcher (periodic.hip, matern.hip), which also writes d K / d theta_deriv, deriv in [0, nderiv); -1:
+// K itself.  A derivative has no diagonal term: identity padding would have no meaning for it, and no caller asks for it.
+static inline bool raw_gram_launch_plan(int64_t n1, int64_t n2, int64_t rows_pad, int64_t cols_pad, int64_t ld, int d, int lower_only, int pad_mode,
+                                        int deriv, int nderiv, GramLaunch *pl)
+{
+    return gram_launch_plan(rows_pad, cols_pad, ld, d, lower_only, pl) && n1 >= 1 && n2 >= 1 && n1 <= rows_pad && n2 <= cols_pad && deriv >= -1 &&
+           deriv < nderiv && !(deriv >= 0 && pad_mode == PAD_IDENT);
 }

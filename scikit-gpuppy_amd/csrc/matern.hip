@@ -14,6 +14,7 @@
 
 #include "common.h"
 #include "gram_tile.h"
+#include "nll_grad_tile.h"
 #include "radial.h"   // MaternRadial: the radial factors at q, one sqrt and one exp for all of them
 
 // what the deriv variant writes (the parameter's group; MD_W: its coordinate is a second argument)
@@ -93,15 +94,13 @@ int launch_matern_gram(const double *xi, int64_t n1, const double *xj, int64_t n
 {
     const int d = md->d;
     GramLaunch pl;
-    // (a derivative has no diagonal term: identity padding would have no meaning for it, and no caller asks for it)
-    if (!gram_launch_plan(rows_pad, cols_pad, ld, d, lower_only, &pl) || n1 < 1 || n2 < 1 || n1 > rows_pad || n2 > cols_pad || deriv < -1 ||
-        deriv >= 2 + d || (deriv >= 0 && pad_mode == PAD_IDENT) || (md->nu2 != 3 && md->nu2 != 5)) {
+    if (!raw_gram_launch_plan(n1, n2, rows_pad, cols_pad, ld, d, lower_only, pad_mode, deriv, 2 + d, &pl) || (md->nu2 != 3 && md->nu2 != 5)) {
         gpx_set_error("launch_matern_gram: bad shape (n1=%ld n2=%ld rows_pad=%ld cols_pad=%ld ld=%ld d=%d deriv=%d nu2=%d)", (long)n1, (long)n2,
                       (long)rows_pad, (long)cols_pad, (long)ld, d, deriv, md->nu2);
         return GPX_ERR_BAD_ARG;
     }
     ProfScope ps(prof, s, GPX_K_GRAM, pl.bytes);
-    const double *w = md->wdev;
+    const double *w = md->par;
     const int kind = deriv < 2 ? deriv : MD_W, kd = deriv < 2 ? 0 : deriv - 2;
 #define MATERN_GRAM(NU2, DERIV, diag)                                                                                                       \
     hipLaunchKernelGGL((matern_gram_kernel<NU2, DERIV>), pl.grid, dim3(256), pl.lds, s, xi, (long)n1, xj, (long)n2, d, w, md->v, md->vt, diag, \
@@ -119,104 +118,48 @@ int launch_matern_gram(const double *xi, int64_t n1, const double *xj, int64_t n
 }
 
 // ---------------------------------------------------------------------------------------------
-// Gradient of the negative log likelihood: ONE pass over the j <= i half of K^-1 recomputes the radial factors on the fly and
-// accumulates, with M_ij = Kinv_ij - a_i a_j,
-//   S_0 = sum M Kf,   A_k = sum M G delta_k^2,   T = sum over the pairs with x_i == x_j of M     (T = tr Kinv - a.a without duplicate rows)
-// so that  g_0 = S_0 / 2,  g_1 = vt T / 2,  g_{2+k} = -w_k A_k / 4.
-// The frame is periodic_nll_grad_kernel's: grid.y sweeps of MAT_KC coordinates each (d + 2 accumulators do not fit in registers at
-// d = 64); a sweep forms q over ALL d coordinates in a runtime loop, then the weighted squares of its own coordinates.  A lane owns a
-// column j and reads it from the k-major copy of the inputs (coalesced); the block's 8 rows sit in LDS.
-// partial[sweep][block][MAT_NC]: [0] = S_0, [1 + kk] = A of coordinate sweep MAT_KC + kk, [MAT_KC + 1] = T.
+// Gradient of the negative log likelihood: the one pass of nll_grad_tile.h with the radial factors Kf and G of q_ij and, per coordinate,
+// the one sum A_k = sum M G delta_k^2, so that  g_0 = S_0 / 2,  g_1 = vt T / 2,  g_{2+k} = -w_k A_k / 4.
 // ---------------------------------------------------------------------------------------------
+template <int NU2>
+struct MaternGrad {
+    static constexpr int KC = MAT_KC, NA = 1, NC = MAT_NC;
+    const double *w;   // [d]
+    double v;
+    struct Coord { double wk; };
+
+    __device__ __forceinline__ Coord coord(int k) const { return {w[k]}; }
+    __device__ __forceinline__ double add_q(const Coord &c, double e, double q) const { return fma(c.wk * e, e, q); }
+    __device__ __forceinline__ double pair(double mij, double wgt, double q, bool equal, double &s0, double &t) const
+    {
+        const double m = mij * wgt;
+        const MaternRadial<NU2> rad(v, q);
+        s0 = fma(m, rad.kf(), s0);
+        if (equal) t += m;
+        return m * rad.g();
+    }
+    __device__ __forceinline__ void sweep(const Coord &, double wq, double e, double (&acc)[NC], int kk) const
+    {
+        acc[1 + kk] = fma(wq, e * e, acc[1 + kk]);
+    }
+};
+
 template <int NU2>
 __global__ __launch_bounds__(256) void matern_nll_grad_kernel(const double *__restrict__ Kinv, long ld, long n, long npad, int d,
                                                              const double *__restrict__ alpha, const double *__restrict__ x,
                                                              const double *__restrict__ xT, const double *__restrict__ w, double v,
                                                              double *__restrict__ partial)
 {
-    constexpr int R = 8, KC = MAT_KC, NC = MAT_NC;
-    __shared__ double xs[R][GPX_MAX_D];
-    __shared__ double as[R];
-    __shared__ double red[4][NC];
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    const int rb = gridDim.x - 1 - blockIdx.x;
-    const long i0 = (long)rb * R;
-    const int k0 = blockIdx.y * KC;
-    for (int q = t; q < R * GPX_MAX_D; q += 256) {
-        const int r = q / GPX_MAX_D, k = q - r * GPX_MAX_D;
-        xs[r][k] = (k < d && i0 + r < n) ? x[(i0 + r) * d + k] : 0.0;
-    }
-    if (t < R) as[t] = alpha[i0 + t];
-    __syncthreads();
-    double acc[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) acc[c] = 0.0;
-    for (long j = t; j < i0 + R && j < n; j += 256) {
-        const double aj = alpha[j];
-        double q[R], mx[R], wq[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) { q[r] = 0.0; mx[r] = 0.0; }
-        for (int k = 0; k < d; ++k) {
-            const double wk = w[k];
-            const double xjk = xT[(long)k * npad + j];
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const double e = xs[r][k] - xjk;
-                mx[r] = fmax(mx[r], fabs(e));
-                q[r] = fma(wk * e, e, q[r]);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const long i = i0 + r;
-            const bool live = i < n && j <= i;
-            const double mij = live ? Kinv[i * ld + j] - as[r] * aj : 0.0;
-            const double m = mij * ((j < i) ? 2.0 : 1.0);
-            const MaternRadial<NU2> rad(v, q[r]);
-            acc[0] = fma(m, rad.kf(), acc[0]);
-            if (live && mx[r] == 0.0) acc[NC - 1] += m;
-            wq[r] = m * rad.g();
-        }
-#pragma unroll
-        for (int kk = 0; kk < KC; ++kk) {
-            const int k = k0 + kk;
-            if (k < d) {
-                const double xjk = xT[(long)k * npad + j];
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const double e = xs[r][k] - xjk;
-                    acc[1 + kk] = fma(wq[r], e * e, acc[1 + kk]);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const double s = wave_sum(acc[c]);
-        if (lane == 0) red[wave][c] = s;
-    }
-    __syncthreads();
-    if (t < NC) partial[((long)blockIdx.y * gridDim.x + rb) * NC + t] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+    nll_grad_tile(MaternGrad<NU2>{w, v}, Kinv, ld, n, npad, d, alpha, x, xT, partial);
 }
 
-// partial [sweeps, npad / 8, MAT_NC] scratch, out_dev [sweeps, MAT_NC]; sweeps = ceil(d / MAT_KC)
-static int launch_matern_nll_grad(const double *Kinv, int64_t ld, int64_t n, int64_t npad, const MaternData *md, const double *alpha, double *partial,
-                                  double *out_dev, hipStream_t s, Profiler *prof)
+int launch_matern_nll_grad(const double *Kinv, int64_t ld, int64_t n, int64_t npad, const MaternData *md, const double *alpha, double *partial,
+                           hipStream_t s)
 {
-    const unsigned nblk = (unsigned)(npad / 8);
-    const int sweeps = (md->d + MAT_KC - 1) / MAT_KC;
-    {
-        ProfScope ps(prof, s, GPX_K_QUAD, 4.0 * (double)npad * (double)npad * sweeps);
-        const dim3 grid(nblk, (unsigned)sweeps);
-        if (md->nu2 == 5)
-            hipLaunchKernelGGL(matern_nll_grad_kernel<5>, grid, dim3(256), 0, s, Kinv, (long)ld, (long)n, (long)npad, md->d, alpha,
-                               (const double *)md->x, (const double *)md->xT, (const double *)md->wdev, md->v, partial);
-        else
-            hipLaunchKernelGGL(matern_nll_grad_kernel<3>, grid, dim3(256), 0, s, Kinv, (long)ld, (long)n, (long)npad, md->d, alpha,
-                               (const double *)md->x, (const double *)md->xT, (const double *)md->wdev, md->v, partial);
-        GPX_HIP(hipGetLastError());
-    }
-    for (int y = 0; y < sweeps; ++y) GPX_TRY(launch_sum_columns(partial + (int64_t)y * nblk * MAT_NC, nblk, MAT_NC, out_dev + y * MAT_NC, s));
+    const dim3 grid((unsigned)(npad / 8), (unsigned)((md->d + MAT_KC - 1) / MAT_KC));
+    hipLaunchKernelGGL(md->nu2 == 5 ? matern_nll_grad_kernel<5> : matern_nll_grad_kernel<3>, grid, dim3(256), 0, s, Kinv, (long)ld, (long)n, (long)npad,
+                       md->d, alpha, (const double *)md->x, (const double *)md->xT, (const double *)md->par, md->v, partial);
+    GPX_HIP(hipGetLastError());
     return 0;
 }
 
@@ -422,119 +365,45 @@ int launch_matern_build_many(int layout, int nu2, const double *x, int64_t n, in
     return 0;
 }
 
-// ---- parameters and inputs of a Matern model ----------------------------------------------------------------------
+// ---- parameters of a Matern model ------------------------------------------------------------------------------------------
 int matern_parse(const double *theta, int d, int nu2, MaternData *out)
 {
     if (nu2 != 3 && nu2 != 5) {
         gpx_set_error("matern kernel: nu2 = 2 nu = %d (3 or 5 supported)", nu2);
         return GPX_ERR_BAD_ARG;
     }
-    if (!theta || d < 1 || d > GPX_MAX_D) {
-        gpx_set_error("matern kernel: bad theta / d=%d (1..%d supported)", d, GPX_MAX_D);
-        return GPX_ERR_BAD_ARG;
-    }
-    out->d = d;
     out->nu2 = nu2;
-    out->v = exp(theta[0]);
-    out->vt = exp(theta[1]);   // theta[1] = -inf gives vt = 0
-    if (!(out->v > 0.0) || !isfinite(out->v) || !isfinite(out->vt)) {
-        gpx_set_error("matern kernel: theta gives v=%g vt=%g", out->v, out->vt);
-        return GPX_ERR_BAD_ARG;
-    }
-    for (int k = 0; k < d; ++k) {
-        out->w[k] = exp(theta[2 + k]);
+    GPX_TRY(raw_parse_head("matern", theta, d, out, out->w));
+    for (int k = 0; k < d; ++k)
         if (!(out->w[k] >= 0.0) || !isfinite(out->w[k])) {
             gpx_set_error("matern kernel: theta gives w[%d]=%g", k, out->w[k]);
             return GPX_ERR_BAD_ARG;
         }
-    }
     return 0;
-}
-
-__global__ __launch_bounds__(256) void matern_transpose_kernel(const double *__restrict__ x, long n, long npad, int d, double *__restrict__ xT)
-{
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= npad * d) return;
-    const long k = e / npad, j = e - k * npad;
-    xT[e] = j < n ? x[j * d + k] : 0.0;
-}
-
-int matern_upload(MaternData *md, const double *x, int64_t n, int64_t npad, hipStream_t s)
-{
-    const int d = md->d;
-    GPX_TRY(dalloc(&md->wdev, d));
-    GPX_TRY(dalloc(&md->x, n * d));
-    GPX_TRY(dalloc(&md->xT, npad * d));
-    GPX_HIP(hipMemcpyAsync(md->wdev, md->w, sizeof(double) * d, hipMemcpyHostToDevice, s));
-    GPX_HIP(hipMemcpyAsync(md->x, x, sizeof(double) * n * d, hipMemcpyDefault, s));
-    hipLaunchKernelGGL(matern_transpose_kernel, dim3((unsigned)((npad * d + 255) / 256)), dim3(256), 0, s, (const double *)md->x, (long)n, (long)npad,
-                       d, md->xT);
-    GPX_HIP(hipGetLastError());
-    GPX_HIP(hipStreamSynchronize(s));   // md->w may be a caller's stack object
-    return 0;
-}
-
-void matern_release(MaternData *md)
-{
-    if (!md) return;
-    for (double *p : {md->x, md->xT, md->wdev})
-        if (p) dfree(p);
-    delete md;
 }
 
 // ---- C-ABI ---------------------------------------------------------------------------------------------------------
-#define NEED_MATERN(h, what)                                                                                   \
-    do {                                                                                                       \
-        if ((h)->kind != KernelKind::Matern) { gpx_set_error(what ": not a gpx_matern_fit handle"); return GPX_ERR_STATE; } \
-    } while (0)
-
 extern "C" int gpx_matern_gram(const double *xi, int64_t n1, const double *xj, int64_t n2, int d, const double *theta, int nu2, int deriv,
                                double *out)
 {
-    GPX_TRY(gpx_require_device());
-    if (!xi || !xj || !out || n1 < 1 || n2 < 1) { gpx_set_error("gpx_matern_gram: null pointer or n < 1"); return GPX_ERR_BAD_ARG; }
+    GPX_TRY(raw_gram_args("gpx_matern_gram", xi, n1, xj, n2, out));
     MaternData md;
     GPX_TRY(matern_parse(theta, d, nu2, &md));
     if (deriv < -1 || deriv >= 2 + d) { gpx_set_error("gpx_matern_gram: deriv=%d (-1 .. %d)", deriv, 1 + d); return GPX_ERR_BAD_ARG; }
-    const int64_t rp = round_up(n1, TILE), cp = round_up(n2, TILE);
-    hipStream_t s = nullptr;
-    Scratch sc(s);
-    double *a = nullptr, *b = nullptr, *o = nullptr, *w = nullptr;
-    // (the parameters through the call's own scratch: nothing of md outlives the call)
-    GPX_TRY(sc.take(&w, d));
-    GPX_HIP(hipMemcpy(w, md.w, sizeof(double) * d, hipMemcpyHostToDevice));
-    md.wdev = w;
-    GPX_TRY(sc.take(&a, n1 * d));
-    GPX_HIP(hipMemcpy(a, xi, sizeof(double) * n1 * d, hipMemcpyDefault));
-    if (xj == xi && n1 == n2) b = a;
-    else {
-        GPX_TRY(sc.take(&b, n2 * d));
-        GPX_HIP(hipMemcpy(b, xj, sizeof(double) * n2 * d, hipMemcpyDefault));
-    }
-    GPX_TRY(sc.take(&o, rp * cp));
-    GPX_TRY(launch_matern_gram(a, n1, b, n2, &md, 0.0, 0, PAD_ZERO, o, cp, rp, cp, s, nullptr, deriv));
-    GPX_HIP(hipMemcpy2D(out, sizeof(double) * n2, o, sizeof(double) * cp, sizeof(double) * n2, n1, hipMemcpyDefault));
-    return 0;
+    return raw_gram(&md, xi, n1, xj, n2, deriv, out);
 }
 
 // d nll / d theta [2 + d] at the handle's theta
 extern "C" int gpx_matern_nll_grad(gpx_handle *h, double *grad_out)
 {
     CHECK_H(h);
-    NEED_MATERN(h, "gpx_matern_nll_grad");
+    GPX_TRY(need_kind(h, KernelKind::Matern, "gpx_matern_nll_grad"));
     if (!grad_out) { gpx_set_error("null argument"); return GPX_ERR_BAD_ARG; }
     GPX_TRY(ensure_kinv(h));
-    const MaternData *md = h->mat;
-    const int d = md->d, sweeps = (d + MAT_KC - 1) / MAT_KC;
-    Scratch sc(h->stream);
-    double *buf = nullptr;
-    const int64_t nb = h->npad / 8;
-    GPX_TRY(sc.take(&buf, (nb + 1) * sweeps * MAT_NC));
-    double *outd = buf + nb * sweeps * MAT_NC;
-    GPX_TRY(launch_matern_nll_grad(h->Kinv, h->npad, h->n, h->npad, md, h->alpha, buf, outd, h->stream, &h->prof));
+    const MaternData *md = handle_matern(h);
+    const int d = md->d;
     double o[(GPX_MAX_D / MAT_KC) * MAT_NC];
-    GPX_HIP(hipMemcpyAsync(o, outd, sizeof(double) * sweeps * MAT_NC, hipMemcpyDeviceToHost, h->stream));
-    GPX_HIP(hipStreamSynchronize(h->stream));
+    GPX_TRY(raw_nll_grad_sums(h, MAT_KC, MAT_NC, o));
     std::vector<double> g(2 + d);
     g[0] = 0.5 * o[0];                       // d K / d theta_0 = Kf
     g[1] = 0.5 * md->vt * o[MAT_NC - 1];     // vt on equality
@@ -543,19 +412,22 @@ extern "C" int gpx_matern_nll_grad(gpx_handle *h, double *grad_out)
     return 0;
 }
 
-#define NEED_MATERN52(h, what)                                                                                                              \
-    do {                                                                                                                                    \
-        NEED_MATERN(h, what);                                                                                                               \
-        if ((h)->mat->nu2 != 5) { gpx_set_error(what ": nu = 3/2 has no Hessian at the origin: the fused propagation serves nu = 5/2 alone"); return GPX_ERR_STATE; } \
-    } while (0)
+// the fused propagation of a Matern handle: nu = 5/2 alone
+static int need_matern52(const gpx_handle *h, const char *what)
+{
+    GPX_TRY(need_kind(h, KernelKind::Matern, what));
+    if (handle_matern(h)->nu2 == 5) return 0;
+    gpx_set_error("%s: nu = 3/2 has no Hessian at the origin: the fused propagation serves nu = 5/2 alone", what);
+    return GPX_ERR_STATE;
+}
 
 // propagate_GA_many with cov = MaternCovariance(2.5): gpx_propagate_approx_many's loop on this kernel's right-hand sides
 extern "C" int gpx_matern_propagate_approx_many(gpx_handle *h, const double *U, const double *Sigma, int sigma_shared, int64_t b, double *mean,
                                                 double *var, double *sigma2, double *rest)
 {
     CHECK_H(h);
-    NEED_MATERN52(h, "gpx_matern_propagate_approx_many");
-    return approx_many_run(h, h->mat->d, U, Sigma, sigma_shared, b, mean, var, sigma2, rest, "gpx_matern_propagate_approx_many",
+    GPX_TRY(need_matern52(h, "gpx_matern_propagate_approx_many"));
+    return approx_many_run(h, handle_dim(h), U, Sigma, sigma_shared, b, mean, var, sigma2, rest, "gpx_matern_propagate_approx_many",
                            rows_build_of(h, GPX_ROWS_APPROX));
 }
 
@@ -563,6 +435,6 @@ extern "C" int gpx_matern_propagate_approx_many(gpx_handle *h, const double *U, 
 extern "C" int gpx_matern_propagate_dvh_many(gpx_handle *h, const double *U, int64_t b, double *dvh_out, double *sigma2_out)
 {
     CHECK_H(h);
-    NEED_MATERN52(h, "gpx_matern_propagate_dvh_many");
-    return dvh_many_run(h, h->mat->d, U, b, dvh_out, sigma2_out, "gpx_matern_propagate_dvh_many", rows_build_of(h, GPX_ROWS_DVH));
+    GPX_TRY(need_matern52(h, "gpx_matern_propagate_dvh_many"));
+    return dvh_many_run(h, handle_dim(h), U, b, dvh_out, sigma2_out, "gpx_matern_propagate_dvh_many", rows_build_of(h, GPX_ROWS_DVH));
 }

@@ -12,6 +12,7 @@
 
 #include "common.h"
 #include "gram_tile.h"
+#include "nll_grad_tile.h"
 #include "periodic_math.h"
 
 // what the deriv variant writes (the parameter's group; its coordinate is a second argument)
@@ -105,9 +106,7 @@ int launch_periodic_gram(const double *xi, int64_t n1, const double *xj, int64_t
 {
     const int d = pd->d;
     GramLaunch pl;
-    // (a derivative has no diagonal term: identity padding would have no meaning for it, and no caller asks for it)
-    if (!gram_launch_plan(rows_pad, cols_pad, ld, d, lower_only, &pl) || n1 < 1 || n2 < 1 || n1 > rows_pad || n2 > cols_pad || deriv < -1 ||
-        deriv >= 2 + 3 * d || (deriv >= 0 && pad_mode == PAD_IDENT)) {
+    if (!raw_gram_launch_plan(n1, n2, rows_pad, cols_pad, ld, d, lower_only, pad_mode, deriv, 2 + 3 * d, &pl)) {
         gpx_set_error("launch_periodic_gram: bad shape (n1=%ld n2=%ld rows_pad=%ld cols_pad=%ld ld=%ld d=%d deriv=%d)", (long)n1, (long)n2,
                       (long)rows_pad, (long)cols_pad, (long)ld, d, deriv);
         return GPX_ERR_BAD_ARG;
@@ -128,125 +127,69 @@ int launch_periodic_gram(const double *xi, int64_t n1, const double *xj, int64_t
 
 // ---------------------------------------------------------------------------------------------
 // Gradient of the negative log likelihood (Covariance._d_nll_d_theta, skgpuppy/Covariance.py:266-282, with
-// PeriodicCovariance._d_cov_d_theta, :399-433): ONE pass over the j <= i half of K^-1 recomputes Kf_ij = v exp(-q_ij) on the fly and
-// accumulates, with M_ij = Kinv_ij - a_i a_j and s, c = sin, cos(pi delta_k / p_k),
-//   S_0 = sum M Kf,  A_k = sum M Kf delta_k^2,  B_k = sum M Kf delta_k s c,  C_k = sum M Kf s^2,  T = sum over the pairs with x_i == x_j of M
-// (T = tr Kinv - a.a without duplicate rows), so that
+// PeriodicCovariance._d_cov_d_theta, :399-433): the one pass of nll_grad_tile.h with Kf_ij = v exp(-q_ij) and, per coordinate and with
+// s, c = sin, cos(pi delta_k / p_k), the three sums
+//   A_k = sum M Kf delta_k^2,  B_k = sum M Kf delta_k s c,  C_k = sum M Kf s^2
+// so that
 //   g_0 = S_0 / 2,  g_1 = vt T / 2,  g_{w_k} = -w_k A_k / 4,  g_{p_k} = (pi w2_k / p_k) B_k / 2,  g_{w2_k} = -w2_k C_k / 4.
-// 3 d + 2 accumulators do not fit in registers at d = 64: grid.y sweeps of KC coordinates each.  A sweep forms q over ALL d
-// coordinates (a runtime loop: no coordinate beyond d is ever evaluated, no per-thread array is indexed by it), then the three
-// weighted terms of its own KC coordinates with the sine and cosine formed once more -- per pair d + KC sines and KC cosines,
-// 3 KC + 2 accumulators, whatever d is.  From d = 9 on every sweep repeats q: 2 x the sines at d = 16, 4.5 x at d = 64.
-// A lane owns a column j and reads it from the k-major copy of the inputs (coalesced); the block's 8 rows sit in LDS.
-// partial[sweep][block][3 KC + 2]: [0] = S_0, [1 + 3 kk ..] = A, B, C of coordinate sweep KC + kk, [3 KC + 1] = T.
+// A sweep forms the sine and cosine of its own KC coordinates once more -- per pair d + KC sines and KC cosines, 3 KC + 2 accumulators,
+// whatever d is.  From d = 9 on every sweep repeats q: 2 x the sines at d = 16, 4.5 x at d = 64.
 // ---------------------------------------------------------------------------------------------
+template <int KC_>
+struct PeriodicGrad {
+    static constexpr int KC = KC_, NA = 3, NC = NA * KC + 2;
+    const double *par;   // [4][d]: w / 2, fl(1 / p), its correction, w2 / 2
+    int d;
+    double v;
+    struct Coord { double hw, ih, il, hw2; };
+
+    __device__ __forceinline__ Coord coord(int k) const { return {par[k], par[d + k], par[2 * d + k], par[3 * d + k]}; }
+    __device__ __forceinline__ double add_q(const Coord &c, double e, double q) const
+    {
+        q = fma(c.hw * e, e, q);
+        const double sn = sinpi_half(periodic_reduce(e, c.ih, c.il));
+        return fma(c.hw2 * sn, sn, q);
+    }
+    __device__ __forceinline__ double pair(double mij, double wgt, double q, bool equal, double &s0, double &t) const
+    {
+        const double wq = mij * wgt * v * exp_nonpos(-q);
+        s0 += wq;
+        if (equal) t += mij * wgt;
+        return wq;
+    }
+    __device__ __forceinline__ void sweep(const Coord &c, double wq, double e, double (&acc)[NC], int kk) const
+    {
+        const double rr = periodic_reduce(e, c.ih, c.il), sn = sinpi_half(rr), cs = cospi_half(rr);
+        acc[1 + 3 * kk] = fma(wq, e * e, acc[1 + 3 * kk]);
+        acc[2 + 3 * kk] = fma(wq, e * (sn * cs), acc[2 + 3 * kk]);
+        acc[3 + 3 * kk] = fma(wq, sn * sn, acc[3 + 3 * kk]);
+    }
+};
+
 template <int KC>
 __global__ __launch_bounds__(256) void periodic_nll_grad_kernel(const double *__restrict__ Kinv, long ld, long n, long npad, int d,
                                                                const double *__restrict__ alpha, const double *__restrict__ x,
                                                                const double *__restrict__ xT, const double *__restrict__ par, double v,
                                                                double *__restrict__ partial)
 {
-    constexpr int R = 8, NC = 3 * KC + 2;
-    __shared__ double xs[R][GPX_MAX_D];
-    __shared__ double as[R];
-    __shared__ double red[4][NC];
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    const int rb = gridDim.x - 1 - blockIdx.x;
-    const long i0 = (long)rb * R;
-    const int k0 = blockIdx.y * KC;
-    for (int q = t; q < R * GPX_MAX_D; q += 256) {
-        const int r = q / GPX_MAX_D, k = q - r * GPX_MAX_D;
-        xs[r][k] = (k < d && i0 + r < n) ? x[(i0 + r) * d + k] : 0.0;
-    }
-    if (t < R) as[t] = alpha[i0 + t];
-    __syncthreads();
-    double acc[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) acc[c] = 0.0;
-    for (long j = t; j < i0 + R && j < n; j += 256) {
-        const double aj = alpha[j];
-        double q[R], mx[R], wq[R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) { q[r] = 0.0; mx[r] = 0.0; }
-        for (int k = 0; k < d; ++k) {
-            const double hw = par[k], ih = par[d + k], il = par[2 * d + k], hw2 = par[3 * d + k];
-            const double xjk = xT[(long)k * npad + j];
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const double e = xs[r][k] - xjk;
-                mx[r] = fmax(mx[r], fabs(e));
-                q[r] = fma(hw * e, e, q[r]);
-                const double sn = sinpi_half(periodic_reduce(e, ih, il));
-                q[r] = fma(hw2 * sn, sn, q[r]);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const long i = i0 + r;
-            const bool live = i < n && j <= i;
-            const double mij = live ? Kinv[i * ld + j] - as[r] * aj : 0.0;
-            const double wgt = (j < i) ? 2.0 : 1.0;
-            wq[r] = mij * wgt * v * exp_nonpos(-q[r]);
-            acc[0] += wq[r];
-            if (live && mx[r] == 0.0) acc[NC - 1] += mij * wgt;
-        }
-#pragma unroll
-        for (int kk = 0; kk < KC; ++kk) {
-            const int k = k0 + kk;
-            if (k < d) {
-                const double ih = par[d + k], il = par[2 * d + k];
-                const double xjk = xT[(long)k * npad + j];
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const double e = xs[r][k] - xjk;
-                    const double rr = periodic_reduce(e, ih, il), sn = sinpi_half(rr), cs = cospi_half(rr);
-                    acc[1 + 3 * kk] = fma(wq[r], e * e, acc[1 + 3 * kk]);
-                    acc[2 + 3 * kk] = fma(wq[r], e * (sn * cs), acc[2 + 3 * kk]);
-                    acc[3 + 3 * kk] = fma(wq[r], sn * sn, acc[3 + 3 * kk]);
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const double s = wave_sum(acc[c]);
-        if (lane == 0) red[wave][c] = s;
-    }
-    __syncthreads();
-    if (t < NC) partial[((long)blockIdx.y * gridDim.x + rb) * NC + t] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+    nll_grad_tile(PeriodicGrad<KC>{par, d, v}, Kinv, ld, n, npad, d, alpha, x, xT, partial);
 }
 
 int launch_periodic_nll_grad(const double *Kinv, int64_t ld, int64_t n, int64_t npad, const PeriodicData *pd, const double *alpha,
-                             double *partial, double *out_dev, hipStream_t s, Profiler *prof)
+                             double *partial, hipStream_t s)
 {
-    const unsigned nblk = (unsigned)(npad / 8);
     const int sweeps = (pd->d + PER_KC - 1) / PER_KC;
-    {
-        ProfScope ps(prof, s, GPX_K_QUAD, 4.0 * (double)npad * (double)npad * sweeps);
-        hipLaunchKernelGGL(periodic_nll_grad_kernel<PER_KC>, dim3(nblk, (unsigned)sweeps), dim3(256), 0, s, Kinv, (long)ld, (long)n, (long)npad,
-                           pd->d, alpha, (const double *)pd->x, (const double *)pd->xT, (const double *)pd->par, pd->v, partial);
-        GPX_HIP(hipGetLastError());
-    }
-    for (int y = 0; y < sweeps; ++y) GPX_TRY(launch_sum_columns(partial + (int64_t)y * nblk * PER_NC, nblk, PER_NC, out_dev + y * PER_NC, s));
+    hipLaunchKernelGGL(periodic_nll_grad_kernel<PER_KC>, dim3((unsigned)(npad / 8), (unsigned)sweeps), dim3(256), 0, s, Kinv, (long)ld, (long)n,
+                       (long)npad, pd->d, alpha, (const double *)pd->x, (const double *)pd->xT, (const double *)pd->par, pd->v, partial);
+    GPX_HIP(hipGetLastError());
     return 0;
 }
 
-// ---- parameters and inputs of a periodic model -------------------------------------------------------------------
+// ---- parameters of a periodic model ---------------------------------------------------------------------------
 int periodic_parse(const double *theta, int d, PeriodicData *out)
 {
-    if (!theta || d < 1 || d > GPX_MAX_D) {
-        gpx_set_error("periodic kernel: bad theta / d=%d (1..%d supported)", d, GPX_MAX_D);
-        return GPX_ERR_BAD_ARG;
-    }
-    out->d = d;
-    out->v = exp(theta[0]);
-    out->vt = exp(theta[1]);   // theta[1] = -inf gives vt = 0
-    if (!(out->v > 0.0) || !isfinite(out->v) || !isfinite(out->vt)) {
-        gpx_set_error("periodic kernel: theta gives v=%g vt=%g", out->v, out->vt);
-        return GPX_ERR_BAD_ARG;
-    }
+    GPX_TRY(raw_parse_head("periodic", theta, d, out, out->w));
     for (int k = 0; k < d; ++k) {
-        out->w[k] = exp(theta[2 + k]);
         out->p[k] = exp(theta[2 + d + k]);
         out->w2[k] = exp(theta[2 + 2 * d + k]);
         if (!(out->w[k] >= 0.0) || !isfinite(out->w[k]) || !(out->p[k] > 0.0) || !isfinite(out->p[k]) || !(out->w2[k] >= 0.0) ||
@@ -258,106 +201,28 @@ int periodic_parse(const double *theta, int d, PeriodicData *out)
     return 0;
 }
 
-__global__ __launch_bounds__(256) void periodic_transpose_kernel(const double *__restrict__ x, long n, long npad, int d, double *__restrict__ xT)
-{
-    const long e = (long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= npad * d) return;
-    const long k = e / npad, j = e - k * npad;
-    xT[e] = j < n ? x[j * d + k] : 0.0;
-}
-
-// the kernels' constant block [4][d]: w / 2, ih = fl(1 / p), il = fl((1 - ih p) ih) (periodic_math.h), w2 / 2
-static void periodic_pack(const PeriodicData &pd, double *host)
-{
-    const int d = pd.d;
-    for (int k = 0; k < d; ++k) {
-        const double ih = 1.0 / pd.p[k];
-        host[k] = 0.5 * pd.w[k];
-        host[d + k] = ih;
-        host[2 * d + k] = isfinite(ih) ? fma(-ih, pd.p[k], 1.0) * ih : 0.0;   // (a subnormal p: ih = inf is refused by nothing, q is then NaN)
-        host[3 * d + k] = 0.5 * pd.w2[k];
-    }
-}
-
-int periodic_upload(PeriodicData *pd, const double *x, int64_t n, int64_t npad, hipStream_t s)
-{
-    const int d = pd->d;
-    double host[4 * GPX_MAX_D];
-    periodic_pack(*pd, host);
-    GPX_TRY(dalloc(&pd->par, 4 * d));
-    GPX_HIP(hipMemcpyAsync(pd->par, host, sizeof(double) * 4 * d, hipMemcpyHostToDevice, s));
-    {
-        GPX_TRY(dalloc(&pd->x, n * d));
-        GPX_TRY(dalloc(&pd->xT, npad * d));
-        GPX_HIP(hipMemcpyAsync(pd->x, x, sizeof(double) * n * d, hipMemcpyDefault, s));
-        hipLaunchKernelGGL(periodic_transpose_kernel, dim3((unsigned)((npad * d + 255) / 256)), dim3(256), 0, s, (const double *)pd->x, (long)n,
-                           (long)npad, d, pd->xT);
-        GPX_HIP(hipGetLastError());
-    }
-    GPX_HIP(hipStreamSynchronize(s));   // host is a stack buffer
-    return 0;
-}
-
-void periodic_release(PeriodicData *pd)
-{
-    if (!pd) return;
-    for (double *p : {pd->x, pd->xT, pd->par})
-        if (p) dfree(p);
-    delete pd;
-}
-
 // ---- C-ABI: the stand-alone Gram --------------------------------------------------------------------------------
 extern "C" int gpx_periodic_gram(const double *xi, int64_t n1, const double *xj, int64_t n2, int d, const double *theta, int deriv,
                                  double *out)
 {
-    GPX_TRY(gpx_require_device());
-    if (!xi || !xj || !out || n1 < 1 || n2 < 1) { gpx_set_error("gpx_periodic_gram: null pointer or n < 1"); return GPX_ERR_BAD_ARG; }
+    GPX_TRY(raw_gram_args("gpx_periodic_gram", xi, n1, xj, n2, out));
     PeriodicData pd;
     GPX_TRY(periodic_parse(theta, d, &pd));
     if (deriv < -1 || deriv >= 2 + 3 * d) { gpx_set_error("gpx_periodic_gram: deriv=%d (-1 .. %d)", deriv, 1 + 3 * d); return GPX_ERR_BAD_ARG; }
-    const int64_t rp = round_up(n1, TILE), cp = round_up(n2, TILE);
-    hipStream_t s = nullptr;
-    Scratch sc(s);
-    double *a = nullptr, *b = nullptr, *o = nullptr, *par = nullptr;
-    GPX_TRY(sc.take(&par, 4 * d));
-    {
-        // (the parameter block through the call's own scratch: nothing of pd outlives the call)
-        double host[4 * GPX_MAX_D];
-        periodic_pack(pd, host);
-        GPX_HIP(hipMemcpy(par, host, sizeof(double) * 4 * d, hipMemcpyHostToDevice));
-    }
-    pd.par = par;
-    GPX_TRY(sc.take(&a, n1 * d));
-    GPX_HIP(hipMemcpy(a, xi, sizeof(double) * n1 * d, hipMemcpyDefault));
-    if (xj == xi && n1 == n2) b = a;
-    else {
-        GPX_TRY(sc.take(&b, n2 * d));
-        GPX_HIP(hipMemcpy(b, xj, sizeof(double) * n2 * d, hipMemcpyDefault));
-    }
-    GPX_TRY(sc.take(&o, rp * cp));
-    GPX_TRY(launch_periodic_gram(a, n1, b, n2, &pd, 0.0, 0, PAD_ZERO, o, cp, rp, cp, s, nullptr, deriv));
-    GPX_HIP(hipMemcpy2D(out, sizeof(double) * n2, o, sizeof(double) * cp, sizeof(double) * n2, n1, hipMemcpyDefault));
-    return 0;
+    return raw_gram(&pd, xi, n1, xj, n2, deriv, out);
 }
 
 // d nll / d theta [2 + 3 d] at the handle's theta
 extern "C" int gpx_periodic_nll_grad(gpx_handle *h, double *grad_out)
 {
     CHECK_H(h);
-    if (h->kind != KernelKind::Periodic) { gpx_set_error("gpx_periodic_nll_grad: not a gpx_periodic_fit handle"); return GPX_ERR_STATE; }
+    GPX_TRY(need_kind(h, KernelKind::Periodic, "gpx_periodic_nll_grad"));
     if (!grad_out) { gpx_set_error("null argument"); return GPX_ERR_BAD_ARG; }
     GPX_TRY(ensure_kinv(h));
-    const PeriodicData *pd = h->per;
-    const int d = pd->d, sweeps = (d + PER_KC - 1) / PER_KC;
-    Scratch sc(h->stream);
-    double *buf = nullptr;
-    const int64_t nb = h->npad / 8;
-    GPX_TRY(sc.take(&buf, (nb + 1) * sweeps * PER_NC));
-    double *outd = buf + nb * sweeps * PER_NC;
-    GPX_TRY(launch_periodic_nll_grad(h->Kinv, h->npad, h->n, h->npad, pd, h->alpha, buf, outd, h->stream, &h->prof));
+    const PeriodicData *pd = handle_periodic(h);
+    const int d = pd->d;
     double o[(GPX_MAX_D / PER_KC) * PER_NC];
-    GPX_HIP(hipMemcpyAsync(o, outd, sizeof(double) * sweeps * PER_NC, hipMemcpyDeviceToHost, h->stream));
-    GPX_HIP(hipStreamSynchronize(h->stream));
+    GPX_TRY(raw_nll_grad_sums(h, PER_KC, PER_NC, o));
     std::vector<double> g(2 + 3 * d);
     g[0] = 0.5 * o[0];                                        // dK/dtheta_0 = Kf                     (Covariance.py:417-419)
     g[1] = 0.5 * pd->vt * o[PER_NC - 1];                      // vt on equality                        (:420-422)

@@ -180,13 +180,20 @@ static int predict_common(gpx_handle *h, const double *xs, const double *kv, con
     return rc;
 }
 
+// gpx_predict / gpx_periodic_predict / gpx_matern_predict after their CHECK_H (which names the entry point): each takes the handles of
+// its own kind alone
+static int predict_entry(gpx_handle *h, KernelKind kind, const char *what, const double *xs, int64_t m, double *mean_out, double *var_out)
+{
+    GPX_TRY(kind == KernelKind::Gaussian ? need_kernel(h, what) : need_kind(h, kind, what));
+    if (m < 0 || (m > 0 && (!xs || !mean_out || !var_out))) { gpx_set_error("%s: bad arguments", what); return GPX_ERR_BAD_ARG; }
+    if (m == 0) return 0;
+    return predict_common(h, xs, nullptr, nullptr, m, mean_out, var_out);
+}
+
 extern "C" int gpx_predict(gpx_handle *h, const double *xs, int64_t m, double *mean_out, double *var_out)
 {
     CHECK_H(h);
-    NEED_KERNEL(h, "gpx_predict");
-    if (m < 0 || (m > 0 && (!xs || !mean_out || !var_out))) { gpx_set_error("gpx_predict: bad arguments"); return GPX_ERR_BAD_ARG; }
-    if (m == 0) return 0;
-    return predict_common(h, xs, nullptr, nullptr, m, mean_out, var_out);
+    return predict_entry(h, KernelKind::Gaussian, "gpx_predict", xs, m, mean_out, var_out);
 }
 
 // estimate_many / estimate with cov = PeriodicCovariance (skgpuppy/GaussianProcess.py:68-80, :94-111): kv = cov_matrix_ij(x_star, x) with the
@@ -194,10 +201,7 @@ extern "C" int gpx_predict(gpx_handle *h, const double *xs, int64_t m, double *m
 extern "C" int gpx_periodic_predict(gpx_handle *h, const double *xs, int64_t m, double *mean_out, double *var_out)
 {
     CHECK_H(h);
-    if (h->kind != KernelKind::Periodic) { gpx_set_error("gpx_periodic_predict: not a gpx_periodic_fit handle"); return GPX_ERR_STATE; }
-    if (m < 0 || (m > 0 && (!xs || !mean_out || !var_out))) { gpx_set_error("gpx_periodic_predict: bad arguments"); return GPX_ERR_BAD_ARG; }
-    if (m == 0) return 0;
-    return predict_common(h, xs, nullptr, nullptr, m, mean_out, var_out);
+    return predict_entry(h, KernelKind::Periodic, "gpx_periodic_predict", xs, m, mean_out, var_out);
 }
 
 // estimate_many / estimate with cov = MaternCovariance: the rows come from matern_gram_kernel with the +vt on equality, k = v + vt for
@@ -205,10 +209,7 @@ extern "C" int gpx_periodic_predict(gpx_handle *h, const double *xs, int64_t m, 
 extern "C" int gpx_matern_predict(gpx_handle *h, const double *xs, int64_t m, double *mean_out, double *var_out)
 {
     CHECK_H(h);
-    if (h->kind != KernelKind::Matern) { gpx_set_error("gpx_matern_predict: not a gpx_matern_fit handle"); return GPX_ERR_STATE; }
-    if (m < 0 || (m > 0 && (!xs || !mean_out || !var_out))) { gpx_set_error("gpx_matern_predict: bad arguments"); return GPX_ERR_BAD_ARG; }
-    if (m == 0) return 0;
-    return predict_common(h, xs, nullptr, nullptr, m, mean_out, var_out);
+    return predict_entry(h, KernelKind::Matern, "gpx_matern_predict", xs, m, mean_out, var_out);
 }
 
 // estimate_many for ANY operator (skgpuppy/GaussianProcess.py:68-80): kv = cov.cov_matrix_ij(x_star, x) [m, n] and

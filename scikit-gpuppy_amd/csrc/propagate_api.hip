@@ -482,7 +482,7 @@ int grad_many_run(gpx_handle *h, int d, const double *U, int64_t b, double *mean
 // row elementwise (handle_gram_has_vt), gpx_predict's on a Gaussian handle do not (GaussianCovariance.cov_matrix_ij is the vectorised Gram
 // without it, Covariance.py:466-483): the C row of a Gaussian handle is therefore built with vt = 0 here, so that mean and variance are
 // gpx_predict's at every query.  No derivative carries the term on either kind.
-static inline double grad_row_vt(const gpx_handle *h) { return handle_gram_has_vt(h) ? h->mat->vt : 0.0; }
+static inline double grad_row_vt(const gpx_handle *h) { return handle_gram_has_vt(h) ? h->raw->vt : 0.0; }
 
 // the kinds that have a closed-form input gradient: gpx_fit (Gaussian) and gpx_matern_fit (either nu) handles
 static int need_grad_kernel(const gpx_handle *h, const char *what)
@@ -502,7 +502,7 @@ extern "C" int gpx_predict_mean_grad(gpx_handle *h, const double *xs, int64_t m,
     GPX_TRY(need_grad_kernel(h, "gpx_predict_mean_grad"));
     if (m == 0) return 0;
     const bool matern = h->kind == KernelKind::Matern;
-    const MaternData *md = h->mat;
+    const MaternData *md = matern ? handle_matern(h) : nullptr;
     const int d = handle_dim(h);
     const int S = predict_mean_grad_splits(m, h->npad);
     hipStream_t s = h->stream;
@@ -513,7 +513,7 @@ extern "C" int gpx_predict_mean_grad(gpx_handle *h, const double *xs, int64_t m,
     GPX_TRY(sc.take(&od, m * (1 + d)));
     double *dmd = od + m;
     GPX_HIP(hipMemcpyAsync(ud, xs, sizeof(double) * m * d, hipMemcpyDefault, s));
-    GPX_TRY(launch_predict_mean_grad(matern ? md->x : h->x, h->n, h->npad, d, matern ? md->nu2 : 0, ud, m, matern ? md->wdev : h->wdev, h->alpha,
+    GPX_TRY(launch_predict_mean_grad(matern ? md->x : h->x, h->n, h->npad, d, matern ? md->nu2 : 0, ud, m, matern ? md->par : h->wdev, h->alpha,
                                      matern ? md->v : h->v, grad_row_vt(h), S, part, mean_out ? od : nullptr, dmean_out ? dmd : nullptr, s,
                                      &h->prof));
     if (mean_out) GPX_HIP(hipMemcpyAsync(mean_out, od, sizeof(double) * m, hipMemcpyDefault, s));
@@ -538,9 +538,9 @@ RowsBuild rows_build_of(gpx_handle *h, int layout)
 {
     if (h->kind == KernelKind::Matern)
         return [h, layout](const double *ud, const double *sd, int64_t sstride, int64_t bc, int64_t mp) -> int {
-            const MaternData *md = h->mat;
+            const MaternData *md = handle_matern(h);
             const bool tr = layout == GPX_ROWS_APPROX;
-            return launch_matern_build_many(layout, md->nu2, md->x, h->n, h->npad, md->d, ud, tr ? sd : nullptr, tr ? sstride : 0, bc, mp, md->wdev, md->v,
+            return launch_matern_build_many(layout, md->nu2, md->x, h->n, h->npad, md->d, ud, tr ? sd : nullptr, tr ? sstride : 0, bc, mp, md->par, md->v,
                                             md->vt, h->Z, h->stream, &h->prof);
         };
     switch (layout) {
@@ -575,7 +575,7 @@ extern "C" int gpx_rows_build(gpx_handle *h, int layout, const double *U, const 
                                                 : "the handle was built from a supplied matrix (gpx_fit_matrix): no inputs / theta to evaluate the kernel on");
         return GPX_ERR_STATE;
     }
-    if (h->kind == KernelKind::Matern && h->mat->nu2 != 5 && layout != GPX_ROWS_GRAD) {
+    if (h->kind == KernelKind::Matern && handle_matern(h)->nu2 != 5 && layout != GPX_ROWS_GRAD) {
         gpx_set_error("gpx_rows_build: the handle holds a MaternCovariance model with nu = 3/2 (gpx_matern_fit), which has no Hessian at the origin: "
                       "GPX_ROWS_GRAD is its only layout");
         return GPX_ERR_STATE;

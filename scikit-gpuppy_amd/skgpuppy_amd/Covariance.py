@@ -168,6 +168,24 @@ class Covariance(object):
         self._mm_cache = (key, model)
         return model
 
+    def _fitted_model_at(self, x, t, theta, check_theta, build):
+        """the fused classes' device model build(x, t, theta) fitted at theta, cached on (x, t, theta) identity/bytes: L-BFGS-B asks
+        for the value and the gradient at the same theta in two separate calls.  The cache is cleared before the new fit: a
+        constructor that raises leaves no closed model behind."""
+        xa = _gpx.f64(x)
+        ta = _gpx.f64(t)
+        th = check_theta(theta, xa.shape[1]).copy()
+        key = (xa.ctypes.data if xa is x else id(x), xa.shape, ta.tobytes(), th.tobytes())
+        cached = getattr(self, "_ml_cache", None)
+        if cached is not None and cached[0] == key:
+            return cached[1]
+        if cached is not None:
+            cached[1].close()
+        self._ml_cache = None
+        model = build(xa, ta, th)
+        self._ml_cache = (key, model)
+        return model
+
     def _log_det_cov_matrix(self, x, theta):
         """log det of cov_matrix(x, theta) (Covariance.py:189-195: numpy slogdet); here 2 sum log diag of its Cholesky factor,
         computed on the GPU from the operator's own matrix"""
@@ -236,6 +254,7 @@ class Covariance(object):
     def __getstate__(self):
         state = dict(self.__dict__)
         state.pop("_mm_cache", None)     # device handles never enter a pickle
+        state.pop("_ml_cache", None)
         return state
 
 
@@ -374,21 +393,8 @@ class GaussianCovariance(Covariance):
         return -0.5 * K * (dk * dk) * w[j - 2]
 
     def _model_at(self, x, t, theta):
-        """device model fitted at theta, cached on (x, t, theta) identity/bytes: L-BFGS-B asks for the value and the
-        gradient at the same theta in two separate calls."""
         from .GaussianProcess import _DeviceModel
-        xa = _gpx.f64(x)
-        ta = _gpx.f64(t)
-        th = _theta(theta, xa.shape[1]).copy()
-        key = (xa.ctypes.data if xa is x else id(x), xa.shape, ta.tobytes(), th.tobytes())
-        cached = getattr(self, "_ml_cache", None)
-        if cached is not None and cached[0] == key:
-            return cached[1]
-        if cached is not None:
-            cached[1].close()
-        model = _DeviceModel(xa, ta, th)
-        self._ml_cache = (key, model)
-        return model
+        return self._fitted_model_at(x, t, theta, _theta, _DeviceModel)
 
     def _negativeloglikelihood(self, x, t, theta):
         """N/2 log 2pi + 1/2 log det K + 1/2 t^T K^-1 t on the GPU (Covariance.py:197-216); 1e20 when K cannot be
@@ -413,11 +419,6 @@ class GaussianCovariance(Covariance):
         _gpx.check(_gpx.lib.gpx_nll_grad(model.handle, _gpx.ptr(g)), "gpx_nll_grad")
         return g
 
-    def __getstate__(self):
-        state = Covariance.__getstate__(self)
-        state.pop("_ml_cache", None)     # device handles never enter a pickle
-        return state
-
     def get_Hessian(self, u, xi, theta):
         # (Covariance.py:660-674)
         with np.errstate(divide="ignore"):
@@ -438,36 +439,6 @@ class GaussianCovariance(Covariance):
         return np.atleast_2d(-diff * w * e).T
 
 
-class _PeriodicModel(_MatrixModel):
-    """Owner of one gpx_periodic_fit handle: K of the periodic kernel assembled and factored on the device.  Everything a matrix
-    model answers, plus the kernel's own prediction and likelihood gradient."""
-
-    def __init__(self, x, t_centered, theta):
-        x = _gpx.f64(x)
-        if x.ndim != 2:
-            raise ValueError("x must be an (n, d) array")
-        self.n, self.d = x.shape
-        theta = _periodic_theta(theta, self.d)
-        t = np.zeros(self.n) if t_centered is None else _gpx.f64(t_centered)
-        if t.shape != (self.n,):
-            raise ValueError("t must have %d entries" % self.n)
-        self._h = ctypes.c_void_p()
-        _gpx.check(_gpx.lib.gpx_periodic_fit(_gpx.ptr(x), _gpx.ptr(t), self.n, self.d, _gpx.ptr(theta), None, ctypes.byref(self._h)),
-                   "gpx_periodic_fit")
-
-    def predict(self, xs):
-        m = xs.shape[0]
-        mean = np.empty(m)
-        var = np.empty(m)
-        _gpx.check(_gpx.lib.gpx_periodic_predict(self.handle, _gpx.ptr(xs), m, _gpx.ptr(mean), _gpx.ptr(var)), "gpx_periodic_predict")
-        return mean, var
-
-    def nll_grad(self):
-        g = np.empty(2 + 3 * self.d)
-        _gpx.check(_gpx.lib.gpx_periodic_nll_grad(self.handle, _gpx.ptr(g)), "gpx_periodic_nll_grad")
-        return g
-
-
 def _periodic_theta(theta, d):
     th = _gpx.f64(theta)
     if th.ndim != 1 or th.shape[0] != 2 + 3 * d:
@@ -475,7 +446,153 @@ def _periodic_theta(theta, d):
     return th
 
 
-class PeriodicCovariance(Covariance):
+class _RawInputModel(_MatrixModel):
+    """Owner of one gpx_periodic_fit / gpx_matern_fit handle: K of a kernel on the raw inputs assembled and factored on the device.
+    Everything a matrix model answers, plus the kernel's own prediction and likelihood gradient.  A kind names its entry points
+    (gpx_<_KIND>_fit / _predict / _nll_grad) and its theta checker; `extra`: what its fit takes after theta."""
+
+    _KIND = None
+    _check_theta = None
+
+    def __init__(self, x, t_centered, theta, *extra):
+        x = _gpx.f64(x)
+        if x.ndim != 2:
+            raise ValueError("x must be an (n, d) array")
+        self.n, self.d = x.shape
+        theta = self._check_theta(theta, self.d)
+        self._ntheta = theta.shape[0]
+        t = np.zeros(self.n) if t_centered is None else _gpx.f64(t_centered)
+        if t.shape != (self.n,):
+            raise ValueError("t must have %d entries" % self.n)
+        self._h = ctypes.c_void_p()
+        self._call("fit", _gpx.ptr(x), _gpx.ptr(t), self.n, self.d, _gpx.ptr(theta), *(extra + (None, ctypes.byref(self._h))))
+
+    def _call(self, what, *args):
+        name = "gpx_%s_%s" % (self._KIND, what)
+        _gpx.check(getattr(_gpx.lib, name)(*args), name)
+
+    def predict(self, xs):
+        m = xs.shape[0]
+        mean = np.empty(m)
+        var = np.empty(m)
+        self._call("predict", self.handle, _gpx.ptr(xs), m, _gpx.ptr(mean), _gpx.ptr(var))
+        return mean, var
+
+    def nll_grad(self):
+        g = np.empty(self._ntheta)
+        self._call("nll_grad", self.handle, _gpx.ptr(g))
+        return g
+
+
+class _PeriodicModel(_RawInputModel):
+    _KIND, _check_theta = "periodic", staticmethod(_periodic_theta)
+
+
+class _MaternModel(_RawInputModel):
+    """nu2 = 2 nu.  For nu = 5/2 the handle also serves the batched propagation calls that UncertaintyPropagationApprox makes on it."""
+    _KIND, _check_theta = "matern", staticmethod(_theta)
+
+    def __init__(self, x, t_centered, theta, nu2):
+        self.nu2 = int(nu2)
+        _RawInputModel.__init__(self, x, t_centered, theta, self.nu2)
+
+
+class _RawInputCovariance(Covariance):
+    """What PeriodicCovariance and MaternCovariance share: the matrix methods of a kernel built on the base class's conventions --
+    cov_matrix AND cov_matrix_ij carry the +vt on exact equality -- as the fused HIP path (the kind's Gram kernel on the raw inputs,
+    Cholesky on the Gram tiles, one-pass likelihood gradient).  A subclass that overrides one of the matrix builders falls back to the
+    generic device route of `Covariance` (`_fused()` decides per instance), as for GaussianCovariance.  A kind names its device model
+    (`_MODEL`, whose theta checker and gpx_<kind>_gram it uses) and what its entry points take after theta (`_extra`)."""
+
+    _MATRIX_METHODS = GaussianCovariance._MATRIX_METHODS
+    _MODEL = None
+
+    def _extra(self):
+        return ()
+
+    def _fused(self):
+        """True when every matrix-defining method of this instance is the fused one of this base"""
+        cls = type(self)
+        return all(getattr(cls, m) is getattr(_RawInputCovariance, m) for m in self._MATRIX_METHODS)
+
+    def _new_model(self, x, t, theta):
+        return self._MODEL(x, t, theta, *self._extra())
+
+    def _gram(self, xi, xj, theta, deriv):
+        a = _gpx.f64(xi)
+        b = a if xj is xi else _gpx.f64(xj)
+        if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1]:
+            raise ValueError("inputs must be (n, d) arrays with equal d")
+        th = self._MODEL._check_theta(theta, a.shape[1])
+        K = np.empty((a.shape[0], b.shape[0]), dtype=np.float64)
+        if K.size:
+            name = "gpx_%s_gram" % self._MODEL._KIND
+            _gpx.check(getattr(_gpx.lib, name)(_gpx.ptr(a), a.shape[0], _gpx.ptr(b), b.shape[0], a.shape[1], _gpx.ptr(th),
+                                               *(self._extra() + (int(deriv), _gpx.ptr(K)))), name)
+        return K
+
+    def cov_matrix_ij(self, xi, xj, theta):
+        """N1 x N2 matrix of the kernel, +vt wherever two rows are equal (Covariance.py:137-152 over the scalar kernel) -- HIP Gram
+        kernel."""
+        return self._gram(xi, xj, theta, -1)
+
+    def cov_matrix(self, x, theta):
+        # (Covariance.py:155-164): cov_matrix_ij(x, x) -- a subclass's own cross-covariance if it has one
+        return self.cov_matrix_ij(x, x, theta)
+
+    def _d_cov_matrix_d_theta_ij(self, xi, xj, theta, j):
+        """d K / d theta_j entry-wise (Covariance.py:236-253 over _d_cov_d_theta) from the kernel's derivative variant.  An accessor:
+        the likelihood gradient never forms these matrices (periodic_nll_grad_kernel, matern_nll_grad_kernel)."""
+        if not 0 <= j < len(theta):
+            raise ValueError("j must be in [0, %d)" % len(theta))
+        return self._gram(xi, xj, theta, j)
+
+    def _d_cov_matrix_d_theta(self, x, theta, j):
+        # (Covariance.py:256-265)
+        return self._d_cov_matrix_d_theta_ij(x, x, theta, j)
+
+    def inv_cov_matrix(self, x, theta, cov_matrix=None):
+        """K^-1 (Covariance.py:167-187) from a device fit: K never leaves the device"""
+        if cov_matrix is not None or not self._fused():
+            return Covariance.inv_cov_matrix(self, x, theta, cov_matrix)
+        model = self._new_model(x, None, theta)
+        try:
+            return model.kinv()
+        finally:
+            model.close()
+
+    def _log_det_cov_matrix(self, x, theta):
+        """log det K (Covariance.py:189-195) from the Cholesky factor of a device fit"""
+        if not self._fused():
+            return Covariance._log_det_cov_matrix(self, x, theta)
+        model = self._new_model(x, None, theta)
+        try:
+            return model.logdet()
+        finally:
+            model.close()
+
+    def _model_at(self, x, t, theta):
+        return self._fitted_model_at(x, t, theta, self._MODEL._check_theta, self._new_model)
+
+    def _negativeloglikelihood(self, x, t, theta):
+        """N/2 log 2pi + 1/2 log det K + 1/2 t^T K^-1 t on the GPU (Covariance.py:197-216); 1e20 when K cannot be factored, like the
+        reference's except branch."""
+        if not self._fused():
+            return Covariance._negativeloglikelihood(self, x, t, theta)
+        try:
+            return self._model_at(x, t, theta).nll()
+        except (np.linalg.LinAlgError, ValueError, ZeroDivisionError):
+            return 1.0e+20
+
+    def _d_nll_d_theta(self, x, t, theta):
+        """gradient of the NLL (Covariance.py:266-282): one fused pass over K^-1 on the GPU instead of one derivative matrix per
+        parameter evaluated entry by entry in Python."""
+        if not self._fused():
+            return Covariance._d_nll_d_theta(self, x, t, theta)
+        return self._model_at(x, t, theta).nll_grad()
+
+
+class PeriodicCovariance(_RawInputCovariance):
     """ARD squared exponential times a periodic factor per dimension, theta = (log v, log vt, log w_1..d, log p_1..d, log w2_1..d)
     (skgpuppy/Covariance.py:361-433):  k(xi, xj) = v exp(-1/2 sum_k [w_k delta_k^2 + w2_k sin^2(pi delta_k / p_k)]) + (vt iff xi == xj).
 
@@ -486,12 +603,7 @@ class PeriodicCovariance(Covariance):
     the generic device route of `Covariance` (`_fused()`), as for GaussianCovariance.  Like the reference's it offers no Jacobian /
     Hessian: the propagation classes treat it as any generic operator."""
 
-    _MATRIX_METHODS = GaussianCovariance._MATRIX_METHODS
-
-    def _fused(self):
-        """True when every matrix-defining method of this instance is PeriodicCovariance's own"""
-        cls = type(self)
-        return cls is PeriodicCovariance or all(getattr(cls, m) is getattr(PeriodicCovariance, m) for m in self._MATRIX_METHODS)
+    _MODEL = _PeriodicModel
 
     @staticmethod
     def _split(xi, theta):
@@ -544,130 +656,8 @@ class PeriodicCovariance(Covariance):
             return -0.5 * (np.sin(np.pi / p[i] * diff[i]) ** 2 * w2[i]) * kf
         return None
 
-    def _gram(self, xi, xj, theta, deriv):
-        a = _gpx.f64(xi)
-        b = a if xj is xi else _gpx.f64(xj)
-        if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1]:
-            raise ValueError("inputs must be (n, d) arrays with equal d")
-        th = _periodic_theta(theta, a.shape[1])
-        K = np.empty((a.shape[0], b.shape[0]), dtype=np.float64)
-        if K.size:
-            _gpx.check(_gpx.lib.gpx_periodic_gram(_gpx.ptr(a), a.shape[0], _gpx.ptr(b), b.shape[0], a.shape[1], _gpx.ptr(th), int(deriv),
-                                                  _gpx.ptr(K)), "gpx_periodic_gram")
-        return K
 
-    def cov_matrix_ij(self, xi, xj, theta):
-        """N1 x N2 matrix of the kernel, +vt wherever two rows are equal (Covariance.py:137-152 over :369-386) -- HIP Gram kernel."""
-        return self._gram(xi, xj, theta, -1)
-
-    def cov_matrix(self, x, theta):
-        # (Covariance.py:155-164): cov_matrix_ij(x, x) -- a subclass's own cross-covariance if it has one
-        return self.cov_matrix_ij(x, x, theta)
-
-    def _d_cov_matrix_d_theta_ij(self, xi, xj, theta, j):
-        """d K / d theta_j entry-wise (Covariance.py:236-253 over :399-433) from the kernel's derivative variant.  An accessor: the
-        likelihood gradient never forms these matrices (periodic_nll_grad_kernel)."""
-        if not 0 <= j < len(theta):
-            raise ValueError("j must be in [0, %d)" % len(theta))
-        return self._gram(xi, xj, theta, j)
-
-    def _d_cov_matrix_d_theta(self, x, theta, j):
-        # (Covariance.py:256-265)
-        return self._d_cov_matrix_d_theta_ij(x, x, theta, j)
-
-    def inv_cov_matrix(self, x, theta, cov_matrix=None):
-        """K^-1 (Covariance.py:167-187) from a device fit: K never leaves the device"""
-        if cov_matrix is not None or not self._fused():
-            return Covariance.inv_cov_matrix(self, x, theta, cov_matrix)
-        model = _PeriodicModel(x, None, theta)
-        try:
-            return model.kinv()
-        finally:
-            model.close()
-
-    def _log_det_cov_matrix(self, x, theta):
-        """log det K (Covariance.py:189-195) from the Cholesky factor of a device fit"""
-        if not self._fused():
-            return Covariance._log_det_cov_matrix(self, x, theta)
-        model = _PeriodicModel(x, None, theta)
-        try:
-            return model.logdet()
-        finally:
-            model.close()
-
-    def _model_at(self, x, t, theta):
-        """device model fitted at theta, cached on (x, t, theta) identity/bytes: L-BFGS-B asks for the value and the
-        gradient at the same theta in two separate calls."""
-        xa = _gpx.f64(x)
-        ta = _gpx.f64(t)
-        th = _periodic_theta(theta, xa.shape[1]).copy()
-        key = (xa.ctypes.data if xa is x else id(x), xa.shape, ta.tobytes(), th.tobytes())
-        cached = getattr(self, "_ml_cache", None)
-        if cached is not None and cached[0] == key:
-            return cached[1]
-        if cached is not None:
-            cached[1].close()
-        self._ml_cache = None
-        model = _PeriodicModel(xa, ta, th)
-        self._ml_cache = (key, model)
-        return model
-
-    def _negativeloglikelihood(self, x, t, theta):
-        """N/2 log 2pi + 1/2 log det K + 1/2 t^T K^-1 t on the GPU (Covariance.py:197-216); 1e20 when K cannot be factored, like the
-        reference's except branch."""
-        if not self._fused():
-            return Covariance._negativeloglikelihood(self, x, t, theta)
-        try:
-            return self._model_at(x, t, theta).nll()
-        except (np.linalg.LinAlgError, ValueError, ZeroDivisionError):
-            return 1.0e+20
-
-    def _d_nll_d_theta(self, x, t, theta):
-        """gradient of the NLL (Covariance.py:266-282 with :399-433): one fused pass over K^-1 on the GPU instead of 2 + 3 d
-        derivative matrices evaluated entry by entry in Python."""
-        if not self._fused():
-            return Covariance._d_nll_d_theta(self, x, t, theta)
-        return self._model_at(x, t, theta).nll_grad()
-
-    def __getstate__(self):
-        state = Covariance.__getstate__(self)
-        state.pop("_ml_cache", None)     # device handles never enter a pickle
-        return state
-
-
-class _MaternModel(_MatrixModel):
-    """Owner of one gpx_matern_fit handle: K of the Matern kernel assembled and factored on the device.  Everything a matrix
-    model answers, plus the kernel's own prediction and likelihood gradient (and, for nu = 5/2, the batched propagation calls
-    that UncertaintyPropagationApprox makes on the handle)."""
-
-    def __init__(self, x, t_centered, theta, nu2):
-        x = _gpx.f64(x)
-        if x.ndim != 2:
-            raise ValueError("x must be an (n, d) array")
-        self.n, self.d = x.shape
-        self.nu2 = int(nu2)
-        theta = _theta(theta, self.d)
-        t = np.zeros(self.n) if t_centered is None else _gpx.f64(t_centered)
-        if t.shape != (self.n,):
-            raise ValueError("t must have %d entries" % self.n)
-        self._h = ctypes.c_void_p()
-        _gpx.check(_gpx.lib.gpx_matern_fit(_gpx.ptr(x), _gpx.ptr(t), self.n, self.d, _gpx.ptr(theta), self.nu2, None, ctypes.byref(self._h)),
-                   "gpx_matern_fit")
-
-    def predict(self, xs):
-        m = xs.shape[0]
-        mean = np.empty(m)
-        var = np.empty(m)
-        _gpx.check(_gpx.lib.gpx_matern_predict(self.handle, _gpx.ptr(xs), m, _gpx.ptr(mean), _gpx.ptr(var)), "gpx_matern_predict")
-        return mean, var
-
-    def nll_grad(self):
-        g = np.empty(2 + self.d)
-        _gpx.check(_gpx.lib.gpx_matern_nll_grad(self.handle, _gpx.ptr(g)), "gpx_matern_nll_grad")
-        return g
-
-
-class MaternCovariance(Covariance):
+class MaternCovariance(_RawInputCovariance):
     """ARD Matern kernel with nu = 3/2 or 5/2, theta = (log v, log vt, log w_1..d) as for GaussianCovariance.  With delta = xi - xj,
     q = sum_k w_k delta_k^2 and s = sqrt(2 nu q):
         nu = 5/2:  k = v (1 + s + s^2 / 3) exp(-s)        nu = 3/2:  k = v (1 + s) exp(-s)        (+ vt iff xi == xj elementwise).
@@ -679,7 +669,7 @@ class MaternCovariance(Covariance):
     get_Jacobian / get_Hessian, so UncertaintyPropagationApprox and the inverse propagation run fused on the device for it; nu = 3/2
     (no Hessian at the origin) is propagated as any generic operator without derivatives."""
 
-    _MATRIX_METHODS = GaussianCovariance._MATRIX_METHODS
+    _MODEL = _MaternModel
 
     def __init__(self, nu=2.5):
         Covariance.__init__(self)
@@ -691,10 +681,8 @@ class MaternCovariance(Covariance):
     def _nu2(self):
         return int(round(2 * self.nu))
 
-    def _fused(self):
-        """True when every matrix-defining method of this instance is MaternCovariance's own"""
-        cls = type(self)
-        return cls is MaternCovariance or all(getattr(cls, m) is getattr(MaternCovariance, m) for m in self._MATRIX_METHODS)
+    def _extra(self):
+        return (self._nu2,)
 
     def _radial(self, diff, theta):
         """(s, v exp(-s), w) at the difference diff"""
@@ -751,94 +739,6 @@ class MaternCovariance(Covariance):
         s, e, w = self._radial(diff, theta)
         wd = diff * w
         return (5.0 / 3.0) * e * (5.0 * np.outer(wd, wd) - np.diag(w) * (1.0 + s))
-
-    def _gram(self, xi, xj, theta, deriv):
-        a = _gpx.f64(xi)
-        b = a if xj is xi else _gpx.f64(xj)
-        if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1]:
-            raise ValueError("inputs must be (n, d) arrays with equal d")
-        th = _theta(theta, a.shape[1])
-        K = np.empty((a.shape[0], b.shape[0]), dtype=np.float64)
-        if K.size:
-            _gpx.check(_gpx.lib.gpx_matern_gram(_gpx.ptr(a), a.shape[0], _gpx.ptr(b), b.shape[0], a.shape[1], _gpx.ptr(th), self._nu2,
-                                                int(deriv), _gpx.ptr(K)), "gpx_matern_gram")
-        return K
-
-    def cov_matrix_ij(self, xi, xj, theta):
-        """N1 x N2 matrix of the kernel, +vt wherever two rows are equal -- HIP Gram kernel."""
-        return self._gram(xi, xj, theta, -1)
-
-    def cov_matrix(self, x, theta):
-        # cov_matrix_ij(x, x) -- a subclass's own cross-covariance if it has one
-        return self.cov_matrix_ij(x, x, theta)
-
-    def _d_cov_matrix_d_theta_ij(self, xi, xj, theta, j):
-        """d K / d theta_j entry-wise from the kernel's derivative variant.  An accessor: the likelihood gradient never forms these
-        matrices (matern_nll_grad_kernel)."""
-        if not 0 <= j < len(theta):
-            raise ValueError("j must be in [0, %d)" % len(theta))
-        return self._gram(xi, xj, theta, j)
-
-    def _d_cov_matrix_d_theta(self, x, theta, j):
-        return self._d_cov_matrix_d_theta_ij(x, x, theta, j)
-
-    def inv_cov_matrix(self, x, theta, cov_matrix=None):
-        """K^-1 from a device fit: K never leaves the device"""
-        if cov_matrix is not None or not self._fused():
-            return Covariance.inv_cov_matrix(self, x, theta, cov_matrix)
-        model = _MaternModel(x, None, theta, self._nu2)
-        try:
-            return model.kinv()
-        finally:
-            model.close()
-
-    def _log_det_cov_matrix(self, x, theta):
-        """log det K from the Cholesky factor of a device fit"""
-        if not self._fused():
-            return Covariance._log_det_cov_matrix(self, x, theta)
-        model = _MaternModel(x, None, theta, self._nu2)
-        try:
-            return model.logdet()
-        finally:
-            model.close()
-
-    def _model_at(self, x, t, theta):
-        """device model fitted at theta, cached on (x, t, theta) identity/bytes: L-BFGS-B asks for the value and the
-        gradient at the same theta in two separate calls."""
-        xa = _gpx.f64(x)
-        ta = _gpx.f64(t)
-        th = _theta(theta, xa.shape[1]).copy()
-        key = (xa.ctypes.data if xa is x else id(x), xa.shape, ta.tobytes(), th.tobytes())
-        cached = getattr(self, "_ml_cache", None)
-        if cached is not None and cached[0] == key:
-            return cached[1]
-        if cached is not None:
-            cached[1].close()
-        self._ml_cache = None
-        model = _MaternModel(xa, ta, th, self._nu2)
-        self._ml_cache = (key, model)
-        return model
-
-    def _negativeloglikelihood(self, x, t, theta):
-        """N/2 log 2pi + 1/2 log det K + 1/2 t^T K^-1 t on the GPU; 1e20 when K cannot be factored, like the base class's."""
-        if not self._fused():
-            return Covariance._negativeloglikelihood(self, x, t, theta)
-        try:
-            return self._model_at(x, t, theta).nll()
-        except (np.linalg.LinAlgError, ValueError, ZeroDivisionError):
-            return 1.0e+20
-
-    def _d_nll_d_theta(self, x, t, theta):
-        """gradient of the NLL: one fused pass over K^-1 on the GPU instead of 2 + d derivative matrices evaluated entry by entry in
-        Python."""
-        if not self._fused():
-            return Covariance._d_nll_d_theta(self, x, t, theta)
-        return self._model_at(x, t, theta).nll_grad()
-
-    def __getstate__(self):
-        state = Covariance.__getstate__(self)
-        state.pop("_ml_cache", None)     # device handles never enter a pickle
-        return state
 
 
 class _SPGPDeviceModel(object):

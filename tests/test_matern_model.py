@@ -206,6 +206,21 @@ def test_class_surface():
         skgpuppy_amd.MaternCovariance(nu=2.0)
 
 
+@pytest.mark.parametrize("base", [skgpuppy_amd.PeriodicCovariance, skgpuppy_amd.MaternCovariance])
+def test_fused_is_decided_per_subclass_on_the_common_base(base):
+    """both raw-input kinds take _fused() from one base: a subclass that overrides no matrix method stays fused (its own scalar
+    accessors do not count), one that overrides cov_matrix_ij takes the generic route"""
+    class Plain(base):
+        def get_theta(self, x, t):
+            return base.get_theta(self, x, t)
+
+    class Own(base):
+        def cov_matrix_ij(self, xi, xj, theta):
+            return skgpuppy_amd.Covariance.cov_matrix_ij(self, xi, xj, theta)
+
+    assert Plain()._fused() is True and Own()._fused() is False
+
+
 def test_abi_has_the_matern_entry_points():
     for name in NAMES:
         assert hasattr(_gpx.lib, name) and name in _gpx.SIGNATURES
