@@ -33,6 +33,9 @@ void gpx_set_error(const char *fmt, ...);
     } while (0)
 
 static inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
+// rows an input owns in a right-hand-side block of the batched row calls (GPX_ROWS_*, include/gpx.h): the ONE definition, for the build
+// frame (rows_tile.h), its launcher, gpx_rows_build / gpx_rows_reduce and the chunk loop
+__host__ __device__ constexpr int rows_per_input(int layout, int d) { return layout == GPX_ROWS_DVH ? 2 * d + 1 : layout == GPX_ROWS_APPROX ? d + 2 : d + 1; }
 
 // ---- exp for non-positive arguments (every exponent on the path is -1/2 of a squared distance, or a sum of such) ----
 // Plain Cody-Waite: n = rint(x log2 e), r = x - n ln2 (two-term), degree-12 Taylor polynomial on |r| <= ln2/2
@@ -240,11 +243,6 @@ int matern_parse(const double *theta, int d, int nu2, MaternData *out);    // ho
 // inputs; lower_only / pad_mode / padding contract as launch_gram.  deriv >= 0: d K / d theta_deriv instead (no add_diag)
 int launch_matern_gram(const double *xi, int64_t n1, const double *xj, int64_t n2, const MaternData *md, double add_diag, int lower_only,
                        int pad_mode, double *out, int64_t ld, int64_t rows_pad, int64_t cols_pad, hipStream_t s, Profiler *prof, int deriv = -1);
-// the right-hand-side rows of nb inputs in the row layout `layout` (GPX_ROWS_*; nu2 = 3: GPX_ROWS_GRAD alone; Sigma read for GPX_ROWS_APPROX
-// alone): Z [rows_pad, npad], the rest of the last 128-row tile cleared
-int launch_matern_build_many(int layout, int nu2, const double *x, int64_t n, int64_t npad, int d, const double *U_dev, const double *Sigma_dev,
-                             int64_t sigma_stride, int64_t nb, int64_t rows_pad, const double *w_dev, double v, double vt, double *Z, hipStream_t s,
-                             Profiler *prof);
 constexpr int MAT_KC = 8;                        // coordinates per sweep of the gradient pass
 constexpr int MAT_NC = MAT_KC + 2;               // sums per sweep: S_0, A_k of the sweep's k, T
 // the gradient pass alone (raw_nll_grad_sums): partial [sweeps, npad / 8, MAT_NC]; sweeps = ceil(d / MAT_KC)
@@ -455,18 +453,24 @@ int launch_trace(const double *x, int64_t n, int64_t npad, int d, const double *
                  const double *Sigma_dev, const double *cplain, double *tr, hipStream_t s);
 int launch_cjh(const double *x, int64_t n, int d, const double *u_dev, const double *w_dev, double v, double vt, double *C,
                double *J, double *H, hipStream_t s);
-int launch_approx_build_many(const double *x, int64_t n, int64_t npad, int d, const double *U_dev, const double *Sigma_dev,
-                             int64_t sigma_stride, int64_t nb, int64_t rows_pad, const double *w_dev, double v, double vt, double *Z,
-                             hipStream_t s, Profiler *prof);
+// The right-hand-side rows of nb inputs in the row layout `layout` (GPX_ROWS_*) into Z [rows_pad, npad], the rest of the last 128-row tile
+// cleared: the one launcher of every build kernel (frame: rows_tile.h).  nu2 = 0: the Gaussian kernel (propagate.hip), 3 / 5: Matern
+// (matern.hip; nu2 = 3: GPX_ROWS_GRAD alone).  Sigma is read for GPX_ROWS_APPROX alone.
+int launch_rows_build(int nu2, int layout, const double *x, int64_t n, int64_t npad, int d, const double *U_dev, const double *Sigma_dev,
+                      int64_t sigma_stride, int64_t nb, int64_t rows_pad, const double *w_dev, double v, double vt, double *Z, hipStream_t s,
+                      Profiler *prof);
+// a build kernel by its parameter list (the kernels keep the lists they had): exactly one is set, neither where there is no such kernel
+struct RowsKernel {
+    void (*with_sigma)(const double *, long, long, int, const double *, const double *, long, long, const double *, double, double, double *);
+    void (*plain)(const double *, long, long, int, const double *, long, const double *, double, double, double *);
+};
+RowsKernel matern_rows_kernel(int nu2, int layout, bool regs);   // matern.hip's kernels of the launcher's table; regs: d <= 8
 int launch_approx_reduce_many(const double *Zs, int64_t npad, int d, const double *y, const double *Sigma_dev, int64_t sigma_stride,
                               int64_t nb, double vplusvt, double *out, int64_t ldo, hipStream_t s, Profiler *prof);
 // the pair form (a model held as K^-1, not as a factor): R = the built rows, Y = R K^-1, alpha = K^-1 t; v.Kinv v = r_v.y_v, beta.v = r_v.alpha,
 // tr.Kinv C = y_C.r_tr
 int launch_approx_reduce_many_pair(const double *R, const double *Y, int64_t npad, int d, const double *alpha, const double *Sigma_dev,
                                    int64_t sigma_stride, int64_t nb, double vplusvt, double *out, int64_t ldo, hipStream_t s, Profiler *prof);
-// the same kernel's rows [C, J_1..J_d] per query (gpx_predict_grad)
-int launch_grad_build_many(const double *x, int64_t n, int64_t npad, int d, const double *U_dev, int64_t nb, int64_t rows_pad, const double *w_dev,
-                           double v, double vt, double *Z, hipStream_t s, Profiler *prof);
 // ---- launchers of predict_grad.hip: the predictor's input gradients ----
 // mean [nb] and dmean [nb, d] from alpha alone (nu2 = 0: the Gaussian kernel, 3 / 5: Matern; x raw); partial [S, nb, 1 + d] scratch with
 // S = predict_mean_grad_splits(nb, npad); either output may be null
@@ -481,8 +485,6 @@ int launch_grad_reduce_many(const double *Zs, int64_t npad, int d, const double 
 int launch_grad_reduce_many_pair(const double *R, const double *Y, int64_t npad, int d, const double *alpha, int64_t nb, double vplusvt, double *mean,
                                  double *var, double *dmean, double *dvar, hipStream_t s, Profiler *prof);
 // batched inverse propagation (gpx_propagate_dvh_many): rows [C, J_1..J_d, H_11..H_dd] per input; dvh [nb, d], sigma2 [nb] or null
-int launch_dvh_build_many(const double *x, int64_t n, int64_t npad, int d, const double *U_dev, int64_t nb, int64_t rows_pad,
-                          const double *w_dev, double v, double vt, double *Z, hipStream_t s, Profiler *prof);
 int launch_dvh_reduce_many(const double *Zs, int64_t npad, int d, const double *y, int64_t nb, double vplusvt, double *dvh, double *sigma2,
                            hipStream_t s, Profiler *prof);
 int launch_exact_build(const double *x, int64_t n, int64_t npad, int d, const double *u_dev, const double *w_dev,
@@ -604,12 +606,12 @@ int64_t row_solve_chunk_cap(const gpx_handle *h, int64_t chunk_cap = 0);   // th
 // Zs[0 : mp) <- Z[0 : mp) L^-T (mc real rows, mp = mc rounded up to the tile); red: the fused row sums of tsolve.hip (many rows only)
 int row_solve_run(gpx_handle *h, const RowSolve &rs, int64_t mc, int64_t mp, const GemmReduce *red, bool left = false);
 
-// The chunk loops of gpx_propagate_approx_many and gpx_propagate_dvh_many (propagate_api.hip) for any kernel that has the right-hand
-// sides: build(U_dev, Sigma_dev, sigma_stride, bc, mp) writes the rows of bc inputs into h->Z [mp, npad] (d + 2 rows an input:
-// [C, tr, J_1..J_d]; 2 d + 1: [C, J_1..J_d, H_11..H_dd], no Sigma); the solve, the row reductions and the copies are the loops' own.
+// The chunk loop of the five batched row calls (rows_many_run, propagate_api.hip) under its three names, one per row layout, for any kernel
+// that has the right-hand sides: build(U_dev, Sigma_dev, sigma_stride, bc, mp) writes the rows of bc inputs into h->Z [mp, npad] (Sigma for
+// GPX_ROWS_APPROX alone); the solve or the product with K^-1, the row reductions and the copies are the loop's own.
 using RowsBuild = std::function<int(const double *, const double *, int64_t, int64_t, int64_t)>;
-// The build of the handle's kind for a row layout (GPX_ROWS_*): the ONE place that launches the build kernels, for the five batched entry
-// points and for gpx_rows_build alike.  The caller has checked that the kind has the layout (Gaussian: all; Matern 5/2: all; 3/2: GRAD).
+// The build of the handle's kind for a row layout (GPX_ROWS_*): the ONE caller of launch_rows_build, for the five batched entry points and
+// for gpx_rows_build alike.  The caller has checked that the kind has the layout (Gaussian: all; Matern 5/2: all; 3/2: GRAD).
 RowsBuild rows_build_of(gpx_handle *h, int layout);
 int approx_many_run(gpx_handle *h, int d, const double *U, const double *Sigma, int sigma_shared, int64_t b, double *mean, double *var, double *sigma2,
                     double *rest, const char *what, const RowsBuild &build);

@@ -16,6 +16,7 @@
 #include "gram_tile.h"
 #include "nll_grad_tile.h"
 #include "radial.h"   // MaternRadial: the radial factors at q, one sqrt and one exp for all of them
+#include "rows_tile.h"
 
 // what the deriv variant writes (the parameter's group; MD_W: its coordinate is a second argument)
 enum { MD_V = 0, MD_VT = 1, MD_W = 2 };
@@ -164,163 +165,18 @@ int launch_matern_nll_grad(const double *Kinv, int64_t ld, int64_t n, int64_t np
 }
 
 // ---------------------------------------------------------------------------------------------
-// Batched Approx and inverse propagation, nu = 5/2: the build kernels of approx_build_many_kernel / dvh_build_many_kernel (propagate.hip)
-// with the Matern kernel's three radial factors in place of the Gaussian kernel's single c.  With diff = x_i - u, a = w . diff,
-// q = a . diff, s = sqrt(5 q), e = v exp(-s):
-//   C = e (1 + s + s^2 / 3) (+vt iff x_i == u elementwise)     J_k = -a_k G,  G = (5/3) e (1 + s)
-//   H_kl = (5/3) e [5 a_k a_l - delta_kl w_k (1 + s)],   tr(H Sigma) = (5/3) e [5 a^T Sigma a - (1 + s) sum_k w_k Sigma_kk]
-// DVH = false: row b (d + 2) + r of Z is [C, tr, J_1..J_d]; DVH = true: row b (2 d + 1) + r is [C, J_1..J_d, H_11..H_dd] (no Sigma).
-// The body is one function over a compile-time row layout (MB_APPROX, MB_DVH, and MB_GRAD: row b (d + 1) + r is [C, J_1..J_d], the rows of
-// gpx_predict_grad, which needs one derivative only and therefore serves nu = 3/2 as well: NU2 selects the radial factors).
-// Same workgroup (128 columns of x k-major in LDS, AB_INPUTS inputs, four per wave, u / w / Sigma wave-uniform), 16-byte stores, one
-// exp and one sqrt per (input, column).  DR > 0: d <= DR and a stays in registers; DR = 0: any d, recomputed from the LDS tile.
+// The build kernels of the batched row calls on the Matern kernel: the frame of rows_tile.h with the MaternRows<NU2> policy.
+// matern52_build_many_kernel<DR, DVH> (nu = 5/2): the APPROX rows [C, tr, J_1..J_d] or, DVH = true, the DVH rows [C, J_1..J_d, H_11..H_dd];
+// matern_grad_build_many_kernel<DR, NU2>: the GRAD rows [C, J_1..J_d] of gpx_predict_grad, one derivative only, so nu = 3/2 as well.
+// DR = 8: d <= 8; DR = 0: any d.  launch_rows_build (propagate.hip) launches them.
 // ---------------------------------------------------------------------------------------------
-constexpr int MB_COLS = 128;
-constexpr int MB_INPUTS = 16;
-
-enum { MB_APPROX = GPX_ROWS_APPROX, MB_DVH = GPX_ROWS_DVH, MB_GRAD = GPX_ROWS_GRAD };   // the public row layouts (include/gpx.h)
-
-template <int DR, int ROWS, int NU2>
-__device__ __forceinline__ void matern_build_many(const double *__restrict__ x, long n, long npad, int d, const double *__restrict__ U,
-                                                  const double *__restrict__ Sigma, long sigma_stride, long nb, const double *__restrict__ w_in,
-                                                  double v, double vt, double *__restrict__ Z)
-{
-    const double *w = w_in;
-    constexpr bool DVH = ROWS == MB_DVH, TR = ROWS == MB_APPROX;
-    static_assert(NU2 == 5 || ROWS == MB_GRAD, "nu = 3/2 has no Hessian at the origin");
-    extern __shared__ __attribute__((aligned(16))) double mb_smem[];
-    double *x_s = mb_smem;   // [d][128] raw inputs of the tile's columns, k-major
-    const int t = threadIdx.x;
-    const long col0 = (long)blockIdx.x * MB_COLS;
-    for (int e = t; e < MB_COLS * d; e += 256) {
-        const int c = e & (MB_COLS - 1), k = e >> 7;
-        const long gc = col0 + c;
-        x_s[k * MB_COLS + c] = (gc < n) ? x[gc * d + k] : 0.0;
-    }
-    __syncthreads();
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
-    const long c = col0 + 2 * lane;
-    const bool in0 = c < n, in1 = c + 1 < n;
-    const long nrow = DVH ? 2 * d + 1 : TR ? d + 2 : d + 1;
-    const int jrow = TR ? 2 : 1;   // first row of J
-    for (int j = 0; j < MB_INPUTS / 4; ++j) {
-        const long b = (long)blockIdx.y * MB_INPUTS + 4 * j + wave;   // wave-uniform
-        if (b >= nb) break;
-        // (the new layout alone, so that the older instantiations stay the code they were: w and the tests k < d are formed per input --
-        // held across the inputs they spill scalar registers, as predict_grad.hip explains)
-        if constexpr (ROWS == MB_GRAD) asm volatile("" : "+s"(w), "+s"(d));
-        const double *u = U + b * d;
-        double *zrow = Z + b * nrow * npad + c;
-        double wd0[DR > 0 ? DR : 1], wd1[DR > 0 ? DR : 1];
-        double q0 = 0.0, q1 = 0.0;
-        bool same0 = true, same1 = true;
-        if constexpr (DR > 0) {
-#pragma unroll
-            for (int k = 0; k < DR; ++k) {
-                wd0[k] = 0.0; wd1[k] = 0.0;
-                if (k < d) {
-                    const v2d xv = *reinterpret_cast<const v2d *>(&x_s[k * MB_COLS + 2 * lane]);
-                    const double uk = u[k], wk = w[k];
-                    const double d0 = xv.x - uk, d1 = xv.y - uk;
-                    same0 = same0 && (xv.x == uk);
-                    same1 = same1 && (xv.y == uk);
-                    wd0[k] = wk * d0; wd1[k] = wk * d1;
-                    q0 = fma(wd0[k], d0, q0);
-                    q1 = fma(wd1[k], d1, q1);
-                }
-            }
-        } else {
-            for (int k = 0; k < d; ++k) {
-                const v2d xv = *reinterpret_cast<const v2d *>(&x_s[k * MB_COLS + 2 * lane]);
-                const double uk = u[k], wk = w[k];
-                const double d0 = xv.x - uk, d1 = xv.y - uk;
-                same0 = same0 && (xv.x == uk);
-                same1 = same1 && (xv.y == uk);
-                q0 = fma(wk * d0, d0, q0);
-                q1 = fma(wk * d1, d1, q1);
-            }
-        }
-        // columns past n: every row of the block is zero there
-        const MaternRadial<NU2> r0(in0 ? v : 0.0, q0), r1(in1 ? v : 0.0, q1);
-        const double c0 = r0.kf(), c1 = r1.kf(), g0 = r0.g(), g1 = r1.g();
-        const double f0 = (5.0 / 3.0) * r0.e, f1 = (5.0 / 3.0) * r1.e;   // H = f [5 a a^T - diag(w) (1 + s)]
-        const double p0 = 1.0 + r0.s, p1 = 1.0 + r1.s;
-        v2d o;
-        o.x = (in0 && same0) ? c0 + vt : c0;
-        o.y = (in1 && same1) ? c1 + vt : c1;
-        *reinterpret_cast<v2d *>(zrow) = o;
-        double s0 = 0.0, s1 = 0.0, wdiag = 0.0;
-        if constexpr (DR > 0) {
-#pragma unroll
-            for (int a = 0; a < DR; ++a) {
-                if (a < d) {
-                    v2d jk;
-                    jk.x = -wd0[a] * g0; jk.y = -wd1[a] * g1;
-                    *reinterpret_cast<v2d *>(zrow + (long)(jrow + a) * npad) = jk;
-                    if constexpr (DVH) {
-                        const double wa = w[a];
-                        v2d hk;
-                        hk.x = f0 * fma(5.0 * wd0[a], wd0[a], -wa * p0); hk.y = f1 * fma(5.0 * wd1[a], wd1[a], -wa * p1);
-                        *reinterpret_cast<v2d *>(zrow + (long)(1 + d + a) * npad) = hk;
-                    } else if constexpr (TR) {
-                        const double *S = Sigma + b * sigma_stride;
-                        double t0 = 0.0, t1 = 0.0;
-#pragma unroll
-                        for (int e = 0; e < DR; ++e)
-                            if (e < d) {
-                                const double sg = S[a * d + e];
-                                t0 = fma(sg, wd0[e], t0);
-                                t1 = fma(sg, wd1[e], t1);
-                            }
-                        s0 = fma(wd0[a], t0, s0);
-                        s1 = fma(wd1[a], t1, s1);
-                        wdiag = fma(w[a], S[a * d + a], wdiag);
-                    }
-                }
-            }
-        } else {
-            if constexpr (ROWS == MB_GRAD) asm volatile("" : "+s"(w), "+s"(d), "+s"(u));
-            for (int a = 0; a < d; ++a) {
-                const v2d xa = *reinterpret_cast<const v2d *>(&x_s[a * MB_COLS + 2 * lane]);
-                const double wa = w[a], ua = u[a];
-                const double a0 = wa * (xa.x - ua), a1 = wa * (xa.y - ua);
-                v2d jk;
-                jk.x = -a0 * g0; jk.y = -a1 * g1;
-                *reinterpret_cast<v2d *>(zrow + (long)(jrow + a) * npad) = jk;
-                if constexpr (DVH) {
-                    v2d hk;
-                    hk.x = f0 * fma(5.0 * a0, a0, -wa * p0); hk.y = f1 * fma(5.0 * a1, a1, -wa * p1);
-                    *reinterpret_cast<v2d *>(zrow + (long)(1 + d + a) * npad) = hk;
-                } else if constexpr (TR) {
-                    const double *S = Sigma + b * sigma_stride;
-                    double t0 = 0.0, t1 = 0.0;
-                    for (int e = 0; e < d; ++e) {
-                        const v2d xv = *reinterpret_cast<const v2d *>(&x_s[e * MB_COLS + 2 * lane]);
-                        const double sg = S[a * d + e], ue = u[e], we = w[e];
-                        t0 = fma(sg, we * (xv.x - ue), t0);
-                        t1 = fma(sg, we * (xv.y - ue), t1);
-                    }
-                    s0 = fma(a0, t0, s0);
-                    s1 = fma(a1, t1, s1);
-                    wdiag = fma(wa, S[a * d + a], wdiag);
-                }
-            }
-        }
-        if constexpr (TR) {
-            o.x = f0 * fma(5.0, s0, -p0 * wdiag);
-            o.y = f1 * fma(5.0, s1, -p1 * wdiag);
-            *reinterpret_cast<v2d *>(zrow + npad) = o;
-        }
-    }
-}
-
 template <int DR, bool DVH>
 __global__ __launch_bounds__(256) void matern52_build_many_kernel(const double *__restrict__ x, long n, long npad, int d,
                                                                  const double *__restrict__ U, const double *__restrict__ Sigma,
                                                                  long sigma_stride, long nb, const double *__restrict__ w, double v, double vt,
                                                                  double *__restrict__ Z)
 {
-    matern_build_many<DR, DVH ? MB_DVH : MB_APPROX, 5>(x, n, npad, d, U, Sigma, sigma_stride, nb, w, v, vt, Z);
+    rows_build_tile<DR, DVH ? GPX_ROWS_DVH : GPX_ROWS_APPROX>(MaternRows<5>{v, vt}, x, n, npad, d, U, Sigma, sigma_stride, nb, w, Z);
 }
 
 template <int DR, int NU2>
@@ -328,41 +184,17 @@ __global__ __launch_bounds__(256) void matern_grad_build_many_kernel(const doubl
                                                                     const double *__restrict__ U, long nb, const double *__restrict__ w, double v,
                                                                     double vt, double *__restrict__ Z)
 {
-    matern_build_many<DR, MB_GRAD, NU2>(x, n, npad, d, U, nullptr, 0, nb, w, v, vt, Z);
+    rows_build_tile<DR, GPX_ROWS_GRAD>(MaternRows<NU2>{v, vt}, x, n, npad, d, U, nullptr, 0, nb, w, Z);
 }
 
-// Z [rows_pad, npad]: rows [0, nb nrow) written by the kernel (every column, zeros from n on), the rest of the last 128-row tile cleared
-int launch_matern_build_many(int layout, int nu2, const double *x, int64_t n, int64_t npad, int d, const double *U_dev, const double *Sigma_dev,
-                             int64_t sigma_stride, int64_t nb, int64_t rows_pad, const double *w_dev, double v, double vt, double *Z, hipStream_t s,
-                             Profiler *prof)
+// this file's part of launch_rows_build's table: neither kernel where the family has no such rows (nu = 3/2: GPX_ROWS_GRAD alone)
+RowsKernel matern_rows_kernel(int nu2, int layout, bool regs)
 {
-    if (nb <= 0) return 0;
-    const bool dvh = layout == MB_DVH;
-    const int64_t rows = nb * (dvh ? 2 * d + 1 : layout == MB_GRAD ? d + 1 : d + 2);
-    if (npad % MB_COLS || rows > rows_pad || d < 1 || d > GPX_MAX_D || (nu2 != 5 && layout != MB_GRAD)) { gpx_set_error("matern_build_many: bad block shape"); return GPX_ERR_BAD_ARG; }
-    ProfScope ps(prof, s, GPX_K_GRAM, 8.0 * (double)rows_pad * (double)npad);
-    if (rows_pad > rows) GPX_HIP(hipMemsetAsync(Z + rows * npad, 0, sizeof(double) * (rows_pad - rows) * npad, s));
-    const dim3 grid((unsigned)(npad / MB_COLS), (unsigned)((nb + MB_INPUTS - 1) / MB_INPUTS));
-    const size_t lds = sizeof(double) * MB_COLS * d;
-#define MATERN_BUILD(DR, DVH)                                                                                                                  \
-    hipLaunchKernelGGL((matern52_build_many_kernel<DR, DVH>), grid, dim3(256), lds, s, x, (long)n, (long)npad, d, U_dev, Sigma_dev, (long)sigma_stride, \
-                       (long)nb, w_dev, v, vt, Z)
-#define MATERN_GRAD_BUILD(DR, NU2)                                                                                                              \
-    hipLaunchKernelGGL((matern_grad_build_many_kernel<DR, NU2>), grid, dim3(256), lds, s, x, (long)n, (long)npad, d, U_dev, (long)nb, w_dev, v, vt, Z)
-    if (layout == MB_GRAD) {
-        if (nu2 == 5) { if (d <= 8) MATERN_GRAD_BUILD(8, 5); else MATERN_GRAD_BUILD(0, 5); }
-        else { if (d <= 8) MATERN_GRAD_BUILD(8, 3); else MATERN_GRAD_BUILD(0, 3); }
-    } else if (dvh) {
-        if (d <= 8) MATERN_BUILD(8, true);
-        else MATERN_BUILD(0, true);
-    } else {
-        if (d <= 8) MATERN_BUILD(8, false);
-        else MATERN_BUILD(0, false);
-    }
-#undef MATERN_BUILD
-#undef MATERN_GRAD_BUILD
-    GPX_HIP(hipGetLastError());
-    return 0;
+    if (layout == GPX_ROWS_GRAD && nu2 == 5) return {nullptr, regs ? matern_grad_build_many_kernel<8, 5> : matern_grad_build_many_kernel<0, 5>};
+    if (layout == GPX_ROWS_GRAD && nu2 == 3) return {nullptr, regs ? matern_grad_build_many_kernel<8, 3> : matern_grad_build_many_kernel<0, 3>};
+    if (layout == GPX_ROWS_DVH && nu2 == 5) return {regs ? matern52_build_many_kernel<8, true> : matern52_build_many_kernel<0, true>, nullptr};
+    if (layout == GPX_ROWS_APPROX && nu2 == 5) return {regs ? matern52_build_many_kernel<8, false> : matern52_build_many_kernel<0, false>, nullptr};
+    return {nullptr, nullptr};
 }
 
 // ---- parameters of a Matern model ------------------------------------------------------------------------------------------

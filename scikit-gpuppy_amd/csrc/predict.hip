@@ -22,7 +22,7 @@ int64_t row_solve_chunk_cap(const gpx_handle *h, int64_t chunk_cap)
 {
     int64_t cap = ((int64_t)8 << 30) / (h->npad * (int64_t)sizeof(double));   // rows per 8 GB buffer (two of them: Z and Zs)
     cap = std::max<int64_t>(TILE, cap / TILE * TILE);
-    cap = std::min<int64_t>(cap, 32768);
+    cap = std::min<int64_t>(cap, 32768);   // (tests/test_spgp_pseudo.py, CHUNK_ROWS: its chunk-seam test is cut for this figure)
     if (chunk_cap > 0) cap = std::min<int64_t>(cap, std::max<int64_t>(TILE, chunk_cap / TILE * TILE));
     return cap;
 }

@@ -9,14 +9,14 @@
 //   predict_mean_grad_kernel (+ predict_mean_grad_sum_kernel)   mu and grad mu from alpha alone: one fused pass over the M x N pairs, no solve,
 //                                                               nothing N-wide stored                                (gpx_predict_mean_grad)
 //   grad_reduce_many_kernel                                     the row products of the solved block [C, J_1..J_d] of every query
-//                                                               (built by approx_build_many_kernel<DR, true> / matern_grad_build_many_kernel)
+//                                                               (built by the GRAD instantiations of rows_build_tile, rows_tile.h)
 //                                                                                                                     (gpx_predict_grad)
 #include "common.h"
 #include "radial.h"
 
 // ---------------------------------------------------------------------------------------------
 // mu and grad mu from alpha.  A workgroup owns PG_QUERIES queries, four per wave (u and w are wave-uniform: scalar loads), and one of the
-// S ranges of 128-column tiles; a tile of x sits k-major in LDS (the staging of approx_build_many_kernel), alpha comes as 16-byte loads.
+// S ranges of 128-column tiles; a tile of x sits k-major in LDS (the staging of rows_build_tile, rows_tile.h), alpha comes as 16-byte loads.
 // A lane forms q and the radial factors of its two columns and accumulates, per query,
 //   sum C_i alpha_i  (C_i = c_i + vt iff x_i == u elementwise: gpx_predict's mean)   and   sum w_k delta_k g_i alpha_i  (no vt)
 // for the PG_KC coordinates of its sweep: blockIdx.z sweeps of PG_KC coordinates each (1 + d accumulators for four queries do not fit in

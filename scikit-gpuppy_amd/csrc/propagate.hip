@@ -10,6 +10,7 @@
 //       -> exact_sum_kernel: each thread owns a column j (coalesced Kinv reads), a workgroup owns 16
 //          rows; the d^2 inner loop is factorised as exp(e_i + e_j + b_i . a_j), b_i = Lambda^-1 a_i / 4.
 #include "common.h"
+#include "rows_tile.h"
 
 // ---------------------------------------------------------------------------------------------
 // Approx: per-row quantities for a given u.   VM rows: 0 = C, 1..d = J_k.   AUX rows: 1..d = H_kk
@@ -116,169 +117,58 @@ int launch_dot_pairs(const std::vector<std::pair<const double *, const double *>
 }
 
 // ---------------------------------------------------------------------------------------------
-// Batched Approx (gpx_propagate_approx_many): the d + 2 vectors of MANY inputs as the rows of a right-hand-side block for
-// the many-right-hand-side triangular solver.  Row b (d + 2) + r of Z (leading dimension npad):
-//   r = 0: C_i (+vt iff x_i == u_b elementwise)   r = 1: tr_i = tracedot(H_i, Sigma_b)   r = 2 + k: J_ik
-// A workgroup owns 128 columns (a lane two adjacent ones: 16-byte stores, 1 KB per wave and row) and AB_INPUTS inputs, four per
-// wave; the x tile sits in LDS k-major as in gram_kernel, and the input's u, w, Sigma are wave-uniform: they come through the
-// scalar cache (loads only).  One exp per (input, column).  DR > 0: d <= DR and the scaled differences w_k (x_ik - u_k) stay
-// in registers; DR = 0: any d, they are recomputed from the LDS tile.
-// GRAD: the row layout of gpx_predict_grad instead -- row b (d + 1) + r is [C, J_1..J_d]: no tr row, Sigma is not read.
+// The build kernels of the batched row calls on the Gaussian kernel: the frame of rows_tile.h with the GaussRows policy.
+// approx_build_many_kernel<DR, GRAD>: the APPROX rows [C, tr, J_1..J_d] (GRAD: the rows [C, J_1..J_d] of gpx_predict_grad, Sigma not read);
+// dvh_build_many_kernel<DR>: the DVH rows [C, J_1..J_d, H_11..H_dd].  DR = 8: d <= 8; DR = 0: any d.
 // ---------------------------------------------------------------------------------------------
-constexpr int AB_COLS = 128;
-constexpr int AB_INPUTS = 16;
-
 template <int DR, bool GRAD = false>
 __global__ __launch_bounds__(256) void approx_build_many_kernel(const double *__restrict__ x, long n, long npad, int d,
                                                                const double *__restrict__ U, const double *__restrict__ Sigma,
                                                                long sigma_stride, long nb, const double *__restrict__ w, double v,
                                                                double vt, double *__restrict__ Z)
 {
-    extern __shared__ __attribute__((aligned(16))) double ab_smem[];
-    double *x_s = ab_smem;   // [d][128] raw inputs of the tile's columns, k-major
-    const int t = threadIdx.x;
-    const long col0 = (long)blockIdx.x * AB_COLS;
-    for (int e = t; e < AB_COLS * d; e += 256) {
-        const int c = e & (AB_COLS - 1), k = e >> 7;
-        const long gc = col0 + c;
-        x_s[k * AB_COLS + c] = (gc < n) ? x[gc * d + k] : 0.0;
-    }
-    __syncthreads();
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
-    const long c = col0 + 2 * lane;
-    const bool in0 = c < n, in1 = c + 1 < n;
-    const int nrow = GRAD ? d + 1 : d + 2, jrow = GRAD ? 1 : 2;   // jrow: first row of J
-    for (int j = 0; j < AB_INPUTS / 4; ++j) {
-        const long b = (long)blockIdx.y * AB_INPUTS + 4 * j + wave;   // wave-uniform
-        if (b >= nb) break;
-        const double *u = U + b * d, *S = GRAD ? nullptr : Sigma + b * sigma_stride;
-        double *zrow = Z + b * nrow * npad + c;
-        double wd0[DR > 0 ? DR : 1], wd1[DR > 0 ? DR : 1];
-        double q0 = 0.0, q1 = 0.0;
-        bool same0 = true, same1 = true;
-        if constexpr (DR > 0) {
-#pragma unroll
-            for (int k = 0; k < DR; ++k) {
-                wd0[k] = 0.0; wd1[k] = 0.0;
-                if (k < d) {
-                    const v2d xv = *reinterpret_cast<const v2d *>(&x_s[k * AB_COLS + 2 * lane]);
-                    const double uk = u[k], wk = w[k];
-                    const double d0 = xv.x - uk, d1 = xv.y - uk;
-                    same0 = same0 && (xv.x == uk);
-                    same1 = same1 && (xv.y == uk);
-                    wd0[k] = wk * d0; wd1[k] = wk * d1;
-                    q0 = fma(wd0[k], d0, q0);
-                    q1 = fma(wd1[k], d1, q1);
-                }
-            }
-        } else {
-            for (int k = 0; k < d; ++k) {
-                const v2d xv = *reinterpret_cast<const v2d *>(&x_s[k * AB_COLS + 2 * lane]);
-                const double uk = u[k], wk = w[k];
-                const double d0 = xv.x - uk, d1 = xv.y - uk;
-                same0 = same0 && (xv.x == uk);
-                same1 = same1 && (xv.y == uk);
-                q0 = fma(wk * d0, d0, q0);
-                q1 = fma(wk * d1, d1, q1);
-            }
-        }
-        const double c0 = in0 ? v * exp(-0.5 * q0) : 0.0, c1 = in1 ? v * exp(-0.5 * q1) : 0.0;
-        v2d o;
-        o.x = (in0 && same0) ? c0 + vt : c0;
-        o.y = (in1 && same1) ? c1 + vt : c1;
-        *reinterpret_cast<v2d *>(zrow) = o;
-        // tr = c ( (w delta)^T Sigma (w delta) - sum_k w_k Sigma_kk ), full Sigma (trace_kernel) ; J_k = -w_k delta_k c
-        double s0 = 0.0, s1 = 0.0, wdiag = 0.0;
-        if constexpr (DR > 0) {
-#pragma unroll
-            for (int a = 0; a < DR; ++a) {
-                if (a < d) {
-                    if constexpr (!GRAD) {
-                        double r0 = 0.0, r1 = 0.0;
-#pragma unroll
-                        for (int e = 0; e < DR; ++e)
-                            if (e < d) {
-                                const double sg = S[a * d + e];
-                                r0 = fma(sg, wd0[e], r0);
-                                r1 = fma(sg, wd1[e], r1);
-                            }
-                        s0 = fma(wd0[a], r0, s0);
-                        s1 = fma(wd1[a], r1, s1);
-                        wdiag = fma(w[a], S[a * d + a], wdiag);
-                    }
-                    v2d jk;
-                    jk.x = -wd0[a] * c0; jk.y = -wd1[a] * c1;
-                    *reinterpret_cast<v2d *>(zrow + (long)(jrow + a) * npad) = jk;
-                }
-            }
-        } else {
-            for (int a = 0; a < d; ++a) {
-                const v2d xa = *reinterpret_cast<const v2d *>(&x_s[a * AB_COLS + 2 * lane]);
-                const double a0 = w[a] * (xa.x - u[a]), a1 = w[a] * (xa.y - u[a]);
-                if constexpr (!GRAD) {
-                    double r0 = 0.0, r1 = 0.0;
-                    for (int e = 0; e < d; ++e) {
-                        const v2d xv = *reinterpret_cast<const v2d *>(&x_s[e * AB_COLS + 2 * lane]);
-                        const double sg = S[a * d + e], ue = u[e], we = w[e];
-                        r0 = fma(sg, we * (xv.x - ue), r0);
-                        r1 = fma(sg, we * (xv.y - ue), r1);
-                    }
-                    s0 = fma(a0, r0, s0);
-                    s1 = fma(a1, r1, s1);
-                    wdiag = fma(w[a], S[a * d + a], wdiag);
-                }
-                v2d jk;
-                jk.x = -a0 * c0; jk.y = -a1 * c1;
-                *reinterpret_cast<v2d *>(zrow + (long)(jrow + a) * npad) = jk;
-            }
-        }
-        if constexpr (!GRAD) {
-            o.x = c0 * (s0 - wdiag);
-            o.y = c1 * (s1 - wdiag);
-            *reinterpret_cast<v2d *>(zrow + npad) = o;
-        }
-    }
+    rows_build_tile<DR, GRAD ? GPX_ROWS_GRAD : GPX_ROWS_APPROX>(GaussRows{v, vt}, x, n, npad, d, U, Sigma, sigma_stride, nb, w, Z);
 }
 
-// Z [rows_pad, npad]: rows [0, nb (d + 2)) written by the kernel (every column, zeros from n on), the rest of the last 128-row tile cleared
-int launch_approx_build_many(const double *x, int64_t n, int64_t npad, int d, const double *U_dev, const double *Sigma_dev,
-                             int64_t sigma_stride, int64_t nb, int64_t rows_pad, const double *w_dev, double v, double vt, double *Z,
-                             hipStream_t s, Profiler *prof)
+template <int DR>
+__global__ __launch_bounds__(256) void dvh_build_many_kernel(const double *__restrict__ x, long n, long npad, int d,
+                                                            const double *__restrict__ U, long nb, const double *__restrict__ w, double v,
+                                                            double vt, double *__restrict__ Z)
 {
-    if (nb <= 0) return 0;
-    const int64_t rows = nb * (d + 2);
-    if (npad % AB_COLS || rows > rows_pad) { gpx_set_error("approx_build_many: bad block shape"); return GPX_ERR_BAD_ARG; }
-    ProfScope ps(prof, s, GPX_K_GRAM, 8.0 * (double)rows_pad * (double)npad);
-    if (rows_pad > rows) GPX_HIP(hipMemsetAsync(Z + rows * npad, 0, sizeof(double) * (rows_pad - rows) * npad, s));
-    const dim3 grid((unsigned)(npad / AB_COLS), (unsigned)((nb + AB_INPUTS - 1) / AB_INPUTS));
-    const size_t lds = sizeof(double) * AB_COLS * d;
-    if (d <= 8)
-        hipLaunchKernelGGL(approx_build_many_kernel<8>, grid, dim3(256), lds, s, x, (long)n, (long)npad, d, U_dev, Sigma_dev,
-                           (long)sigma_stride, (long)nb, w_dev, v, vt, Z);
-    else
-        hipLaunchKernelGGL(approx_build_many_kernel<0>, grid, dim3(256), lds, s, x, (long)n, (long)npad, d, U_dev, Sigma_dev,
-                           (long)sigma_stride, (long)nb, w_dev, v, vt, Z);
-    GPX_HIP(hipGetLastError());
-    return 0;
+    rows_build_tile<DR, GPX_ROWS_DVH>(GaussRows{v, vt}, x, n, npad, d, U, nullptr, 0, nb, w, Z);
 }
 
-// the rows of gpx_predict_grad: Z [rows_pad, npad], rows [0, nb (d + 1)) = [C, J_1..J_d] per query, the rest of the last tile cleared
-int launch_grad_build_many(const double *x, int64_t n, int64_t npad, int d, const double *U_dev, int64_t nb, int64_t rows_pad, const double *w_dev,
-                           double v, double vt, double *Z, hipStream_t s, Profiler *prof)
+// this file's part of launch_rows_build's table (matern.hip's: matern_rows_kernel)
+static RowsKernel gauss_rows_kernel(int layout, bool regs)
+{
+    if (layout == GPX_ROWS_APPROX) return {regs ? approx_build_many_kernel<8, false> : approx_build_many_kernel<0, false>, nullptr};
+    if (layout == GPX_ROWS_GRAD) return {regs ? approx_build_many_kernel<8, true> : approx_build_many_kernel<0, true>, nullptr};
+    if (layout == GPX_ROWS_DVH) return {nullptr, regs ? dvh_build_many_kernel<8> : dvh_build_many_kernel<0>};
+    return {nullptr, nullptr};
+}
+
+// The ONE launcher of every build kernel.  nu2 = 0: the Gaussian kernel, 3 / 5: Matern (RadialOf's convention, radial.h; nu2 = 3 has the
+// GRAD layout alone).  Z [rows_pad, npad]: rows [0, nb rows_per_input(layout, d)) are written by the kernel (every column, zeros from n
+// on), the rest of the last 128-row tile is cleared.  Sigma is read for GPX_ROWS_APPROX alone.
+int launch_rows_build(int nu2, int layout, const double *x, int64_t n, int64_t npad, int d, const double *U_dev, const double *Sigma_dev,
+                      int64_t sigma_stride, int64_t nb, int64_t rows_pad, const double *w_dev, double v, double vt, double *Z, hipStream_t s,
+                      Profiler *prof)
 {
     if (nb <= 0) return 0;
-    const int64_t rows = nb * (d + 1);
-    if (npad % AB_COLS || rows > rows_pad || d < 1 || d > GPX_MAX_D) { gpx_set_error("grad_build_many: bad block shape"); return GPX_ERR_BAD_ARG; }
+    const int64_t rows = nb * rows_per_input(layout, d);
+    const RowsKernel k = nu2 == 0 ? gauss_rows_kernel(layout, d <= 8) : matern_rows_kernel(nu2, layout, d <= 8);   // (family, layout, d <= 8)
+    if (npad % RT_COLS || rows > rows_pad || d < 1 || d > GPX_MAX_D || (!k.with_sigma && !k.plain)) {
+        gpx_set_error("rows_build: bad block shape (nu2=%d layout=%d npad=%ld d=%d rows_pad=%ld)", nu2, layout, (long)npad, d, (long)rows_pad);
+        return GPX_ERR_BAD_ARG;
+    }
     ProfScope ps(prof, s, GPX_K_GRAM, 8.0 * (double)rows_pad * (double)npad);
     if (rows_pad > rows) GPX_HIP(hipMemsetAsync(Z + rows * npad, 0, sizeof(double) * (rows_pad - rows) * npad, s));
-    const dim3 grid((unsigned)(npad / AB_COLS), (unsigned)((nb + AB_INPUTS - 1) / AB_INPUTS));
-    const size_t lds = sizeof(double) * AB_COLS * d;
-    if (d <= 8)
-        hipLaunchKernelGGL((approx_build_many_kernel<8, true>), grid, dim3(256), lds, s, x, (long)n, (long)npad, d, U_dev, (const double *)nullptr, 0L,
-                           (long)nb, w_dev, v, vt, Z);
+    const dim3 grid((unsigned)(npad / RT_COLS), (unsigned)((nb + RT_INPUTS - 1) / RT_INPUTS));
+    const size_t lds = sizeof(double) * RT_COLS * d;
+    if (k.with_sigma)
+        hipLaunchKernelGGL(k.with_sigma, grid, dim3(256), lds, s, x, (long)n, (long)npad, d, U_dev, Sigma_dev, (long)sigma_stride, (long)nb, w_dev, v, vt, Z);
     else
-        hipLaunchKernelGGL((approx_build_many_kernel<0, true>), grid, dim3(256), lds, s, x, (long)n, (long)npad, d, U_dev, (const double *)nullptr, 0L,
-                           (long)nb, w_dev, v, vt, Z);
+        hipLaunchKernelGGL(k.plain, grid, dim3(256), lds, s, x, (long)n, (long)npad, d, U_dev, (long)nb, w_dev, v, vt, Z);
     GPX_HIP(hipGetLastError());
     return 0;
 }
@@ -393,118 +283,6 @@ int launch_approx_reduce_many_pair(const double *R, const double *Y, int64_t npa
     ProfScope ps(prof, s, GPX_K_REDUCE, 16.0 * (double)nb * (double)(d + 2) * (double)npad);
     hipLaunchKernelGGL(approx_reduce_pair_kernel, dim3((unsigned)nb), dim3(256), 0, s, R, Y, (long)npad, d, alpha, Sigma_dev,
                        (long)sigma_stride, vplusvt, out, (long)ldo);
-    GPX_HIP(hipGetLastError());
-    return 0;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Batched inverse propagation (gpx_propagate_dvh_many): the 2 d + 1 vectors of MANY inputs as right-hand sides of the same solver.
-// Row b (2 d + 1) + r of Z (leading dimension npad):
-//   r = 0: C_i (+vt iff x_i == u_b elementwise)   r = 1 + k: J_ik = -w_k delta_k c_i   r = 1 + d + k: H_i,kk = ((w_k delta_k)^2 - w_k) c_i
-// (the arithmetic of approx_build_kernel).  The structure is approx_build_many_kernel's: 128 columns of x k-major in LDS, AB_INPUTS
-// inputs per workgroup, four per wave, u and w wave-uniform, 16-byte stores, one exp per (input, column); there is no Sigma.
-// DR > 0: d <= DR, the scaled differences stay in registers; DR = 0: any d, recomputed from the LDS tile.
-// ---------------------------------------------------------------------------------------------
-template <int DR>
-__global__ __launch_bounds__(256) void dvh_build_many_kernel(const double *__restrict__ x, long n, long npad, int d,
-                                                            const double *__restrict__ U, long nb, const double *__restrict__ w, double v,
-                                                            double vt, double *__restrict__ Z)
-{
-    extern __shared__ __attribute__((aligned(16))) double ab_smem[];
-    double *x_s = ab_smem;   // [d][128] raw inputs of the tile's columns, k-major
-    const int t = threadIdx.x;
-    const long col0 = (long)blockIdx.x * AB_COLS;
-    for (int e = t; e < AB_COLS * d; e += 256) {
-        const int c = e & (AB_COLS - 1), k = e >> 7;
-        const long gc = col0 + c;
-        x_s[k * AB_COLS + c] = (gc < n) ? x[gc * d + k] : 0.0;
-    }
-    __syncthreads();
-    const int wave = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
-    const long c = col0 + 2 * lane;
-    const bool in0 = c < n, in1 = c + 1 < n;
-    const long nrow = 2 * d + 1;
-    for (int j = 0; j < AB_INPUTS / 4; ++j) {
-        const long b = (long)blockIdx.y * AB_INPUTS + 4 * j + wave;   // wave-uniform
-        if (b >= nb) break;
-        const double *u = U + b * d;
-        double *zrow = Z + b * nrow * npad + c;
-        double wd0[DR > 0 ? DR : 1], wd1[DR > 0 ? DR : 1];
-        double q0 = 0.0, q1 = 0.0;
-        bool same0 = true, same1 = true;
-        if constexpr (DR > 0) {
-#pragma unroll
-            for (int k = 0; k < DR; ++k) {
-                wd0[k] = 0.0; wd1[k] = 0.0;
-                if (k < d) {
-                    const v2d xv = *reinterpret_cast<const v2d *>(&x_s[k * AB_COLS + 2 * lane]);
-                    const double uk = u[k], wk = w[k];
-                    const double d0 = xv.x - uk, d1 = xv.y - uk;
-                    same0 = same0 && (xv.x == uk);
-                    same1 = same1 && (xv.y == uk);
-                    wd0[k] = wk * d0; wd1[k] = wk * d1;
-                    q0 = fma(wd0[k], d0, q0);
-                    q1 = fma(wd1[k], d1, q1);
-                }
-            }
-        } else {
-            for (int k = 0; k < d; ++k) {
-                const v2d xv = *reinterpret_cast<const v2d *>(&x_s[k * AB_COLS + 2 * lane]);
-                const double uk = u[k], wk = w[k];
-                const double d0 = xv.x - uk, d1 = xv.y - uk;
-                same0 = same0 && (xv.x == uk);
-                same1 = same1 && (xv.y == uk);
-                q0 = fma(wk * d0, d0, q0);
-                q1 = fma(wk * d1, d1, q1);
-            }
-        }
-        const double c0 = in0 ? v * exp(-0.5 * q0) : 0.0, c1 = in1 ? v * exp(-0.5 * q1) : 0.0;
-        v2d o;
-        o.x = (in0 && same0) ? c0 + vt : c0;
-        o.y = (in1 && same1) ? c1 + vt : c1;
-        *reinterpret_cast<v2d *>(zrow) = o;
-        if constexpr (DR > 0) {
-#pragma unroll
-            for (int a = 0; a < DR; ++a) {
-                if (a < d) {
-                    const double wa = w[a];
-                    v2d jk, hk;
-                    jk.x = -wd0[a] * c0; jk.y = -wd1[a] * c1;
-                    hk.x = (wd0[a] * wd0[a] - wa) * c0; hk.y = (wd1[a] * wd1[a] - wa) * c1;
-                    *reinterpret_cast<v2d *>(zrow + (long)(1 + a) * npad) = jk;
-                    *reinterpret_cast<v2d *>(zrow + (long)(1 + d + a) * npad) = hk;
-                }
-            }
-        } else {
-            for (int a = 0; a < d; ++a) {
-                const v2d xa = *reinterpret_cast<const v2d *>(&x_s[a * AB_COLS + 2 * lane]);
-                const double wa = w[a], ua = u[a];
-                const double a0 = wa * (xa.x - ua), a1 = wa * (xa.y - ua);
-                v2d jk, hk;
-                jk.x = -a0 * c0; jk.y = -a1 * c1;
-                hk.x = (a0 * a0 - wa) * c0; hk.y = (a1 * a1 - wa) * c1;
-                *reinterpret_cast<v2d *>(zrow + (long)(1 + a) * npad) = jk;
-                *reinterpret_cast<v2d *>(zrow + (long)(1 + d + a) * npad) = hk;
-            }
-        }
-    }
-}
-
-// Z [rows_pad, npad]: rows [0, nb (2 d + 1)) written by the kernel (every column, zeros from n on), the rest of the last 128-row tile cleared
-int launch_dvh_build_many(const double *x, int64_t n, int64_t npad, int d, const double *U_dev, int64_t nb, int64_t rows_pad,
-                          const double *w_dev, double v, double vt, double *Z, hipStream_t s, Profiler *prof)
-{
-    if (nb <= 0) return 0;
-    const int64_t rows = nb * (2 * d + 1);
-    if (npad % AB_COLS || rows > rows_pad || d < 1 || d > GPX_MAX_D) { gpx_set_error("dvh_build_many: bad block shape"); return GPX_ERR_BAD_ARG; }
-    ProfScope ps(prof, s, GPX_K_GRAM, 8.0 * (double)rows_pad * (double)npad);
-    if (rows_pad > rows) GPX_HIP(hipMemsetAsync(Z + rows * npad, 0, sizeof(double) * (rows_pad - rows) * npad, s));
-    const dim3 grid((unsigned)(npad / AB_COLS), (unsigned)((nb + AB_INPUTS - 1) / AB_INPUTS));
-    const size_t lds = sizeof(double) * AB_COLS * d;
-    if (d <= 8)
-        hipLaunchKernelGGL(dvh_build_many_kernel<8>, grid, dim3(256), lds, s, x, (long)n, (long)npad, d, U_dev, (long)nb, w_dev, v, vt, Z);
-    else
-        hipLaunchKernelGGL(dvh_build_many_kernel<0>, grid, dim3(256), lds, s, x, (long)n, (long)npad, d, U_dev, (long)nb, w_dev, v, vt, Z);
     GPX_HIP(hipGetLastError());
     return 0;
 }

@@ -165,10 +165,6 @@ extern "C" int gpx_propagate_approx(gpx_handle *h, const double *u, const double
     return 0;
 }
 
-// Batched Approx: b inputs as b (d + 2) right-hand sides [C, tr, J_1..J_d] of the many-right-hand-side solver that serves
-// gpx_predict.  With K = L L^T, y = L^-1 t and z_v = L^-1 v every sum of gpx_propagate_approx is a row product of the solved block:
-// beta.v = z_v.y, v.Kinv v = |z_v|^2, tr.Kinv C = z_tr.z_C.  No K^-1, no use of the handle's single-u cache, one synchronisation
-// per chunk; an input never straddles two chunks.
 // The batched row calls on a model held as K^-1 (a pseudo-input model: no factor to solve against): the chunk's rows R are built into h->Z as
 // for the solve, then Y = R K^-1 is ONE fp64 product per chunk (K^-1 symmetric, so R Kinv^T of launch_gemm_nt is it) and the row reductions
 // run in their pair form on (R, Y, alpha).  Chunks are cut as row_solve_begin cuts them; an element of Y is one contraction over npad in the
@@ -191,100 +187,86 @@ static int pair_rows_product(gpx_handle *h, const PairRows &pr, int64_t mp)
     return launch_gemm_nt(h->Z, h->npad, h->Kinv, h->npad, pr.Y, h->npad, mp, h->npad, h->npad, 1.0, 0.0, 0, h->stream, &h->prof);
 }
 
-static int approx_many_run_pair(gpx_handle *h, int d, const double *U, const double *Sigma, int sigma_shared, int64_t b, double *mean, double *var,
-                                double *sigma2, double *rest, const RowsBuild &build)
+// ---- the ONE chunk loop of the five batched row calls ------------------------------------------------------------------------------------
+// What a layout's reduction leaves in the chunk's device block od and where it goes: part i is `per` doubles an input from od + off bchunk,
+// copied to host + b0 per (host null: not wanted; required: the call refuses a null one).
+constexpr int ROWS_OUTS = 4;
+struct RowsOut { double *host; int64_t off, per; bool required; };
+
+constexpr int GRAD_OUT_DMEAN = 2;   // the part of the GRAD outputs that may be left out
+
+// the row reduction of a chunk's bc inputs into od: on the solved block Zs with y = L^-1 t (a factor handle), or in the pair form on
+// (R = h->Z, Y, alpha) (a K^-1 handle)
+static int rows_reduce(gpx_handle *h, int layout, int d, const double *Zs, const double *Y, const double *sd, int64_t sstride, int64_t bc, double *od,
+                       int64_t bchunk, const RowsOut (&outs)[ROWS_OUTS])
 {
     hipStream_t s = h->stream;
-    const int nrow = d + 2;
+    const double kuu = h->v + h->vt;
+    if (layout == GPX_ROWS_DVH)   // dvh [bchunk, d] | sigma2 [bchunk]
+        return launch_dvh_reduce_many(Zs, h->npad, d, h->y, bc, kuu, od, od + bchunk * d, s, &h->prof);
+    if (layout == GPX_ROWS_APPROX) {   // mean | var | sigma2 | rest, [bchunk] each
+        if (Y) return launch_approx_reduce_many_pair(h->Z, Y, h->npad, d, h->alpha, sd, sstride, bc, kuu, od, bchunk, s, &h->prof);
+        return launch_approx_reduce_many(Zs, h->npad, d, h->y, sd, sstride, bc, kuu, od, bchunk, s, &h->prof);
+    }
+    double *vd = od + bchunk, *dmd = outs[GRAD_OUT_DMEAN].host ? vd + bchunk : nullptr, *dvd = vd + bchunk + bchunk * d;   // mean | var | dmean [, d] | dvar [, d]
+    if (Y) return launch_grad_reduce_many_pair(h->Z, Y, h->npad, d, h->alpha, bc, kuu, od, vd, dmd, dvd, s, &h->prof);
+    return launch_grad_reduce_many(Zs, h->npad, d, h->y, bc, kuu, od, vd, dmd, dvd, s, &h->prof);
+}
+
+// b inputs as b rows_per_input(layout, d) right-hand sides: per chunk stage U (and Sigma: APPROX alone), build, solve (a factor handle) or
+// multiply by K^-1 (h->no_factor), reduce, copy out; one synchronisation per chunk, an input never straddles two chunks.  Scratch goes back
+// with the RowSolve / PairRows on every path.
+static int rows_many_run(gpx_handle *h, int layout, int d, const double *U, const double *Sigma, int sigma_shared, int64_t b,
+                         const RowsOut (&outs)[ROWS_OUTS], const char *what, const RowsBuild &build)
+{
+    const bool approx = layout == GPX_ROWS_APPROX, pair = h->no_factor;
+    bool missing = !U || (approx && !Sigma);
+    int64_t nout = 0;
+    for (const RowsOut &o : outs) {
+        missing = missing || (o.required && !o.host);
+        nout = std::max(nout, o.off + o.per);
+    }
+    if (b < 0 || (b > 0 && missing)) { gpx_set_error("%s: bad arguments", what); return GPX_ERR_BAD_ARG; }
+    if (b == 0) return 0;
+    assert(!(pair && layout == GPX_ROWS_DVH));   // no pair form of the DVH reduction: its entry points refuse such a handle (CHECK_H)
+    hipStream_t s = h->stream;
+    const int nrow = rows_per_input(layout, d);
+    RowSolve rs(s);
     PairRows pr(s);
-    GPX_TRY(pair_rows_begin(h, b * nrow, pr));
-    const int64_t bchunk = pr.chunk / nrow;           // inputs per chunk (chunk >= 128 > d + 2)
-    const int64_t nsig = sigma_shared ? 1 : bchunk, sstride = sigma_shared ? 0 : (int64_t)d * d;
+    if (pair) GPX_TRY(pair_rows_begin(h, b * nrow, pr));
+    else GPX_TRY(row_solve_begin(h, b * nrow, rs));
+    Scratch &sc = pair ? pr.sc : rs.sc;
+    const int64_t chunk = pair ? pr.chunk : rs.chunk, bchunk = chunk / nrow;   // inputs per chunk
+    if (bchunk < 1) { gpx_set_error("%s: a chunk of %ld rows holds no input of %d rows", what, (long)chunk, nrow); return GPX_ERR_STATE; }
+    const int64_t d2 = (int64_t)d * d, sstride = sigma_shared ? 0 : d2;
     double *ud = nullptr, *sd = nullptr, *od = nullptr;
-    GPX_TRY(pr.sc.take(&ud, bchunk * d));
-    GPX_TRY(pr.sc.take(&sd, nsig * d * d));
-    GPX_TRY(pr.sc.take(&od, 4 * bchunk));
-    if (sigma_shared) GPX_HIP(hipMemcpyAsync(sd, Sigma, sizeof(double) * d * d, hipMemcpyDefault, s));
+    GPX_TRY(sc.take(&ud, bchunk * d));
+    if (approx) GPX_TRY(sc.take(&sd, (sigma_shared ? 1 : bchunk) * d2));
+    GPX_TRY(sc.take(&od, nout * bchunk));
+    if (approx && sigma_shared) GPX_HIP(hipMemcpyAsync(sd, Sigma, sizeof(double) * d2, hipMemcpyDefault, s));
     for (int64_t b0 = 0; b0 < b; b0 += bchunk) {
-        const int64_t bc = std::min<int64_t>(bchunk, b - b0), mp = round_up(bc * nrow, TILE);
+        const int64_t bc = std::min<int64_t>(bchunk, b - b0), mc = bc * nrow, mp = round_up(mc, TILE);
         GPX_HIP(hipMemcpyAsync(ud, U + b0 * d, sizeof(double) * bc * d, hipMemcpyDefault, s));
-        if (!sigma_shared) GPX_HIP(hipMemcpyAsync(sd, Sigma + b0 * d * d, sizeof(double) * bc * d * d, hipMemcpyDefault, s));
+        if (approx && !sigma_shared) GPX_HIP(hipMemcpyAsync(sd, Sigma + b0 * d2, sizeof(double) * bc * d2, hipMemcpyDefault, s));
         GPX_TRY(build(ud, sd, sstride, bc, mp));
-        GPX_TRY(pair_rows_product(h, pr, mp));
-        GPX_TRY(launch_approx_reduce_many_pair(h->Z, pr.Y, h->npad, d, h->alpha, sd, sstride, bc, h->v + h->vt, od, bchunk, s, &h->prof));
-        GPX_HIP(hipMemcpyAsync(mean + b0, od, sizeof(double) * bc, hipMemcpyDefault, s));
-        GPX_HIP(hipMemcpyAsync(var + b0, od + bchunk, sizeof(double) * bc, hipMemcpyDefault, s));
-        if (sigma2) GPX_HIP(hipMemcpyAsync(sigma2 + b0, od + 2 * bchunk, sizeof(double) * bc, hipMemcpyDefault, s));
-        if (rest) GPX_HIP(hipMemcpyAsync(rest + b0, od + 3 * bchunk, sizeof(double) * bc, hipMemcpyDefault, s));
+        if (pair) GPX_TRY(pair_rows_product(h, pr, mp));
+        else GPX_TRY(row_solve_run(h, rs, mc, mp, nullptr));
+        GPX_TRY(rows_reduce(h, layout, d, rs.Zs, pair ? pr.Y : nullptr, sd, sstride, bc, od, bchunk, outs));
+        for (const RowsOut &o : outs)
+            if (o.host) GPX_HIP(hipMemcpyAsync(o.host + b0 * o.per, od + o.off * bchunk, sizeof(double) * bc * o.per, hipMemcpyDefault, s));
         GPX_HIP(hipStreamSynchronize(s));             // the chunk's one synchronisation
     }
     return 0;
 }
 
-static int grad_many_run_pair(gpx_handle *h, int d, const double *U, int64_t b, double *mean, double *var, double *dmean, double *dvar,
-                              const RowsBuild &build)
-{
-    hipStream_t s = h->stream;
-    const int nrow = d + 1;
-    PairRows pr(s);
-    GPX_TRY(pair_rows_begin(h, b * nrow, pr));
-    const int64_t bchunk = pr.chunk / nrow;           // queries per chunk (chunk >= 128 > d + 1)
-    double *ud = nullptr, *od = nullptr;
-    GPX_TRY(pr.sc.take(&ud, bchunk * d));
-    GPX_TRY(pr.sc.take(&od, bchunk * (2 + 2 * d)));   // mean [bchunk] | var [bchunk] | dmean [bchunk, d] | dvar [bchunk, d]
-    double *vd = od + bchunk, *dmd = vd + bchunk, *dvd = dmd + bchunk * d;
-    for (int64_t b0 = 0; b0 < b; b0 += bchunk) {
-        const int64_t bc = std::min<int64_t>(bchunk, b - b0), mp = round_up(bc * nrow, TILE);
-        GPX_HIP(hipMemcpyAsync(ud, U + b0 * d, sizeof(double) * bc * d, hipMemcpyDefault, s));
-        GPX_TRY(build(ud, nullptr, 0, bc, mp));
-        GPX_TRY(pair_rows_product(h, pr, mp));
-        GPX_TRY(launch_grad_reduce_many_pair(h->Z, pr.Y, h->npad, d, h->alpha, bc, h->v + h->vt, od, vd, dmean ? dmd : nullptr, dvd, s, &h->prof));
-        GPX_HIP(hipMemcpyAsync(mean + b0, od, sizeof(double) * bc, hipMemcpyDefault, s));
-        GPX_HIP(hipMemcpyAsync(var + b0, vd, sizeof(double) * bc, hipMemcpyDefault, s));
-        if (dmean) GPX_HIP(hipMemcpyAsync(dmean + b0 * d, dmd, sizeof(double) * bc * d, hipMemcpyDefault, s));
-        GPX_HIP(hipMemcpyAsync(dvar + b0 * d, dvd, sizeof(double) * bc * d, hipMemcpyDefault, s));
-        GPX_HIP(hipStreamSynchronize(s));             // the chunk's one synchronisation
-    }
-    return 0;
-}
-
+// Batched Approx: b inputs as b (d + 2) right-hand sides [C, tr, J_1..J_d] of the many-right-hand-side solver that serves gpx_predict.  With
+// K = L L^T, y = L^-1 t and z_v = L^-1 v every sum of gpx_propagate_approx is a row product of the solved block: beta.v = z_v.y,
+// v.Kinv v = |z_v|^2, tr.Kinv C = z_tr.z_C.  No K^-1, no use of the handle's single-u cache.
 int approx_many_run(gpx_handle *h, int d, const double *U, const double *Sigma, int sigma_shared, int64_t b, double *mean, double *var, double *sigma2,
                     double *rest, const char *what, const RowsBuild &build)
 {
-    if (b < 0 || (b > 0 && (!U || !Sigma || !mean || !var))) { gpx_set_error("%s: bad arguments", what); return GPX_ERR_BAD_ARG; }
-    if (b == 0) return 0;
-    if (h->no_factor) return approx_many_run_pair(h, d, U, Sigma, sigma_shared, b, mean, var, sigma2, rest, build);
-    hipStream_t s = h->stream;
-    const int nrow = d + 2;
-    RowSolve rs(s);
-    GPX_TRY(row_solve_begin(h, b * nrow, rs));
-    const int64_t bchunk = rs.chunk / nrow;           // inputs per chunk (chunk >= 128 > d + 2)
-    const int64_t nsig = sigma_shared ? 1 : bchunk;
-    double *ud = nullptr, *sd = nullptr, *od = nullptr;
-    int rc = 0;
-    GPX_TRY(rs.sc.take(&ud, bchunk * d));
-    GPX_TRY(rs.sc.take(&sd, nsig * d * d));
-    GPX_TRY(rs.sc.take(&od, 4 * bchunk));
-    hipError_t e = hipSuccess;
-    if (sigma_shared) e = hipMemcpyAsync(sd, Sigma, sizeof(double) * d * d, hipMemcpyDefault, s);
-    if (e != hipSuccess) { gpx_set_error("copy Sigma failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; }
-    const int64_t sstride = sigma_shared ? 0 : (int64_t)d * d;
-    for (int64_t b0 = 0; b0 < b && rc == 0; b0 += bchunk) {
-        const int64_t bc = std::min<int64_t>(bchunk, b - b0), mc = bc * nrow, mp = round_up(mc, TILE);
-        e = hipMemcpyAsync(ud, U + b0 * d, sizeof(double) * bc * d, hipMemcpyDefault, s);
-        if (e == hipSuccess && !sigma_shared) e = hipMemcpyAsync(sd, Sigma + b0 * d * d, sizeof(double) * bc * d * d, hipMemcpyDefault, s);
-        if (e != hipSuccess) { gpx_set_error("copy U / Sigma failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
-        if ((rc = build(ud, sd, sstride, bc, mp))) break;
-        if ((rc = row_solve_run(h, rs, mc, mp, nullptr))) break;
-        if ((rc = launch_approx_reduce_many(rs.Zs, h->npad, d, h->y, sd, sstride, bc, h->v + h->vt, od, bchunk, s, &h->prof))) break;
-        e = hipMemcpyAsync(mean + b0, od, sizeof(double) * bc, hipMemcpyDefault, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(var + b0, od + bchunk, sizeof(double) * bc, hipMemcpyDefault, s);
-        if (e == hipSuccess && sigma2) e = hipMemcpyAsync(sigma2 + b0, od + 2 * bchunk, sizeof(double) * bc, hipMemcpyDefault, s);
-        if (e == hipSuccess && rest) e = hipMemcpyAsync(rest + b0, od + 3 * bchunk, sizeof(double) * bc, hipMemcpyDefault, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { gpx_set_error("propagate copy-out failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
-    }
-    return rc;
+    const RowsOut outs[ROWS_OUTS] = {{mean, 0, 1, true}, {var, 1, 1, true}, {sigma2, 2, 1, false}, {rest, 3, 1, false}};
+    return rows_many_run(h, GPX_ROWS_APPROX, d, U, Sigma, sigma_shared, b, outs, what, build);
 }
 
 extern "C" int gpx_propagate_approx_many(gpx_handle *h, const double *U, const double *Sigma, int sigma_shared, int64_t b,
@@ -403,35 +385,11 @@ extern "C" int gpx_propagate_dvh(gpx_handle *h, const double *u, double *dvh_out
 // Batched inverse propagation: b inputs as b (2 d + 1) right-hand sides [C, J_1..J_d, H_11..H_dd] of the many-right-hand-side solver, the
 // loop of gpx_propagate_approx_many.  With y = L^-1 t and z_v = L^-1 v the three sums of gpx_propagate_dvh are row products of the solved
 // block: J_k.Kinv J_k = |z_Jk|^2, beta.J_k = z_Jk.y, (Kinv C).H_kk = z_C.z_Hkk; sigma2 = (v + vt) - |z_C|^2.  No K^-1, no use of the handle's
-// single-u cache (have_u, V, KV), one synchronisation per chunk; an input never straddles two chunks.
+// single-u cache (have_u, V, KV).
 int dvh_many_run(gpx_handle *h, int d, const double *U, int64_t b, double *dvh_out, double *sigma2_out, const char *what, const RowsBuild &build)
 {
-    if (b < 0 || (b > 0 && (!U || !dvh_out))) { gpx_set_error("%s: bad arguments", what); return GPX_ERR_BAD_ARG; }
-    if (b == 0) return 0;
-    hipStream_t s = h->stream;
-    const int nrow = 2 * d + 1;
-    RowSolve rs(s);
-    GPX_TRY(row_solve_begin(h, b * nrow, rs));
-    const int64_t bchunk = rs.chunk / nrow;           // inputs per chunk
-    if (bchunk < 1) { gpx_set_error("%s: a chunk of %ld rows holds no input of %d rows", what, (long)rs.chunk, nrow); return GPX_ERR_STATE; }
-    double *ud = nullptr, *od = nullptr;
-    int rc = 0;
-    GPX_TRY(rs.sc.take(&ud, bchunk * d));
-    GPX_TRY(rs.sc.take(&od, bchunk * (d + 1)));       // dvh [bchunk, d] | sigma2 [bchunk]
-    double *s2d = od + bchunk * d;
-    for (int64_t b0 = 0; b0 < b && rc == 0; b0 += bchunk) {
-        const int64_t bc = std::min<int64_t>(bchunk, b - b0), mc = bc * nrow, mp = round_up(mc, TILE);
-        hipError_t e = hipMemcpyAsync(ud, U + b0 * d, sizeof(double) * bc * d, hipMemcpyDefault, s);
-        if (e != hipSuccess) { gpx_set_error("copy U failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
-        if ((rc = build(ud, nullptr, 0, bc, mp))) break;
-        if ((rc = row_solve_run(h, rs, mc, mp, nullptr))) break;
-        if ((rc = launch_dvh_reduce_many(rs.Zs, h->npad, d, h->y, bc, h->v + h->vt, od, s2d, s, &h->prof))) break;
-        e = hipMemcpyAsync(dvh_out + b0 * d, od, sizeof(double) * bc * d, hipMemcpyDefault, s);
-        if (e == hipSuccess && sigma2_out) e = hipMemcpyAsync(sigma2_out + b0, s2d, sizeof(double) * bc, hipMemcpyDefault, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { gpx_set_error("propagate copy-out failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
-    }
-    return rc;
+    const RowsOut outs[ROWS_OUTS] = {{dvh_out, 0, d, true}, {sigma2_out, d, 1, false}, {nullptr, 0, 0, false}, {nullptr, 0, 0, false}};
+    return rows_many_run(h, GPX_ROWS_DVH, d, U, nullptr, 0, b, outs, what, build);
 }
 
 extern "C" int gpx_propagate_dvh_many(gpx_handle *h, const double *U, int64_t b, double *dvh_out, double *sigma2_out)
@@ -443,39 +401,12 @@ extern "C" int gpx_propagate_dvh_many(gpx_handle *h, const double *U, int64_t b,
 
 // ---- the predictor's input gradients (kernels: predict_grad.hip) -----------------------------------------------------------------------
 // b queries as b (d + 1) right-hand sides [C, J_1..J_d] of the many-right-hand-side solver, the loop of gpx_propagate_approx_many with one row
-// fewer: mean = z_C.y, var = (v + vt) - |z_C|^2, dmean_k = -z_Jk.y, dvar_k = 2 z_C.z_Jk.  One synchronisation per chunk; a query never
-// straddles two chunks.
+// fewer: mean = z_C.y, var = (v + vt) - |z_C|^2, dmean_k = -z_Jk.y, dvar_k = 2 z_C.z_Jk.
 int grad_many_run(gpx_handle *h, int d, const double *U, int64_t b, double *mean, double *var, double *dmean, double *dvar, const char *what,
                   const RowsBuild &build)
 {
-    if (b < 0 || (b > 0 && (!U || !mean || !var || !dvar))) { gpx_set_error("%s: bad arguments", what); return GPX_ERR_BAD_ARG; }
-    if (b == 0) return 0;
-    if (h->no_factor) return grad_many_run_pair(h, d, U, b, mean, var, dmean, dvar, build);
-    hipStream_t s = h->stream;
-    const int nrow = d + 1;
-    RowSolve rs(s);
-    GPX_TRY(row_solve_begin(h, b * nrow, rs));
-    const int64_t bchunk = rs.chunk / nrow;           // queries per chunk (chunk >= 128 > d + 1)
-    double *ud = nullptr, *od = nullptr;
-    int rc = 0;
-    GPX_TRY(rs.sc.take(&ud, bchunk * d));
-    GPX_TRY(rs.sc.take(&od, bchunk * (2 + 2 * d)));   // mean [bchunk] | var [bchunk] | dmean [bchunk, d] | dvar [bchunk, d]
-    double *vd = od + bchunk, *dmd = vd + bchunk, *dvd = dmd + bchunk * d;
-    for (int64_t b0 = 0; b0 < b && rc == 0; b0 += bchunk) {
-        const int64_t bc = std::min<int64_t>(bchunk, b - b0), mc = bc * nrow, mp = round_up(mc, TILE);
-        hipError_t e = hipMemcpyAsync(ud, U + b0 * d, sizeof(double) * bc * d, hipMemcpyDefault, s);
-        if (e != hipSuccess) { gpx_set_error("copy xs failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
-        if ((rc = build(ud, nullptr, 0, bc, mp))) break;
-        if ((rc = row_solve_run(h, rs, mc, mp, nullptr))) break;
-        if ((rc = launch_grad_reduce_many(rs.Zs, h->npad, d, h->y, bc, h->v + h->vt, od, vd, dmean ? dmd : nullptr, dvd, s, &h->prof))) break;
-        e = hipMemcpyAsync(mean + b0, od, sizeof(double) * bc, hipMemcpyDefault, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(var + b0, vd, sizeof(double) * bc, hipMemcpyDefault, s);
-        if (e == hipSuccess && dmean) e = hipMemcpyAsync(dmean + b0 * d, dmd, sizeof(double) * bc * d, hipMemcpyDefault, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(dvar + b0 * d, dvd, sizeof(double) * bc * d, hipMemcpyDefault, s);
-        if (e == hipSuccess) e = hipStreamSynchronize(s);
-        if (e != hipSuccess) { gpx_set_error("gradient copy-out failed: %s", hipGetErrorString(e)); rc = GPX_ERR_HIP; break; }
-    }
-    return rc;
+    const RowsOut outs[ROWS_OUTS] = {{mean, 0, 1, true}, {var, 1, 1, true}, {dmean, 2, d, false}, {dvar, 2 + d, d, true}};
+    return rows_many_run(h, GPX_ROWS_GRAD, d, U, nullptr, 0, b, outs, what, build);
 }
 
 // The value differentiated is the handle's own predictor.  gpx_matern_predict's cross-covariance rows carry +vt where a query equals a training
@@ -532,34 +463,18 @@ extern "C" int gpx_predict_grad(gpx_handle *h, const double *xs, int64_t m, doub
 }
 
 // ---- the build of every batched call, and the two stages alone (test / tool access) ----------------------------------------------------
-// Each lambda writes the rows of bc inputs into h->Z [mp, npad] on the handle's stream; h->Z is read when the build runs (the chunk loop
-// has sized it by then).  Sigma reaches the APPROX layout alone.
+// The lambda writes the rows of bc inputs into h->Z [mp, npad] on the handle's stream; h->Z is read when the build runs (the chunk loop
+// has sized it by then).  Sigma reaches the APPROX layout alone.  A Gaussian handle builds its GRAD C row with grad_row_vt.
 RowsBuild rows_build_of(gpx_handle *h, int layout)
 {
-    if (h->kind == KernelKind::Matern)
-        return [h, layout](const double *ud, const double *sd, int64_t sstride, int64_t bc, int64_t mp) -> int {
-            const MaternData *md = handle_matern(h);
-            const bool tr = layout == GPX_ROWS_APPROX;
-            return launch_matern_build_many(layout, md->nu2, md->x, h->n, h->npad, md->d, ud, tr ? sd : nullptr, tr ? sstride : 0, bc, mp, md->par, md->v,
-                                            md->vt, h->Z, h->stream, &h->prof);
-        };
-    switch (layout) {
-    case GPX_ROWS_APPROX:
-        return [h](const double *ud, const double *sd, int64_t sstride, int64_t bc, int64_t mp) -> int {
-            return launch_approx_build_many(h->x, h->n, h->npad, h->d, ud, sd, sstride, bc, mp, h->wdev, h->v, handle_vt_on_equal(h), h->Z, h->stream, &h->prof);
-        };
-    case GPX_ROWS_DVH:
-        return [h](const double *ud, const double *, int64_t, int64_t bc, int64_t mp) -> int {
-            return launch_dvh_build_many(h->x, h->n, h->npad, h->d, ud, bc, mp, h->wdev, h->v, handle_vt_on_equal(h), h->Z, h->stream, &h->prof);
-        };
-    default:
-        return [h](const double *ud, const double *, int64_t, int64_t bc, int64_t mp) -> int {
-            return launch_grad_build_many(h->x, h->n, h->npad, h->d, ud, bc, mp, h->wdev, h->v, grad_row_vt(h), h->Z, h->stream, &h->prof);
-        };
-    }
+    return [h, layout](const double *ud, const double *sd, int64_t sstride, int64_t bc, int64_t mp) -> int {
+        const bool tr = layout == GPX_ROWS_APPROX, matern = h->kind == KernelKind::Matern;
+        const MaternData *md = matern ? handle_matern(h) : nullptr;
+        const double vt = matern ? md->vt : layout == GPX_ROWS_GRAD ? grad_row_vt(h) : handle_vt_on_equal(h);
+        return launch_rows_build(matern ? md->nu2 : 0, layout, matern ? md->x : h->x, h->n, h->npad, matern ? md->d : h->d, ud, tr ? sd : nullptr,
+                                 tr ? sstride : 0, bc, mp, matern ? md->par : h->wdev, matern ? md->v : h->v, vt, h->Z, h->stream, &h->prof);
+    };
 }
-
-static inline int rows_per_input(int layout, int d) { return layout == GPX_ROWS_DVH ? 2 * d + 1 : layout == GPX_ROWS_APPROX ? d + 2 : d + 1; }
 
 extern "C" int gpx_rows_build(gpx_handle *h, int layout, const double *U, const double *Sigma, int sigma_shared, int64_t b, double *rows_out)
 {

@@ -1,5 +1,5 @@
 // radial.h -- the radial factors of the stationary ARD kernels at q = sum_k w_k delta_k^2, one copy for every kernel that needs them
-// (matern.hip: Gram, likelihood gradient, right-hand-side blocks; predict_grad.hip: the predictor's input gradient).
+// (matern.hip: Gram, likelihood gradient; rows_tile.h: the right-hand-side blocks; predict_grad.hip: the predictor's input gradient).
 //   kf(): the noise-free kernel      g(): d kf / d delta_k = -w_k delta_k g()
 #pragma once
 #include "common.h"
@@ -13,7 +13,7 @@ struct MaternRadial {
     __device__ __forceinline__ double g() const { return NU2 == 5 ? (5.0 / 3.0) * e * (1.0 + s) : 3.0 * e; }
 };
 
-// the Gaussian kernel in the same shape: c = v exp(-q / 2) is its own g (the arithmetic of approx_build_many_kernel, propagate.hip)
+// the Gaussian kernel in the same shape: c = v exp(-q / 2) is its own g (GaussRows of rows_tile.h forms its one factor through it)
 struct GaussRadial {
     double e;
     __device__ __forceinline__ GaussRadial(double v, double q) : e(v * exp(-0.5 * q)) {}

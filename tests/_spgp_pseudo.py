@@ -17,8 +17,8 @@ import numpy as np
 import _dense_ld as dl
 
 # name: (N, d, m) -- A: two 128-tiles of pseudo-inputs, ragged; B: one tile; C: d > 8 (the other instantiation of every builder and
-# reduction), m just over one tile
-MODELS = {"A": (700, 3, 150), "B": (300, 2, 30), "C": (400, 9, 130)}
+# reduction), m just over one tile; D: one tile at d = 8, the model of the chunk-seam test (a chunk of 32768 rows is cheap at npad = 128)
+MODELS = {"A": (700, 3, 150), "B": (300, 2, 30), "C": (400, 9, 130), "D": (300, 8, 100)}
 NQ = 77                     # queries / inputs of the large batch: 77 (d + 2) and 77 (d + 1) are no multiples of 128 for d = 2, 3, 9
 
 

@@ -11,7 +11,8 @@ also holds the inputs and the two rules; tests/test_rows_model.py shows that the
     nullable outputs;
 (d) refusals leave the output untouched.
 
-Which case reaches which instantiation (the launchers dispatch on d <= 8; a case = kind, layout, d; every N of its d):
+Which case reaches which instantiation of the build frame (csrc/rows_tile.h: rows_build_tile<DR, LAYOUT> with the GaussRows / MaternRows<NU2>
+policy; launch_rows_build dispatches on kernel family, layout and d <= 8; a case = kind, layout, d; every N of its d):
   approx_build_many_kernel<8, false>          (a) gauss approx d = 1, 3, 8 (k < d live at 1 and 3)      <0, false>  d = 9, 17, 64
   approx_build_many_kernel<8, true>           (a) gauss grad d = 1, 3, 8                               <0, true>   d = 9, 17, 64
   dvh_build_many_kernel<8>                    (a) gauss dvh d = 1, 3, 8                                <0>         d = 9, 17, 64

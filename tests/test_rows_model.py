@@ -5,7 +5,12 @@ rejects every seeded defect at the shapes tests/test_rows.py runs on the device.
            _matern_ld.jacobian_hessian and C against _matern_ld.kernel_parts; C and J of every kind against _predict_grad_model.rows; J and H_kk
            against central differences of the kernel in long double; d = 1, 3, 9
   floor    rho of the rows (over every case of _rows_ld.all_cases()) and rho_ref of every reduction case, printed
-  defects  _rows_ld.ROW_DEFECTS at N = 129 (127 padded columns), d = 3 and 9; _rows_ld.REDUCE_DEFECTS at npad = 768, d = 8 and 9"""
+  defects  _rows_ld.ROW_DEFECTS at N = 129 (127 padded columns), d = 3 and 9; _rows_ld.REDUCE_DEFECTS at npad = 768, d = 8 and 9
+  build    the eight APPROX / DVH instantiations of the build frame (csrc/rows_tile.h) keep everything in registers and their occupancy"""
+import os
+import re
+import shutil
+import subprocess
 import types
 
 import numpy as np
@@ -18,6 +23,7 @@ import _matern_ld as ml
 import _predict_grad_model as pg
 import _rows_ld as rl
 
+PKG_PARENT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scikit-gpuppy_amd")
 LD = rl.LD
 EPS_LD = float(np.finfo(LD).eps)
 MODEL_D = (1, 3, 9)
@@ -178,3 +184,45 @@ def test_reduce_defects_are_rejected(defect, d):
         rl.assert_within({k: rl.distances(clean[k][0], want[k][0], want[k][1]) for k in want}, rho)
         with pytest.raises(AssertionError):
             rl.assert_within({k: rl.distances(bad[k][0], want[k][0], want[k][1]) for k in want}, rho, defect)
+
+
+# ------------------------------------------------------------------------------------------------
+# the build kernels' resources
+# ------------------------------------------------------------------------------------------------
+# fragment of the mangled name -> (the least waves per SIMD, the most scalar registers spilled into vector lanes): the figures of the three
+# separate kernel bodies that the frame replaced; the six GRAD instantiations are held by tests/test_predict_grad_model.py
+BUILD_FLOORS = {"propagate.hip": {"approx_build_many_kernelILi8ELb0E": (6, 22), "approx_build_many_kernelILi0ELb0E": (7, 0),
+                                  "dvh_build_many_kernelILi8E": (7, 0), "dvh_build_many_kernelILi0E": (8, 0)},
+                "matern.hip": {"matern52_build_many_kernelILi8ELb0E": (7, 42), "matern52_build_many_kernelILi0ELb0E": (7, 19),
+                               "matern52_build_many_kernelILi8ELb1E": (6, 24), "matern52_build_many_kernelILi0ELb1E": (6, 18)}}
+
+
+@pytest.mark.timeout(1800)
+@pytest.mark.parametrize("src", sorted(BUILD_FLOORS))
+def test_build_kernels_keep_everything_in_registers(src, tmp_path):
+    """-Rpass-analysis=kernel-resource-usage (the recipe of tests/test_predict_grad_model.py): no scratch, no spilled vector register, an
+    occupancy not below the floor of each APPROX / DVH instantiation, and no more scalar registers spilled into vector lanes than the
+    separate bodies spilled (five of the eight did: 18 to 42; the other three spill none)"""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", os.path.join(PKG_PARENT, "csrc", src), "-o",
+                          str(tmp_path / (src + ".o")), "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    usage, name = {}, None
+    for line in out.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            usage[name] = {}
+            continue
+        m = re.search(r"remark:\s+(ScratchSize \[bytes/lane\]|SGPRs Spill|VGPRs Spill|Occupancy \[waves/SIMD\]): (\d+)", line)
+        if m and name:
+            usage[name][m.group(1).split(" ")[0]] = int(m.group(2))
+    missed = []
+    for frag, (floor, sgpr_spill) in BUILD_FLOORS[src].items():
+        hits = {k: u for k, u in usage.items() if frag in k}
+        assert len(hits) == 1, (frag, sorted(usage))
+        for k, u in hits.items():
+            print(k, u, "floor", floor, "scalar spill at most", sgpr_spill)
+            if not (u["ScratchSize"] == 0 and u["SGPRs"] <= sgpr_spill and u["VGPRs"] == 0 and u["Occupancy"] >= floor):
+                missed.append((k, u, floor, sgpr_spill))
+    assert not missed, missed

@@ -19,6 +19,8 @@ d = 9, m = 130, the d > 8 instantiations, m just over one tile; b = 1 and b = 77
 7. refusals     every other entry point returns GPX_ERR_STATE naming the pseudo-input model; pseudo_gp() needs the SPGP route; HG / MC refuse.
 8. unchanged    UncertaintyPropagationExact(gp_spgp) gives the same bits before and after pseudo_gp(); estimate_many_gradient on the SPGP GP
                 is still its central-difference definition.
+9. seam         the K^-1 form of the batched calls' chunk loop across one chunk boundary (model D: m = 100, d = 8): the inputs on both sides
+                of the seam, the first and the last are the b = 1 call bit for bit.
 
 With GPX_DENSE_BOUNDS_RECORD=<file> every comparison of 2. appends its rho_ref, bound and worst ratios (profiles/r23_spgp_pseudo.txt)."""
 import ctypes
@@ -430,3 +432,29 @@ def test_parent_routes_unchanged():
     np.testing.assert_array_equal(dm, ((mu[2::2] - mu[1::2]) / (2.0 * h)).T)
     np.testing.assert_array_equal(dv, ((vv[2::2] - vv[1::2]) / (2.0 * h)).T)
     pgp.close()
+
+
+# ------------------------------------------------------------------------------------------------
+# 9. the chunk seam of the K^-1 form
+# ------------------------------------------------------------------------------------------------
+CHUNK_ROWS = 32768                                       # row_solve_chunk_cap at npad = 128
+
+
+def test_chunk_seam_of_the_pair_form():
+    """npad = 128, d = 8: a chunk holds 32768 // 10 = 3276 inputs of d + 2 rows (approx_many; B = 3300 is 33000 rows) and 32768 // 9 = 3640
+    queries of d + 1 rows (predict_grad; B = 3700).  Every output is finite, and the last input of the first chunk, the first of the second,
+    the first and the last of the batch equal the call on that input alone bit for bit."""
+    c = case("D")
+    assert c.m <= 128 and c.d == 8
+    U = dl._grid(np.random.RandomState(4100 + 97 * c.d).uniform(1, 9, (3700, c.d)))
+    for title, B, nrow, call in (("approx_many", 3300, c.d + 2, lambda V: approx_many(c.h, V, c.S)),
+                                 ("predict_grad", 3700, c.d + 1, lambda V: predict_grad(c.h, V))):
+        first = CHUNK_ROWS // nrow                       # inputs in the first chunk
+        assert first < B <= 2 * first and first == {"approx_many": 3276, "predict_grad": 3640}[title]
+        full = call(U[:B])
+        for k, g in full.items():
+            assert np.all(np.isfinite(g)), (title, k)
+        for i in (0, first - 1, first, B - 1):
+            alone = call(U[i:i + 1])
+            for k, g in full.items():
+                np.testing.assert_array_equal(alone[k][0], g[i], err_msg="%s %s input %d" % (title, k, i))
