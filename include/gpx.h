@@ -446,6 +446,11 @@ int gpx_bench_emu_i8(int64_t rows, int64_t cols, int64_t K, int nmod, int iters,
  * doubles; C needs no more than its natural 8 bytes and ldc may be odd).  rows = 0 or cols = 0 is a valid empty product. */
 int gpx_emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t rows, int64_t cols,
                         int64_t K);
+/* C[i, j] -= sum_k A[i, k] A[j, k] for j <= i < rows through the emulated update, by column panels of 1024 from ONE residue image of A
+ * (every row split once, with the same bit count in either role): the update of the factorisation's deferred columns (DESIGN.md
+ * section 5.1).  Nothing above the diagonal is written.  Arguments as gpx_emu_gemm_nt_sub with B = A, cols = rows; tile_rows > 0: a
+ * smaller row tile of the image (rounded up to 1024), for tests.  Synchronous. */
+int gpx_emu_syrk_lower_sub(const double *A, int64_t lda, int64_t rows, int64_t K, double *C, int64_t ldc, int64_t tile_rows);
 /* The two integer kernels of the emulated update alone, on device buffers (tests).  Synchronous.
  * gpx_emu_rebuild: C[rows, cols] -= X 2^-(sa[row] + sb[col]), X the integer in [-P/2, P/2) whose residues modulo the first nmod
  * (2 .. 16) moduli are the bytes R[l * sr + row * ldr + col]; a scale of 0x7fffffff marks a non-finite row or column (NaN).  ldr and sr

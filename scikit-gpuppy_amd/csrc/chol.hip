@@ -446,17 +446,18 @@ extern "C" int gpx_dev_set_panel_share(int ranks)
 // it does not give up.  That is the first panel (nothing but the Gram kernel's remainder runs beside it) and the panels whose trailing
 // update has fewer than GPX_SQK_TILES tiles left (default 1000: the last six panels at N = 16384).  GPX_SQK_FROM = p forces it from
 // panel p on (0: everywhere; -1: never).
-//   b0: the panel's first block column, rows: block rows of its square, nrem: block rows below the square (the trailing update that
-//   runs beside the chain: nrem (nrem + 1) / 2 tiles of triangle + nrem x rows of the next panel's columns), share: ranks that split it
+//   b0: the panel's first block column, beside: tiles of the trailing update that runs beside the chain (with nrem block rows below a
+//   square of `rows`: nrem (nrem + 1) / 2 tiles of triangle + nrem x rows of the panel's own columns -- fewer where the update stops
+//   at a group's last column, Lookahead::beside_tiles), share: ranks that split it
 //   from_p: GPX_SQK_FROM = p > 0 counts (the owner's panel step has always read only 0 and -1, and keeps doing so)
 static long sqk_from() { static const long v = env_long("GPX_SQK_FROM", -2); return v; }   // -2: the rule decides
-static bool square_launch_wanted(int64_t b0, int64_t rows, int64_t nrem, int share, bool from_p)
+static bool square_launch_wanted(int64_t b0, int64_t beside, int share, bool from_p)
 {
     static const long tiles = env_long("GPX_SQK_TILES", 1000);
     if (sqk_from() == -1 || !chol_dataflow_supported(CHOL_NBP)) return false;
     if (sqk_from() == 0) return true;
     if (sqk_from() > 0 && from_p) return b0 >= sqk_from() * CHOL_NBP;
-    return b0 == 0 || (nrem * (nrem + 1) / 2 + nrem * rows) / share < tiles;
+    return b0 == 0 || beside / share < tiles;
 }
 
 // The panel step of the multi-GPU host's panel owner (skgpuppy_amd/distributed.py -> gpx_dev_chol_panel / gpx_dev_chol_panel_next /
@@ -482,7 +483,7 @@ int chol_panel_factor_piped(double *L, int64_t ld, int64_t nblk_all, int64_t B0,
     double *Csq = L + c0 * ld + c0;
     if (P) GPX_TRY(launch_gemm_nt(P, ldp, P, ldp, Csq, ld, w, w, kp, -1.0, 1.0, 0, s, prof));
     const int64_t nrem = nblk_all - B1;
-    const bool sqk = B1 - B0 == CHOL_NBP && B0 % CHOL_NBP == 0 && square_launch_wanted(B0, B1 - B0, nrem, g_panel_share, false);
+    const bool sqk = B1 - B0 == CHOL_NBP && B0 % CHOL_NBP == 0 && square_launch_wanted(B0, nrem * (nrem + 1) / 2 + nrem * (B1 - B0), g_panel_share, false);
     // what the call leaves queued (buffer, events, internal stream): everything queued sits in body(), every way out passes the hand-over below it
     std::vector<void *> scratch;
     Events events;
@@ -685,6 +686,23 @@ static int64_t dflow_max_blocks() { static const int64_t v = env_long("GPX_DFLOW
 // Callers without look-ahead streams (SPGP's M x M blocks, gpx_spd_inverse) use the kernel between 9 and 64 block rows (GPX_DFLOW_SMALL=0:
 // never) -- a 2048 x 2048 factorisation is a chain of 16 steps, 1.0 ms there against 2.2 ms of dependent launches.
 static bool dflow_small_enabled() { static const bool v = env_long("GPX_DFLOW_SMALL", 1) != 0; return v; }
+// The far columns by group on the int8 path (Lookahead::group_boundary).  GPX_FIT_EMU: 0 never (the fp64 schedule, bit for bit), 1
+// wherever the rules below allow it, unset: from FIT_EMU_MIN_BLOCKS block rows on; GPX_FIT_EMU_GROUP: outer panels per group.
+// Panels per group for a factor of nblk block rows, 0 = the fp64 schedule: the emulated path takes K = 1024 G (emu_enabled: GPX_EMU_F64,
+// GPX_EMU_MIN_K) and there are at least two groups.  A function of nblk and the environment alone.
+// Measured (profiles/r25_fit_emu.txt; G = 4 and 8 against the fp64 schedule at N = 8192 ... 32768, interleaved on one box): groups of
+// four win at every size: by 2 % at N = 8192 (5.94 against 6.07-6.11 ms), by 8 % at 12288 and more above.  On from N = 12288: below it
+// the fit keeps the fp64 tile arithmetic, which every other schedule of such a fit reproduces bit for bit -- the whole matrix as one
+// dataflow launch among them (GPX_DFLOW_MAX_BLOCKS; tests/test_dataflow.py holds alpha at N = 9000 to the last bit), and that launch
+// has no emulated update.  The 0.13 ms at 8192 do not pay for giving that up.
+constexpr long FIT_EMU_MIN_BLOCKS = 96, FIT_EMU_GROUP = 4;
+static int64_t fit_emu_group(int64_t nblk)
+{
+    static const long on = env_long("GPX_FIT_EMU", -1), group = std::max(1L, env_long("GPX_FIT_EMU_GROUP", FIT_EMU_GROUP));
+    if (on == 0 || (on < 0 && nblk < FIT_EMU_MIN_BLOCKS)) return 0;
+    const int64_t panels = (nblk + CHOL_NBP - 1) / CHOL_NBP;
+    return emu_enabled(CHOL_PANEL_COLS * group) && panels > group ? group : 0;
+}
 
 // Probes every pair of streams the look-ahead schedule lets wait for each other (cached per pair).  Called by the fit while the
 // streams are still idle -- before the Gram launch is queued on `s`.
@@ -784,9 +802,14 @@ struct Lookahead {
     hipStream_t s_blk = nullptr;   // CU reservation: the blockers (nres of them) run on a stream of their own
     int nres = 0;
     bool reserved = false, released = false;
+    bool blk_gone = false;         // a reservation was dropped at a group boundary: ev_blk_gone passes once its blockers have left
+    // The far columns by group (fit_emu_group): T(p) stops at the first column of the group after p's; behind a group's last panel ONE
+    // emulated symmetric update of depth 1024 G brings every column right of the group up to date (group_boundary).
+    int64_t G = 0;                 // panels per group; 0: every T(p) runs to the last column (the fp64 schedule)
+    EmuSyrk esy;
     bool sq_split_prev = false;   // T(p - 1) ran in the split tail form: diagonal square p + 1 has its tiles marked by ev_sqp[p - 1]
     Events events;
-    hipEvent_t ev0 = nullptr, ev_blk = nullptr;
+    hipEvent_t ev0 = nullptr, ev_blk = nullptr, ev_blk_gone = nullptr;
     std::vector<hipEvent_t> ev_pf, ev_next, ev_top, ev_tu, ev_first, ev_sqp;
     // GPX_DEBUG: host clock (us since the factorisation's first launch) at which each panel's launches had been queued -- in the tail the
     // kernels are so short that the HOST's enqueue rate (60 launches per panel) can become the critical path
@@ -816,8 +839,25 @@ struct Lookahead {
         (void)hipStreamSynchronize(s);
         events.clear();
         if (sqk_buf) dfree(sqk_buf);
+        emu_syrk_free(esy);
     }
     int64_t bnd(int64_t p) const { return Bs[std::min<int64_t>(p, P)]; }
+    // first block column that T(p) leaves to the next group boundary (nblk: none)
+    int64_t far_blk(int64_t p) const { return G ? bnd((p / G + 1) * G) : nblk; }
+    // panel p ends a group that another one follows: the boundary's update takes the place of Q(p) and T(p)
+    bool boundary(int64_t p) const { return G && (p + 1) % G == 0 && p + 1 < P; }
+    // tiles of T(p)'s triangle part: rows [B2, nblk), columns [B2, far) at and below the diagonal
+    int64_t bulk_tiles(int64_t p) const
+    {
+        const int64_t nrem = nblk - bnd(p + 2), wt = std::max<int64_t>(0, std::min(nrem, far_blk(p) - bnd(p + 2)));
+        return nrem <= 0 ? 0 : wt * (wt + 1) / 2 + (nrem - wt) * wt;
+    }
+    // tiles of the fp64 update that runs beside chain(pp): T(pp - 1), its narrow part included; behind a boundary none
+    int64_t beside_tiles(int64_t pp) const
+    {
+        if (pp == 0 || boundary(pp - 1)) return 0;
+        return (nblk - bnd(pp + 1)) * (bnd(pp + 1) - bnd(pp)) + bulk_tiles(pp - 1);
+    }
     // work of the caller that rides along on the main stream, behind panel p's trailing update (common.h: panel_final)
     int hook(int64_t p, int64_t slack, bool last) const { return panel_final ? (*panel_final)(p, slack, last) : 0; }
     // panel q has rows below its square, and a stream to solve them on column by column alongside its chain
@@ -846,9 +886,16 @@ struct Lookahead {
         // (the column solves wait for the kernels' counters from another stream: needs streams that run side by side)
         concurrent = token.solo && streams_run_concurrently(s_pan, s) && (!s_top || streams_run_concurrently(s_top, s));
         trap_on = trap_enabled() && concurrent;
+        // the group route: decided by nblk and the environment -- and by the pool: a workspace that does not fit (dalloc trims the pool
+        // before it gives up) leaves the fp64 schedule, the one way the route depends on anything but size
+        G = fit_emu_group(nblk);
+        if (G) {
+            emu_syrk_plan(esy, (nblk - bnd(G)) * TILE, (int64_t)CHOL_PANEL_COLS * G);
+            if (emu_syrk_alloc(esy)) G = 0;
+        }
         sqk_use.assign((size_t)P, 0);
         for (int64_t pp = 0; concurrent && pp < P; ++pp)
-            sqk_use[(size_t)pp] = square_launch_wanted(bnd(pp), bnd(pp + 1) - bnd(pp), nblk - bnd(pp + 1), 1, true);
+            sqk_use[(size_t)pp] = square_launch_wanted(bnd(pp), beside_tiles(pp), 1, true);
         sqk_tabs.resize((size_t)P);
         tops.resize((size_t)P + 1);
         if (std::count(sqk_use.begin(), sqk_use.end(), 1)) GPX_TRY(dalloc(&sqk_buf, (P * SQK_STATE + P * SQK_TAB) / 2 + 2));
@@ -865,6 +912,7 @@ struct Lookahead {
             s_blk = nullptr;
         }
         if (s_blk) GPX_TRY(events.make(&ev_blk));
+        if (s_blk && G) GPX_TRY(events.make(&ev_blk_gone));
         host_t0 = debug_enabled() ? host_now() : 0.0;
         return 0;
     }
@@ -891,6 +939,17 @@ struct Lookahead {
         hipLaunchKernelGGL(set_flag_kernel, dim3(1), dim3(1), 0, s, stop_flag, 1);
         released = true;
     }
+    // A group boundary gives the reserved CUs back: the int8 product (128 KiB of LDS, more than 216 registers per SIMD) cannot use them.
+    // The next short panel reserves again (reserve_now).
+    int drop_reservation()
+    {
+        if (!reserved) return 0;
+        release_blockers();
+        GPX_HIP(hipEventRecord(ev_blk_gone, s_blk));
+        reserved = released = false;
+        blk_gone = true;
+        return 0;
+    }
     // The reservation starts in front of panel p's square update, with the first panel whose bulk launch is short (reserve_below_tiles).
     // (not where the next chain is a square launch already -- small factors, N <= 5120 at the default thresholds: the blockers
     // would be released again a few lines below, 30 us of memset / placement wait / release on the critical path for nothing)
@@ -902,7 +961,9 @@ struct Lookahead {
     int reserve_now(int64_t p)
     {
         const int64_t nrem = nblk - bnd(p + 2);
-        if (!s_blk || reserved || nrem <= 0 || nrem * (nrem + 1) / 2 >= reserve_below_tiles() || (sqk_from() < 0 && use_sqk(p + 1))) return 0;
+        if (!s_blk || reserved || nrem <= 0 || bulk_tiles(p) >= reserve_below_tiles() || (sqk_from() < 0 && use_sqk(p + 1))) return 0;
+        if (blk_gone) GPX_HIP(hipStreamWaitEvent(s, ev_blk_gone, 0));   // (the flag is cleared only once the blockers it released have read it)
+        blk_gone = false;
         GPX_HIP(hipMemsetAsync(stop_flag, 0, 2 * sizeof(int), s));
         GPX_HIP(hipEventRecord(ev_blk, s));
         GPX_HIP(hipStreamWaitEvent(s_blk, ev_blk, 0));
@@ -1028,9 +1089,11 @@ struct Lookahead {
         const double *Pr = L + (B2 * TILE) * ld + B0 * TILE;       // panel p, rows >= B2
         int merged = GPX_ERR_STATE;
         constexpr long trap_min = 1024;
-        if (trap_on && nrem * (nrem + 1) / 2 >= trap_min && B2 - B1 == CHOL_NBP)
+        // the group route: the triangle part ends at column far(p) -- wt of its nrem tile columns (rows still run to nblk)
+        const int64_t fc = std::min(nblk, std::max(B2, far_blk(p))), wt = fc - B2;
+        if (trap_on && bulk_tiles(p) >= trap_min && B2 - B1 == CHOL_NBP)
             merged = launch_syrk_trap_signal(Pr, ld, Ptop, ld, L + (B2 * TILE) * ld + B1 * TILE, ld, nrem * TILE, (B2 - B1) * TILE, K, -1.0, 1.0,
-                                             sig + p * CHOL_NBP, s, prof);
+                                             sig + p * CHOL_NBP, s, prof, wt * TILE);
         if (merged != 0 && merged != GPX_ERR_STATE) return merged;
         if (merged != 0)
             GPX_TRY(launch_gemm_nt(Pr, ld, Ptop, ld, L + (B2 * TILE) * ld + B1 * TILE, ld, nrem * TILE, (B2 - B1) * TILE,
@@ -1050,7 +1113,20 @@ struct Lookahead {
             else GPX_HIP(hipStreamWaitEvent(s_top, ev_first[p], 0));
             GPX_TRY(top_column(L, ld, B1, B1, Dinv, &top, prof));
         }
-        if (merged != 0 && p + 2 < P && B3 > B2) {
+        if (merged != 0 && wt < nrem) {
+            // the same in the group route (nothing where panel p + 1 ends its group): diagonal square p + 2 first and marked, the rows
+            // below it down to row far(p) as a trapezoid, the rows from far(p) on as a rectangle
+            if (wt > 0) {
+                GPX_TRY(launch_gemm_nt(Pr, ld, Pr, ld, L + (B2 * TILE) * ld + B2 * TILE, ld, (B3 - B2) * TILE, (B3 - B2) * TILE, K, -1.0, 1.0, 1, s, prof));
+                GPX_HIP(hipEventRecord(ev_sqp[p], s));
+                sq_split_prev = true;
+                if (B3 < fc)
+                    GPX_TRY(launch_gemm_nt(Pr + ((B3 - B2) * TILE) * ld, ld, Pr, ld, L + (B3 * TILE) * ld + B2 * TILE, ld, (fc - B3) * TILE, wt * TILE, K,
+                                           -1.0, 1.0, 1, s, prof));
+                GPX_TRY(launch_gemm_nt(Pr + (wt * TILE) * ld, ld, Pr, ld, L + (fc * TILE) * ld + B2 * TILE, ld, (nblk - fc) * TILE, wt * TILE, K, -1.0, 1.0, 0,
+                                       s, prof));
+            }
+        } else if (merged != 0 && p + 2 < P && B3 > B2) {
             GPX_TRY(launch_gemm_nt(Pr, ld, Pr, ld, L + (B2 * TILE) * ld + B2 * TILE, ld, (B3 - B2) * TILE, (B3 - B2) * TILE, K, -1.0, 1.0, 1, s, prof));
             GPX_HIP(hipEventRecord(ev_sqp[p], s));
             sq_split_prev = true;
@@ -1061,6 +1137,37 @@ struct Lookahead {
             GPX_TRY(launch_gemm_nt(Pr, ld, Pr, ld, L + (B2 * TILE) * ld + B2 * TILE, ld, nrem * TILE, nrem * TILE, K, -1.0, 1.0, 1, s, prof));
         // once the remaining bulk launches no longer fill the chip the reservation has nothing left to protect
         if (B3 >= nblk) release_blockers();   // the last bulk launch is queued
+        return 0;
+    }
+    // Group boundary behind panel p, in the place of Q(p) and T(p): every column right of the group takes the group's columns at once,
+    // C[i, j] -= sum_k L[i, k] L[j, k] over the group's k for far <= j <= i, on the int8 path (emu.hip, emu_syrk_lower_sub's pieces).
+    // All of it on the main stream, column panels in ascending order, so that every later T(q) -- which rewrites the same columns -- is
+    // ordered behind it; the new cross-stream edges are events: the next chain and the next panel's column solves wait for column
+    // panel 0 alone (ev_next, ev_tu) and run underneath the remaining column panels.  The group's rows >= far are complete: the column
+    // solves of the earlier panels were waited for by their T(q), panel p's are waited for here (its square launch's share: ev_pf).
+    // A failed pivot leaves NaN rows whose residues are zero and whose outputs are NaN: no wait depends on them.
+    int group_boundary(int64_t p)
+    {
+        const int64_t g0 = bnd(p + 1 - G), B1 = bnd(p + 1), rows = (nblk - B1) * TILE, K = (B1 - g0) * TILE;
+        if (piped(p)) GPX_HIP(hipStreamWaitEvent(s, ev_top[p], 0));
+        else GPX_TRY(trsm_right_lt(L + (B1 * TILE) * ld, ld, (nblk - B1) * TILE, L, ld, Dinv, bnd(p), B1, s, prof));
+        GPX_TRY(drop_reservation());
+        sq_split_prev = false;
+        double *C = L + (B1 * TILE) * ld + B1 * TILE;
+        emu_syrk_plan(esy, rows, K);
+        GPX_TRY(emu_syrk_split(esy, L + (B1 * TILE) * ld + g0 * TILE, ld, rows, s));
+        GPX_TRY(emu_syrk_panel(esy, 0, C, ld, rows, s, prof, TILE));
+        GPX_HIP(hipEventRecord(ev_next[p], s));
+        GPX_TRY(start_chain(p + 1));
+        sqk_open_gate(p + 1, s);
+        if (piped(p + 1)) {   // as behind a narrow launch (trailing_update): panel p + 1's rows below its square are complete
+            GPX_HIP(hipEventRecord(ev_tu[p], s));
+            GPX_HIP(hipStreamWaitEvent(s_top, ev_tu[p], 0));
+            if (use_sqk(p + 1)) follow_square(p + 1);
+            else GPX_HIP(hipStreamWaitEvent(s_top, ev_first[p], 0));
+            GPX_TRY(top_column(L, ld, B1, B1, Dinv, &tops[(size_t)p + 1], prof));
+        }
+        for (int64_t q = 1; q * CHOL_PANEL_COLS < rows; ++q) GPX_TRY(emu_syrk_panel(esy, q, C, ld, rows, s, prof, TILE));
         return 0;
     }
     // The rest of chain(q) and of S(q), q = p + 1, behind the main stream's launches of this panel: a square launch runs already (one
@@ -1119,10 +1226,13 @@ int chol_factor(double *L, int64_t ld, int64_t nblk, double *Dinv, double *diagL
     for (int64_t p = 0; p <= last; ++p) {
         GPX_HIP(hipStreamWaitEvent(s, la.ev_pf[p], 0));   // diagonal square of panel p is factored
         if (p == last) return la.hook(p, 0, true);
-        GPX_TRY(la.reserve_now(p));
-        GPX_TRY(la.square_update(p));
-        GPX_TRY(la.start_chain(p + 1));
-        GPX_TRY(la.trailing_update(p));
+        if (la.boundary(p)) GPX_TRY(la.group_boundary(p));
+        else {
+            GPX_TRY(la.reserve_now(p));
+            GPX_TRY(la.square_update(p));
+            GPX_TRY(la.start_chain(p + 1));
+            GPX_TRY(la.trailing_update(p));
+        }
         GPX_TRY(la.hook(p, (nblk - la.bnd(p + 2) + CHOL_NBP - 1) / CHOL_NBP, false));
         GPX_TRY(la.finish_chain(p + 1));
         la.mark();

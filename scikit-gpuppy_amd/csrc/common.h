@@ -261,7 +261,7 @@ int launch_gemm_nt(const double *A, int64_t lda, const double *B, int64_t ldb, d
                    hipStream_t s, Profiler *prof, int ktrim = 0, int tri = 0, int small_tiles = 0, int *variant = nullptr);
 // narrow update + bulk SYRK of a panel as ONE trapezoid launch that counts its finished narrow tiles in *sig_dev (gemm.hip)
 int launch_syrk_trap_signal(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t M, int64_t off_cols, int64_t K,
-                            double alpha, double beta, int *sig_dev, hipStream_t s, Profiler *prof);
+                            double alpha, double beta, int *sig_dev, hipStream_t s, Profiler *prof, int64_t tri_cols = 0);
 // batched form: problem z = (p, q), q < nq, has its operand at base + p * sp + q * sq (elements)
 // tri (read from the A descriptor; square problems only): the contraction skips the zero part of one triangular operand
 enum { GEMM_TRI_NONE = 0, GEMM_TRI_A_UPPER = 1, GEMM_TRI_A_LOWER = 2, GEMM_TRI_B_LOWER = 3, GEMM_TRI_B_LOWER_PAIRED = 4 /* internal */,
@@ -393,6 +393,24 @@ int emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t ldb, 
 bool emu_enabled(int64_t K);
 int emu_moduli();                        // GPX_EMU_MODULI (default 16, 2 .. 16)
 int emu_scale_bits(int64_t K, int L);    // alpha + beta: the largest s with K 2^s < P / 2
+
+// The symmetric update of the factorisation's far columns (emu.hip): C[i, j] -= sum_k A[i, k] A[j, k], j <= i < rows, by column panels of
+// 1024 from ONE residue image of A.  plan sets the geometry of one update and grows the sizes (call it for the largest update before
+// alloc, then for each update before its split); alloc / free: the pool; split, then the column panels in ascending order, each on the
+// stream the caller picks (a panel reads the image and the scales, and writes its own columns of C only).
+struct EmuSyrk {
+    int8_t *img = nullptr, *rr = nullptr;
+    int *sig = nullptr;
+    int L = 0, bits = 0;
+    int64_t K = 0, rows_pad = 0, rt = 0, tiles = 0, img_bytes = 0, r_bytes = 0, sig_n = 0;
+};
+void emu_syrk_plan(EmuSyrk &w, int64_t rows, int64_t K, int64_t tile_rows = 0);
+int emu_syrk_alloc(EmuSyrk &w);
+void emu_syrk_free(EmuSyrk &w);
+int emu_syrk_split(const EmuSyrk &w, const double *A, int64_t lda, int64_t rows, hipStream_t s);
+int emu_syrk_panel(const EmuSyrk &w, int64_t q, double *C, int64_t ldc, int64_t rows, hipStream_t s, Profiler *prof, int diag_tile = 1);
+int emu_syrk_lower_sub(const double *A, int64_t lda, int64_t rows, int64_t K, double *C, int64_t ldc, const EmuSyrk &w, hipStream_t s, Profiler *prof,
+                       const hipEvent_t *panel_done = nullptr);
 
 // The left-looking form of the many-row solve (tsolve.hip, trsm_right_lt_slabs): every solved slab is split ONCE into a persistent
 // residue image, with a row scale derived from a bound on the whole solved row that the caller knows at entry; slab p then takes one

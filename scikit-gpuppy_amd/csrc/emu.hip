@@ -526,6 +526,7 @@ __global__ __launch_bounds__(512, 1) void emu_i8_gemm_kernel(const int8_t *__res
 }
 
 // ---- rebuild: C_ij -= X_ij 2^-(sig_i + tau_j), four consecutive columns per thread ----------------------------------------------
+constexpr long EMU_NO_DIAG = 1L << 40;   // `diag` of a full rectangle
 // X is the integer in [-P/2, P/2) with the L residues r_l, by the direct CRT sum (linear in L):
 //   t_l = r_l c_l mod p_l, any representative with |t_l| <= (p_l + 1) / 2 (|r_l c_l| < 2^15: exact in fp32, one step per modulus);
 //   S = sum_l t_l M_l = X (mod P), summed limb by limb in fp64 (|t_l| <= 128 and limbs below 2^40: every partial sum is an integer
@@ -534,7 +535,7 @@ __global__ __launch_bounds__(512, 1) void emu_i8_gemm_kernel(const int8_t *__res
 //   -+P where X fell outside [-P/2, P/2) makes q's rounding immaterial.  The integer is rounded once to fp64, as before.
 __global__ __launch_bounds__(256) void emu_rebuild_kernel(const int8_t *__restrict__ R, long ldr, long sr, int L, const EmuCrt T,
                                                           const int *__restrict__ sa, const int *__restrict__ sb, double *__restrict__ C,
-                                                          long ldc, long rows, long cols)
+                                                          long ldc, long rows, long cols, long diag, long dmask)
 {
     const long q4 = (cols + 3) >> 2;
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
@@ -549,7 +550,7 @@ __global__ __launch_bounds__(256) void emu_rebuild_kernel(const int8_t *__restri
     const __int128 P = (__int128)(((emu_u128)T.p_hi << 64) | T.p_lo), half = (__int128)(((emu_u128)T.half_hi << 64) | T.half_lo);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        if (j0 + e >= cols) continue;
+        if (j0 + e >= cols || j0 + e > ((i + diag) | dmask)) continue;   // (row i ends at column (i + diag) | dmask -- EMU_NO_DIAG: at cols)
         const int tj = sb[j0 + e];
         if (si == EMU_NONFINITE || tj == EMU_NONFINITE) { c[e] = __builtin_nan(""); continue; }
         double s0 = 0.0, s1 = 0.0, s2 = 0.0;
@@ -667,7 +668,7 @@ int emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t ldb, 
                                (long)(nrp * K), (long)(ncp * K), (int)K, rr, (long)ncp, (long)(nrp * ncp), tm, tn, (int)K);
             const long thr = (long)nr * ((nc + 3) / 4);
             hipLaunchKernelGGL(emu_rebuild_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, (const int8_t *)rr, (long)ncp,
-                               (long)(nrp * ncp), L, emu_crt.t[L], (const int *)sga, (const int *)sgb, C + r0 * ldc + c0, (long)ldc, (long)nr, (long)nc);
+                               (long)(nrp * ncp), L, emu_crt.t[L], (const int *)sga, (const int *)sgb, C + r0 * ldc + c0, (long)ldc, (long)nr, (long)nc, EMU_NO_DIAG, 0L);
         }
         GPX_HIP(hipGetLastError());
     }
@@ -767,13 +768,128 @@ int emu_left_update(const EmuLeft &w, const double *B, int64_t ldb, double *C, i
                            (const int8_t *)w.rb, (long)(w.rt * w.lda), (long)(ncp * K), (int)K, w.rr, (long)ncp, (long)(nrp * ncp), tm, tn, (int)w.lda);
         const long thr = (long)nr * ((cols + 3) / 4);
         hipLaunchKernelGGL(emu_rebuild_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, (const int8_t *)w.rr, (long)ncp, (long)(nrp * ncp), w.L,
-                           emu_crt.t[w.L], (const int *)(w.sig + r0), (const int *)sgb, C + r0 * ldc, (long)ldc, (long)nr, (long)cols);
+                           emu_crt.t[w.L], (const int *)(w.sig + r0), (const int *)sgb, C + r0 * ldc, (long)ldc, (long)nr, (long)cols, EMU_NO_DIAG, 0L);
     }
     GPX_HIP(hipGetLastError());
     return 0;
 }
 
+// ---- the symmetric update of the factorisation's far columns (chol.hip, Lookahead::group_boundary) -------------------------------------
+// C[i, j] -= sum_k A[i, k] A[j, k] for j <= i < rows, by column panels of 1024.  A is split ONCE, every row with its own maximum and
+// the same bit count emu_scale_bits(K, L) / 2 in either role, into the image [row tile][l][rt][K]: column panel q's B operand is rows
+// q 1024 .. of that image (plane stride rt K, as A's).  rt is a multiple of 1024 wherever there is more than one row tile, so a panel's B
+// rows never straddle two; a row tile's planes span at most 2 GiB.  Per column panel and row tile below it one int8 launch and one rebuild
+// that ends every row at the diagonal: nothing above it is written.
+void emu_syrk_plan(EmuSyrk &w, int64_t rows, int64_t K, int64_t tile_rows)
+{
+    w.L = emu_moduli();
+    w.bits = emu_scale_bits(K, w.L) / 2;
+    w.K = K;
+    w.rows_pad = round_up(rows, EMU_BT);
+    int64_t cap = std::max<int64_t>(EMU_SLAB, emu_cap(K, w.L) / EMU_SLAB * EMU_SLAB);
+    if (tile_rows > 0) cap = std::min(cap, round_up(tile_rows, EMU_SLAB));
+    w.rt = w.rows_pad <= cap ? w.rows_pad : cap;
+    w.tiles = (w.rows_pad + w.rt - 1) / w.rt;
+    w.img_bytes = std::max(w.img_bytes, w.tiles * w.rt * K * w.L);
+    w.r_bytes = std::max(w.r_bytes, w.rt * std::min<int64_t>(EMU_SLAB, w.rows_pad) * w.L);
+    w.sig_n = std::max(w.sig_n, w.rows_pad);
+}
+
+// the workspace from the pool; no room (after the pool's own trim): nothing is held and the caller keeps its fp64 route
+int emu_syrk_alloc(EmuSyrk &w)
+{
+    double *a = nullptr, *b = nullptr, *c = nullptr;
+    if (dalloc(&a, (w.img_bytes + 7) / 8) || dalloc(&b, (w.r_bytes + 7) / 8) || dalloc(&c, (w.sig_n + 1) / 2)) {
+        dfree(a); dfree(b); dfree(c);
+        return GPX_ERR_HIP;
+    }
+    w.img = reinterpret_cast<int8_t *>(a);
+    w.rr = reinterpret_cast<int8_t *>(b);
+    w.sig = reinterpret_cast<int *>(c);
+    return 0;
+}
+
+void emu_syrk_free(EmuSyrk &w)
+{
+    dfree(w.img); dfree(w.rr); dfree(w.sig);
+    w.img = w.rr = nullptr;
+    w.sig = nullptr;
+}
+
+static int emu_syrk_fits(const EmuSyrk &w, const char *what)
+{
+    if (w.img && w.tiles * w.rt * w.K * w.L <= w.img_bytes && w.rt * std::min<int64_t>(EMU_SLAB, w.rows_pad) * w.L <= w.r_bytes && w.rows_pad <= w.sig_n) return 0;
+    gpx_set_error("%s: workspace too small for %ld rows x K = %ld", what, (long)w.rows_pad, (long)w.K);
+    return GPX_ERR_STATE;
+}
+
+// rows of A (the geometry of the last emu_syrk_plan) into the image, row scales into w.sig
+int emu_syrk_split(const EmuSyrk &w, const double *A, int64_t lda, int64_t rows, hipStream_t s)
+{
+    GPX_TRY(emu_syrk_fits(w, "emu_syrk_split"));
+    for (int64_t t = 0, r0 = 0; r0 < w.rows_pad; ++t, r0 += w.rt) {
+        const int64_t nrp = std::min(w.rt, w.rows_pad - r0), nr = std::max<int64_t>(0, std::min(nrp, rows - r0));
+        emu_launch_split(A + r0 * lda, (long)lda, (long)nr, (long)nrp, (int)w.K, w.bits, w.L, w.img + t * w.rt * w.K * w.L, (long)(w.rt * w.K), w.sig + r0, s);
+    }
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// column panel q: C[i, j] for q 1024 <= j < min(rows, (q + 1) 1024), j <= i < rows (C: the matrix's first entry)
+// diag_tile (1 or a power of two that divides 1024): row i ends at the last column of its diag_tile x diag_tile diagonal block -- the
+// factorisation's diagonal tiles stay symmetric in full, as its fp64 updates leave them (the products are symmetric to the bit)
+int emu_syrk_panel(const EmuSyrk &w, int64_t q, double *C, int64_t ldc, int64_t rows, hipStream_t s, Profiler *prof, int diag_tile)
+{
+    const int64_t q0 = q * EMU_SLAB, nc = std::min<int64_t>(EMU_SLAB, rows - q0), ncp = round_up(nc, EMU_BT);
+    if (nc <= 0) return 0;
+    GPX_TRY(emu_syrk_fits(w, "emu_syrk_panel"));
+    ProfScope ps(prof, s, GPX_K_GEMM_EMU, 2.0 * (double)(rows - q0) * (double)nc * (double)w.K);
+    const int64_t tb = q0 / w.rt;
+    const int8_t *B = w.img + tb * w.rt * w.K * w.L + (q0 - tb * w.rt) * w.K;
+    for (int64_t t = tb; t < w.tiles; ++t) {
+        const int64_t lo = std::max(t * w.rt, q0), hi = std::min((t + 1) * w.rt, w.rows_pad), nrp = hi - lo, nr = std::min(hi, rows) - lo;
+        if (nr <= 0) break;
+        const int tm = (int)(nrp / EMU_BT), tn = (int)(ncp / EMU_BT);
+        hipLaunchKernelGGL(emu_i8_gemm_kernel, dim3((unsigned)(tm * tn * w.L)), dim3(512), 0, s, w.img + t * w.rt * w.K * w.L + (lo - t * w.rt) * w.K, B,
+                           (long)(w.rt * w.K), (long)(w.rt * w.K), (int)w.K, w.rr, (long)ncp, (long)(nrp * ncp), tm, tn, (int)w.K);
+        const long thr = (long)nr * ((nc + 3) / 4);
+        hipLaunchKernelGGL(emu_rebuild_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, (const int8_t *)w.rr, (long)ncp, (long)(nrp * ncp), w.L,
+                           emu_crt.t[w.L], (const int *)(w.sig + lo), (const int *)(w.sig + q0), C + lo * ldc + q0, (long)ldc, (long)nr, (long)nc, (long)(lo - q0), (long)(diag_tile - 1));
+    }
+    GPX_HIP(hipGetLastError());
+    return 0;
+}
+
+// the whole update on s, column panels in ascending order; panel_done (optional, one event per column panel): recorded behind each
+int emu_syrk_lower_sub(const double *A, int64_t lda, int64_t rows, int64_t K, double *C, int64_t ldc, const EmuSyrk &w, hipStream_t s, Profiler *prof,
+                       const hipEvent_t *panel_done)
+{
+    if (rows <= 0) return 0;
+    GPX_TRY(emu_syrk_split(w, A, lda, rows, s));
+    for (int64_t q = 0; q * EMU_SLAB < rows; ++q) {
+        GPX_TRY(emu_syrk_panel(w, q, C, ldc, rows, s, prof, 1));
+        if (panel_done) GPX_HIP(hipEventRecord(panel_done[q], s));
+    }
+    return 0;
+}
+
 // ---- C-ABI: the emulated product on caller device buffers (tests), the int8 product kernel alone on random residues (its rate) -------
+// the symmetric update: any K that is a multiple of 128 below 2^17; tile_rows > 0: a smaller row tile (rounded up to 1024), for tests
+extern "C" int gpx_emu_syrk_lower_sub(const double *A, int64_t lda, int64_t rows, int64_t K, double *C, int64_t ldc, int64_t tile_rows)
+{
+    GPX_TRY(gpx_require_device());
+    if (rows < 0 || tile_rows < 0 || !A || !C) { gpx_set_error("gpx_emu_syrk_lower_sub: bad arguments"); return GPX_ERR_BAD_ARG; }
+    GPX_TRY(emu_check_args(A, lda, A, lda, ldc, rows, K));
+    if (rows == 0) return 0;
+    EmuSyrk w;
+    emu_syrk_plan(w, rows, K, tile_rows);
+    if (emu_syrk_alloc(w)) return GPX_ERR_HIP;
+    int rc = emu_syrk_lower_sub(A, lda, rows, K, C, ldc, w, 0, nullptr, nullptr);
+    if (hipStreamSynchronize(0) != hipSuccess && rc == 0) { gpx_set_error("gpx_emu_syrk_lower_sub: stream failed"); rc = GPX_ERR_HIP; }
+    emu_syrk_free(w);
+    return rc;
+}
+
 extern "C" int gpx_emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t rows, int64_t cols,
                                    int64_t K)
 {
@@ -804,7 +920,7 @@ extern "C" int gpx_emu_rebuild(const int8_t *R, int64_t ldr, int64_t sr, int nmo
     if (rows == 0 || cols == 0) return 0;
     const long thr = (long)rows * ((cols + 3) / 4);
     hipLaunchKernelGGL(emu_rebuild_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, 0, R, (long)ldr, (long)sr, nmod, emu_crt.t[nmod], sa, sb, C,
-                       (long)ldc, (long)rows, (long)cols);
+                       (long)ldc, (long)rows, (long)cols, EMU_NO_DIAG, 0L);
     GPX_HIP(hipGetLastError());
     GPX_HIP(hipStreamSynchronize(0));
     return 0;

@@ -156,8 +156,11 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_f64_reduce_kernel(const double
 // with CUs reserved for the chain an XCD has fewer places than narrow tiles, and the last column's tiles finish a whole tile later).
 // XCD x (workgroups with blockIdx & 7 == x) takes the narrow 8 x off groups g = x, x + 8, .. (8 tile rows each: 64 tiles that share
 // 8 A and `off` B row panels through that XCD's L2), then its contiguous chunk of the triangle in the grouped order of lower_tile.
+// LIM (the factorisation's near-only updates, chol.hip): the triangle ends at its tile column wt -- rows r >= wt hold off + wt tiles.  Its
+// tiles are enumerated as the wt x wt triangle in lower_tile's order, then the rows below it in groups of 8, column-major inside a group.
+template <bool LIM>
 __global__ __launch_bounds__(256, 2) void gemm_nt_f64_trap_signal_kernel(const double *A, long lda, const double *B, long ldb, double *C, long ldc,
-                                                                        int K, double alpha, double beta, int off, int nt, int *sig)
+                                                                        int K, double alpha, double beta, int off, int nt, int *sig, int wt)
 {
     __shared__ __attribute__((aligned(1024))) double smem[2 * 256 * 16];
     // 224 registers like the plain bulk kernel (the compiler gets by with 208 here): a wave of this kernel must NOT fit into the 216
@@ -181,7 +184,13 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_f64_trap_signal_kernel(const d
     } else {
         int start = 0;
         for (int x = 0; x < xcd; ++x) start += (nwg - x + 7) / 8 - narrow_of(x);
-        lower_tile(start + idx - mine, 0, nt, by, bx);
+        const int lid = start + idx - mine, tri = wt * (wt + 1) / 2;
+        if (!LIM || lid < tri) lower_tile(lid, 0, LIM ? wt : nt, by, bx);
+        else {
+            const int r = lid - tri, g = r / (8 * wt), first = wt + 8 * g, rows = min(8, nt - first), rem = r - g * 8 * wt;
+            bx = rem / rows;
+            by = first + rem - bx * rows;
+        }
         bx += off;
     }
     const bool publish = narrow && sig;
@@ -221,13 +230,16 @@ int launch_syrk_lower_splitk(const double *W, int64_t ldw, double *parts, int64_
 }
 
 int launch_syrk_trap_signal(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t M, int64_t off_cols, int64_t K,
-                            double alpha, double beta, int *sig_dev, hipStream_t s, Profiler *prof)
+                            double alpha, double beta, int *sig_dev, hipStream_t s, Profiler *prof, int64_t tri_cols)
 {
-    if (M % TILE || off_cols % TILE || K % GEMM_BK || K <= 0 || (lda & 1) || (ldb & 1) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15) || alpha == 0.0) {
+    // tri_cols (0: all M): the triangle's columns end there -- C[M, off_cols + tri_cols]
+    if (M % TILE || off_cols % TILE || K % GEMM_BK || K <= 0 || (lda & 1) || (ldb & 1) || ((uintptr_t)A & 15) || ((uintptr_t)B & 15) || alpha == 0.0 ||
+        tri_cols % TILE || tri_cols < 0 || tri_cols > M) {
         gpx_set_error("launch_syrk_trap_signal: shape/alignment not supported");
         return GPX_ERR_BAD_ARG;
     }
-    const int64_t nt = M / TILE, off = off_cols / TILE, tri = nt * (nt + 1) / 2, nwg = tri + off * nt;
+    const bool lim = tri_cols > 0 && tri_cols < M;
+    const int64_t nt = M / TILE, off = off_cols / TILE, wt = lim ? tri_cols / TILE : nt, tri = wt * (wt + 1) / 2 + (nt - wt) * wt, nwg = tri + off * nt;
     const int64_t G = (nt + 7) / 8;
     for (int x = 0; x < 8; ++x) {   // every XCD must have at least as many workgroups as narrow tiles
         int64_t c = 0;
@@ -235,8 +247,12 @@ int launch_syrk_trap_signal(const double *A, int64_t lda, const double *B, int64
         if ((nwg - x + 7) / 8 < c) return GPX_ERR_STATE;
     }
     ProfScope ps(prof, s, GPX_K_GEMM, (double)nwg * 2.0 * TILE * TILE * (double)K, 1);
-    hipLaunchKernelGGL(gemm_nt_f64_trap_signal_kernel, dim3((unsigned)nwg), dim3(256), 0, s, A, (long)lda, B, (long)ldb, C, (long)ldc, (int)K, alpha, beta,
-                       (int)off, (int)nt, sig_dev);
+    if (lim)
+        hipLaunchKernelGGL(gemm_nt_f64_trap_signal_kernel<true>, dim3((unsigned)nwg), dim3(256), 0, s, A, (long)lda, B, (long)ldb, C, (long)ldc, (int)K, alpha,
+                           beta, (int)off, (int)nt, sig_dev, (int)wt);
+    else
+        hipLaunchKernelGGL(gemm_nt_f64_trap_signal_kernel<false>, dim3((unsigned)nwg), dim3(256), 0, s, A, (long)lda, B, (long)ldb, C, (long)ldc, (int)K, alpha,
+                           beta, (int)off, (int)nt, sig_dev, (int)nt);
     GPX_HIP(hipGetLastError());
     return 0;
 }

@@ -124,6 +124,7 @@ SIGNATURES = {
     "gpx_bench_mfma_f64": (_int, [_int, ctypes.POINTER(_dbl)]),
     "gpx_bench_emu_i8": (_int, [_i64, _i64, _i64, _int, _int, ctypes.POINTER(_dbl)]),
     "gpx_emu_gemm_nt_sub": (_int, [_dp, _i64, _dp, _i64, _dp, _i64, _i64, _i64, _i64]),
+    "gpx_emu_syrk_lower_sub": (_int, [_dp, _i64, _i64, _i64, _dp, _i64, _i64]),
     "gpx_emu_rebuild": (_int, [_dp, _i64, _i64, _int, _dp, _dp, _dp, _i64, _i64, _i64]),
     "gpx_emu_i8_gemm": (_int, [_dp, _dp, _i64, _i64, _i64, _int, _dp]),
     "gpx_emu_i8_gemm_ld": (_int, [_dp, _i64, _dp, _i64, _i64, _i64, _int, _dp, _i64]),

@@ -24,6 +24,9 @@ def short(n):
         return "G44P"
     if "trap_signal" in n:
         return "TRAP"
+    for frag, name in (("emu_i8_gemm", "EMU-I8"), ("emu_rebuild", "EMU-RB"), ("emu_split", "EMU-SP"), ("emu_row_scale", "EMU-SC")):   # a group boundary's items
+        if frag in n:
+            return name
     m = re.search(r"gemm_nt_f64_kernelILi(\d)ELi(\d)ELb(\d)", n)
     if m:
         return "G%s%s%s" % (m.group(1), m.group(2), "L" if m.group(3) == "1" else "")

@@ -2,7 +2,8 @@
 // runtime call it makes (launches, event records, stream waits, memsets, synchronisations) and every external launcher it calls is
 // replaced by a function that prints one line -- streams, events (numbered by first use) and pointers (as offsets) by name.  Needs no GPU.
 //   hipcc -O1 -std=c++17 --offload-arch=gfx950 -I<tree>/scikit-gpuppy_amd/csrc -DCHOL_PATH='"<tree>/scikit-gpuppy_amd/csrc/chol.hip"' \
-//         -x hip replay_chol.hip -o replay          (a tree from before fills.hip / the three-argument panel hook: add -DREPLAY_R10_TREE)
+//         -x hip replay_chol.hip -o replay          (a tree from before fills.hip / the three-argument panel hook: add -DREPLAY_R10_TREE;
+//                                                    from before the far columns by group: -DREPLAY_NO_FIT_EMU)
 //   GPX_CONCURRENT_STREAMS=1 [GPX_SQK_FROM=.. ...] ./replay NBLK MODE > log
 //   MODE 0: chol_factor on one stream, 1: with a chain stream, 2: chain + column streams; 3 .. 6: the panel step over all panels
 //   (3: internal slice stream, 4: caller streams, no head rows, 5 / 6: caller streams, head rows, two / three ranks share the update).
@@ -27,13 +28,30 @@ int launch_gemm_nt(const double *A, int64_t lda, const double *B, int64_t ldb, d
     printf("gemm s%d A%ld B%ld C%ld %ld %ld %ld a%g b%g lo%d kt%d tri%d sm%d\n", sid(s), off(A), off(B), off(C), (long)M, (long)N, (long)K, alpha, beta, lower_only, ktrim, tri, small_tiles);
     return 0;
 }
+#ifdef REPLAY_NO_FIT_EMU   // a tree from before the far columns by group (no tri_cols, no emu_syrk_*)
 int launch_syrk_trap_signal(const double *A, int64_t, const double *B, int64_t, double *C, int64_t, int64_t M, int64_t oc, int64_t K, double, double, int *sig,
                             hipStream_t s, Profiler *)
 {
+    const int64_t tc = 0;
+#else
+int launch_syrk_trap_signal(const double *A, int64_t, const double *B, int64_t, double *C, int64_t, int64_t M, int64_t oc, int64_t K, double, double, int *sig,
+                            hipStream_t s, Profiler *, int64_t tc)
+{
+#endif
     if (getenv("MOCK_TRAP_FAIL")) return GPX_ERR_STATE;
-    printf("trap s%d A%ld B%ld C%ld %ld %ld %ld sig%ld\n", sid(s), off(A), off(B), off(C), (long)M, (long)oc, (long)K, off(sig));
+    printf("trap s%d A%ld B%ld C%ld %ld %ld %ld sig%ld", sid(s), off(A), off(B), off(C), (long)M, (long)oc, (long)K, off(sig));
+    if (tc > 0 && tc < M) printf(" cols%ld", (long)tc);
+    printf("\n");
     return 0;
 }
+#ifndef REPLAY_NO_FIT_EMU
+bool emu_enabled(int64_t K) { const char *e = getenv("GPX_EMU_MIN_K"); return K >= (e ? atol(e) : 4096L) && K % 128 == 0; }
+void emu_syrk_plan(EmuSyrk &w, int64_t rows, int64_t K, int64_t) { w.rows_pad = rows; w.K = K; }
+int emu_syrk_alloc(EmuSyrk &) { return getenv("MOCK_EMU_NO_ROOM") ? GPX_ERR_HIP : 0; }
+void emu_syrk_free(EmuSyrk &) {}
+int emu_syrk_split(const EmuSyrk &w, const double *A, int64_t, int64_t rows, hipStream_t s) { printf("emu-split s%d A%ld %ld %ld\n", sid(s), off(A), (long)rows, (long)w.K); return 0; }
+int emu_syrk_panel(const EmuSyrk &w, int64_t q, double *C, int64_t, int64_t rows, hipStream_t s, Profiler *, int dt) { printf("emu-panel s%d q%ld C%ld %ld %ld dt%d\n", sid(s), (long)q, off(C), (long)rows, (long)w.K, dt); return 0; }
+#endif
 int64_t chol_dataflow_state_ints(int64_t nbr) { return 41 * nbr; }
 int64_t chol_dataflow_table_ints(int64_t nbr) { return 12 * nbr; }
 bool chol_dataflow_supported(int64_t nbr) { return nbr <= 128; }
