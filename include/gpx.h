@@ -451,6 +451,14 @@ int gpx_emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t l
  * section 5.1).  Nothing above the diagonal is written.  Arguments as gpx_emu_gemm_nt_sub with B = A, cols = rows; tile_rows > 0: a
  * smaller row tile of the image (rounded up to 1024), for tests.  Synchronous. */
 int gpx_emu_syrk_lower_sub(const double *A, int64_t lda, int64_t rows, int64_t K, double *C, int64_t ldc, int64_t tile_rows);
+/* The same as the factorisation calls it (tests); gpx_emu_syrk_lower_sub is the (diag_tile, plan_rows) = (1, 0) call of it.
+ * diag_tile (1, or a power of two that divides 1024): row i ends at the last column of its diag_tile x diag_tile diagonal block, column
+ * min(rows - 1, i | (diag_tile - 1)) -- the diagonal blocks are updated in full, above the diagonal too, and nothing else above it is
+ * written.  plan_rows (0, or at least rows): when larger than rows, the workspace is planned and allocated for plan_rows rows and planned
+ * again for `rows` before the split, the order in which the factorisation reuses one allocation for every later, smaller update; the
+ * result does not depend on it.  Other values: GPX_ERR_BAD_ARG before anything is allocated or queued. */
+int gpx_emu_syrk_lower_sub_ex(const double *A, int64_t lda, int64_t rows, int64_t K, double *C, int64_t ldc, int64_t tile_rows, int diag_tile,
+                              int64_t plan_rows);
 /* The two integer kernels of the emulated update alone, on device buffers (tests).  Synchronous.
  * gpx_emu_rebuild: C[rows, cols] -= X 2^-(sa[row] + sb[col]), X the integer in [-P/2, P/2) whose residues modulo the first nmod
  * (2 .. 16) moduli are the bytes R[l * sr + row * ldr + col]; a scale of 0x7fffffff marks a non-finite row or column (NaN).  ldr and sr
@@ -459,6 +467,10 @@ int gpx_emu_syrk_lower_sub(const double *A, int64_t lda, int64_t rows, int64_t K
  * A [nmod][rows][K], B [nmod][cols][K], R [nmod][rows][cols]; rows, cols multiples of 256, K of 128 below 2^17, A and B 16-byte aligned. */
 int gpx_emu_rebuild(const int8_t *R, int64_t ldr, int64_t sr, int nmod, const int *sa, const int *sb, double *C, int64_t ldc, int64_t rows,
                     int64_t cols);
+/* gpx_emu_rebuild with the row end the symmetric update uses: row i is updated up to column min(cols - 1, (i + diag) | dmask) and not
+ * beyond (nothing where that is negative); dmask + 1 is a power of two, |diag| <= 2^40.  gpx_emu_rebuild is the (2^40, 0) call of it. */
+int gpx_emu_rebuild_ex(const int8_t *R, int64_t ldr, int64_t sr, int nmod, const int *sa, const int *sb, double *C, int64_t ldc, int64_t rows,
+                       int64_t cols, int64_t diag, int64_t dmask);
 int gpx_emu_i8_gemm(const int8_t *A, const int8_t *B, int64_t rows, int64_t cols, int64_t K, int nmod, int8_t *R);
 /* the same with the kernel's strides: planes A [nmod][rows][lda] (lda >= K, a multiple of 16, 255 lda + K < 2^31) and R [nmod][rows][ldr]
  * (ldr >= cols); R and ldr need no alignment (the residues are stored byte by byte).
@@ -513,6 +525,13 @@ int gpx_dev_gemm_nt(const double *A, int64_t lda, const double *B, int64_t ldb, 
  * the shape is too small for this launch. */
 int gpx_dev_syrk_trap(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t M, int64_t off_cols,
                       int64_t K, double alpha, double beta, int *count_dev, void *stream);
+/* the same with the triangle's columns ending at tri_cols (a multiple of 128 in 0 .. M, else GPX_ERR_BAD_ARG; 0 and M: all of it, the
+ * launch above): the near-only update of the factorisation.  Written is C [M, off_cols + tri_cols], by 128-tiles: tile row r holds
+ * off_cols / 128 + min(r + 1, tri_cols / 128) tiles -- the first off_cols columns in full, then the lower triangle up to its tile column
+ * tri_cols / 128, below which every row holds all tri_cols columns; nothing right of that is read or written.  The counters and
+ * GPX_ERR_STATE as above.  gpx_dev_syrk_trap is the tri_cols = 0 call of it. */
+int gpx_dev_syrk_trap_cols(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t M, int64_t off_cols,
+                           int64_t K, double alpha, double beta, int64_t tri_cols, int *count_dev, void *stream);
 /* (lower_only: only the 128-tiles on/below the diagonal of a square C are computed; with N > M the first N - M columns are
  * full and the remaining M x M square is lower-triangular by tiles) */
 

@@ -410,7 +410,7 @@ void emu_syrk_free(EmuSyrk &w);
 int emu_syrk_split(const EmuSyrk &w, const double *A, int64_t lda, int64_t rows, hipStream_t s);
 int emu_syrk_panel(const EmuSyrk &w, int64_t q, double *C, int64_t ldc, int64_t rows, hipStream_t s, Profiler *prof, int diag_tile = 1);
 int emu_syrk_lower_sub(const double *A, int64_t lda, int64_t rows, int64_t K, double *C, int64_t ldc, const EmuSyrk &w, hipStream_t s, Profiler *prof,
-                       const hipEvent_t *panel_done = nullptr);
+                       const hipEvent_t *panel_done = nullptr, int diag_tile = 1);
 
 // The left-looking form of the many-row solve (tsolve.hip, trsm_right_lt_slabs): every solved slab is split ONCE into a persistent
 // residue image, with a row scale derived from a bound on the whole solved row that the caller knows at entry; slab p then takes one

@@ -862,12 +862,12 @@ int emu_syrk_panel(const EmuSyrk &w, int64_t q, double *C, int64_t ldc, int64_t 
 
 // the whole update on s, column panels in ascending order; panel_done (optional, one event per column panel): recorded behind each
 int emu_syrk_lower_sub(const double *A, int64_t lda, int64_t rows, int64_t K, double *C, int64_t ldc, const EmuSyrk &w, hipStream_t s, Profiler *prof,
-                       const hipEvent_t *panel_done)
+                       const hipEvent_t *panel_done, int diag_tile)
 {
     if (rows <= 0) return 0;
     GPX_TRY(emu_syrk_split(w, A, lda, rows, s));
     for (int64_t q = 0; q * EMU_SLAB < rows; ++q) {
-        GPX_TRY(emu_syrk_panel(w, q, C, ldc, rows, s, prof, 1));
+        GPX_TRY(emu_syrk_panel(w, q, C, ldc, rows, s, prof, diag_tile));
         if (panel_done) GPX_HIP(hipEventRecord(panel_done[q], s));
     }
     return 0;
@@ -875,19 +875,31 @@ int emu_syrk_lower_sub(const double *A, int64_t lda, int64_t rows, int64_t K, do
 
 // ---- C-ABI: the emulated product on caller device buffers (tests), the int8 product kernel alone on random residues (its rate) -------
 // the symmetric update: any K that is a multiple of 128 below 2^17; tile_rows > 0: a smaller row tile (rounded up to 1024), for tests
-extern "C" int gpx_emu_syrk_lower_sub(const double *A, int64_t lda, int64_t rows, int64_t K, double *C, int64_t ldc, int64_t tile_rows)
+// diag_tile: emu_syrk_panel's; plan_rows > rows: the workspace is planned and allocated for plan_rows rows and planned again for `rows`
+// before the split, as the factorisation does for every group boundary after its largest (chol.hip)
+extern "C" int gpx_emu_syrk_lower_sub_ex(const double *A, int64_t lda, int64_t rows, int64_t K, double *C, int64_t ldc, int64_t tile_rows, int diag_tile,
+                                         int64_t plan_rows)
 {
     GPX_TRY(gpx_require_device());
-    if (rows < 0 || tile_rows < 0 || !A || !C) { gpx_set_error("gpx_emu_syrk_lower_sub: bad arguments"); return GPX_ERR_BAD_ARG; }
+    if (rows < 0 || tile_rows < 0 || !A || !C || diag_tile < 1 || (diag_tile & (diag_tile - 1)) || EMU_SLAB % diag_tile || (plan_rows && plan_rows < rows)) {
+        gpx_set_error("gpx_emu_syrk_lower_sub: bad arguments");
+        return GPX_ERR_BAD_ARG;
+    }
     GPX_TRY(emu_check_args(A, lda, A, lda, ldc, rows, K));
     if (rows == 0) return 0;
     EmuSyrk w;
-    emu_syrk_plan(w, rows, K, tile_rows);
+    emu_syrk_plan(w, std::max(rows, plan_rows), K, tile_rows);
     if (emu_syrk_alloc(w)) return GPX_ERR_HIP;
-    int rc = emu_syrk_lower_sub(A, lda, rows, K, C, ldc, w, 0, nullptr, nullptr);
+    if (plan_rows > rows) emu_syrk_plan(w, rows, K, tile_rows);
+    int rc = emu_syrk_lower_sub(A, lda, rows, K, C, ldc, w, 0, nullptr, nullptr, diag_tile);
     if (hipStreamSynchronize(0) != hipSuccess && rc == 0) { gpx_set_error("gpx_emu_syrk_lower_sub: stream failed"); rc = GPX_ERR_HIP; }
     emu_syrk_free(w);
     return rc;
+}
+
+extern "C" int gpx_emu_syrk_lower_sub(const double *A, int64_t lda, int64_t rows, int64_t K, double *C, int64_t ldc, int64_t tile_rows)
+{
+    return gpx_emu_syrk_lower_sub_ex(A, lda, rows, K, C, ldc, tile_rows, 1, 0);
 }
 
 extern "C" int gpx_emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t rows, int64_t cols,
@@ -907,23 +919,30 @@ extern "C" int gpx_emu_gemm_nt_sub(const double *A, int64_t lda, const double *B
 }
 
 // The two integer kernels alone on caller device buffers (tests/test_emulated_rebuild.py).  Synchronous.
-extern "C" int gpx_emu_rebuild(const int8_t *R, int64_t ldr, int64_t sr, int nmod, const int *sa, const int *sb, double *C, int64_t ldc, int64_t rows,
-                               int64_t cols)
+// diag, dmask: the kernel's -- row i ends at column (i + diag) | dmask (dmask + 1 a power of two), or at cols - 1 if that is smaller
+extern "C" int gpx_emu_rebuild_ex(const int8_t *R, int64_t ldr, int64_t sr, int nmod, const int *sa, const int *sb, double *C, int64_t ldc, int64_t rows,
+                                  int64_t cols, int64_t diag, int64_t dmask)
 {
     GPX_TRY(gpx_require_device());
     // the kernel reads four residue bytes at once, also in the column tail: rows of R are 4-byte aligned and padded to a multiple of 4
     if (!R || !sa || !sb || !C || rows < 0 || cols < 0 || nmod < 2 || nmod > EMU_MAXL || ldr < round_up(cols, 4) || (ldr | sr) & 3 ||
-        (uintptr_t)R & 3 || sr < rows * ldr || ldc < cols) {
+        (uintptr_t)R & 3 || sr < rows * ldr || ldc < cols || dmask < 0 || (dmask & (dmask + 1)) || diag < -EMU_NO_DIAG || diag > EMU_NO_DIAG) {
         gpx_set_error("gpx_emu_rebuild: bad arguments");
         return GPX_ERR_BAD_ARG;
     }
     if (rows == 0 || cols == 0) return 0;
     const long thr = (long)rows * ((cols + 3) / 4);
     hipLaunchKernelGGL(emu_rebuild_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, 0, R, (long)ldr, (long)sr, nmod, emu_crt.t[nmod], sa, sb, C,
-                       (long)ldc, (long)rows, (long)cols, EMU_NO_DIAG, 0L);
+                       (long)ldc, (long)rows, (long)cols, (long)diag, (long)dmask);
     GPX_HIP(hipGetLastError());
     GPX_HIP(hipStreamSynchronize(0));
     return 0;
+}
+
+extern "C" int gpx_emu_rebuild(const int8_t *R, int64_t ldr, int64_t sr, int nmod, const int *sa, const int *sb, double *C, int64_t ldc, int64_t rows,
+                               int64_t cols)
+{
+    return gpx_emu_rebuild_ex(R, ldr, sr, nmod, sa, sb, C, ldc, rows, cols, EMU_NO_DIAG, 0);
 }
 
 // The two splits alone on caller device buffers (tests/test_emulated_split.py).  Synchronous.

@@ -622,8 +622,14 @@ extern "C" int gpx_dev_syrk_splitk(const double *W, int64_t ldw, const double *W
     return launch_syrk_lower_splitk(W, ldw, parts, m, kchunk, nchunks, alpha, (hipStream_t)stream, W2);
 }
 
+extern "C" int gpx_dev_syrk_trap_cols(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t M, int64_t off_cols,
+                                      int64_t K, double alpha, double beta, int64_t tri_cols, int *count_dev, void *stream)
+{
+    return launch_syrk_trap_signal(A, lda, B, ldb, C, ldc, M, off_cols, K, alpha, beta, count_dev, (hipStream_t)stream, nullptr, tri_cols);
+}
+
 extern "C" int gpx_dev_syrk_trap(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t M, int64_t off_cols,
                                  int64_t K, double alpha, double beta, int *count_dev, void *stream)
 {
-    return launch_syrk_trap_signal(A, lda, B, ldb, C, ldc, M, off_cols, K, alpha, beta, count_dev, (hipStream_t)stream, nullptr);
+    return gpx_dev_syrk_trap_cols(A, lda, B, ldb, C, ldc, M, off_cols, K, alpha, beta, 0, count_dev, stream);
 }

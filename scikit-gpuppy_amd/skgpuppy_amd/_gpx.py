@@ -125,7 +125,9 @@ SIGNATURES = {
     "gpx_bench_emu_i8": (_int, [_i64, _i64, _i64, _int, _int, ctypes.POINTER(_dbl)]),
     "gpx_emu_gemm_nt_sub": (_int, [_dp, _i64, _dp, _i64, _dp, _i64, _i64, _i64, _i64]),
     "gpx_emu_syrk_lower_sub": (_int, [_dp, _i64, _i64, _i64, _dp, _i64, _i64]),
+    "gpx_emu_syrk_lower_sub_ex": (_int, [_dp, _i64, _i64, _i64, _dp, _i64, _i64, _int, _i64]),
     "gpx_emu_rebuild": (_int, [_dp, _i64, _i64, _int, _dp, _dp, _dp, _i64, _i64, _i64]),
+    "gpx_emu_rebuild_ex": (_int, [_dp, _i64, _i64, _int, _dp, _dp, _dp, _i64, _i64, _i64, _i64, _i64]),
     "gpx_emu_i8_gemm": (_int, [_dp, _dp, _i64, _i64, _i64, _int, _dp]),
     "gpx_emu_i8_gemm_ld": (_int, [_dp, _i64, _dp, _i64, _i64, _i64, _int, _dp, _i64]),
     "gpx_emu_split": (_int, [_dp, _i64, _i64, _i64, _i64, _int, _int, _dp, _i64, _dp]),
@@ -143,6 +145,7 @@ SIGNATURES = {
                                        _dbl, _i64, ctypes.c_void_p]),
     "gpx_dev_syrk_splitk": (_int, [_dp, _i64, _dp, _dp, _i64, _i64, _int, _dbl, ctypes.c_void_p]),
     "gpx_dev_syrk_trap": (_int, [_dp, _i64, _dp, _i64, _dp, _i64, _i64, _i64, _i64, _dbl, _dbl, ctypes.c_void_p, ctypes.c_void_p]),
+    "gpx_dev_syrk_trap_cols": (_int, [_dp, _i64, _dp, _i64, _dp, _i64, _i64, _i64, _i64, _dbl, _dbl, _i64, ctypes.c_void_p, ctypes.c_void_p]),
     "gpx_dev_potrf_leaf": (_int, [_dp, _i64, _dp, _dp, ctypes.c_void_p, _int, ctypes.c_void_p]),
     "gpx_dev_chol_panel": (_int, [_dp, _i64, _i64, _i64, _i64, _dp, _dp, ctypes.c_void_p, ctypes.c_void_p]),
     "gpx_dev_chol_panel_next": (_int, [_dp, _i64, _i64, _i64, _i64, _dp, _i64, _i64, _dp, _dp, ctypes.c_void_p, ctypes.c_void_p]),

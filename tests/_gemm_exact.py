@@ -148,8 +148,14 @@ def mask_lower(M, N):
     return np.where(j < i + off, WRITTEN, np.where(j == i + off, DIAGONAL, UNTOUCHED)).astype(np.int8)
 
 
-def mask_trapezoid(M, off_cols):
-    return mask_lower(M, off_cols + M)
+def mask_trapezoid(M, off_cols, tri_cols=0):
+    """tri_cols (0 or M: all): the triangle's columns end there -- tile row r holds off_cols / 128 + min(r + 1, tri_cols / 128) tiles, the
+    last of them a diagonal tile only where the triangle still runs (r < tri_cols / 128); the rows below are written in full"""
+    assert 0 <= tri_cols <= M and tri_cols % TILE == 0
+    m = mask_lower(M, off_cols + M)
+    if 0 < tri_cols < M:
+        m[:, (off_cols + tri_cols) // TILE:] = UNTOUCHED
+    return m
 
 
 def mask_splitk(m, nchunks):

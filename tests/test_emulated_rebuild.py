@@ -155,6 +155,92 @@ def test_rebuild_nonfinite_scale_marks_its_row_or_column(L):
     assert (got[:, :, COLS:] == C0[:, :, COLS:]).all()
 
 
+# ---- the row end of the symmetric update: row i stops behind column (i + diag) | dmask -------------------------------------
+DIAGS, DMASKS = (0, 5, 256, -3), (0, 31, 127)
+
+
+def row_end_mask(rows, cols, diag, dmask):
+    """True where gpx_emu_rebuild_ex updates: column j of row i for j <= (i + diag) | dmask (Python's | on negative integers is the
+    two's-complement one the kernel computes: (-3) | 31 = -1, a row that ends before column 0)"""
+    return np.array([[j <= ((i + diag) | dmask) for j in range(cols)] for i in range(rows)])
+
+
+def test_row_end_mask():
+    m = row_end_mask(12, 5, -3, 0)
+    assert not m[:3].any() and m[3].tolist() == [True, False, False, False, False] and m[7:].all()
+    assert not row_end_mask(12, 5, -3, 31)[:3].any() and row_end_mask(12, 5, -3, 31)[3:].all()
+    assert (row_end_mask(12, 5, 0, 0) == np.tril(np.ones((12, 5), bool))).all()
+    m = row_end_mask(140, 130, 0, 127)
+    assert m[:128, :128].all() and not m[:128, 128:].any() and m[128:].all()
+    assert row_end_mask(140, 130, 256, 0).all() and row_end_mask(140, 130, 5, 31).sum(1)[[0, 26, 27, 122, 123]].tolist() == [32, 32, 64, 128, 130]
+    # diag = 0, -3 and 5 without a mask end a row at every position inside a thread's four columns, in both shapes
+    for rows, cols in ((12, 5), (140, 130)):
+        ends = set(int(e) % 4 for d in (0, 5, -3) for e in row_end_mask(rows, cols, d, 0).sum(1) if 0 < e < cols)
+        assert ends == {0, 1, 2, 3}, (rows, cols, ends)
+
+
+def _shaped_case(rows, cols, ldr, seed):
+    """(residues [16][rows][ldr] int8, sigma [rows], tau [cols], fl(X) [rows][cols]): the chosen integers, row by row, as often as they fit"""
+    rng = np.random.default_rng(seed)
+    xs = _chosen_integers(16, rng)
+    res = rng.integers(-128, 128, (16, rows, ldr), dtype=np.int8)      # the padding columns hold junk the kernel must not use
+    xd = np.empty((rows, cols))
+    for n in range(rows * cols):
+        X = xs[n % len(xs)]
+        i, j = divmod(n, cols)
+        res[:, i, j] = [balanced(X, p) for p in MODULI[:16]]
+        xd[i, j] = _convert(X)
+    return res, rng.integers(-30, 70, rows).astype(np.int32), rng.integers(-30, 70, cols).astype(np.int32), xd
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rows,cols,ldr,ldc", [(12, 5, 12, 7), (140, 130, 136, 133)])
+def test_rebuild_row_end_bit_for_bit(rows, cols, ldr, ldc):
+    """16 moduli; cols no multiple of 4, so that a row's end falls at every position inside a thread's four columns: up to the row end
+    the existing model to the bit, behind it C0's bits -- NaN, then a sentinel pattern"""
+    from conftest import torch
+    from skgpuppy_amd import _gpx
+    res, sig, tau, xd = _shaped_case(rows, cols, ldr, 300 + cols)
+    term = np.ldexp(xd, -(sig[:, None] + tau[None, :]))
+    rng = np.random.default_rng(cols)
+    inside = term * rng.standard_normal(term.shape) + rng.standard_normal(term.shape)
+    r, s, t = (torch.as_tensor(np.ascontiguousarray(v)).cuda() for v in (res, sig, tau))
+    p = lambda x: ctypes.c_void_p(x.data_ptr())
+    sentinel = 3.0 + (np.arange(rows * cols) % 509).reshape(rows, cols) / 512.0
+    for dmask in DMASKS:
+        for diag in DIAGS:
+            m = row_end_mask(rows, cols, diag, dmask)
+            for name, beyond in (("NaN", np.full((rows, cols), np.nan)), ("sentinel", sentinel)):
+                C0 = np.full((rows, ldc), 7.25)                          # beyond the row of the window: untouched
+                C0[:, :cols] = np.where(m, inside, beyond)
+                want = C0.copy()
+                want[:, :cols] = np.where(m, C0[:, :cols] - term, beyond)
+                c = torch.as_tensor(C0).cuda()
+                _gpx.check(_gpx.lib.gpx_emu_rebuild_ex(p(r), ldr, rows * ldr, 16, p(s), p(t), p(c), ldc, rows, cols, diag, dmask), "gpx_emu_rebuild_ex")
+                got = c.cpu().numpy()
+                bad = _bits(got) != _bits(want)
+                assert not bad.any(), (diag, dmask, name, int(bad.sum()), np.argwhere(bad)[:5], got[bad][:5], want[bad][:5])
+            print("%d x %d diag %d dmask %d: %d of %d entries updated" % (rows, cols, diag, dmask, m.sum(), m.size))
+    # the full rectangle through the new entry is gpx_emu_rebuild
+    C0 = np.full((rows, ldc), 7.25)
+    C0[:, :cols] = inside
+    c1, c2 = torch.as_tensor(C0).cuda(), torch.as_tensor(C0).cuda()
+    _gpx.check(_gpx.lib.gpx_emu_rebuild(p(r), ldr, rows * ldr, 16, p(s), p(t), p(c1), ldc, rows, cols), "gpx_emu_rebuild")
+    _gpx.check(_gpx.lib.gpx_emu_rebuild_ex(p(r), ldr, rows * ldr, 16, p(s), p(t), p(c2), ldc, rows, cols, 2 ** 40, 0), "gpx_emu_rebuild_ex")
+    assert (_bits(c1.cpu().numpy()) == _bits(c2.cpu().numpy())).all()
+
+
+@pytest.mark.gpu
+def test_rebuild_ex_refuses_a_mask_that_is_no_power_of_two_minus_one():
+    from conftest import torch
+    from skgpuppy_amd import _gpx
+    r, s, c = torch.zeros(16 * 4 * 8, dtype=torch.int8).cuda(), torch.zeros(8, dtype=torch.int32).cuda(), torch.full((4 * 8,), 1.5, dtype=torch.float64).cuda()
+    p = lambda x: ctypes.c_void_p(x.data_ptr())
+    for diag, dmask in ((0, 2), (0, 126), (0, -1), (2 ** 41, 0), (-2 ** 41, 0)):
+        assert _gpx.lib.gpx_emu_rebuild_ex(p(r), 8, 32, 16, p(s), p(s), p(c), 8, 4, 8, diag, dmask) == _gpx.GPX_ERR_BAD_ARG, (diag, dmask)
+    assert bool((c == 1.5).all())
+
+
 # ---- the int8 product --------------------------------------------------------------------------------------------------
 _MAXR, _MAXC, _MAXK = 512, 768, 384
 

@@ -14,6 +14,7 @@ import pytest
 from conftest import torch
 
 import _gemm_exact as gx
+import _trap_model as tm
 from skgpuppy_amd import _gpx
 
 pytestmark = pytest.mark.gpu
@@ -362,19 +363,26 @@ def test_syrk_splitk(kchunk, nchunks, with_w2):
 
 
 # ---- the trapezoid launch with its counters --------------------------------------------------------------------------------------------------
-def _trap_setup(M, off_cols, K):
+def _trap_setup(M, off_cols, K, tri_cols=0):
+    """tri_cols in (0, M): the rows of B behind the triangle's last column hold NaN -- the launch must not read them"""
     rng = np.random.RandomState(_seed(M, off_cols, K))
     N = off_cols + M
     A, B, C0 = gx.operands(rng, M, N, K)
     alpha, beta = gx.scalars(rng)
     wa, wb, wc = gx.windows(M, N, K)
-    return dict(N=N, A=A, B=B, C0=C0, alpha=alpha, beta=beta, wa=wa, wb=wb, wc=wc, abuf=wa.new(A), bbuf=wb.new(B))
+    Bdev = B.copy()
+    if 0 < tri_cols < M:
+        Bdev[off_cols + tri_cols:] = np.nan
+    return dict(N=N, A=A, B=B, C0=C0, alpha=alpha, beta=beta, wa=wa, wb=wb, wc=wc, abuf=wa.new(A), bbuf=wb.new(Bdev))
 
 
-def _trap_launch(s, M, off_cols, K, count):
+def _trap_launch(s, M, off_cols, K, count, tri_cols=None):
+    """tri_cols None: gpx_dev_syrk_trap, else gpx_dev_syrk_trap_cols"""
     da, db, dc = _up(s["abuf"]), _up(s["bbuf"]), _up(s["wc"].new(s["C0"]))
-    st = lib.gpx_dev_syrk_trap(_at(da, s["wa"].offset), s["wa"].ld, _at(db, s["wb"].offset), s["wb"].ld, _at(dc, s["wc"].offset), s["wc"].ld,
-                               M, off_cols, K, s["alpha"], s["beta"], _at(count) if count is not None else None, None)
+    args = (_at(da, s["wa"].offset), s["wa"].ld, _at(db, s["wb"].offset), s["wb"].ld, _at(dc, s["wc"].offset), s["wc"].ld, M, off_cols, K, s["alpha"],
+            s["beta"])
+    cnt = _at(count) if count is not None else None
+    st = lib.gpx_dev_syrk_trap(*args, cnt, None) if tri_cols is None else lib.gpx_dev_syrk_trap_cols(*args, tri_cols, cnt, None)
     return st, da, db, dc
 
 
@@ -403,6 +411,65 @@ def test_syrk_trap_too_small_is_refused():
     assert st == _gpx.GPX_ERR_STATE
     assert gx.same_bits(_down(dc), s["wc"].new(s["C0"]))
     assert _down(count).tolist() == [0] * 8 + [7] * 4
+
+
+def _trap_case_id(c):
+    return "off%d-nt%d-wt%d" % c
+
+
+@pytest.mark.parametrize("off,nt,wt", tm.DEVICE_CASES, ids=[_trap_case_id(c) for c in tm.DEVICE_CASES])
+def test_syrk_trap_cols(off, nt, wt):
+    """the column-limited launch (gemm_nt_f64_trap_signal_kernel<true>) alone, at the smallest shapes the launcher accepts: tile row r
+    holds off + min(r + 1, wt) tiles, everything right of that keeps C0, the rows of B the launch has no tile for are NaN"""
+    M, off_cols, tri_cols, K = nt * 128, off * 128, wt * 128, 48
+    assert tm.accepts(off, nt, wt) and tm.shape(off, nt, wt)[0]
+    s = _trap_setup(M, off_cols, K, tri_cols)
+    assert np.isnan(s["bbuf"]).any()
+    want = gx.reference(s["A"], s["B"], s["C0"], s["alpha"], s["beta"])
+    written = gx.mask_trapezoid(M, off_cols, tri_cols)
+    assert ((written != gx.UNTOUCHED) == tm.mask(off, nt, wt)).all()
+    for with_count in (True, False):
+        count = _up(np.array([0] * off + [7] * 4, dtype=np.int32)) if with_count else None
+        st, da, db, dc = _trap_launch(s, M, off_cols, K, count, tri_cols)
+        assert st == 0, "the launcher refuses a shape the model accepts: %d, %s" % (st, _gpx.last_error())
+        got = _down(dc)
+        gx.check(s["wc"].view(got), want, s["C0"], written, guards=[(got, s["wc"], "C")])
+        assert gx.same_bits(_down(da), s["abuf"]) and gx.same_bits(_down(db), s["bbuf"])
+        if with_count:
+            assert _down(count).tolist() == [nt] * off + [7] * 4
+
+
+@pytest.mark.parametrize("off,nt,wt", tm.REFUSED_CASES, ids=[_trap_case_id(c) for c in tm.REFUSED_CASES])
+def test_syrk_trap_cols_one_tile_row_too_small_is_refused(off, nt, wt):
+    """one tile row fewer than the smallest shape the rule accepts with this width: GPX_ERR_STATE, as the model decides, and nothing is touched"""
+    M, off_cols, tri_cols, K = nt * 128, off * 128, wt * 128, 48
+    assert not tm.accepts(off, nt, wt) and tm.accepts(off, nt + 1, wt)
+    s = _trap_setup(M, off_cols, K, tri_cols)
+    count = _up(np.array([0] * off + [7] * 4, dtype=np.int32))
+    st, da, db, dc = _trap_launch(s, M, off_cols, K, count, tri_cols)
+    assert st == _gpx.GPX_ERR_STATE
+    assert gx.same_bits(_down(dc), s["wc"].new(s["C0"]))
+    assert gx.same_bits(_down(da), s["abuf"]) and gx.same_bits(_down(db), s["bbuf"])
+    assert _down(count).tolist() == [0] * off + [7] * 4
+
+
+def test_syrk_trap_cols_without_a_limit_is_syrk_trap():
+    """tri_cols = 0 and tri_cols = M: the bytes of gpx_dev_syrk_trap, counters included (10 tile rows, one full column: the smallest
+    shape the rule accepts without a limit)"""
+    off, nt, K = 1, 10, 48
+    M, off_cols = nt * 128, off * 128
+    assert tm.accepts(off, nt, nt) and not tm.accepts(off, nt - 1, nt - 1)
+    s = _trap_setup(M, off_cols, K)
+    out = []
+    for tri_cols in (None, 0, M):
+        count = _up(np.array([0] * off + [7] * 4, dtype=np.int32))
+        st, _da, _db, dc = _trap_launch(s, M, off_cols, K, count, tri_cols)
+        _gpx.check(st, "gpx_dev_syrk_trap_cols")
+        out.append((_down(dc), _down(count).tolist()))
+    gx.check(s["wc"].view(out[0][0]), gx.reference(s["A"], s["B"], s["C0"], s["alpha"], s["beta"]), s["C0"], gx.mask_trapezoid(M, off_cols),
+             guards=[(out[0][0], s["wc"], "C")])
+    for got, counters in out[1:]:
+        assert gx.same_bits(got, out[0][0]) and counters == out[0][1] == [nt] * off + [7] * 4
 
 
 # ---- refusals ----------------------------------------------------------------------------------------------------------------------------------
@@ -446,7 +513,20 @@ def test_refusals_leave_c_untouched():
         assert st == _gpx.GPX_ERR_BAD_ARG, name
         assert variant == V["NONE"], name
         assert _gpx.last_error(), name
-    assert gx.same_bits(_down(dc), cbuf) and gx.same_bits(_down(da), a0)
+    # the trapezoid's column limit: negative, no multiple of 128, beyond M (here M = 256 rows, no full columns: A, B and C as above)
+    count = _up(np.array([7] * 4, dtype=np.int32))
+
+    def trap(tri_cols, c=dc):
+        return lib.gpx_dev_syrk_trap_cols(_at(da, wa.offset), wa.ld, _at(db, wb.offset), wb.ld, _at(c, wc.offset), wc.ld, M, 0, K, 1.0, 1.0, tri_cols,
+                                          _at(count), None)
+
+    for tri_cols in (-128, -1, 64, 129, 384):
+        assert trap(tri_cols) == _gpx.GPX_ERR_BAD_ARG, tri_cols
+        assert _gpx.last_error(), tri_cols
+    assert gx.same_bits(_down(dc), cbuf) and gx.same_bits(_down(da), a0) and _down(count).tolist() == [7] * 4
+    dc2 = _up(cbuf)                                             # the same call with a limit it can have goes through, on a copy of C
+    assert trap(128, dc2) == 0
+    gx.check(wc.view(_down(dc2)), gx.reference(A, B, C0, 1.0, 1.0), C0, gx.mask_trapezoid(M, 0, 128), guards=[(_down(dc2), wc, "C")])
     st, variant = call()                                       # and the same call without a defect goes through
     assert st == 0 and variant == V["64X64"]
     gx.check(wc.view(_down(dc)), gx.reference(A, B, C0, 1.0, 1.0), C0, gx.mask_plain(M, N), guards=[(_down(dc), wc, "C")])

@@ -145,6 +145,38 @@ def test_split_k_mask():
     assert (gx.mask_trapezoid(256, 128) == np.array([[1, 2, 0], [1, 1, 2]])).all()
 
 
+def test_trapezoid_mask_with_a_column_limit():
+    import _trap_model as tm
+    # 4 tile rows, one full column, the triangle cut behind its second tile column: the rows below the cut are written in full
+    assert (gx.mask_trapezoid(512, 128, 256) == np.array([[1, 2, 0, 0, 0], [1, 1, 2, 0, 0], [1, 1, 1, 0, 0], [1, 1, 1, 0, 0]])).all()
+    for tri_cols in (0, 512):                                  # no limit, either way of saying it
+        assert (gx.mask_trapezoid(512, 128, tri_cols) == gx.mask_lower(512, 640)).all()
+    for off, nt, wt in tm.DEVICE_CASES + ((2, 5, 0), (2, 5, 5), (1, 9, 1)):
+        m = gx.mask_trapezoid(nt * 128, off * 128, wt * 128)
+        assert ((m != gx.UNTOUCHED) == tm.mask(off, nt, wt)).all(), (off, nt, wt)
+        lim_wt = tm.shape(off, nt, wt)[1]
+        assert [tuple(t) for t in np.argwhere(m == gx.DIAGONAL)] == [(r, off + r) for r in range(lim_wt)]
+    with pytest.raises(AssertionError):
+        gx.mask_trapezoid(512, 128, 640)
+    with pytest.raises(AssertionError):
+        gx.mask_trapezoid(512, 128, 64)
+
+
+def test_a_tile_right_of_the_column_limit_written_fails():
+    """what a launch that ignored tri_cols would leave: the triangle's tiles right of the limit hold the result"""
+    M, off_cols, tri_cols, K = 512, 128, 256, 16
+    rng = np.random.RandomState(9)
+    A, B, C0 = gx.operands(rng, M, off_cols + M, K)
+    want = gx.reference(A, B, C0, ALPHA, BETA)
+    lim, full = gx.mask_trapezoid(M, off_cols, tri_cols), gx.mask_trapezoid(M, off_cols)
+    ok = np.where(gx.expand(lim) != gx.UNTOUCHED, want, C0)
+    gx.check(ok, want, C0, lim)
+    with pytest.raises(AssertionError):
+        gx.check(np.where(gx.expand(full) != gx.UNTOUCHED, want, C0), want, C0, lim)
+    with pytest.raises(AssertionError):                        # and the limited result does not pass for the whole trapezoid
+        gx.check(ok, want, C0, full)
+
+
 def test_launch_codes_match_the_header():
     text = open(os.path.join(ROOT, "include", "gpx.h")).read()
     names = dict((n, tuple(int(v) for v in a.split(","))) for n, a in re.findall(r"GPX_GEMM_V_(\w+) = GPX_GEMM_VARIANT\(([^)]*)\)", text))

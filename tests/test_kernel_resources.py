@@ -55,6 +55,9 @@ def test_register_budget_of_the_cu_reservation(tmp_path):
     for frag in ("gemm_nt_f64_trap_signal_kernel", "gemm_nt_f64_kernelILi4ELi4E"):
         for k, u in pick(gemm, frag).items():
             assert alloc(u) > FREE, (k, u)
+    # both instantiations of the trapezoid kernel are among them: the whole triangle and the column-limited one (LIM)
+    trap = sorted(pick(gemm, "gemm_nt_f64_trap_signal_kernel"))
+    assert len(trap) == 2 and [("signal_kernelILb%dE" % b) in k for b, k in enumerate(trap)] == [True, True], trap
     # the chain's own small GEMMs must fit on them (two waves per SIMD)
     for frag in ("gemm_nt_f64_kernelILi2ELi2E", "gemm_nt_f64_kernelILi1ELi4E", "gemm_nt_f64_kernelILi1ELi1E"):
         for k, u in pick(gemm, frag).items():
