@@ -806,7 +806,7 @@ struct Lookahead {
     // The far columns by group (fit_emu_group): T(p) stops at the first column of the group after p's; behind a group's last panel ONE
     // emulated symmetric update of depth 1024 G brings every column right of the group up to date (group_boundary).
     int64_t G = 0;                 // panels per group; 0: every T(p) runs to the last column (the fp64 schedule)
-    EmuSyrk esy;
+    EmuFrame esy;
     bool sq_split_prev = false;   // T(p - 1) ran in the split tail form: diagonal square p + 1 has its tiles marked by ev_sqp[p - 1]
     Events events;
     hipEvent_t ev0 = nullptr, ev_blk = nullptr, ev_blk_gone = nullptr;
@@ -839,7 +839,7 @@ struct Lookahead {
         (void)hipStreamSynchronize(s);
         events.clear();
         if (sqk_buf) dfree(sqk_buf);
-        emu_syrk_free(esy);
+        emu_free(esy);
     }
     int64_t bnd(int64_t p) const { return Bs[std::min<int64_t>(p, P)]; }
     // first block column that T(p) leaves to the next group boundary (nblk: none)
@@ -890,8 +890,8 @@ struct Lookahead {
         // before it gives up) leaves the fp64 schedule, the one way the route depends on anything but size
         G = fit_emu_group(nblk);
         if (G) {
-            emu_syrk_plan(esy, (nblk - bnd(G)) * TILE, (int64_t)CHOL_PANEL_COLS * G);
-            if (emu_syrk_alloc(esy)) G = 0;
+            esy.reserve(emu_syrk_plan((nblk - bnd(G)) * TILE, (int64_t)CHOL_PANEL_COLS * G));   // the first boundary's update, the largest
+            if (emu_alloc(esy, nullptr)) G = 0;
         }
         sqk_use.assign((size_t)P, 0);
         for (int64_t pp = 0; concurrent && pp < P; ++pp)
@@ -1140,7 +1140,7 @@ struct Lookahead {
         return 0;
     }
     // Group boundary behind panel p, in the place of Q(p) and T(p): every column right of the group takes the group's columns at once,
-    // C[i, j] -= sum_k L[i, k] L[j, k] over the group's k for far <= j <= i, on the int8 path (emu.hip, emu_syrk_lower_sub's pieces).
+    // C[i, j] -= sum_k L[i, k] L[j, k] over the group's k for far <= j <= i, on the int8 path (emu.hip: emu_syrk_split, emu_syrk_panel).
     // All of it on the main stream, column panels in ascending order, so that every later T(q) -- which rewrites the same columns -- is
     // ordered behind it; the new cross-stream edges are events: the next chain and the next panel's column solves wait for column
     // panel 0 alone (ev_next, ev_tu) and run underneath the remaining column panels.  The group's rows >= far are complete: the column
@@ -1154,7 +1154,7 @@ struct Lookahead {
         GPX_TRY(drop_reservation());
         sq_split_prev = false;
         double *C = L + (B1 * TILE) * ld + B1 * TILE;
-        emu_syrk_plan(esy, rows, K);
+        esy.use(emu_syrk_plan(rows, K));
         GPX_TRY(emu_syrk_split(esy, L + (B1 * TILE) * ld + g0 * TILE, ld, rows, s));
         GPX_TRY(emu_syrk_panel(esy, 0, C, ld, rows, s, prof, TILE));
         GPX_HIP(hipEventRecord(ev_next[p], s));

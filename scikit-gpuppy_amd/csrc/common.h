@@ -310,10 +310,10 @@ struct TriSolver;
 // row sums  sum_c Zs_rc^2, sum_c Zs_rc y_c  of its columns in the slots of those columns
 // emu (estimate_many only; a workspace grown by trsm_emu_need for at least these rows): the deep updates go through emu_gemm_nt_sub
 // where emu_enabled(K) holds
-struct EmuWork;
+struct EmuFrame;
 int trsm_right_lt_squares(double *Z, double *Zs, int64_t ldz, int64_t rows, const TriSolver *ts, int64_t p0, int64_t p1,
-                          hipStream_t s, Profiler *prof, const GemmReduce *red = nullptr, const EmuWork *emu = nullptr);
-void trsm_emu_need(EmuWork &w, int64_t rows, const TriSolver *ts, int64_t p0, int64_t p1);
+                          hipStream_t s, Profiler *prof, const GemmReduce *red = nullptr, const EmuFrame *emu = nullptr);
+void trsm_emu_need(EmuFrame &w, int64_t rows, const TriSolver *ts, int64_t p0, int64_t p1);
 int launch_slab_reduce(const double *Zs, int64_t ldz, int64_t rows, int64_t width, const double *y, double *p2, double *py, int64_t nslots, int64_t slot,
                        hipStream_t s);
 int launch_predict_finish(const double *p2, const double *py, int64_t nslots, int64_t m, double vplusvt, double *mean, double *var, hipStream_t s,
@@ -383,62 +383,61 @@ struct Scratch {
 
 // fp64 product emulated on int8 matrix cores (emu.hip, Ozaki scheme II): C[rows, cols] -= A[rows, K] B[cols, K]^T, row-major;
 // K a multiple of 128 below 2^17.  emu_enabled(K): GPX_EMU_F64 (default 1) and K >= GPX_EMU_MIN_K (default 4096); the path depends on K only.
-// Workspace (int8 residues of A / B tiles, product residues, row scales): emu_work_need grows it to cover a product's shape,
-// emu_work_alloc takes it into the caller's Scratch.
-struct EmuWork { int8_t *ra = nullptr, *rb = nullptr, *rr = nullptr; int *sig = nullptr; int64_t a_bytes = 0, b_bytes = 0, r_bytes = 0, sig_n = 0; };
-void emu_work_need(EmuWork &w, int64_t rows, int64_t cols, int64_t K);
-int emu_work_alloc(EmuWork &w, Scratch &sc);
-int emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t rows, int64_t cols, int64_t K,
-                    const EmuWork &w, hipStream_t s, Profiler *prof);
 bool emu_enabled(int64_t K);
 int emu_moduli();                        // GPX_EMU_MODULI (default 16, 2 .. 16)
-int emu_scale_bits(int64_t K, int L);    // alpha + beta: the largest s with K 2^s < P / 2
-
-// The symmetric update of the factorisation's far columns (emu.hip): C[i, j] -= sum_k A[i, k] A[j, k], j <= i < rows, by column panels of
-// 1024 from ONE residue image of A.  plan sets the geometry of one update and grows the sizes (call it for the largest update before
-// alloc, then for each update before its split); alloc / free: the pool; split, then the column panels in ascending order, each on the
-// stream the caller picks (a panel reads the image and the scales, and writes its own columns of C only).
-struct EmuSyrk {
-    int8_t *img = nullptr, *rr = nullptr;
-    int *sig = nullptr;
-    int L = 0, bits = 0;
-    int64_t K = 0, rows_pad = 0, rt = 0, tiles = 0, img_bytes = 0, r_bytes = 0, sig_n = 0;
+constexpr int EMU_SLAB = 1024;           // columns of a slab of the left-looking solve (tsolve.hip: PB) and of a column panel of the symmetric update
+// One operand as emu_i8_gemm_kernel reads it: plane l at res + l plane, rows ld bytes apart; the rows' scale exponents (for the rebuild).
+struct EmuOperand { const int8_t *res; int64_t ld, plane; const int *scale; };
+// A tiled residue image [row tile][l][rt][ld] of rows_pad rows, a row tile's planes at most 2 GiB; from_row: rows `row` .. the end of their tile
+struct EmuImage {
+    int8_t *base = nullptr;
+    int64_t ld = 0, rt = 0, tiles = 0, rows_pad = 0, L = 0;   // row stride (bytes), rows per tile, tiles, padded rows, moduli
+    int64_t plane() const { return rt * ld; }
+    int8_t *tile(int64_t t) const { return base + t * plane() * L; }
+    EmuOperand from_row(int64_t row, const int *sig) const { return {tile(row / rt) + row % rt * ld, ld, plane(), sig + row}; }
 };
-void emu_syrk_plan(EmuSyrk &w, int64_t rows, int64_t K, int64_t tile_rows = 0);
-int emu_syrk_alloc(EmuSyrk &w);
-void emu_syrk_free(EmuSyrk &w);
-int emu_syrk_split(const EmuSyrk &w, const double *A, int64_t lda, int64_t rows, hipStream_t s);
-int emu_syrk_panel(const EmuSyrk &w, int64_t q, double *C, int64_t ldc, int64_t rows, hipStream_t s, Profiler *prof, int diag_tile = 1);
-int emu_syrk_lower_sub(const double *A, int64_t lda, int64_t rows, int64_t K, double *C, int64_t ldc, const EmuSyrk &w, hipStream_t s, Profiler *prof,
-                       const hipEvent_t *panel_done = nullptr, int diag_tile = 1);
-
-// The left-looking form of the many-row solve (tsolve.hip, trsm_right_lt_slabs): every solved slab is split ONCE into a persistent
-// residue image, with a row scale derived from a bound on the whole solved row that the caller knows at entry; slab p then takes one
-// emulated update of depth 1024 p.  plan sizes the image for `rows` rows of a solve over `slabs` slabs (tile_rows > 0: a smaller row
-// tile, for tests), alloc takes it into the caller's Scratch, begin derives a chunk's scales from its bounds and clears the status word
-// (device; non-zero after the chunk: a bound was wrong, the chunk's result is to be discarded).
-struct EmuLeft {
-    int8_t *img = nullptr, *rb = nullptr, *rr = nullptr;
-    int *sig = nullptr;
-    double *bound = nullptr;
-    int L = 0, abits = 0, bbits = 0;
-    int64_t lda = 0, rows_pad = 0, rt = 0, tiles = 0, img_bytes = 0, b_bytes = 0, r_bytes = 0;
-    int *status() const { return sig + rows_pad + 1024; }
+// A plan is a pure function of a shape: the geometry of A's image, the rows ct of B's column tile, the bits of either role, and what the
+// shape needs: bytes of the image, of B's tile and of a tile pair's product residues, the number of scales (ints) and of row bounds (doubles).
+struct EmuNeed { int64_t img = 0, b = 0, r = 0, sig = 0, bound = 0; };
+struct EmuPlan { EmuImage a; int64_t ct = 0; int abits = 0, bbits = 0; EmuNeed need; };
+// The workspace of all three drivers: the plan in use and the blocks held.  reserve() grows what emu_alloc will take so that it covers a
+// plan; use() sets the geometry of the next update on the blocks held (every driver checks that they cover it).  emu_alloc takes every
+// block of `held` from the pool or none: sc owns them from there on and gives them back, without one the caller does (emu_free).
+struct EmuFrame : EmuPlan {
+    EmuNeed held;                          // what reserve() has grown and emu_alloc took
+    int8_t *rb = nullptr, *rr = nullptr;   // B's tile, the product residues (the image is a.base)
+    int *sig = nullptr;                    // the scales of A's rows_pad rows, then of B's tile, then the left-looking solve's status word
+    double *bound = nullptr;               // the left-looking solve's row bounds (callers that derive them on the device)
+    void reserve(const EmuPlan &p);
+    void use(const EmuPlan &p) { int8_t *img = a.base; static_cast<EmuPlan &>(*this) = p; a.base = img; }
+    int *status() const { return sig + a.rows_pad + EMU_SLAB; }
 };
-bool emu_left_enabled();                 // GPX_EMU_LEFT (default 1)
-void emu_left_plan(EmuLeft &w, int64_t rows, int64_t slabs, int64_t tile_rows = 0);
-int emu_left_alloc(EmuLeft &w, Scratch &sc);
-int emu_left_begin(const EmuLeft &w, const double *bound, int64_t rows, hipStream_t s);
-int emu_left_split(const EmuLeft &w, const double *X, int64_t ldx, int64_t rows, int64_t q, hipStream_t s);
-int emu_left_update(const EmuLeft &w, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t rows, int64_t cols, int64_t K, hipStream_t s,
+int emu_alloc(EmuFrame &w, Scratch *sc);
+void emu_free(EmuFrame &w);
+EmuPlan emu_work_plan(int64_t rows, int64_t cols, int64_t K);   // the recursion's update: reserve the plan of every shape to come
+int emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t rows, int64_t cols, int64_t K,
+                    const EmuFrame &w, hipStream_t s, Profiler *prof);
+// The symmetric update of the factorisation's far columns: C[i, j] -= sum_k A[i, k] A[j, k], j <= i < rows, by column panels of 1024 from ONE
+// image of A (ld = K).  Reserve the largest update's plan, emu_alloc, use each update's plan before its split; then the column panels in
+// ascending order, each on the stream the caller picks (a panel reads the image and the scales, and writes its own columns of C only).
+EmuPlan emu_syrk_plan(int64_t rows, int64_t K, int64_t tile_rows = 0);
+int emu_syrk_split(const EmuFrame &w, const double *A, int64_t lda, int64_t rows, hipStream_t s);
+int emu_syrk_panel(const EmuFrame &w, int64_t q, double *C, int64_t ldc, int64_t rows, hipStream_t s, Profiler *prof, int diag_tile = 1);
+// The left-looking many-row solve (tsolve.hip, trsm_right_lt_slabs): every solved slab is split ONCE into a persistent image (ld = 1024
+// (slabs - 1)) with a row scale derived from a bound on the whole solved row; slab p then takes one update of depth 1024 p.  tile_rows > 0:
+// a smaller row tile, for tests; begin: a chunk's scales from its bounds, the status word cleared (non-zero afterwards: discard the chunk).
+EmuPlan emu_left_plan(int64_t rows, int64_t slabs, int64_t tile_rows = 0);
+int emu_left_begin(const EmuFrame &w, const double *bound, int64_t rows, hipStream_t s);
+int emu_left_split(const EmuFrame &w, const double *X, int64_t ldx, int64_t rows, int64_t q, hipStream_t s);
+int emu_left_update(const EmuFrame &w, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t rows, int64_t cols, int64_t K, hipStream_t s,
                     Profiler *prof);
 // Zs <- Z L^-T over all slabs of the solver's factor, left-looking from slab 4 on (slabs 0 .. 3 as trsm_right_lt_squares, their updates
 // emulated through emu where emu_enabled(K) holds: with the default GPX_EMU_MIN_K none of them); w: planned and allocated for at least
 // these rows, begun with their bounds
 int trsm_right_lt_slabs(double *Z, double *Zs, int64_t ldz, int64_t rows, const TriSolver *ts, hipStream_t s, Profiler *prof, const GemmReduce *red,
-                        const EmuLeft &w, const EmuWork *emu = nullptr);
+                        const EmuFrame &w, const EmuFrame *emu = nullptr);
 int launch_row_bounds(const double *kdiag, double v, int64_t m, double *bound, hipStream_t s);   // bound_i = sqrt(kdiag_i), or sqrt(v) without kdiag
-// The two fall-back decisions of the route, apart from the image that does not fit (emu_left_alloc).  Which solves take it: the caller bounds
+// The two fall-back decisions of the route, apart from the image that does not fit (emu_alloc).  Which solves take it: the caller bounds
 // every solved row, the many-row solver runs (not the few-vector one) against prepared squares over five slabs or more, and the switches
 // allow it -- the factor's shape and the kind of call alone, never the number of rows beyond `few`.
 bool emu_left_route(bool bounded, bool few, bool ready, int64_t slabs);
@@ -610,9 +609,9 @@ struct RowSolve {
     int64_t chunk = 0;
     bool few = false;       // a handful of rows: the few-right-hand-side solver (one sweep over the factor's triangle)
     double *Zs = nullptr;   // [chunk, npad]
-    EmuWork ew;
-    const EmuWork *emu = nullptr;
-    EmuLeft left;           // the left-looking order's residue image and the chunk's row bounds (device), when the caller bounds its rows
+    EmuFrame ew;
+    const EmuFrame *emu = nullptr;
+    EmuFrame left;           // the left-looking order's residue image and the chunk's row bounds (device), when the caller bounds its rows
     bool use_left = false;
     explicit RowSolve(hipStream_t s) : sc(s) {}
 };

@@ -33,7 +33,6 @@ typedef unsigned v4u __attribute__((ext_vector_type(4)));
 
 constexpr int EMU_MAXL = 16;
 constexpr int EMU_BT = 256;   // int8 block tile: 256 x 256, 2 x 4 waves of 128 x 64 (4 x 2 MFMAs of 32 x 32), two waves per SIMD
-constexpr int EMU_SLAB = 1024; // columns of one slab of the left-looking solve (tsolve.hip: PB)
 constexpr int EMU_BK = 128;   // k bytes per LDS stage (one 128-byte row per operand row, the fp64 kernel's image geometry)
 
 // pairwise coprime (256 = 2^8, 255 = 3 5 17, 253 = 11 23, 247 = 13 19, the rest prime); the first L are used
@@ -99,14 +98,15 @@ int emu_moduli()
     static const int v = [] { const char *e = getenv("GPX_EMU_MODULI"); const int l = e ? atoi(e) : EMU_MAXL; return std::min(EMU_MAXL, std::max(2, l)); }();
     return v;
 }
+static bool emu_k_ok(int64_t K) { return K > 0 && K % EMU_BK == 0 && K < (1 << 17); }   // the int8 k-stage; K 2^14 < 2^31 in the int32 accumulators
 bool emu_enabled(int64_t K)
 {
     static const int on = [] { const char *e = getenv("GPX_EMU_F64"); return e ? atoi(e) : 1; }();
     static const long min_k = [] { const char *e = getenv("GPX_EMU_MIN_K"); return e ? atol(e) : 4096L; }();
-    return on && K >= min_k && K < (1 << 17) && K % EMU_BK == 0;
+    return on && K >= min_k && emu_k_ok(K);
 }
 // alpha + beta: the largest integer s with K 2^s < P / 2
-int emu_scale_bits(int64_t K, int L)
+static int emu_scale_bits(int64_t K, int L)
 {
     double log2p = 0.0;
     for (int l = 0; l < L; ++l) log2p += log2((double)EMU_MODULI[l]);
@@ -592,27 +592,98 @@ static void emu_launch_split_fixed(const double *X, long ldx, long rows, long ro
 }
 
 // ---- workspace -------------------------------------------------------------------------------------------------------------
-// Residues of a row tile of A and a column tile of B and the product residues of their block, each at most 2 GiB: at N = M = 16384
-// (K = 8192) one tile of each; deeper products (K = 32768 at N = 65536) loop over row tiles and, inside, column tiles.  Every bound below
-// grows with rows, so a workspace sized for a predict chunk serves every shorter chunk.
+// One frame for the three drivers below (common.h: EmuFrame).  Residues of a row tile of A, of a column tile of B and the product residues
+// of their block, each at most 2 GiB: at N = M = 16384 (K = 8192) one tile of each; deeper products (K = 32768 at N = 65536) loop over row
+// tiles and, inside, column tiles.  Every need grows with rows, so a workspace reserved for a predict chunk serves every shorter chunk.
 static int64_t emu_cap(int64_t K, int L) { return std::max<int64_t>(EMU_BT, (((int64_t)1 << 31) / (K * L)) / EMU_BT * EMU_BT); }
 
-void emu_work_need(EmuWork &w, int64_t rows, int64_t cols, int64_t K)
+void EmuFrame::reserve(const EmuPlan &p)
 {
-    const int L = emu_moduli();
-    const int64_t cap = emu_cap(K, L), rt = std::min(round_up(rows, EMU_BT), cap), ct = std::min(round_up(cols, EMU_BT), cap);
-    w.a_bytes = std::max(w.a_bytes, rt * K * L);
-    w.b_bytes = std::max(w.b_bytes, ct * K * L);
-    w.r_bytes = std::max(w.r_bytes, std::min(rt * ct * L, (int64_t)1 << 31));
-    w.sig_n = std::max(w.sig_n, rt + ct);
+    held = {std::max(held.img, p.need.img), std::max(held.b, p.need.b), std::max(held.r, p.need.r), std::max(held.sig, p.need.sig),
+            std::max(held.bound, p.need.bound)};
 }
 
-int emu_work_alloc(EmuWork &w, Scratch &sc)
+// n blocks from the pool (an empty one is skipped) or none: after a refusal what was taken has gone back at once (nothing is queued on it)
+static int emu_take(double **q, const int64_t *bytes, int n, Scratch *sc)
 {
-    GPX_TRY(sc.take(&w.ra, w.a_bytes));
-    GPX_TRY(sc.take(&w.rb, w.b_bytes));
-    GPX_TRY(sc.take(&w.rr, w.r_bytes));
-    return sc.take(&w.sig, w.sig_n);
+    int rc = 0;
+    for (int i = 0; i < n; ++i) q[i] = nullptr;
+    for (int i = 0; i < n && !rc; ++i)
+        if (bytes[i]) rc = dalloc(&q[i], (bytes[i] + 7) / 8);
+    for (int i = 0; i < n; ++i)
+        if (q[i] && rc) { dfree(q[i]); q[i] = nullptr; }
+        else if (q[i] && sc) sc->blocks.push_back(q[i]);
+    return rc;
+}
+
+int emu_alloc(EmuFrame &w, Scratch *sc)
+{
+    double *q[5];
+    const int64_t bytes[5] = {w.held.img, w.held.b, w.held.r, w.held.sig * (int64_t)sizeof(int), w.held.bound * (int64_t)sizeof(double)};
+    const int rc = emu_take(q, bytes, 5, sc);   // no room: the caller keeps its other route
+    w.a.base = (int8_t *)q[0]; w.rb = (int8_t *)q[1]; w.rr = (int8_t *)q[2];
+    w.sig = (int *)q[3]; w.bound = q[4];
+    return rc;
+}
+
+void emu_free(EmuFrame &w)
+{
+    for (void *p : {(void *)w.a.base, (void *)w.rb, (void *)w.rr, (void *)w.sig, (void *)w.bound}) dfree(p);
+    w.a.base = w.rb = w.rr = nullptr; w.sig = nullptr; w.bound = nullptr;
+}
+
+// the blocks held cover plan p (the frame's own, or the recursion's plan of one product) and the product residues of a full tile pair
+static int emu_fits(const EmuFrame &w, const EmuPlan &p, const char *what)
+{
+    const EmuNeed &h = w.held, &n = p.need;
+    if (w.a.base && n.img <= h.img && n.b <= h.b && n.r <= h.r && p.a.rt * p.ct * p.a.L <= h.r && n.sig <= h.sig && n.bound <= h.bound) return 0;
+    gpx_set_error("%s: workspace too small for %ld rows x K = %ld", what, (long)p.a.rows_pad, (long)p.a.ld);
+    return GPX_ERR_STATE;
+}
+
+// a plan's first fields: L moduli, rows of ld bytes, the scale bits of a product of depth ld (halves: bits / 2 in either role)
+static EmuPlan emu_plan_begin(int64_t ld, bool halves)
+{
+    EmuPlan p;
+    p.a.L = emu_moduli();
+    p.a.ld = ld;
+    p.bbits = emu_scale_bits(ld, (int)p.a.L) / 2;
+    p.abits = halves ? p.bbits : emu_scale_bits(ld, (int)p.a.L) - p.bbits;
+    return p;
+}
+
+// ---- the tile step: what every driver does for one (row tile, column tile) pair ----------------------------------------------------
+// R_l = (A_l B_l^T) mod p_l over tm x tn blocks of 256 x 256, R as planes of [256 tm][ldr] bytes sr apart; what emu_i8_gemm_kernel takes
+// for granted (its comment) is checked here, once for every caller
+static int emu_launch_product(const EmuOperand &a, const EmuOperand &b, int8_t *R, int64_t ldr, int64_t sr, int64_t tm, int64_t tn, int64_t K, int L,
+                              hipStream_t s)
+{
+    const int64_t lim = (int64_t)1 << 31;
+    if (!emu_k_ok(K) || b.ld != K || a.ld < K || L * a.plane > lim || L * b.plane > lim || (EMU_BT - 1) * a.ld + K >= lim || tm * tn * L > INT32_MAX) {
+        gpx_set_error("emu: int8 product of %ld x %ld blocks, K = %ld, row stride %ld, %d moduli outside the kernel's range", (long)tm, (long)tn, (long)K, (long)a.ld, L);
+        return GPX_ERR_STATE;
+    }
+    hipLaunchKernelGGL(emu_i8_gemm_kernel, dim3((unsigned)(tm * tn * L)), dim3(512), 0, s, a.res, b.res, (long)a.plane, (long)b.plane, (int)K, R, (long)ldr,
+                       (long)sr, (int)tm, (int)tn, (int)a.ld);
+    return 0;
+}
+
+static void emu_launch_rebuild(const int8_t *R, int64_t ldr, int64_t sr, int L, const int *sa, const int *sb, double *C, int64_t ldc, int64_t rows,
+                               int64_t cols, int64_t diag, int64_t dmask, hipStream_t s)
+{
+    const long thr = (long)rows * ((cols + 3) / 4);
+    hipLaunchKernelGGL(emu_rebuild_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, R, (long)ldr, (long)sr, L, emu_crt.t[L], sa, sb, C, (long)ldc,
+                       (long)rows, (long)cols, (long)diag, (long)dmask);
+}
+
+// C[nr, nc] -= A B^T for nr rows of a (nrp: padded to 256, the rows of residues) and nc of b (ncp), through rr as planes of [nrp][ncp];
+// row i of C ends at column (i + diag) | dmask (EMU_NO_DIAG, 0: the full rectangle)
+static int emu_tile_update(const EmuOperand &a, const EmuOperand &b, int8_t *rr, double *C, int64_t ldc, int64_t nr, int64_t nrp, int64_t nc, int64_t ncp,
+                           int64_t K, int L, int64_t diag, int64_t dmask, hipStream_t s)
+{
+    GPX_TRY(emu_launch_product(a, b, rr, ncp, nrp * ncp, nrp / EMU_BT, ncp / EMU_BT, K, L, s));
+    emu_launch_rebuild(rr, ncp, nrp * ncp, L, a.scale, b.scale, C, ldc, nr, nc, diag, dmask, s);
+    return 0;
 }
 
 // What the kernels take for granted of a caller outside the library (gpx_emu_gemm_nt_sub; tsolve.hip passes slabs of 128-padded matrices at
@@ -621,7 +692,7 @@ int emu_work_alloc(EmuWork &w, Scratch &sc)
 // A and B that start on 16 bytes (base pointers 16-byte aligned, lda and ldb even): the split kernels read pairs of doubles.
 static int emu_check_args(const double *A, int64_t lda, const double *B, int64_t ldb, int64_t ldc, int64_t cols, int64_t K)
 {
-    if (K <= 0 || K % EMU_BK || K >= (1 << 17)) {
+    if (!emu_k_ok(K)) {
         gpx_set_error("emu_gemm_nt_sub: K = %ld is not a multiple of %d in [%d, 2^17)", (long)K, EMU_BK, EMU_BK);
         return GPX_ERR_BAD_ARG;
     }
@@ -638,37 +709,38 @@ static int emu_check_args(const double *A, int64_t lda, const double *B, int64_t
     return 0;
 }
 
-// ---- C[rows, cols] -= A[rows, K] B[cols, K]^T (row-major, fp64), in a workspace sized by emu_work_need for at least these shapes ----------
+// ---- C[rows, cols] -= A[rows, K] B[cols, K]^T (row-major, fp64), in a workspace that holds emu_work_plan of at least these shapes ---------
+// Row tiles of `cap` rows with a ragged last one, each split into the image's one tile; B's column tile shrunk while a tile pair's
+// product residues would pass 2 GiB (its block and scales stay sized for the unshrunk tile).  bits - bits / 2 for A, bits / 2 for B.
+EmuPlan emu_work_plan(int64_t rows, int64_t cols, int64_t K)
+{
+    EmuPlan p = emu_plan_begin(K, false);
+    const int64_t L = p.a.L, cap = emu_cap(K, (int)L);
+    p.a.tiles = 1;
+    p.a.rt = p.a.rows_pad = std::min(round_up(rows, EMU_BT), cap);
+    p.ct = std::min(round_up(cols, EMU_BT), cap);
+    p.need = {p.a.rt * K * L, p.ct * K * L, std::min(p.a.rt * p.ct * L, (int64_t)1 << 31), p.a.rt + p.ct, 0};
+    while (p.ct > EMU_BT && p.a.rt * p.ct * L > ((int64_t)1 << 31)) p.ct -= EMU_BT;
+    return p;
+}
+
 int emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t rows, int64_t cols, int64_t K,
-                    const EmuWork &w, hipStream_t s, Profiler *prof)
+                    const EmuFrame &w, hipStream_t s, Profiler *prof)
 {
     if (rows <= 0 || cols <= 0) return 0;
-    if (K % EMU_BK || K >= (1 << 17)) { gpx_set_error("emu_gemm_nt_sub: K = %ld out of range", (long)K); return GPX_ERR_BAD_ARG; }
-    const int L = emu_moduli();
-    const int bits = emu_scale_bits(K, L), abits = bits - bits / 2, bbits = bits / 2;
-    const int64_t cap = emu_cap(K, L);
-    const int64_t rt = std::min<int64_t>(round_up(rows, EMU_BT), cap);
-    int64_t ct = std::min<int64_t>(round_up(cols, EMU_BT), cap);
-    while (ct > EMU_BT && rt * ct * L > ((int64_t)1 << 31)) ct -= EMU_BT;
-    if (!w.ra || rt * K * L > w.a_bytes || ct * K * L > w.b_bytes || rt * ct * L > w.r_bytes || rt + ct > w.sig_n) {
-        gpx_set_error("emu_gemm_nt_sub: workspace too small for %ld x %ld x %ld", (long)rows, (long)cols, (long)K);
-        return GPX_ERR_STATE;
-    }
+    if (!emu_k_ok(K)) { gpx_set_error("emu_gemm_nt_sub: K = %ld out of range", (long)K); return GPX_ERR_BAD_ARG; }
+    const EmuPlan p = emu_work_plan(rows, cols, K);
+    GPX_TRY(emu_fits(w, p, "emu_gemm_nt_sub"));
     ProfScope ps(prof, s, GPX_K_GEMM_EMU, 2.0 * (double)rows * (double)cols * (double)K);
-    int8_t *ra = w.ra, *rb = w.rb, *rr = w.rr;
-    int *sga = w.sig, *sgb = sga + rt;
-    for (int64_t r0 = 0; r0 < rows; r0 += rt) {
-        const int64_t nr = std::min(rt, rows - r0), nrp = round_up(nr, EMU_BT);
-        emu_launch_split(A + r0 * lda, (long)lda, (long)nr, (long)nrp, (int)K, abits, L, ra, (long)(nrp * K), sga, s);
-        for (int64_t c0 = 0; c0 < cols; c0 += ct) {
-            const int64_t nc = std::min(ct, cols - c0), ncp = round_up(nc, EMU_BT);
-            emu_launch_split(B + c0 * ldb, (long)ldb, (long)nc, (long)ncp, (int)K, bbits, L, rb, (long)(ncp * K), sgb, s);
-            const int tm = (int)(nrp / EMU_BT), tn = (int)(ncp / EMU_BT);
-            hipLaunchKernelGGL(emu_i8_gemm_kernel, dim3((unsigned)(tm * tn * L)), dim3(512), 0, s, (const int8_t *)ra, (const int8_t *)rb,
-                               (long)(nrp * K), (long)(ncp * K), (int)K, rr, (long)ncp, (long)(nrp * ncp), tm, tn, (int)K);
-            const long thr = (long)nr * ((nc + 3) / 4);
-            hipLaunchKernelGGL(emu_rebuild_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, (const int8_t *)rr, (long)ncp,
-                               (long)(nrp * ncp), L, emu_crt.t[L], (const int *)sga, (const int *)sgb, C + r0 * ldc + c0, (long)ldc, (long)nr, (long)nc, EMU_NO_DIAG, 0L);
+    const int L = (int)p.a.L;
+    int *sga = w.sig, *sgb = sga + p.a.rt;
+    for (int64_t r0 = 0; r0 < rows; r0 += p.a.rt) {
+        const int64_t nr = std::min(p.a.rt, rows - r0), nrp = round_up(nr, EMU_BT);
+        emu_launch_split(A + r0 * lda, (long)lda, (long)nr, (long)nrp, (int)K, p.abits, L, w.a.base, (long)(nrp * K), sga, s);
+        for (int64_t c0 = 0; c0 < cols; c0 += p.ct) {
+            const int64_t nc = std::min(p.ct, cols - c0), ncp = round_up(nc, EMU_BT);
+            emu_launch_split(B + c0 * ldb, (long)ldb, (long)nc, (long)ncp, (int)K, p.bbits, L, w.rb, (long)(ncp * K), sgb, s);
+            GPX_TRY(emu_tile_update({w.a.base, K, nrp * K, sga}, {w.rb, K, ncp * K, sgb}, w.rr, C + r0 * ldc + c0, ldc, nr, nrp, nc, ncp, K, L, EMU_NO_DIAG, 0, s));
         }
         GPX_HIP(hipGetLastError());
     }
@@ -677,98 +749,69 @@ int emu_gemm_nt_sub(const double *A, int64_t lda, const double *B, int64_t ldb, 
 
 // ---- the left-looking solve's share (tsolve.hip, trsm_right_lt_slabs): a persistent residue image of the solved slabs -------------------
 // Slab p of the solve takes ONE update of depth K = 1024 p against every solved slab before it.  Each solved slab is split once, with the
-// scale its row's bound gave at entry, into the image [row tile][l][rt][lda] (lda = 1024 (P - 1) columns; a row tile's planes span at most
-// 2 GiB, its base is formed here in 64 bits); every later update reads columns 0 .. K of it through the int8 kernel's row stride.
-// abits / bbits come from the deepest K of the call, so one image serves every depth.
-bool emu_left_enabled()
-{
-    static const int on = [] { const char *e = getenv("GPX_EMU_LEFT"); return e ? atoi(e) : 1; }();
-    return on != 0;
-}
-
+// scale its row's bound gave at entry, into the image (ld = 1024 (P - 1) columns, equal row tiles: 2 x 8192 rows at N = M = 16384, not
+// 8704 + 7680); every later update reads columns 0 .. K of it through the int8 kernel's row stride.  abits / bbits come from the deepest
+// K of the call, so one image serves every depth.
 bool emu_left_route(bool bounded, bool few, bool ready, int64_t slabs)
 {
-    return bounded && !few && ready && slabs >= 5 && emu_left_enabled() && emu_enabled(4 * EMU_SLAB);
+    static const int on = [] { const char *e = getenv("GPX_EMU_LEFT"); return e ? atoi(e) : 1; }();   // (default 1)
+    return bounded && !few && ready && slabs >= 5 && on && emu_enabled(4 * EMU_SLAB);
 }
 
-void emu_left_plan(EmuLeft &w, int64_t rows, int64_t slabs, int64_t tile_rows)
+EmuPlan emu_left_plan(int64_t rows, int64_t slabs, int64_t tile_rows)
 {
-    w.L = emu_moduli();
-    w.lda = EMU_SLAB * (slabs - 1);
-    const int bits = emu_scale_bits(w.lda, w.L);
-    w.abits = bits - bits / 2;
-    w.bbits = bits / 2;
-    w.rows_pad = round_up(rows, EMU_BT);
-    int64_t cap = emu_cap(w.lda, w.L);
+    EmuPlan p = emu_plan_begin(EMU_SLAB * (slabs - 1), false);
+    EmuImage &a = p.a;
+    a.rows_pad = round_up(rows, EMU_BT);
+    int64_t cap = emu_cap(a.ld, (int)a.L);
     if (tile_rows > 0) cap = std::min(cap, round_up(tile_rows, EMU_BT));
-    w.tiles = (w.rows_pad + cap - 1) / cap;
-    w.rt = round_up((w.rows_pad + w.tiles - 1) / w.tiles, EMU_BT);   // equal row tiles: 2 x 8192 rows at N = M = 16384, not 8704 + 7680
-    w.img_bytes = w.tiles * w.rt * w.lda * w.L;
-    w.b_bytes = EMU_SLAB * w.lda * w.L;
-    w.r_bytes = w.rt * EMU_SLAB * w.L;
-}
-
-int emu_left_alloc(EmuLeft &w, Scratch &sc)
-{
-    int rc = sc.take(&w.img, w.img_bytes);
-    if (!rc) rc = sc.take(&w.rb, w.b_bytes);
-    if (!rc) rc = sc.take(&w.rr, w.r_bytes);
-    if (!rc) rc = sc.take(&w.sig, w.rows_pad + EMU_SLAB + 1);   // row scales, the B tile's row scales, the status word
-    if (!rc) rc = sc.take(&w.bound, w.rows_pad);                // the chunk's row bounds (callers that derive them on the device)
-    if (rc) {   // no room: what was taken goes back at once (nothing is queued on it), the caller keeps its other route
-        for (void *p : {(void *)w.img, (void *)w.rb, (void *)w.rr, (void *)w.sig, (void *)w.bound})
-            if (p) dfree(sc.release((double *)p));
-        w.img = w.rb = w.rr = nullptr;
-        w.sig = nullptr;
-        w.bound = nullptr;
-    }
-    return rc;
+    a.tiles = (a.rows_pad + cap - 1) / cap;
+    a.rt = round_up((a.rows_pad + a.tiles - 1) / a.tiles, EMU_BT);
+    p.ct = EMU_SLAB;
+    p.need = {a.tiles * a.rt * a.ld * a.L, p.ct * a.ld * a.L, a.rt * p.ct * a.L, a.rows_pad + EMU_SLAB + 1, a.rows_pad};
+    return p;
 }
 
 // the row scales of one chunk from its bounds (device, `rows` of them; the padding rows take bound 0), status cleared
-int emu_left_begin(const EmuLeft &w, const double *bound, int64_t rows, hipStream_t s)
+int emu_left_begin(const EmuFrame &w, const double *bound, int64_t rows, hipStream_t s)
 {
-    if (rows > w.rows_pad) { gpx_set_error("emu_left_begin: %ld rows in a workspace of %ld", (long)rows, (long)w.rows_pad); return GPX_ERR_STATE; }
+    if (rows > w.a.rows_pad) { gpx_set_error("emu_left_begin: %ld rows in a workspace of %ld", (long)rows, (long)w.a.rows_pad); return GPX_ERR_STATE; }
     GPX_HIP(hipMemsetAsync(w.status(), 0, sizeof(int), s));
-    hipLaunchKernelGGL(emu_scale_from_bound_kernel, dim3((unsigned)((w.rows_pad + 255) / 256)), dim3(256), 0, s, bound, (long)rows, (long)w.rows_pad,
+    hipLaunchKernelGGL(emu_scale_from_bound_kernel, dim3((unsigned)((w.a.rows_pad + 255) / 256)), dim3(256), 0, s, bound, (long)rows, (long)w.a.rows_pad,
                        w.abits, w.sig, w.status());
     GPX_HIP(hipGetLastError());
     return 0;
 }
 
 // solved slab q (X: its first column, `rows` rows, 1024 columns) into the image
-int emu_left_split(const EmuLeft &w, const double *X, int64_t ldx, int64_t rows, int64_t q, hipStream_t s)
+int emu_left_split(const EmuFrame &w, const double *X, int64_t ldx, int64_t rows, int64_t q, hipStream_t s)
 {
-    for (int64_t t = 0, r0 = 0; r0 < rows; ++t, r0 += w.rt) {
-        const int64_t nr = std::min(w.rt, rows - r0), nrp = round_up(nr, EMU_BT);
-        emu_launch_split_fixed(X + r0 * ldx, (long)ldx, (long)nr, (long)nrp, EMU_SLAB, w.abits, w.L, w.img + t * w.rt * w.lda * w.L + q * EMU_SLAB,
-                               (long)w.lda, (long)(w.rt * w.lda), w.sig + r0, w.status(), s);
+    for (int64_t t = 0, r0 = 0; r0 < rows; ++t, r0 += w.a.rt) {
+        const int64_t nr = std::min(w.a.rt, rows - r0), nrp = round_up(nr, EMU_BT);
+        emu_launch_split_fixed(X + r0 * ldx, (long)ldx, (long)nr, (long)nrp, EMU_SLAB, w.abits, (int)w.a.L, w.a.tile(t) + q * EMU_SLAB, (long)w.a.ld,
+                               (long)w.a.plane(), w.sig + r0, w.status(), s);
     }
     GPX_HIP(hipGetLastError());
     return 0;
 }
 
 // C[rows, cols] -= Zs[:, 0:K) B[cols, K]^T with Zs read from the image (K = 1024 p, cols <= 1024): split B (its scales, then its
-// residues), then per row tile one int8 launch and one rebuild
-int emu_left_update(const EmuLeft &w, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t rows, int64_t cols, int64_t K, hipStream_t s,
+// residues), then the tile step per row tile
+int emu_left_update(const EmuFrame &w, const double *B, int64_t ldb, double *C, int64_t ldc, int64_t rows, int64_t cols, int64_t K, hipStream_t s,
                     Profiler *prof)
 {
-    if (K <= 0 || K > w.lda || K % EMU_SLAB || cols <= 0 || cols > EMU_SLAB || rows > w.rows_pad) {
+    if (K <= 0 || K > w.a.ld || K % EMU_SLAB || cols <= 0 || cols > EMU_SLAB || rows > w.a.rows_pad) {
         gpx_set_error("emu_left_update: %ld x %ld x %ld outside the image", (long)rows, (long)cols, (long)K);
         return GPX_ERR_STATE;
     }
+    GPX_TRY(emu_fits(w, w, "emu_left_update"));
     ProfScope ps(prof, s, GPX_K_GEMM_EMU, 2.0 * (double)rows * (double)cols * (double)K);
     const int64_t ncp = round_up(cols, EMU_BT);
-    int *sgb = w.sig + w.rows_pad;
-    emu_launch_split(B, (long)ldb, (long)cols, (long)ncp, (int)K, w.bbits, w.L, w.rb, (long)(ncp * K), sgb, s);
-    for (int64_t t = 0, r0 = 0; r0 < rows; ++t, r0 += w.rt) {
-        const int64_t nr = std::min(w.rt, rows - r0), nrp = round_up(nr, EMU_BT);
-        const int tm = (int)(nrp / EMU_BT), tn = (int)(ncp / EMU_BT);
-        hipLaunchKernelGGL(emu_i8_gemm_kernel, dim3((unsigned)(tm * tn * w.L)), dim3(512), 0, s, (const int8_t *)(w.img + t * w.rt * w.lda * w.L),
-                           (const int8_t *)w.rb, (long)(w.rt * w.lda), (long)(ncp * K), (int)K, w.rr, (long)ncp, (long)(nrp * ncp), tm, tn, (int)w.lda);
-        const long thr = (long)nr * ((cols + 3) / 4);
-        hipLaunchKernelGGL(emu_rebuild_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, (const int8_t *)w.rr, (long)ncp, (long)(nrp * ncp), w.L,
-                           emu_crt.t[w.L], (const int *)(w.sig + r0), (const int *)sgb, C + r0 * ldc, (long)ldc, (long)nr, (long)cols, EMU_NO_DIAG, 0L);
+    const EmuOperand b{w.rb, K, ncp * K, w.sig + w.a.rows_pad};
+    emu_launch_split(B, (long)ldb, (long)cols, (long)ncp, (int)K, w.bbits, (int)w.a.L, w.rb, (long)b.plane, w.sig + w.a.rows_pad, s);
+    for (int64_t r0 = 0; r0 < rows; r0 += w.a.rt) {
+        const int64_t nr = std::min(w.a.rt, rows - r0), nrp = round_up(nr, EMU_BT);
+        GPX_TRY(emu_tile_update(w.a.from_row(r0, w.sig), b, w.rr, C + r0 * ldc, ldc, nr, nrp, cols, ncp, K, (int)w.a.L, EMU_NO_DIAG, 0, s));
     }
     GPX_HIP(hipGetLastError());
     return 0;
@@ -776,60 +819,30 @@ int emu_left_update(const EmuLeft &w, const double *B, int64_t ldb, double *C, i
 
 // ---- the symmetric update of the factorisation's far columns (chol.hip, Lookahead::group_boundary) -------------------------------------
 // C[i, j] -= sum_k A[i, k] A[j, k] for j <= i < rows, by column panels of 1024.  A is split ONCE, every row with its own maximum and
-// the same bit count emu_scale_bits(K, L) / 2 in either role, into the image [row tile][l][rt][K]: column panel q's B operand is rows
-// q 1024 .. of that image (plane stride rt K, as A's).  rt is a multiple of 1024 wherever there is more than one row tile, so a panel's B
-// rows never straddle two; a row tile's planes span at most 2 GiB.  Per column panel and row tile below it one int8 launch and one rebuild
-// that ends every row at the diagonal: nothing above it is written.
-void emu_syrk_plan(EmuSyrk &w, int64_t rows, int64_t K, int64_t tile_rows)
+// the same bit count emu_scale_bits(K, L) / 2 in either role, into the image (ld = K): column panel q's B operand is rows q 1024 .. of
+// that image.  rt is a multiple of 1024 wherever there is more than one row tile, so a panel's B rows never straddle two.  Per column
+// panel and row tile below it the tile step, whose rebuild ends every row at the diagonal: nothing above it is written.
+EmuPlan emu_syrk_plan(int64_t rows, int64_t K, int64_t tile_rows)
 {
-    w.L = emu_moduli();
-    w.bits = emu_scale_bits(K, w.L) / 2;
-    w.K = K;
-    w.rows_pad = round_up(rows, EMU_BT);
-    int64_t cap = std::max<int64_t>(EMU_SLAB, emu_cap(K, w.L) / EMU_SLAB * EMU_SLAB);
+    EmuPlan p = emu_plan_begin(K, true);
+    EmuImage &a = p.a;
+    a.rows_pad = round_up(rows, EMU_BT);
+    int64_t cap = std::max<int64_t>(EMU_SLAB, emu_cap(K, (int)a.L) / EMU_SLAB * EMU_SLAB);
     if (tile_rows > 0) cap = std::min(cap, round_up(tile_rows, EMU_SLAB));
-    w.rt = w.rows_pad <= cap ? w.rows_pad : cap;
-    w.tiles = (w.rows_pad + w.rt - 1) / w.rt;
-    w.img_bytes = std::max(w.img_bytes, w.tiles * w.rt * K * w.L);
-    w.r_bytes = std::max(w.r_bytes, w.rt * std::min<int64_t>(EMU_SLAB, w.rows_pad) * w.L);
-    w.sig_n = std::max(w.sig_n, w.rows_pad);
+    a.rt = std::min(a.rows_pad, cap);
+    a.tiles = (a.rows_pad + a.rt - 1) / a.rt;
+    p.ct = std::min<int64_t>(EMU_SLAB, a.rows_pad);
+    p.need = {a.tiles * a.rt * K * a.L, 0, a.rt * p.ct * a.L, a.rows_pad, 0};
+    return p;
 }
 
-// the workspace from the pool; no room (after the pool's own trim): nothing is held and the caller keeps its fp64 route
-int emu_syrk_alloc(EmuSyrk &w)
+// rows of A (the geometry of the plan in use) into the image, row scales into w.sig
+int emu_syrk_split(const EmuFrame &w, const double *A, int64_t lda, int64_t rows, hipStream_t s)
 {
-    double *a = nullptr, *b = nullptr, *c = nullptr;
-    if (dalloc(&a, (w.img_bytes + 7) / 8) || dalloc(&b, (w.r_bytes + 7) / 8) || dalloc(&c, (w.sig_n + 1) / 2)) {
-        dfree(a); dfree(b); dfree(c);
-        return GPX_ERR_HIP;
-    }
-    w.img = reinterpret_cast<int8_t *>(a);
-    w.rr = reinterpret_cast<int8_t *>(b);
-    w.sig = reinterpret_cast<int *>(c);
-    return 0;
-}
-
-void emu_syrk_free(EmuSyrk &w)
-{
-    dfree(w.img); dfree(w.rr); dfree(w.sig);
-    w.img = w.rr = nullptr;
-    w.sig = nullptr;
-}
-
-static int emu_syrk_fits(const EmuSyrk &w, const char *what)
-{
-    if (w.img && w.tiles * w.rt * w.K * w.L <= w.img_bytes && w.rt * std::min<int64_t>(EMU_SLAB, w.rows_pad) * w.L <= w.r_bytes && w.rows_pad <= w.sig_n) return 0;
-    gpx_set_error("%s: workspace too small for %ld rows x K = %ld", what, (long)w.rows_pad, (long)w.K);
-    return GPX_ERR_STATE;
-}
-
-// rows of A (the geometry of the last emu_syrk_plan) into the image, row scales into w.sig
-int emu_syrk_split(const EmuSyrk &w, const double *A, int64_t lda, int64_t rows, hipStream_t s)
-{
-    GPX_TRY(emu_syrk_fits(w, "emu_syrk_split"));
-    for (int64_t t = 0, r0 = 0; r0 < w.rows_pad; ++t, r0 += w.rt) {
-        const int64_t nrp = std::min(w.rt, w.rows_pad - r0), nr = std::max<int64_t>(0, std::min(nrp, rows - r0));
-        emu_launch_split(A + r0 * lda, (long)lda, (long)nr, (long)nrp, (int)w.K, w.bits, w.L, w.img + t * w.rt * w.K * w.L, (long)(w.rt * w.K), w.sig + r0, s);
+    GPX_TRY(emu_fits(w, w, "emu_syrk_split"));
+    for (int64_t t = 0, r0 = 0; r0 < w.a.rows_pad; ++t, r0 += w.a.rt) {
+        const int64_t nrp = std::min(w.a.rt, w.a.rows_pad - r0), nr = std::max<int64_t>(0, std::min(nrp, rows - r0));
+        emu_launch_split(A + r0 * lda, (long)lda, (long)nr, (long)nrp, (int)w.a.ld, w.abits, (int)w.a.L, w.a.tile(t), (long)w.a.plane(), w.sig + r0, s);
     }
     GPX_HIP(hipGetLastError());
     return 0;
@@ -838,45 +851,27 @@ int emu_syrk_split(const EmuSyrk &w, const double *A, int64_t lda, int64_t rows,
 // column panel q: C[i, j] for q 1024 <= j < min(rows, (q + 1) 1024), j <= i < rows (C: the matrix's first entry)
 // diag_tile (1 or a power of two that divides 1024): row i ends at the last column of its diag_tile x diag_tile diagonal block -- the
 // factorisation's diagonal tiles stay symmetric in full, as its fp64 updates leave them (the products are symmetric to the bit)
-int emu_syrk_panel(const EmuSyrk &w, int64_t q, double *C, int64_t ldc, int64_t rows, hipStream_t s, Profiler *prof, int diag_tile)
+int emu_syrk_panel(const EmuFrame &w, int64_t q, double *C, int64_t ldc, int64_t rows, hipStream_t s, Profiler *prof, int diag_tile)
 {
+    const EmuImage &a = w.a;
     const int64_t q0 = q * EMU_SLAB, nc = std::min<int64_t>(EMU_SLAB, rows - q0), ncp = round_up(nc, EMU_BT);
     if (nc <= 0) return 0;
-    GPX_TRY(emu_syrk_fits(w, "emu_syrk_panel"));
-    ProfScope ps(prof, s, GPX_K_GEMM_EMU, 2.0 * (double)(rows - q0) * (double)nc * (double)w.K);
-    const int64_t tb = q0 / w.rt;
-    const int8_t *B = w.img + tb * w.rt * w.K * w.L + (q0 - tb * w.rt) * w.K;
-    for (int64_t t = tb; t < w.tiles; ++t) {
-        const int64_t lo = std::max(t * w.rt, q0), hi = std::min((t + 1) * w.rt, w.rows_pad), nrp = hi - lo, nr = std::min(hi, rows) - lo;
+    GPX_TRY(emu_fits(w, w, "emu_syrk_panel"));
+    ProfScope ps(prof, s, GPX_K_GEMM_EMU, 2.0 * (double)(rows - q0) * (double)nc * (double)a.ld);
+    for (int64_t t = q0 / a.rt; t < a.tiles; ++t) {
+        const int64_t lo = std::max(t * a.rt, q0), hi = std::min((t + 1) * a.rt, a.rows_pad), nrp = hi - lo, nr = std::min(hi, rows) - lo;
         if (nr <= 0) break;
-        const int tm = (int)(nrp / EMU_BT), tn = (int)(ncp / EMU_BT);
-        hipLaunchKernelGGL(emu_i8_gemm_kernel, dim3((unsigned)(tm * tn * w.L)), dim3(512), 0, s, w.img + t * w.rt * w.K * w.L + (lo - t * w.rt) * w.K, B,
-                           (long)(w.rt * w.K), (long)(w.rt * w.K), (int)w.K, w.rr, (long)ncp, (long)(nrp * ncp), tm, tn, (int)w.K);
-        const long thr = (long)nr * ((nc + 3) / 4);
-        hipLaunchKernelGGL(emu_rebuild_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, s, (const int8_t *)w.rr, (long)ncp, (long)(nrp * ncp), w.L,
-                           emu_crt.t[w.L], (const int *)(w.sig + lo), (const int *)(w.sig + q0), C + lo * ldc + q0, (long)ldc, (long)nr, (long)nc, (long)(lo - q0), (long)(diag_tile - 1));
+        GPX_TRY(emu_tile_update(a.from_row(lo, w.sig), a.from_row(q0, w.sig), w.rr, C + lo * ldc + q0, ldc, nr, nrp, nc, ncp, a.ld, (int)a.L, lo - q0,
+                                diag_tile - 1, s));
     }
     GPX_HIP(hipGetLastError());
     return 0;
 }
 
-// the whole update on s, column panels in ascending order; panel_done (optional, one event per column panel): recorded behind each
-int emu_syrk_lower_sub(const double *A, int64_t lda, int64_t rows, int64_t K, double *C, int64_t ldc, const EmuSyrk &w, hipStream_t s, Profiler *prof,
-                       const hipEvent_t *panel_done, int diag_tile)
-{
-    if (rows <= 0) return 0;
-    GPX_TRY(emu_syrk_split(w, A, lda, rows, s));
-    for (int64_t q = 0; q * EMU_SLAB < rows; ++q) {
-        GPX_TRY(emu_syrk_panel(w, q, C, ldc, rows, s, prof, diag_tile));
-        if (panel_done) GPX_HIP(hipEventRecord(panel_done[q], s));
-    }
-    return 0;
-}
-
 // ---- C-ABI: the emulated product on caller device buffers (tests), the int8 product kernel alone on random residues (its rate) -------
 // the symmetric update: any K that is a multiple of 128 below 2^17; tile_rows > 0: a smaller row tile (rounded up to 1024), for tests
-// diag_tile: emu_syrk_panel's; plan_rows > rows: the workspace is planned and allocated for plan_rows rows and planned again for `rows`
-// before the split, as the factorisation does for every group boundary after its largest (chol.hip)
+// diag_tile: emu_syrk_panel's; plan_rows > rows: the workspace is reserved and allocated for plan_rows rows and the plan of `rows` used
+// for the split, as the factorisation does for every group boundary after its largest (chol.hip); column panels in ascending order
 extern "C" int gpx_emu_syrk_lower_sub_ex(const double *A, int64_t lda, int64_t rows, int64_t K, double *C, int64_t ldc, int64_t tile_rows, int diag_tile,
                                          int64_t plan_rows)
 {
@@ -887,13 +882,14 @@ extern "C" int gpx_emu_syrk_lower_sub_ex(const double *A, int64_t lda, int64_t r
     }
     GPX_TRY(emu_check_args(A, lda, A, lda, ldc, rows, K));
     if (rows == 0) return 0;
-    EmuSyrk w;
-    emu_syrk_plan(w, std::max(rows, plan_rows), K, tile_rows);
-    if (emu_syrk_alloc(w)) return GPX_ERR_HIP;
-    if (plan_rows > rows) emu_syrk_plan(w, rows, K, tile_rows);
-    int rc = emu_syrk_lower_sub(A, lda, rows, K, C, ldc, w, 0, nullptr, nullptr, diag_tile);
+    EmuFrame w;
+    w.reserve(emu_syrk_plan(std::max(rows, plan_rows), K, tile_rows));
+    if (emu_alloc(w, nullptr)) return GPX_ERR_HIP;
+    w.use(emu_syrk_plan(rows, K, tile_rows));
+    int rc = emu_syrk_split(w, A, lda, rows, 0);
+    for (int64_t q = 0; !rc && q * EMU_SLAB < rows; ++q) rc = emu_syrk_panel(w, q, C, ldc, rows, 0, nullptr, diag_tile);
     if (hipStreamSynchronize(0) != hipSuccess && rc == 0) { gpx_set_error("gpx_emu_syrk_lower_sub: stream failed"); rc = GPX_ERR_HIP; }
-    emu_syrk_free(w);
+    emu_free(w);
     return rc;
 }
 
@@ -910,9 +906,9 @@ extern "C" int gpx_emu_gemm_nt_sub(const double *A, int64_t lda, const double *B
     GPX_TRY(emu_check_args(A, lda, B, ldb, ldc, cols, K));   // before the workspace is sized and allocated
     if (rows == 0 || cols == 0) return 0;
     Scratch sc(0);
-    EmuWork w;
-    emu_work_need(w, rows, cols, K);
-    GPX_TRY(emu_work_alloc(w, sc));
+    EmuFrame w;
+    w.reserve(emu_work_plan(rows, cols, K));
+    GPX_TRY(emu_alloc(w, &sc));
     int rc = emu_gemm_nt_sub(A, lda, B, ldb, C, ldc, rows, cols, K, w, 0, nullptr);
     if (hipStreamSynchronize(0) != hipSuccess && rc == 0) { gpx_set_error("gpx_emu_gemm_nt_sub: stream failed"); rc = GPX_ERR_HIP; }
     return rc;
@@ -931,9 +927,7 @@ extern "C" int gpx_emu_rebuild_ex(const int8_t *R, int64_t ldr, int64_t sr, int 
         return GPX_ERR_BAD_ARG;
     }
     if (rows == 0 || cols == 0) return 0;
-    const long thr = (long)rows * ((cols + 3) / 4);
-    hipLaunchKernelGGL(emu_rebuild_kernel, dim3((unsigned)((thr + 255) / 256)), dim3(256), 0, 0, R, (long)ldr, (long)sr, nmod, emu_crt.t[nmod], sa, sb, C,
-                       (long)ldc, (long)rows, (long)cols, (long)diag, (long)dmask);
+    emu_launch_rebuild(R, ldr, sr, nmod, sa, sb, C, ldc, rows, cols, diag, dmask, 0);
     GPX_HIP(hipGetLastError());
     GPX_HIP(hipStreamSynchronize(0));
     return 0;
@@ -958,7 +952,7 @@ extern "C" int gpx_emu_split(const double *X, int64_t ldx, int64_t rows, int64_t
                              int *sig)
 {
     GPX_TRY(gpx_require_device());
-    if (K % EMU_BK || K >= (1 << 17) || !emu_split_args_ok(X, ldx, rows, rows_pad, K, bits, nmod, res, K, plane, sig)) {
+    if (!emu_k_ok(K) || !emu_split_args_ok(X, ldx, rows, rows_pad, K, bits, nmod, res, K, plane, sig)) {
         gpx_set_error("gpx_emu_split: bad arguments");
         return GPX_ERR_BAD_ARG;
     }
@@ -990,15 +984,13 @@ extern "C" int gpx_emu_i8_gemm_ld(const int8_t *A, int64_t lda, const int8_t *B,
                                   int64_t ldr)
 {
     GPX_TRY(gpx_require_device());
-    if (!A || !B || !R || rows <= 0 || cols <= 0 || rows % EMU_BT || cols % EMU_BT || K <= 0 || K % EMU_BK || K >= (1 << 17) || nmod < 1 ||
+    if (!A || !B || !R || rows <= 0 || cols <= 0 || rows % EMU_BT || cols % EMU_BT || !emu_k_ok(K) || nmod < 1 ||
         nmod > EMU_MAXL || ((uintptr_t)A | (uintptr_t)B) & 15 || rows / EMU_BT * (cols / EMU_BT) * nmod > INT32_MAX || lda < K || lda & 15 ||
         (EMU_BT - 1) * lda + K >= ((int64_t)1 << 31) || ldr < cols) {
         gpx_set_error("gpx_emu_i8_gemm: bad arguments");
         return GPX_ERR_BAD_ARG;
     }
-    const int tm = (int)(rows / EMU_BT), tn = (int)(cols / EMU_BT);
-    hipLaunchKernelGGL(emu_i8_gemm_kernel, dim3((unsigned)(tm * tn * nmod)), dim3(512), 0, 0, A, B, (long)(rows * lda), (long)(cols * K), (int)K, R,
-                       (long)ldr, (long)(rows * ldr), tm, tn, (int)lda);
+    GPX_TRY(emu_launch_product({A, lda, rows * lda, nullptr}, {B, K, cols * K, nullptr}, R, ldr, rows * ldr, rows / EMU_BT, cols / EMU_BT, K, nmod, 0));
     GPX_HIP(hipGetLastError());
     GPX_HIP(hipStreamSynchronize(0));
     return 0;
@@ -1021,7 +1013,7 @@ __global__ void emu_fill_kernel(int8_t *p, long n, unsigned seed)
 extern "C" int gpx_bench_emu_i8(int64_t rows, int64_t cols, int64_t K, int nmod, int iters, double *ms)
 {
     GPX_TRY(gpx_require_device());
-    if (rows % EMU_BT || cols % EMU_BT || K % EMU_BK || K >= (1 << 17) || nmod < 1 || nmod > EMU_MAXL || iters < 1 || !ms) {
+    if (rows % EMU_BT || cols % EMU_BT || !emu_k_ok(K) || nmod < 1 || nmod > EMU_MAXL || iters < 1 || !ms) {
         gpx_set_error("gpx_bench_emu_i8: bad arguments");
         return GPX_ERR_BAD_ARG;
     }
@@ -1033,15 +1025,14 @@ extern "C" int gpx_bench_emu_i8(int64_t rows, int64_t cols, int64_t K, int nmod,
     GPX_TRY(sc.take(&wr, rows * cols * nmod));
     hipLaunchKernelGGL(emu_fill_kernel, dim3(4096), dim3(256), 0, 0, wa, (long)(rows * K * nmod), 1u);
     hipLaunchKernelGGL(emu_fill_kernel, dim3(4096), dim3(256), 0, 0, wb, (long)(cols * K * nmod), 2u);
-    const int tm = (int)(rows / EMU_BT), tn = (int)(cols / EMU_BT);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     float t = 0.0f;
     hipError_t e = hipEventCreate(&e0);
     if (e == hipSuccess) e = hipEventCreate(&e1);
     for (int it = -1; it < iters && e == hipSuccess; ++it) {   // it = -1: warm-up
         if (it == 0) e = hipEventRecord(e0, 0);
-        hipLaunchKernelGGL(emu_i8_gemm_kernel, dim3((unsigned)(tm * tn * nmod)), dim3(512), 0, 0, (const int8_t *)wa, (const int8_t *)wb,
-                           (long)(rows * K), (long)(cols * K), (int)K, wr, (long)cols, (long)(rows * cols), tm, tn, (int)K);
+        rc = emu_launch_product({wa, K, rows * K, nullptr}, {wb, K, cols * K, nullptr}, wr, cols, rows * cols, rows / EMU_BT, cols / EMU_BT, K, nmod, 0);
+        if (rc) break;
         if (e == hipSuccess) e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipEventRecord(e1, 0);

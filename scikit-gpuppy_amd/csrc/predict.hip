@@ -36,13 +36,14 @@ int row_solve_begin(gpx_handle *h, int64_t m, RowSolve &rs, bool bounded, bool a
     rs.few = allow_few && m <= 32 && h->tri.ready() && h->tri.P >= 2;
     // the emulated updates' workspace (emu.hip), once per call: sized for the chunk, it serves every shorter one
     if (!rs.few) trsm_emu_need(rs.ew, rs.chunk, &h->tri, 0, h->tri.P);
-    if (rs.ew.a_bytes) GPX_TRY(emu_work_alloc(rs.ew, rs.sc));
-    rs.emu = rs.ew.ra ? &rs.ew : nullptr;
+    if (rs.ew.held.img) GPX_TRY(emu_alloc(rs.ew, &rs.sc));
+    rs.emu = rs.ew.a.base ? &rs.ew : nullptr;
     // a caller that bounds every solved row (estimate_many) takes the left-looking order over five slabs or more; as above the choice
     // depends on the factor's shape alone.  An image that does not fit leaves the recursion in charge.
     if (emu_left_route(bounded, rs.few, h->tri.ready(), h->tri.P)) {
-        emu_left_plan(rs.left, rs.chunk, h->tri.P);
-        if (emu_left_alloc(rs.left, rs.sc) == 0) rs.use_left = true;
+        rs.left.use(emu_left_plan(rs.chunk, h->tri.P));
+        rs.left.reserve(rs.left);
+        if (emu_alloc(rs.left, &rs.sc) == 0) rs.use_left = true;
         else {   // (the image, its tiles and arrays went back whole; the refusal is no error of this call)
             if (getenv("GPX_DEBUG")) fprintf(stderr, "[gpx] left-looking solve: no room for the residue image (%s): binary recursion\n", gpx_last_error());
             gpx_set_error("%s", "");
@@ -238,9 +239,10 @@ extern "C" int gpx_emu_trsm_left(gpx_handle *h, double *Z, int64_t ldz, int64_t 
     if (!h->tri.ready() || h->tri.P < 5 || !emu_enabled(4096)) { gpx_set_error("gpx_emu_trsm_left: needs a prepared solver over 5 slabs or more and the emulated update"); return GPX_ERR_STATE; }
     hipStream_t s = h->stream;
     Scratch sc(s);
-    EmuLeft w;
-    emu_left_plan(w, rows, h->tri.P, tile_rows);
-    GPX_TRY(emu_left_alloc(w, sc));
+    EmuFrame w;
+    w.use(emu_left_plan(rows, h->tri.P, tile_rows));
+    w.reserve(w);
+    GPX_TRY(emu_alloc(w, &sc));
     GPX_TRY(emu_left_begin(w, bound, rows, s));
     GPX_TRY(trsm_right_lt_slabs(Z, Zs, ldz, rows, &h->tri, s, &h->prof, nullptr, w));
     GPX_HIP(hipMemcpyAsync(status_out, w.status(), sizeof(int), hipMemcpyDeviceToHost, s));

@@ -487,7 +487,7 @@ static int slab_leaf(double *Z, double *Zs, int64_t ldz, int64_t rows, const Tri
 }
 
 int trsm_right_lt_squares(double *Z, double *Zs, int64_t ldz, int64_t rows, const TriSolver *ts, int64_t p0, int64_t p1, hipStream_t s,
-                          Profiler *prof, const GemmReduce *red, const EmuWork *emu)
+                          Profiler *prof, const GemmReduce *red, const EmuFrame *emu)
 {
     const int64_t np = p1 - p0;
     if (np <= 0 || rows <= 0) return 0;
@@ -514,14 +514,14 @@ int trsm_right_lt_squares(double *Z, double *Zs, int64_t ldz, int64_t rows, cons
 }
 
 // the workspace the emulated updates of trsm_right_lt_squares(rows, p0, p1) need (the same recursion, nothing queued)
-void trsm_emu_need(EmuWork &w, int64_t rows, const TriSolver *ts, int64_t p0, int64_t p1)
+void trsm_emu_need(EmuFrame &w, int64_t rows, const TriSolver *ts, int64_t p0, int64_t p1)
 {
     if (p1 - p0 <= 1 || rows <= 0) return;
     int64_t h = 1;
     while (h * 2 < p1 - p0) h *= 2;
     const int64_t pm = p0 + h, c0 = p0 * PB, cm = pm * PB, c1 = std::min<int64_t>(p1 * PB, ts->npad);
     trsm_emu_need(w, rows, ts, p0, pm);
-    if (emu_enabled(cm - c0)) emu_work_need(w, rows, c1 - cm, cm - c0);
+    if (emu_enabled(cm - c0)) w.reserve(emu_work_plan(rows, c1 - cm, cm - c0));
     trsm_emu_need(w, rows, ts, pm, p1);
 }
 
@@ -530,16 +530,16 @@ void trsm_emu_need(EmuWork &w, int64_t rows, const TriSolver *ts, int64_t p0, in
 //     Zs_p = (Z_p - Zs[:, 0:p) L[p, 0:p)^T) inv(L_pp)^T
 // of depth K = 1024 p, so from p = 4 on every update is deep enough for the int8 path (emu_enabled(4096)), where the binary recursion
 // leaves 24 of its 120 slab pairs at K = 1024 and 2048 on the fp64 cores.  It pays because a solved slab is split once: its residues
-// stay in the image of emu.hip (EmuLeft) and every later update reads them there.  Slabs 0 .. 3 run as in the recursion.  On one stream
+// stay in the image of emu.hip (emu_left_plan) and every later update reads them there.  Slabs 0 .. 3 run as in the recursion.  On one stream
 // the split of Zs_p sits between slab p's leaf and slab p + 1's split of L[p + 1, 0:p + 1), which needs nothing of it.
 // ------------------------------------------------------------------------------------------------------------------
 int trsm_right_lt_slabs(double *Z, double *Zs, int64_t ldz, int64_t rows, const TriSolver *ts, hipStream_t s, Profiler *prof, const GemmReduce *red,
-                        const EmuLeft &w, const EmuWork *emu)
+                        const EmuFrame &w, const EmuFrame *emu)
 {
     if (rows <= 0) return 0;
     if (!ts || !ts->Pl) { gpx_set_error("trsm_right_lt_slabs: solver not prepared"); return GPX_ERR_STATE; }
     const int64_t head = 4;
-    if (ts->P <= head || w.lda != PB * (ts->P - 1)) { gpx_set_error("trsm_right_lt_slabs: image planned for another factor"); return GPX_ERR_STATE; }
+    if (ts->P <= head || w.a.ld != PB * (ts->P - 1)) { gpx_set_error("trsm_right_lt_slabs: image planned for another factor"); return GPX_ERR_STATE; }
     GPX_TRY(trsm_right_lt_squares(Z, Zs, ldz, rows, ts, 0, head, s, prof, red, emu));
     for (int64_t q = 0; q < head; ++q) GPX_TRY(emu_left_split(w, Zs + q * PB, ldz, rows, q, s));
     for (int64_t p = head; p < ts->P; ++p) {

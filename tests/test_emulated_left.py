@@ -1,4 +1,4 @@
-"""The left-looking emulated solve (csrc/tsolve.hip trsm_right_lt_slabs, csrc/emu.hip EmuLeft) on the GPU.
+"""The left-looking emulated solve (csrc/tsolve.hip trsm_right_lt_slabs, csrc/emu.hip emu_left_plan / emu_left_update) on the GPU.
 
 Entry point: gpx_emu_trsm_left at the smallest shapes that reach every branch -- npad = 5120 (one emulated slab, K = 4096), 6144 (the
 residues of slabs 0 .. 3 read at two depths), 9216 (five depths), 300 rows (padded to 384), and 640 rows in row tiles of 256 through the

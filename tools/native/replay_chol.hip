@@ -3,7 +3,8 @@
 // replaced by a function that prints one line -- streams, events (numbered by first use) and pointers (as offsets) by name.  Needs no GPU.
 //   hipcc -O1 -std=c++17 --offload-arch=gfx950 -I<tree>/scikit-gpuppy_amd/csrc -DCHOL_PATH='"<tree>/scikit-gpuppy_amd/csrc/chol.hip"' \
 //         -x hip replay_chol.hip -o replay          (a tree from before fills.hip / the three-argument panel hook: add -DREPLAY_R10_TREE;
-//                                                    from before the far columns by group: -DREPLAY_NO_FIT_EMU)
+//                                                    from before the far columns by group: -DREPLAY_NO_FIT_EMU; from before the
+//                                                    emulated updates' one workspace frame: -DREPLAY_THREE_FRAMES)
 //   GPX_CONCURRENT_STREAMS=1 [GPX_SQK_FROM=.. ...] ./replay NBLK MODE > log
 //   MODE 0: chol_factor on one stream, 1: with a chain stream, 2: chain + column streams; 3 .. 6: the panel step over all panels
 //   (3: internal slice stream, 4: caller streams, no head rows, 5 / 6: caller streams, head rows, two / three ranks share the update).
@@ -46,11 +47,21 @@ int launch_syrk_trap_signal(const double *A, int64_t, const double *B, int64_t, 
 }
 #ifndef REPLAY_NO_FIT_EMU
 bool emu_enabled(int64_t K) { const char *e = getenv("GPX_EMU_MIN_K"); return K >= (e ? atol(e) : 4096L) && K % 128 == 0; }
+#ifdef REPLAY_THREE_FRAMES   // a tree from before the one workspace frame (EmuSyrk with its own plan / alloc / free)
 void emu_syrk_plan(EmuSyrk &w, int64_t rows, int64_t K, int64_t) { w.rows_pad = rows; w.K = K; }
 int emu_syrk_alloc(EmuSyrk &) { return getenv("MOCK_EMU_NO_ROOM") ? GPX_ERR_HIP : 0; }
 void emu_syrk_free(EmuSyrk &) {}
-int emu_syrk_split(const EmuSyrk &w, const double *A, int64_t, int64_t rows, hipStream_t s) { printf("emu-split s%d A%ld %ld %ld\n", sid(s), off(A), (long)rows, (long)w.K); return 0; }
-int emu_syrk_panel(const EmuSyrk &w, int64_t q, double *C, int64_t, int64_t rows, hipStream_t s, Profiler *, int dt) { printf("emu-panel s%d q%ld C%ld %ld %ld dt%d\n", sid(s), (long)q, off(C), (long)rows, (long)w.K, dt); return 0; }
+static long depth(const EmuSyrk &w) { return (long)w.K; }
+#else
+typedef EmuFrame EmuSyrk;
+void EmuFrame::reserve(const EmuPlan &) {}
+EmuPlan emu_syrk_plan(int64_t rows, int64_t K, int64_t) { EmuPlan p; p.a.rows_pad = rows; p.a.ld = K; return p; }
+int emu_alloc(EmuFrame &, Scratch *) { return getenv("MOCK_EMU_NO_ROOM") ? GPX_ERR_HIP : 0; }
+void emu_free(EmuFrame &) {}
+static long depth(const EmuFrame &w) { return (long)w.a.ld; }
+#endif
+int emu_syrk_split(const EmuSyrk &w, const double *A, int64_t, int64_t rows, hipStream_t s) { printf("emu-split s%d A%ld %ld %ld\n", sid(s), off(A), (long)rows, depth(w)); return 0; }
+int emu_syrk_panel(const EmuSyrk &w, int64_t q, double *C, int64_t, int64_t rows, hipStream_t s, Profiler *, int dt) { printf("emu-panel s%d q%ld C%ld %ld %ld dt%d\n", sid(s), (long)q, off(C), (long)rows, depth(w), dt); return 0; }
 #endif
 int64_t chol_dataflow_state_ints(int64_t nbr) { return 41 * nbr; }
 int64_t chol_dataflow_table_ints(int64_t nbr) { return 12 * nbr; }
