@@ -228,6 +228,21 @@ int gpx_propagate_exact(gpx_handle *h, const double *u, const double *Sigma, dou
  * first launch (a singular W/2 + Sigma: GPX_ERR_BAD_ARG, nothing written).  An input's result does not depend on its place in the batch; the
  * state of the single-input calls is left alone; the call may build K^-1 on the handle, as gpx_propagate_exact does. */
 int gpx_propagate_exact_many(gpx_handle *h, const double *U, const double *Sigma, int sigma_shared, int64_t b, double *mean, double *var);
+/* The batched Exact moments WITH their closed-form gradients in u and in the diagonal of Sigma (no reference counterpart: the reference's
+ * exact inverse solver runs COBYLA because "Gradient based methods are not suitable ... we would have to calculate the gradient of the GA
+ * propagation of the variance", skgpuppy/InverseUncertaintyPropagation.py:103-104; this is that gradient).  U, Sigma, sigma_shared, b as in
+ * gpx_propagate_exact_many; mean [b] (WITHOUT meant) and var [b]; dmean_du, dvar_du [b, d]: the derivatives in u_k; dmean_ds, dvar_ds [b, d]:
+ * the derivatives in Sigma_kk with every other entry of Sigma held fixed (Sigma itself may be full).  The function differentiated is the one
+ * gpx_propagate_exact_many computes: its normalisers read the diagonal of Sigma only, as the reference's do.  Any output may be NULL, but not
+ * all four gradients; with var, dvar_du and dvar_ds all NULL, K^-1 is neither built nor read and no GEMM is launched.  With a_j = u - x_j,
+ * b_j = A^-1 a_j and the rows h, p_k = h o b_.k, c_k = h o b_.k^2 (2 d + 1 consecutive rows of the product per input), Y_r = Lo r:
+ *   S = 2 h.Y_h,  G_k = p_k.Y_h + h.Y_pk,  Q_k = (c_k.Y_h + h.Y_ck) / 2 + p_k.Y_pk,
+ *   dvar/du_k = nc2 G_k - 2 m dm/du_k,  dvar/ds_k = -nc2 (Q_k / 2 - w_k / (2 w_k s_k + 1) S) - 2 m dm/ds_k.
+ * Per-input Sigma is cut into runs of bit-equal Sigma; EVERY run takes the matrix path, a run of one included.  GPX_EXACT_MANY_SLAB counts
+ * product ROWS here: whole inputs go into each slab, and a setting below 2 d + 1 rows is raised to hold one input.  One synchronisation per
+ * call; an input's results do not depend on its place in the batch; a singular W/2 + Sigma: GPX_ERR_BAD_ARG, nothing written. */
+int gpx_propagate_exact_grad_many(gpx_handle *h, const double *U, const double *Sigma, int sigma_shared, int64_t b, double *mean, double *var,
+                                  double *dmean_du, double *dvar_du, double *dmean_ds, double *dvar_ds);
 /* row-sharded form (multi-GPU host): partial_out[3] = { sum_{i in rows} beta_i l_i, the rows' share of the double sum / nc2,
  * nc2 }; summed over the row panels: mean = p0, var = v + vt - nc2 p1 - p0^2.  Same row alignment as gpx_propagate_approx_rows. */
 int gpx_propagate_exact_rows(gpx_handle *h, const double *u, const double *Sigma, int64_t row0, int64_t row1, double *partial_out);

@@ -522,6 +522,15 @@ int launch_exact_many_build(const double *x, const double *xh, int64_t n, int64_
                             const double *beta, double v, double vt, double nc1, double *H, double *mpart, hipStream_t s, Profiler *prof);
 int launch_exact_many_finish(const double *Y, const double *H, int64_t npad, const double *mpart, int64_t nb, double vplusvt, double nc2,
                              double *out, int64_t ldo, hipStream_t s, Profiler *prof);
+// the gradients of the batched Exact moments (gpx_propagate_exact_grad_many; exact_grad.hip): a slab's 2 d + 1 rows [h, p_1..p_d, c_1..c_d]
+// per input and the partials of the 2 d + 1 mean sums (H == nullptr: those alone), and the six outputs from the rows and Y = H Lo^T;
+// out = [mean | var | dmean_du | dvar_du | dmean_ds | dvar_ds], blocks of ldo inputs, the slab's first input at o0
+int launch_exact_grad_build(const double *x, const double *xh, int64_t n, int64_t npad, int d, const double *U_dev, const double *Uh_dev,
+                            int64_t nb, int64_t rows_pad, const double *w_dev, const double *dinv_diag_dev, const double *Dk_dev,
+                            const double *sgn_dev, const double *Bm_dev, const double *beta, double v, double vt, double nc1, double *H,
+                            double *mpart, hipStream_t s, Profiler *prof);
+int launch_exact_grad_finish(const double *Y, const double *H, int64_t npad, int d, const double *mpart, int64_t nb, double vplusvt, double nc2,
+                             const double *nq_dev, double *out, int64_t ldo, int64_t o0, hipStream_t s, Profiler *prof);
 
 // ---- host orchestration shared by fit.hip, predict.hip and propagate_api.hip ---------------------
 // (helpers, not interface: they stay out of the library's dynamic symbol table)

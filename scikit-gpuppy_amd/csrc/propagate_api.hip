@@ -948,6 +948,123 @@ extern "C" int gpx_propagate_exact_many(gpx_handle *h, const double *U, const do
     return 0;
 }
 
+// Batched Exact with its closed-form gradients in u and in the diagonal of Sigma (kernels and arithmetic: exact_grad.hip).  The frame of
+// gpx_propagate_exact_many with three differences: every run of bit-equal Sigma takes the matrix path, a run of one included (there is no
+// pair-path form of the gradient); an input is 2 d + 1 consecutive rows [h, p_1..p_d, c_1..c_d] of the product, so the slab is counted in
+// product ROWS, whole inputs go into each slab and a slab setting below 2 d + 1 rows is raised to hold one input; and the finish kernel
+// writes all six outputs.  Without var, dvar_du and dvar_ds the call is N-fold work per input: K^-1 is neither built nor read.
+extern "C" int gpx_propagate_exact_grad_many(gpx_handle *h, const double *U, const double *Sigma, int sigma_shared, int64_t b, double *mean,
+                                             double *var, double *dmean_du, double *dvar_du, double *dmean_ds, double *dvar_ds)
+{
+    CHECK_H_PSEUDO_OK(h);
+    NEED_KERNEL(h, "gpx_propagate_exact_grad_many");
+    if (b < 0 || (b > 0 && (!U || !Sigma || (!dmean_du && !dvar_du && !dmean_ds && !dvar_ds)))) {
+        gpx_set_error("gpx_propagate_exact_grad_many: bad arguments (b = %ld, a null U / Sigma, or no gradient asked for)", (long)b);
+        return GPX_ERR_BAD_ARG;
+    }
+    if (b == 0) return 0;
+    const int d = h->d, nrow = 2 * d + 1;
+    const int64_t n = h->n, np = h->npad, d2 = (int64_t)d * d;
+    const bool want_var = var || dvar_du || dvar_ds;
+    hipStream_t s = h->stream;
+    int64_t slab = env_count("GPX_EXACT_MANY_SLAB", 4096);
+    if (slab < TILE || slab % TILE || slab > (1 << 19)) slab = 4096;
+    slab = std::max<int64_t>(slab, round_up(nrow, TILE));
+    const int64_t bslab = slab / nrow;   // whole inputs per slab
+
+    // runs of bit-equal Sigma and their constants, on the host: [dd d | D d | w / (2 w s + 1) d] and, with variances,
+    // [T of Ls / 8 d^2 | its signs d | T of A^-1 / 4 d^2 | its signs d | Bm = 4 T^T diag(signs) d^2]
+    struct Run { int64_t i0, cnt, off; double nc1, nc2; };
+    std::vector<Run> runs;
+    std::vector<double> Sh, arena, res;
+    const int64_t per = 2 + 4 * (int64_t)d;   // mean | var | four [d] blocks, per input
+    int64_t max_cnt = 0;
+    try {
+        Sh.resize((size_t)((sigma_shared ? 1 : b) * d2));
+        res.resize((size_t)(per * b));
+    } catch (const std::bad_alloc &) { gpx_set_error("gpx_propagate_exact_grad_many: out of host memory"); return GPX_ERR_HIP; }
+    GPX_TRY(fetch_small(Sh.data(), Sigma, Sh.size()));
+    for (int64_t i = 0; i < b;) {
+        int64_t j = sigma_shared ? b : i + 1;
+        while (j < b && memcmp(&Sh[(size_t)(i * d2)], &Sh[(size_t)(j * d2)], sizeof(double) * d2) == 0) ++j;
+        runs.push_back({i, j - i, 0, 1.0, 1.0});
+        max_cnt = std::max(max_cnt, j - i);
+        i = j;
+    }
+    try {
+        for (Run &r : runs) {
+            const double *Sg = &Sh[(size_t)(sigma_shared ? 0 : r.i0 * d2)];
+            ExactConstants c;
+            GPX_TRY(exact_constants(h->w, Sg, d, c));
+            r.nc1 = c.nc1;
+            r.nc2 = c.nc2;
+            r.off = (int64_t)arena.size();
+            arena.insert(arena.end(), c.dd.begin(), c.dd.end());
+            for (int k = 0; k < d; ++k) arena.push_back(h->w[k] / (1.0 + h->w[k] * Sg[k * d + k]));
+            for (int k = 0; k < d; ++k) arena.push_back(h->w[k] / (2.0 * h->w[k] * Sg[k * d + k] + 1.0));
+            if (want_var) {
+                const size_t at = arena.size();
+                arena.resize(at + 3 * (size_t)d2 + 2 * (size_t)d);
+                double *T2 = &arena[at + d2 + d], *s2 = T2 + d2, *Bm = s2 + d;
+                sym_square_transform(c.Ls.data(), d, 0.125, &arena[at], &arena[at + d2]);
+                sym_square_transform(c.Ai.data(), d, 0.25, T2, s2);
+                for (int k = 0; k < d; ++k)
+                    for (int m = 0; m < d; ++m) Bm[(size_t)k * d + m] = 4.0 * T2[(size_t)m * d + k] * s2[m];
+            }
+        }
+    } catch (const std::bad_alloc &) { gpx_set_error("gpx_propagate_exact_grad_many: out of host memory"); return GPX_ERR_HIP; }
+
+    if (want_var) GPX_TRY(ensure_kinv(h));
+    Scratch sc(s);
+    double *cd = nullptr, *Ud = nullptr, *od = nullptr;
+    GPX_TRY(sc.take(&cd, (int64_t)arena.size()));
+    GPX_TRY(sc.take(&Ud, b * d));
+    GPX_TRY(sc.take(&od, per * b));
+    const int64_t bmax = std::min(bslab, max_cnt), rows = round_up(bmax * nrow, TILE), npart = np / 64;
+    double *mpart = nullptr, *Hd = nullptr, *Yd = nullptr, *Lo = nullptr, *xt = nullptr, *xh = nullptr, *Uh = nullptr;
+    GPX_TRY(sc.take(&mpart, bmax * nrow * npart));
+    if (want_var) {
+        GPX_TRY(sc.take(&xt, np * d));
+        GPX_TRY(sc.take(&xh, np * d));
+        GPX_TRY(sc.take(&Uh, bmax * d));
+        GPX_TRY(sc.take(&Hd, rows * np));
+        GPX_TRY(sc.take(&Yd, rows * np));
+        GPX_TRY(sc.take(&Lo, np * np));
+    }
+    GPX_HIP(hipMemcpyAsync(cd, arena.data(), sizeof(double) * arena.size(), hipMemcpyHostToDevice, s));
+    GPX_HIP(hipMemcpyAsync(Ud, U, sizeof(double) * b * d, hipMemcpyDefault, s));
+    const double vpv = h->v + h->vt;
+    Profiler *prof = want_var ? &h->prof : nullptr;   // the mean sums alone are N-fold work: outside the Exact class, as in gpx_propagate_exact_many
+    for (const Run &r : runs) {
+        const double *ddd = cd + r.off, *Dkd = ddd + d, *nqd = Dkd + d, *T1 = nqd + d, *s1 = T1 + d2, *T2 = s1 + d, *s2 = T2 + d2, *Bmd = s2 + d;
+        if (want_var) {
+            GPX_TRY(launch_exact_many_transform(h->x, n, np, d, h->x, T1, xt, s));
+            GPX_TRY(launch_exact_weight(h->Kinv, np, n, np, d, h->alpha, xt, s1, Lo, s, &h->prof));
+            GPX_TRY(launch_exact_many_transform(h->x, n, np, d, h->x, T2, xh, s));
+        }
+        for (int64_t b0 = 0; b0 < r.cnt; b0 += bmax) {
+            const int64_t bc = std::min(bmax, r.cnt - b0), rp = round_up(bc * nrow, TILE), i0 = r.i0 + b0;
+            if (want_var) GPX_TRY(launch_exact_many_transform(Ud + i0 * d, bc, bc, d, h->x, T2, Uh, s));
+            GPX_TRY(launch_exact_grad_build(h->x, xh, n, np, d, Ud + i0 * d, Uh, bc, rp, h->wdev, ddd, Dkd, s2, Bmd, h->alpha, h->v, handle_vt_on_equal(h),
+                                            r.nc1, want_var ? Hd : nullptr, mpart, s, prof));
+            if (want_var) GPX_TRY(launch_gemm_nt(Hd, np, Lo, np, Yd, np, rp, np, np, 1.0, 0.0, 0, s, &h->prof, 0, GEMM_TRI_B_LOWER));
+            // the finish kernel indexes its output blocks by the input's place in the whole batch: od + i0 with blocks b inputs long
+            GPX_TRY(launch_exact_grad_finish(want_var ? Yd : nullptr, Hd, np, d, mpart, bc, vpv, r.nc2, nqd, od, b, i0, s, prof));
+        }
+    }
+    GPX_HIP(hipMemcpyAsync(res.data(), od, sizeof(double) * per * b, hipMemcpyDeviceToHost, s));
+    const hipError_t e = sc.wait_and_free();                  // the call's one synchronisation
+    if (e != hipSuccess) { gpx_set_error("gpx_propagate_exact_grad_many: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
+    const double *rm = res.data(), *rv = rm + b, *rmu = rv + b, *rvu = rmu + b * d, *rms = rvu + b * d, *rvs = rms + b * d;
+    if (mean) GPX_HIP(hipMemcpy(mean, rm, sizeof(double) * b, hipMemcpyDefault));
+    if (var) GPX_HIP(hipMemcpy(var, rv, sizeof(double) * b, hipMemcpyDefault));
+    if (dmean_du) GPX_HIP(hipMemcpy(dmean_du, rmu, sizeof(double) * b * d, hipMemcpyDefault));
+    if (dvar_du) GPX_HIP(hipMemcpy(dvar_du, rvu, sizeof(double) * b * d, hipMemcpyDefault));
+    if (dmean_ds) GPX_HIP(hipMemcpy(dmean_ds, rms, sizeof(double) * b * d, hipMemcpyDefault));
+    if (dvar_ds) GPX_HIP(hipMemcpy(dvar_ds, rvs, sizeof(double) * b * d, hipMemcpyDefault));
+    return 0;
+}
+
 // ---- a14 for ANY operator.  The reference's UncertaintyPropagationExact talks to the GP only through _get_beta, _get_W_inv,
 // _inv_cov_matrix, _covariance and x (skgpuppy/UncertaintyPropagation.py:269-290, :323-379): with a Covariance subclass of its own
 // cov_matrix_ij / __call__ it runs and returns numbers -- Girard's correction factors built from theta[2:2+d], applied to the

@@ -33,11 +33,87 @@ def _followers(coestimated):
     return [(group[0], i) for group in coestimated for i in group if i != group[0]]
 
 
+def _reduced(c, I, coestimated):
+    """(c, I, free) of the free variances: the followers of every co-estimation group removed (the successive np.delete of
+    InverseUncertaintyPropagationNumerical.get_best_solution, which is the reference's)"""
+    c, I = np.asarray(c, dtype=float), np.asarray(I, dtype=float)
+    free = np.array(list(range(len(c))))
+    for _lead, i in _followers(coestimated):
+        I = np.delete(I, i)
+        c = np.delete(c, i)
+        free = np.delete(free, i)
+    return c, I, free
+
+
+def slsqp_inverse(value_and_grad, output_variance, c, I, coestimated=[], start=None, acc=1e-8, maxiter=200):
+    """The gradient-based form of InverseUncertaintyPropagationNumerical.get_best_solution: minimise the cost sum_k c_k / (v_k I_k) over the
+    free LOG-variances x_k = log v_k under output_variance - var(v) >= 0, by SLSQP with analytic Jacobians.
+
+    value_and_grad(v_full [d]) -> (var, dvar_dv [d]): the output variance at the input variances v_full and its derivative in each of them
+    (UncertaintyPropagationExact.propagate_GA_gradient gives both; any model of them serves, so the driver runs without a device).
+    The chain rule runs through exp (dv_k / dx_k = v_k) and through the co-estimated followers: v_i = v_lead I_lead / I_i moves with its
+    lead, so dvar_dv_i v_i adds to the lead's derivative.  Cost Jacobian: -c_k / (v_k I_k).  start: the free log-variances (default -10
+    each, the COBYLA path's).  Returns (v_full [d], info) with info = {"x": the free log-variances, "free": their indices, "calls": the
+    number of value_and_grad evaluations, "result": scipy's OptimizeResult}."""
+    from scipy.optimize import minimize
+    c_full, I_full = np.asarray(c, dtype=float), np.asarray(I, dtype=float)
+    followers = _followers(coestimated)
+    cr, Ir, free = _reduced(c_full, I_full, coestimated)
+    pos = dict((int(m), k) for k, m in enumerate(free))
+
+    def expand(x):
+        v = np.zeros(len(c_full))
+        v[free] = np.exp(x)
+        for lead, i in followers:
+            v[i] = v[lead] * I_full[lead] / I_full[i]
+        return v
+
+    memo = {"key": None, "calls": 0}
+
+    def evaluate(x):          # SLSQP asks for the constraint and for its Jacobian at the same x: one propagation serves both
+        key = np.asarray(x, dtype=float).tobytes()
+        if memo["key"] != key:
+            v = expand(x)
+            var, dv = value_and_grad(v)
+            dv = np.asarray(dv, dtype=float)
+            g = np.array([dv[m] * v[m] for m in free])
+            for lead, i in followers:
+                g[pos[lead]] += dv[i] * v[i]
+            memo.update(key=key, var=float(var), g=g, calls=memo["calls"] + 1)
+        return memo["var"], memo["g"]
+
+    cost = lambda x: np.sum(cr / np.exp(x) / Ir)          # noqa: E731
+    cost_jac = lambda x: -cr / np.exp(x) / Ir             # noqa: E731
+    cons = {"type": "ineq", "fun": lambda x: output_variance - evaluate(x)[0], "jac": lambda x: -evaluate(x)[1]}
+    x0 = np.ones(len(cr)) * -10 if start is None else np.asarray(start, dtype=float)
+    res = minimize(cost, x0, jac=cost_jac, constraints=[cons], method="SLSQP", options={"ftol": acc, "maxiter": maxiter})
+    return expand(res.x), {"x": res.x, "free": free, "calls": memo["calls"], "result": res}
+
+
 class InverseUncertaintyPropagationNumerical(InverseUncertaintyPropagation):
     """COBYLA on log-variances with the constraint output_variance - propagate_GA(u, diag(v))[1] >= 0
-    (InverseUncertaintyPropagation.py:55-117)."""
+    (InverseUncertaintyPropagation.py:55-117); method="slsqp": the same cost under the same constraint by SLSQP on the closed-form
+    gradient of the propagated variance (slsqp_inverse), for a upga_class that has propagate_GA_gradient."""
 
-    def get_best_solution(self, startvalue=None):
+    def _best_solution_slsqp(self, startvalue):
+        if not hasattr(self.upga_class, "propagate_GA_gradient"):
+            raise TypeError("method='slsqp' needs a upga_class with propagate_GA_gradient; %s has none" % self.upga_class.__name__)
+        upga = self.upga_class(self.gp)
+
+        def value_and_grad(v):
+            out = upga.propagate_GA_gradient(self.u, np.diag(v))
+            return out[1], out[5]
+
+        v, info = slsqp_inverse(value_and_grad, self.output_variance, self.c, self.I, self.coestimated, startvalue)
+        assert (v > 0).all()
+        self.slsqp_info = info
+        return v
+
+    def get_best_solution(self, startvalue=None, method="cobyla"):
+        if method == "slsqp":
+            return self._best_solution_slsqp(startvalue)
+        if method != "cobyla":
+            raise ValueError("method must be 'cobyla' or 'slsqp', got %r" % (method,))
         from scipy.optimize import fmin_cobyla
         c_full = np.asarray(self.c, dtype=float)
         I_full = np.asarray(self.I, dtype=float)

@@ -524,6 +524,49 @@ class UncertaintyPropagationExact(UncertaintyPropagationGA):
         mean, var = self._moments_many(U, Sigma_x, True)
         return mean + self.gp._get_mean_t(), var
 
+    # ---- the moments with their gradients in u and in the diagonal of Sigma_x (no reference counterpart: the gradient whose absence makes
+    # the reference's exact inverse solver derivative-free, InverseUncertaintyPropagation.py:103-104) ----
+    def propagate_GA_gradient_many(self, U, Sigma_x, h=1e-5):
+        """(mean + meant [B], var [B], d mean / d u [B, d], d var / d u [B, d], d mean / d v [B, d], d var / d v [B, d]) for the rows of
+        U (B, d), v_k = Sigma_x[k, k] with every other entry of Sigma_x held fixed; Sigma_x (d, d) for all inputs or (B, d, d).
+
+        Route "gaussian" (pseudo_gp() included) is fused: ONE gpx_propagate_exact_grad_many call, closed form (gpx.h); h is not used.  Every
+        other route takes central differences through propagate_GA_many, one call per distinct Sigma: the B inputs and their 2 d B shifts by
+        h along each coordinate under Sigma_x, then per k the B inputs under Sigma_x -+ h v_k e_k e_k^T (a relative step; h itself where
+        v_k = 0).  Neither sets Winv, Sigma_x, Deltainv, LambdaInv or the normalisers on this instance."""
+        UU, S = self._many_args(U, Sigma_x)
+        B, d = UU.shape
+        meant = self.gp._get_mean_t()
+        if self.gp._route() == "gaussian":
+            mean, var = np.empty(B), np.empty(B)
+            g = [np.empty((B, d)) for _ in range(4)]
+            st = _gpx.lib.gpx_propagate_exact_grad_many(self.gp._dev().handle, _gpx.ptr(UU), _gpx.ptr(S), int(S.ndim == 2), B, _gpx.ptr(mean),
+                                                        _gpx.ptr(var), *[_gpx.ptr(a) for a in g])
+            _gpx.check(st, "gpx_propagate_exact_grad_many")
+            return (mean + meant, var) + tuple(g)
+        # rows [0, B): the inputs; then per k the B inputs moved by -h and the B moved by +h along k
+        pts = np.concatenate([UU[None]] + [UU[None] + s * h * np.eye(d)[k] for k in range(d) for s in (-1.0, 1.0)]).reshape(-1, d)
+        mu, var = self.propagate_GA_many(pts, S if S.ndim == 2 else np.tile(S, (2 * d + 1, 1, 1)))
+        mu, var = np.asarray(mu).reshape(2 * d + 1, B), np.asarray(var).reshape(2 * d + 1, B)
+        dmu, dvu = ((mu[2::2] - mu[1::2]) / (2.0 * h)).T, ((var[2::2] - var[1::2]) / (2.0 * h)).T
+        dmv, dvv = np.empty((B, d)), np.empty((B, d))
+        for k in range(d):
+            vk = S[..., k, k]
+            step = np.where(vk != 0, h * np.abs(vk), h)
+            side = []
+            for s in (-1.0, 1.0):
+                Sk = S.copy()
+                Sk[..., k, k] = vk + s * step
+                side.append(self.propagate_GA_many(UU, Sk))
+            dmv[:, k] = (side[1][0] - side[0][0]) / (2.0 * step)
+            dvv[:, k] = (side[1][1] - side[0][1]) / (2.0 * step)
+        return mu[0], var[0], dmu, dvu, dmv, dvv
+
+    def propagate_GA_gradient(self, u, Sigma_x, h=1e-5):
+        """single-input twin of propagate_GA_gradient_many: scalars for mean and var, [d] for the four gradients"""
+        uu, S = _u_sigma(self.gp, u, Sigma_x)
+        return tuple(o[0] for o in self.propagate_GA_gradient_many(uu[None], S, h))
+
 
 # ---- the numerical family (UncertaintyPropagation.py:28-52, :90-162) ---------------------------------------------------------------
 class UncertaintyPropagation(object):

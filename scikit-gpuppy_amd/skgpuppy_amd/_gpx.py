@@ -88,6 +88,7 @@ SIGNATURES = {
     "gpx_quadrature_nodes": (_int, [_dp, _dp, _int, _i64, _dp, _i64, _int, _dp]),
     "gpx_propagate_exact": (_int, [_hp, _dp, _dp, ctypes.POINTER(_dbl), ctypes.POINTER(_dbl)]),
     "gpx_propagate_exact_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp, _dp]),
+    "gpx_propagate_exact_grad_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp, _dp, _dp, _dp, _dp, _dp]),
     "gpx_propagate_exact_rows": (_int, [_hp, _dp, _dp, _i64, _i64, _dp]),
     "gpx_exact_mean": (_int, [_hp, _dp, _dp, ctypes.POINTER(_dbl)]),
     "gpx_propagate_exact_matrix": (_int, [_hp, _dp, _dp, _dp, _i64, _int, _dp, _dp, _dp, _dp, _dbl, ctypes.POINTER(_dbl), ctypes.POINTER(_dbl)]),
