@@ -31,7 +31,9 @@ within MARGIN * max(rho_ref, FLOOR), rho_ref the largest distance of the float64
 to a device result.  What the device's arithmetic has and the float64 evaluation has not: q from sqrt(w)-prescaled inputs in the gradient,
 x~_k = fl(sqrt(w_k) x_k): the difference of two prescaled coordinates is off by at most 2 u max_k(sqrt(w_k) |x_k|), hence
 |dq| <= 4 max_k(sqrt(w_k) |x_k|) sqrt(d q) u + d q u and a term's relative error is half of it: 1.3e-14 at d = 64, q = 14 (the largest q of
-a term above 1e-3 v), sqrt(w) |x| <= 0.5 -- under FLOOR, so the rule needs no extra term for it.
+a term above 1e-3 v), sqrt(w) |x| <= 0.5 -- under FLOOR, so the rule needs no extra term for it.  Away from the origin it is not: for
+inputs translated by `shift` (tests/test_shifted_inputs.py: 2^10, 2^17) grad_loss() sums this quantity pair by pair (prescale_loss) and the
+tests admit exactly it, as an absolute allowance outside the margin.
 
 `defect=` plants one of the seeded defects of tests/test_dense_ld_model.py in an evaluation (meant for dt = np.float64)."""
 import os
@@ -153,14 +155,33 @@ def _weights(defect, N, i0, i1, pair):
     return W
 
 
-def grad_sums(x, theta, Kinv, alpha, dt=LD, defect=None):
-    """([S_0, S_1 .. S_d, T], their scales)"""
+def prescale_loss(x, theta, shift, D, dt=LD):
+    """What the device's prescaling costs the terms of a block of pairs when the inputs it sees are x + shift, as bounds per pair:
+    (rq [rows, N], rk [d, rows, N]) for D [d, rows, N] = w_k (x_ik - x_jk)^2.  With m_k = sqrt(w_k) max_i |x_ik + shift|, m = max_k m_k, u = 2^-53 and e_k the exact scaled
+    difference (e_k^2 = D[k] = w_k (x_ik - x_jk)^2), the difference of two prescaled coordinates is off by at most 2 u m_k (module
+    docstring), so
+      |d(e_k^2)| <= 4 u m_k |e_k| + u e_k^2                                                            =: rk[k]   (the factor of S_{1+k})
+      |dq| <= 4 u m sum_k |e_k| + u q <= 4 m sqrt(d q) u + d q u,  a term's relative error half of it  =: rq      (the factor Kf of every sum)
+    rq is the quantity the module docstring derives; rk is the same bound before Cauchy-Schwarz, for the one coordinate."""
+    xr = np.asarray(x, dtype=np.float64)
+    d = xr.shape[1]
+    _v, _vt, w = params(theta, d, dt)
+    u = dt(2.0 ** -53)
+    mk = np.sqrt(w) * np.abs(xr + shift).max(0).astype(dt)
+    q = D.sum(0)
+    rq = (4 * mk.max() * np.sqrt(d * q) * u + d * q * u) / 2
+    rk = np.array([4 * u * mk[k] * np.sqrt(D[k]) + u * D[k] for k in range(d)])
+    return rq, rk
+
+
+def _grad_sums(x, theta, Kinv, alpha, dt, defect, shift):
+    """(sums, scales, loss): loss [d + 2] = sum over the pairs of |term| times its prescale_loss for a device that saw x + shift (0 at shift 0)"""
     xr = np.asarray(x, dtype=np.float64)
     N, d = xr.shape
     v, _vt, w = params(theta, d, dt)
     x = xr.astype(dt)
     Ki, al = np.asarray(Kinv).astype(dt), np.asarray(alpha).astype(dt)
-    S, A = np.zeros(d + 2, dt), np.zeros(d + 2, dt)
+    S, A, E = np.zeros(d + 2, dt), np.zeros(d + 2, dt), np.zeros(d + 2, dt)
     pair = _pair_of(xr, w) if defect == "pair" else None
     for i0 in range(0, N, ROWS):
         i1 = min(N, i0 + ROWS)
@@ -178,10 +199,28 @@ def grad_sums(x, theta, Kinv, alpha, dt=LD, defect=None):
         for k in range(d):
             S[1 + k] += (MK * D[k]).sum()
             A[1 + k] += (AK * D[k]).sum()
+        if shift != 0.0:
+            rq, rk = prescale_loss(xr, theta, shift, D, dt)
+            E[0] += (AK * rq).sum()
+            for k in range(d):
+                E[1 + k] += (AK * (D[k] * rq + rk[k])).sum()
     dg = np.diagonal(Ki)
     S[d + 1] = dg.sum() - al.dot(al)
     A[d + 1] = np.abs(dg).sum() + al.dot(al)
-    return S, A
+    return S, A, E
+
+
+def grad_sums(x, theta, Kinv, alpha, dt=LD, defect=None):
+    """([S_0, S_1 .. S_d, T], their scales)"""
+    return _grad_sums(x, theta, Kinv, alpha, dt, defect, 0.0)[:2]
+
+
+def grad_loss(x, theta, Kinv, alpha, shift):
+    """[d + 2], long double: what the prescaling may cost each entry of gpx_nll_grad when the device saw x + shift (x: the case as seeded) --
+    the sum over the pairs of |term| prescale_loss, combined as grad_from_sums combines the sums.  An ABSOLUTE allowance: the tests take it
+    off |got - model| before the rule (distances(loss=)), outside the margin, so exactly this quantity is admitted and nothing else."""
+    _S, _A, E = _grad_sums(x, theta, Kinv, alpha, LD, None, shift)
+    return grad_from_sums(E, E, theta)[1]
 
 
 def grad_from_sums(S, A, theta):
@@ -342,12 +381,13 @@ def exact_builtin(x, theta, Kinv, alpha, u, Sigma, rows=None, dt=LD, defect=None
 # ------------------------------------------------------------------------------------------------
 # the rule
 # ------------------------------------------------------------------------------------------------
-def distances(got, want, scale):
-    """|got - want| / scale entry by entry in long double; 0 where both the difference and the scale are 0"""
+def distances(got, want, scale, loss=0):
+    """|got - want| / scale entry by entry in long double; 0 where both the difference and the scale are 0.  loss: an absolute allowance
+    per entry, taken off the difference first (grad_loss)"""
     g, w, s = (np.atleast_1d(np.asarray(a)).astype(LD) for a in (got, want, scale))
     if g.shape != w.shape:
         raise ValueError("shape %r against %r" % (g.shape, w.shape))
-    diff = np.abs(g - w)
+    diff = np.maximum(np.abs(g - w) - loss, 0)
     with np.errstate(divide="ignore", invalid="ignore"):
         r = diff / s
     return np.where((diff == 0) & (s == 0), LD(0), r).astype(np.float64)
