@@ -18,6 +18,26 @@ def tracedot(A, B):
     return np.dot(np.ravel(np.asarray(A).T), np.ravel(B))
 
 
+def _signature(a):
+    """content signature of an array: shape, dtype and a hash of ALL its bytes (xxh3 at several GB/s, crc32 otherwise: a few
+    ms for C5's 16 MB of inputs next to a 40 ms fit).  A sampled hash (round 3) missed in-place edits of a few rows and
+    handed back a stale device model; a key on the array's address or id() misses every in-place edit, and a temporary that
+    NumPy places at the address of the one just freed.  The key of every likelihood-model cache of this module."""
+    if a is None:
+        return None
+    a = np.ascontiguousarray(a)
+    if not a.size:
+        return (a.shape, a.dtype.str, 0)
+    buf = memoryview(a).cast("B")
+    try:
+        import xxhash
+        digest = xxhash.xxh3_64_intdigest(buf)
+    except ImportError:
+        import zlib
+        digest = zlib.crc32(buf)
+    return (a.shape, a.dtype.str, digest)
+
+
 class _MatrixModel(object):
     """Owner of one gpx_handle built from a SUPPLIED covariance matrix (gpx_fit_matrix): the device route of the generic operator
     interface -- Cholesky factor of the operator's own cov_matrix(x, theta) (+1e-5 I retry), alpha, lazily K^-1."""
@@ -154,12 +174,19 @@ class Covariance(object):
     # ---- hyper-parameter maximum likelihood ("next" row f1; skgpuppy/Covariance.py:189-337) ----------------
     def _matrix_model_at(self, x, t, theta):
         """device model of the operator's own cov_matrix(x, theta) with targets t, kept for the next call at the same theta
-        (L-BFGS-B asks for the value and the gradient one after the other)"""
+        (L-BFGS-B asks for the value and the gradient one after the other).  The key is the CONTENT of x, t and theta, x hashed in
+        full (`_signature`).  An x that is no numeric array (a user kernel may take rows of anything) has no content key: it is
+        never cached, the model is rebuilt at every call."""
         th = np.array(theta, dtype=float)
         ta = None if t is None else _gpx.f64(t)
-        key = (id(x), np.shape(x), None if ta is None else ta.tobytes(), th.tobytes())
+        try:
+            xa = np.asarray(x)
+        except Exception:
+            xa = None
+        sig = _signature(xa) if xa is not None and xa.dtype.kind in "biuf" else None
+        key = None if sig is None else (sig, None if ta is None else ta.tobytes(), th.tobytes())
         cached = getattr(self, "_mm_cache", None)
-        if cached is not None and cached[0] == key:
+        if cached is not None and key is not None and cached[0] == key:
             return cached[1]
         if cached is not None:
             cached[1].close()
@@ -169,13 +196,13 @@ class Covariance(object):
         return model
 
     def _fitted_model_at(self, x, t, theta, check_theta, build):
-        """the fused classes' device model build(x, t, theta) fitted at theta, cached on (x, t, theta) identity/bytes: L-BFGS-B asks
-        for the value and the gradient at the same theta in two separate calls.  The cache is cleared before the new fit: a
-        constructor that raises leaves no closed model behind."""
+        """the fused classes' device model build(x, t, theta) fitted at theta, cached on the CONTENT of (x, t, theta) -- the float64 x
+        hashed in full (`_signature`), t and theta by their bytes: L-BFGS-B asks for the value and the gradient at the same theta in
+        two separate calls.  The cache is cleared before the new fit: a constructor that raises leaves no closed model behind."""
         xa = _gpx.f64(x)
         ta = _gpx.f64(t)
         th = check_theta(theta, xa.shape[1]).copy()
-        key = (xa.ctypes.data if xa is x else id(x), xa.shape, ta.tobytes(), th.tobytes())
+        key = (_signature(xa), ta.tobytes(), th.tobytes())
         cached = getattr(self, "_ml_cache", None)
         if cached is not None and cached[0] == key:
             return cached[1]
@@ -872,27 +899,10 @@ class SPGPCovariance(Covariance):
         """the Woodbury inverse (Covariance.py:835-863); `cov_matrix` is ignored as in the reference."""
         return self._fit_model(x, None, theta).dense(1)
 
-    @staticmethod
-    def _signature(a):
-        """content signature of an array: shape, dtype and a hash of ALL its bytes (xxh3 at several GB/s, crc32 otherwise: a few
-        ms for C5's 16 MB of inputs next to a 40 ms fit).  A sampled hash (round 3) missed in-place edits of a few rows and
-        handed back a stale device model."""
-        if a is None:
-            return None
-        a = np.ascontiguousarray(a)
-        buf = memoryview(a).cast("B")
-        try:
-            import xxhash
-            digest = xxhash.xxh3_64_intdigest(buf)
-        except ImportError:
-            import zlib
-            digest = zlib.crc32(buf)
-        return (a.shape, a.dtype.str, digest)
-
     def _fit_model(self, x, t, theta):
         """the device model of (x, t, theta), kept until the next different request: L-BFGS asks for the likelihood and
-        its gradient at the same theta, one after the other.  The key is the CONTENT of x, t and theta (hashed in full); `clear_cache()` releases the device buffers, and `ml_estimate` does so when it is done."""
-        key = (self._signature(x), self._signature(t), _gpx.f64(theta).tobytes())
+        its gradient at the same theta, one after the other.  The key is the CONTENT of x, t and theta (hashed in full, `_signature`); `clear_cache()` releases the device buffers, and `ml_estimate` does so when it is done."""
+        key = (_signature(x), _signature(t), _gpx.f64(theta).tobytes())
         cached = getattr(self, "_fit_cache", None)
         if cached is None or cached[0] != key:
             if cached is not None:

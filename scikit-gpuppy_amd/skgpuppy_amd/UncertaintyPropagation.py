@@ -443,7 +443,10 @@ class UncertaintyPropagationExact(UncertaintyPropagationGA):
         return mean.value, var.value
 
     def _explicit_model(self, gp):
-        """device copy of the GP's dense Kinv attribute and beta (padded, symmetrised), rebuilt only when the GP holds another Kinv array"""
+        """device copy of the GP's dense Kinv attribute and beta (padded, symmetrised), rebuilt only when the GP holds another Kinv array.
+        The one cache of the package keyed on IDENTITY: the array is kept alive here, so its id and address cannot be recycled, but an
+        in-place edit of gp.Kinv is NOT seen -- hashing N^2 doubles at every propagation call would cost more than the call.  Assign a new
+        array to change the inverse."""
         Kinv = gp._inv_cov_matrix()
         key = (id(Kinv), Kinv.__array_interface__["data"][0], Kinv.shape)
         cached = getattr(self, "_kinv_model", None)

@@ -43,6 +43,7 @@ import numpy as np
 from _spgp_ld import FLOOR, LD, MARGIN, _grid, bound  # noqa: F401  (the project's one rule: imported, not copied)
 
 ROWS = 64
+NLL_RTOL = 1e-9     # the likelihood of a fitted model against NumPy's Cholesky of the long-double model's K (test_matern.py, test_periodic.py, test_model_cache_content.py)
 D_ALL = (1, 2, 3, 4, 5, 8, 9, 16, 17, 32, 33, 64)
 SMALL_N, SMALL_D = (128, 129, 200), (1, 3, 8)
 CASES = [(700, d) for d in D_ALL] + [(N, d) for N in SMALL_N for d in SMALL_D]      # every (N, d) the GPU tests fit

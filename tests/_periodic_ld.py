@@ -22,7 +22,7 @@ Rules.
 `defect=` plants one of the seeded defects of tests/test_periodic_model.py in an evaluation (meant for dt = np.float64)."""
 import numpy as np
 
-from _dense_ld import FLOOR, LD, MARGIN, ROWS, _grid, assert_within, bound, distances  # noqa: F401  (the project's one rule: imported)
+from _dense_ld import FLOOR, LD, MARGIN, NLL_RTOL, ROWS, _grid, assert_within, bound, distances  # noqa: F401  (the project's one rule: imported)
 
 U = 2.0 ** -53
 PI_LD = LD("3.14159265358979323846264338327950288")

@@ -151,7 +151,7 @@ def test_fit_solve_predict(N, d):
         np.testing.assert_allclose([m0, v0], [mean[q], var[q]], rtol=1e-6, atol=1e-9 * V)
     nll = cov._negativeloglikelihood(x, gp.t, theta)
     np.testing.assert_allclose(nll, mm.nll(), rtol=1e-9)
-    np.testing.assert_allclose(nll, pl.nll(Knp, gp.t), rtol=1e-9)
+    np.testing.assert_allclose(nll, pl.nll(Knp, gp.t), rtol=pl.NLL_RTOL)
     np.testing.assert_allclose(cov._log_det_cov_matrix(x, theta), mm.logdet(), rtol=1e-9)
     np.testing.assert_allclose(cov.inv_cov_matrix(x, theta), mm.kinv(), rtol=1e-6, atol=1e-7 * kscale)
     assert gp._dev().jitter() == 0.0
