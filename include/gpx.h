@@ -291,6 +291,30 @@ int  gpx_propagate_exact_model(gpx_kinv_model *m, const double *x, int d, const 
  * gives finite, tiny or zero outputs. */
 int gpx_sensitivity_many(gpx_handle *h, const double *U, const double *S, int s_shared, int64_t b, double *mean, double *var_mean,
                          double *first, double *total);
+/* The same decomposition, and the two moments a propagation needs, under independent UNIFORM inputs over a box (Oakley and O'Hagan's
+ * setting; no reference counterpart: the reference integrates with nquad).  x_k ~ U(lo_k, hi_k), lo_k <= hi_k, L_k = hi_k - lo_k; c_i the
+ * PLAIN kernel as above; D(A, B) = erf(B) - erf(A) for A <= B.  For an active coordinate (L_k > 0), om = w_k:
+ *   m_ik     = sqrt(pi / (2 om)) / L_k D(sqrt(om / 2) (lo_k - x_ik), sqrt(om / 2) (hi_k - x_ik))                     E[factor k of c_i]
+ *   E_k(i,j) = exp(-1/4 om (x_ik - x_jk)^2) 1/2 sqrt(pi / om) / L_k D(sqrt(om) (lo_k - mid), sqrt(om) (hi_k - mid))   E[factor k of c_i c_j]
+ *              with mid = (x_ik + x_jk) / 2
+ *   mean    = v sum_i beta_i prod_k m_ik
+ *   V       = sum_ij b_ij (prod_k E_k - prod_k m_ik m_jk)                     b_ij = v^2 beta_i beta_j
+ *   first_k = sum_ij b_ij (prod_{l != k} m_il m_jl) (E_k - m_ik m_jk)
+ *   total_k = sum_ij b_ij (prod_{l != k} E_l) (E_k - m_ik m_jk)
+ *   quad    = v^2 sum_ij Kinv_ij prod_k E_k                                   E[k(x)^T K^-1 k(x)]
+ * A coordinate with L_k = 0 is pinned at lo_k: its factor exp(-1/2 w_k (lo_k - x_ik)^2) enters every point's weight and first_k = total_k =
+ * 0.0 exactly.  Every factor lies in [0, 1]; D is evaluated without cancellation (erfc differences for a training point outside the box, a
+ * midpoint expansion for a narrow box, whose width enters as sqrt(om) L itself and never as a difference of two offsets: csrc/erf_diff.h)
+ * and a point far outside gives factors that are tiny or exactly 0.0, never a NaN:
+ * no leave-one-out product is formed by division.  sum_k first_k <= V <= sum_k total_k.  The variance of the GP output under the uniform
+ * law is V + (v + vt) - quad.  quad is the only sum that reads K^-1: on a gpx_fit handle the lazily materialised inverse (built by the call
+ * if need be, as gpx_propagate_exact does), on a pseudo-input handle P; with quad == NULL no K^-1 is read and the handle need not have one.
+ * lo, hi [b, d], or ONE [d] each for every input when box_shared != 0; mean [b] (WITHOUT meant), var_mean [b] = V, first [b, d]; total
+ * [b, d] and quad [b] may be NULL: their sums are then not formed, the other outputs keep their bits.  Host or device pointers.  lo_k >
+ * hi_k, a non-finite bound or width, or a null required pointer: GPX_ERR_BAD_ARG before the first launch, nothing written.  b = 0 is a
+ * no-op.  Handles, chunking (GPX_SENS_CHUNK), summation order and independence of the batch as gpx_sensitivity_many. */
+int gpx_sensitivity_box_many(gpx_handle *h, const double *lo, const double *hi, int box_shared, int64_t b, double *mean, double *var_mean,
+                             double *first, double *total, double *quad);
 
 /* ---- "next" row f1: hyper-parameter likelihood at the handle's theta
  * (Covariance._negativeloglikelihood / _d_nll_d_theta, skgpuppy/Covariance.py:197-216, :266-282, :605-657) ----

@@ -603,6 +603,13 @@ static inline int need_kernel(const gpx_handle *h, const char *what)
 }
 #define NEED_KERNEL(h, what) GPX_TRY(need_kernel(h, what))
 
+// the pair frame the two variance decompositions share (sensitivity.hip: Gaussian inputs, sensitivity_box.hip: uniform inputs over a box)
+constexpr int SEN_KC = 8;                 // active slots per sweep
+constexpr int SEN_R = 8;                  // rows per workgroup
+// inputs per chunk of either call: what 2^27 doubles (1 GiB) of per-point data hold at `per` doubles an input, at most 4096 and at most b;
+// GPX_SENS_CHUNK (read at every call) caps it
+int64_t sens_chunk(int64_t per, int64_t b);
+
 int fetch_small(double *dst, const double *src, size_t n);   // a few doubles from a caller's pointer (host or device) into host memory (runtime.hip)
 int ensure_Z(gpx_handle *h, int64_t rows);
 int ensure_kinv(gpx_handle *h);

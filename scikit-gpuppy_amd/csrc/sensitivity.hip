@@ -39,9 +39,7 @@
 
 #include "common.h"
 
-constexpr int SEN_KC = 8;                 // active slots per sweep
-constexpr int SEN_NC = 2 * SEN_KC + 1;    // sums per sweep: V, first of the sweep's slots, total of the sweep's slots
-constexpr int SEN_R = 8;                  // rows per workgroup
+constexpr int SEN_NC = 2 * SEN_KC + 1;    // sums per sweep: V, first of the sweep's slots, total of the sweep's slots (SEN_KC, SEN_R: common.h)
 // the constants of one input (host, sens_constants): rows [d] each --
 //   0 lmc_l = -1/2 log1p(om sg), 1 lma_l = 1/2 om / (1 + om sg), 2 slot_l (-1: inactive)     by coordinate l
 //   3 c0_q = -1/2 log1p(2 om sg), 4 P_q = om / 4, 5 Q_q = om / 4 / (1 + 2 om sg)              by active slot q
@@ -246,6 +244,14 @@ static int64_t sens_env_count(const char *name, int64_t dflt)
     return end == e ? dflt : (int64_t)v;
 }
 
+int64_t sens_chunk(int64_t per, int64_t b)
+{
+    int64_t chunk = std::min<int64_t>(4096, std::max<int64_t>(1, ((int64_t)1 << 27) / per));
+    const int64_t forced = sens_env_count("GPX_SENS_CHUNK", 0);
+    if (forced > 0) chunk = std::min<int64_t>(forced, 4096);
+    return std::min(chunk, b);
+}
+
 // GPX_SENS_CHUNK (read at every call): the most inputs of a chunk; default: what 2^27 doubles (1 GiB) of per-point data hold, at most 4096
 extern "C" int gpx_sensitivity_many(gpx_handle *h, const double *U, const double *S, int s_shared, int64_t b, double *mean, double *var_mean,
                                     double *first, double *total)
@@ -281,10 +287,7 @@ extern "C" int gpx_sensitivity_many(gpx_handle *h, const double *U, const double
     }
 
     const int64_t per = (3 * (int64_t)d + 2) * np, nrb = np / SEN_R, nbb = (np + 255) / 256;
-    int64_t chunk = std::min<int64_t>(4096, std::max<int64_t>(1, ((int64_t)1 << 27) / per));
-    const int64_t forced = sens_env_count("GPX_SENS_CHUNK", 0);
-    if (forced > 0) chunk = std::min<int64_t>(forced, 4096);
-    chunk = std::min(chunk, b);
+    const int64_t chunk = sens_chunk(per, b);
     const int max_sweeps = (d + SEN_KC - 1) / SEN_KC;
     const int64_t max_cols = chunk * max_sweeps * SEN_NC;
 

@@ -10,7 +10,11 @@ skgpuppy/UncertaintyPropagation.py:135-210.
 
 The call reads (x, beta, v, w) alone -- no K^-1, no factor, no solve: a GaussianProcess on the fused GaussianCovariance route costs N^2 d
 per input, a PseudoInputGP (GaussianProcess.pseudo_gp() of an SPGP model) m^2 d.  Setting all but one Sigma_kk to zero in propagate_GA is
-NOT first_k: that pins the other inputs at u instead of averaging over them."""
+NOT first_k: that pins the other inputs at u instead of averaging over them.
+
+SensitivityAnalysis(gp, distribution="uniform") reads the same (u, Sigma_x) as the centre and the variance of independent UNIFORM inputs,
+x_k ~ U(u_k - sqrt(3 s_k), u_k + sqrt(3 s_k)) -- the design-box setting of global sensitivity analysis (gpx_sensitivity_box_many); the
+*_box methods take the bounds themselves, whatever the distribution argument."""
 import numpy as np
 
 from . import _gpx
@@ -20,7 +24,10 @@ from .GaussianProcess import GaussianProcess, PseudoInputGP
 class SensitivityAnalysis(object):
     """SensitivityAnalysis(gp): gp a GaussianProcess with a fused GaussianCovariance, or a PseudoInputGP."""
 
-    def __init__(self, gp):
+    def __init__(self, gp, distribution="gaussian"):
+        if distribution not in ("gaussian", "uniform"):
+            raise ValueError("distribution must be 'gaussian' or 'uniform', got %r" % (distribution,))
+        self.distribution = distribution
         served = isinstance(gp, PseudoInputGP) or (isinstance(gp, GaussianProcess) and gp._route() == "gaussian")
         if not served:
             route = gp._route() if isinstance(gp, GaussianProcess) else type(gp).__name__
@@ -68,12 +75,58 @@ class SensitivityAnalysis(object):
             raise ValueError("U must be (b, %d)" % d)
         b = len(UU)
         s = self._variances_of(Sigma_x, d, b)
+        if self.distribution == "uniform":
+            half = np.sqrt(3.0 * s)                              # a uniform law of variance s has half-width sqrt(3 s)
+            return self._box_many(UU - half, UU + half, want_total)[:4]
         mean, V, first = np.empty(b), np.empty(b), np.empty((b, d))
         total = np.empty((b, d)) if want_total else None
         st = _gpx.lib.gpx_sensitivity_many(self.gp._dev().handle, _gpx.ptr(UU), _gpx.ptr(s), int(s.ndim == 1), b, _gpx.ptr(mean), _gpx.ptr(V),
                                            _gpx.ptr(first), _gpx.ptr(total) if want_total else None)
         _gpx.check(st, "gpx_sensitivity_many")
         return mean, V, first, total
+
+    def _box_many(self, LO, HI, want_total=True, want_quad=False):
+        """(mean WITHOUT meant [b], V [b], first [b, d], total [b, d] or None, quad [b] or None) under x_k ~ U(LO_k, HI_k): the bounds as
+        given, [b, d] each or one [d] for all rows of the other"""
+        d = self.gp.d
+        lo, hi = _gpx.f64(LO), _gpx.f64(HI)
+        shared = lo.ndim == 1 and hi.ndim == 1
+        if not shared:
+            lo, hi = (_gpx.f64(a) for a in np.broadcast_arrays(np.atleast_2d(lo), np.atleast_2d(hi)))
+        if lo.shape != hi.shape or lo.shape[-1] != d:
+            raise ValueError("lo and hi must be (b, %d) or (%d,), got %s and %s" % (d, d, lo.shape, hi.shape))
+        if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo <= hi)):
+            raise ValueError("the bounds must be finite with lo <= hi")
+        b = 1 if shared else len(lo)
+        mean, V, first = np.empty(b), np.empty(b), np.empty((b, d))
+        total = np.empty((b, d)) if want_total else None
+        quad = np.empty(b) if want_quad else None
+        st = _gpx.lib.gpx_sensitivity_box_many(self.gp._dev().handle, _gpx.ptr(lo), _gpx.ptr(hi), int(shared), b, _gpx.ptr(mean), _gpx.ptr(V),
+                                               _gpx.ptr(first), _gpx.ptr(total) if want_total else None, _gpx.ptr(quad) if want_quad else None)
+        _gpx.check(st, "gpx_sensitivity_box_many")
+        return mean, V, first, total, quad
+
+    def variances_box_many(self, LO, HI):
+        """(means with meant [b], V [b], first [b, d], total [b, d]) under x_k ~ U(LO_ik, HI_ik) for the rows of LO, HI (b, d)"""
+        mean, V, first, total, _q = self._box_many(LO, HI)
+        return mean + self.gp._get_mean_t(), V, first, total
+
+    def variances_box(self, lo, hi):
+        """(mean with meant, V, first [d], total [d]) under x_k ~ U(lo_k, hi_k); lo_k == hi_k pins the coordinate"""
+        d = self.gp.d
+        mean, V, first, total, _q = self._box_many(_gpx.f64(lo).reshape(1, d), _gpx.f64(hi).reshape(1, d))
+        return np.float64(mean[0] + self.gp._get_mean_t()), np.float64(V[0]), first[0], total[0]
+
+    def indices_box_many(self, LO, HI):
+        """(first / V, total / V), each [b, d]; zeros where V == 0"""
+        _mean, V, first, total, _q = self._box_many(LO, HI)
+        return self._ratio(first, V), self._ratio(total, V)
+
+    def indices_box(self, lo, hi):
+        """(first / V, total / V), each [d]; zeros where V == 0"""
+        d = self.gp.d
+        f, t = self.indices_box_many(_gpx.f64(lo).reshape(1, d), _gpx.f64(hi).reshape(1, d))
+        return f[0], t[0]
 
     def variances_many(self, U, Sigma_x):
         """(means with meant [b], V [b], first [b, d], total [b, d]) for the rows of U (b, d); Sigma_x: [d] or a diagonal [d, d] for all of

@@ -571,6 +571,45 @@ class UncertaintyPropagationExact(UncertaintyPropagationGA):
         return tuple(o[0] for o in self.propagate_GA_gradient_many(uu[None], S, h))
 
 
+class UncertaintyPropagationUniform(UncertaintyPropagationGA):
+    """The exact moments of the GP output under independent UNIFORM inputs (no reference counterpart: the reference has nquad and sampling
+    for any law but the Gaussian).  (u, Sigma_x) are the centre and the DIAGONAL covariance of the input: x_k ~ U(u_k - sqrt(3 s_k),
+    u_k + sqrt(3 s_k)), s_k = Sigma_x[k, k]; a non-zero off-diagonal entry is a ValueError (a box has independent sides).
+        mean = E[mu(x)],   variance = Var(mu(x)) + E[sigma^2(x)] = V + (v + vt) - E[k(x)^T K^-1 k(x)]
+    in closed form for the ARD squared-exponential kernel (gpx_sensitivity_box_many; include/gpx.h carries the formulas), v + vt the prior
+    variance UncertaintyPropagationExact uses.  gp: what SensitivityAnalysis serves -- a GaussianProcess with a fused GaussianCovariance,
+    or a PseudoInputGP."""
+
+    def __init__(self, gp):
+        from .SensitivityAnalysis import SensitivityAnalysis     # (that module imports GaussianProcess, which imports this one)
+        UncertaintyPropagationGA.__init__(self, gp)
+        self._sa = SensitivityAnalysis(gp, distribution="uniform")
+
+    def _moments_many(self, U, Sigma_x, want_var):
+        d = self.gp.d
+        UU = _gpx.f64(U)
+        if UU.ndim != 2 or UU.shape[1] != d:
+            raise ValueError("U must be (B, %d), got %s" % (d, UU.shape))
+        half = np.sqrt(3.0 * self._sa._variances_of(Sigma_x, d, len(UU)))
+        mean, V, _first, _total, quad = self._sa._box_many(UU - half, UU + half, want_total=False, want_quad=want_var)
+        if not want_var:
+            return mean, None
+        return mean, V + (self.gp._get_v() + self.gp._get_vt()) - quad
+
+    def propagate_mean(self, u, Sigma_x):
+        return np.float64(self._moments_many(_gpx.f64(u).reshape(1, self.gp.d), self._sa._variances_of(Sigma_x, self.gp.d), False)[0][0]
+                          + self.gp._get_mean_t())
+
+    def propagate_GA(self, u, Sigma_x):
+        mean, var = self._moments_many(_gpx.f64(u).reshape(1, self.gp.d), self._sa._variances_of(Sigma_x, self.gp.d), True)
+        return np.float64(mean[0] + self.gp._get_mean_t()), np.float64(var[0])
+
+    def propagate_GA_many(self, U, Sigma_x):
+        """propagate_GA for the rows of U (B, d); Sigma_x as SensitivityAnalysis.variances_many takes it: (means [B] with meant, variances [B])"""
+        mean, var = self._moments_many(U, Sigma_x, True)
+        return mean + self.gp._get_mean_t(), var
+
+
 # ---- the numerical family (UncertaintyPropagation.py:28-52, :90-162) ---------------------------------------------------------------
 class UncertaintyPropagation(object):
     """Superclass of the propagators that return the output density itself (UncertaintyPropagation.py:28-52)."""

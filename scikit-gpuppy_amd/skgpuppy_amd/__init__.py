@@ -15,6 +15,7 @@ from .UncertaintyPropagation import (  # noqa: F401
     UncertaintyPropagation,
     UncertaintyPropagationMC,
     UncertaintyPropagationNumericalHG,
+    UncertaintyPropagationUniform,
 )
 
 from .InverseUncertaintyPropagation import (  # noqa: F401,E402
@@ -30,6 +31,6 @@ __all__ = [
     "Covariance", "GaussianCovariance", "MaternCovariance", "PeriodicCovariance", "SPGPCovariance", "GaussianProcess", "PseudoInputGP",
     "UncertaintyPropagationGA",
     "UncertaintyPropagationApprox", "UncertaintyPropagationExact", "UncertaintyPropagationLinear", "tracedot",
-    "UncertaintyPropagation", "UncertaintyPropagationMC", "UncertaintyPropagationNumericalHG",
+    "UncertaintyPropagation", "UncertaintyPropagationMC", "UncertaintyPropagationNumericalHG", "UncertaintyPropagationUniform",
     "InverseUncertaintyPropagation", "InverseUncertaintyPropagationApprox", "InverseUncertaintyPropagationNumerical",
 ]
