@@ -291,6 +291,20 @@ int  gpx_propagate_exact_model(gpx_kinv_model *m, const double *x, int d, const 
  * gives finite, tiny or zero outputs. */
 int gpx_sensitivity_many(gpx_handle *h, const double *U, const double *S, int s_shared, int64_t b, double *mean, double *var_mean,
                          double *first, double *total);
+/* The second-order (pair interaction) terms of the same decomposition: with the notation above, for k != l
+ *   second_kl = sum_ij b_ij (prod_{q != k,l} m_q) (E_k - m_k) (E_l - m_l)  =  V^closed_{kl} - first_k - first_l,
+ * the variance of the ANOVA term of mu in (x_k, x_l): with which other input x_k interacts.  Symmetric in (k, l).  With exactly two
+ * uncertain coordinates V = first_k + first_l + second_kl; in general sum_k first_k + sum_{k<l} second_kl <= V and
+ * total_k >= first_k + sum_l second_kl.  Evaluated per (pair of training points, coordinate) cell as
+ *   dh_k = exp(e1) - sg_i sg_j,  e1 = hl_i + hl_j + (lE_k - lm_ik - lm_jk) <= 0,  hl_i = 1/2 sum_active lm_iq,  sg_i = exp(hl_i),
+ * with lE_k - lm_ik - lm_jk ONE quadratic form in (a_i - a_j, a_i + a_j), so that second_kl = sum_ij b_ij' dh_k dh_l over the pairs:
+ * the Gram matrix of the coordinates' cell vectors, formed on the fp64 matrix cores (csrc/sensitivity_second.hip: the form, the proof
+ * of the sign, the lane map).  One exponential per cell; no leave-two-out product is formed by division.
+ * U [b, d]; S [b, d] or ONE [d] when s_shared != 0; second [b, d, d]: symmetric to the bit, its diagonal and every row and column of a
+ * coordinate with s_k = 0 are 0.0 exactly (never computed); fewer than two uncertain coordinates: all 0.0, no launch.  Host or device
+ * pointers.  Handles, refusals (nothing written), b = 0, chunking (GPX_SENS_CHUNK), summation order and independence of the batch as
+ * gpx_sensitivity_many. */
+int gpx_sensitivity_second_many(gpx_handle *h, const double *U, const double *S, int s_shared, int64_t b, double *second);
 /* The same decomposition, and the two moments a propagation needs, under independent UNIFORM inputs over a box (Oakley and O'Hagan's
  * setting; no reference counterpart: the reference integrates with nquad).  x_k ~ U(lo_k, hi_k), lo_k <= hi_k, L_k = hi_k - lo_k; c_i the
  * PLAIN kernel as above; D(A, B) = erf(B) - erf(A) for A <= B.  For an active coordinate (L_k > 0), om = w_k:

@@ -609,6 +609,10 @@ constexpr int SEN_R = 8;                  // rows per workgroup
 // inputs per chunk of either call: what 2^27 doubles (1 GiB) of per-point data hold at `per` doubles an input, at most 4096 and at most b;
 // GPX_SENS_CHUNK (read at every call) caps it
 int64_t sens_chunk(int64_t per, int64_t b);
+// the constants of one Gaussian input (sensitivity.hip states the rows; sensitivity_second.hip reads rows 0 - 2 and na): [SEN_CROWS, d], na, 0
+constexpr int SEN_CROWS = 6;
+static inline int64_t sens_cb_size(int d) { return (int64_t)SEN_CROWS * d + 2; }
+bool sens_constants(const double *w, const double *s, int d, double *c);   // false: a negative or non-finite variance
 
 int fetch_small(double *dst, const double *src, size_t n);   // a few doubles from a caller's pointer (host or device) into host memory (runtime.hip)
 int ensure_Z(gpx_handle *h, int64_t rows);

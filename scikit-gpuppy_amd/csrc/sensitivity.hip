@@ -40,12 +40,10 @@
 #include "common.h"
 
 constexpr int SEN_NC = 2 * SEN_KC + 1;    // sums per sweep: V, first of the sweep's slots, total of the sweep's slots (SEN_KC, SEN_R: common.h)
-// the constants of one input (host, sens_constants): rows [d] each --
+// the constants of one input (host, sens_constants; SEN_CROWS, sens_cb_size: common.h): rows [d] each --
 //   0 lmc_l = -1/2 log1p(om sg), 1 lma_l = 1/2 om / (1 + om sg), 2 slot_l (-1: inactive)     by coordinate l
 //   3 c0_q = -1/2 log1p(2 om sg), 4 P_q = om / 4, 5 Q_q = om / 4 / (1 + 2 om sg)              by active slot q
 // then na
-constexpr int SEN_CROWS = 6;
-static inline int64_t sens_cb_size(int d) { return (int64_t)SEN_CROWS * d + 2; }
 
 // per (input z, point i): aT / mT / loT [z][slot][npad], g / bw [z][npad]; mpart [block][input] = the block's share of the mean
 __global__ __launch_bounds__(256) void sens_build_kernel(const double *__restrict__ x, long n, long npad, int d, const double *__restrict__ U,
@@ -211,7 +209,7 @@ __global__ __launch_bounds__(256, 2) void sens_pair_kernel(const double *__restr
 }
 
 // the host side of one input's constants; false: a negative or non-finite variance
-static bool sens_constants(const double *w, const double *s, int d, double *c)
+bool sens_constants(const double *w, const double *s, int d, double *c)
 {
     int na = 0;
     for (int l = 0; l < d; ++l) {

@@ -7,6 +7,7 @@ skgpuppy/UncertaintyPropagation.py:135-210.
   first_k  = Var_{x_k}(E[mu | x_k])           what x_k's uncertainty produces on its own
   total_k  = E[Var_{x_k}(mu | x_~k)]          what is left when everything but x_k is known: first_k plus every interaction with x_k
   sum_k first_k <= V <= sum_k total_k;  the Sobol indices are first / V and total / V.
+  second_kl = V_kl - first_k - first_l        with WHICH other input x_k interacts (second_order*; gpx_sensitivity_second_many)
 
 The call reads (x, beta, v, w) alone -- no K^-1, no factor, no solve: a GaussianProcess on the fused GaussianCovariance route costs N^2 d
 per input, a PseudoInputGP (GaussianProcess.pseudo_gp() of an SPGP model) m^2 d.  Setting all but one Sigma_kk to zero in propagate_GA is
@@ -158,3 +159,37 @@ class SensitivityAnalysis(object):
         d = self.gp.d
         f, t = self.indices_many(_gpx.f64(u).reshape(1, d), self._variances_of(Sigma_x, d))
         return f[0], t[0]
+
+    # ---- second order: with WHICH other input x_k interacts (gpx_sensitivity_second_many) ----
+    def second_order_many(self, U, Sigma_x):
+        """second [b, d, d]: second[i, k, l] = the variance of the ANOVA term of mu in (x_k, x_l) at input i = V^closed_{kl} - first_k -
+        first_l; symmetric, zero on the diagonal and in the rows and columns of a coordinate without variance.  Gaussian inputs only."""
+        if self.distribution != "gaussian":
+            raise NotImplementedError("second_order*: the closed form serves distribution='gaussian' (the Gaussian law) only, not %r"
+                                      % (self.distribution,))
+        d = self.gp.d
+        UU = _gpx.f64(U)
+        if UU.ndim != 2 or UU.shape[1] != d:
+            raise ValueError("U must be (b, %d)" % d)
+        b = len(UU)
+        s = self._variances_of(Sigma_x, d, b)
+        second = np.empty((b, d, d))
+        st = _gpx.lib.gpx_sensitivity_second_many(self.gp._dev().handle, _gpx.ptr(UU), _gpx.ptr(s), int(s.ndim == 1), b, _gpx.ptr(second))
+        _gpx.check(st, "gpx_sensitivity_second_many")
+        return second
+
+    def second_order(self, u, Sigma_x):
+        """second [d, d] at one input u [d]; Sigma_x: the variances [d] or a diagonal [d, d]"""
+        d = self.gp.d
+        return self.second_order_many(_gpx.f64(u).reshape(1, d), self._variances_of(Sigma_x, d))[0]
+
+    def second_order_indices_many(self, U, Sigma_x):
+        """second / V [b, d, d] with V of variances_many; zeros where V == 0"""
+        second = self.second_order_many(U, Sigma_x)
+        _mean, V, _first, _total = self._many(U, Sigma_x, want_total=False)
+        return self._ratio(second.reshape(len(V), -1), V).reshape(second.shape)
+
+    def second_order_indices(self, u, Sigma_x):
+        """second / V [d, d]; zeros where V == 0"""
+        d = self.gp.d
+        return self.second_order_indices_many(_gpx.f64(u).reshape(1, d), self._variances_of(Sigma_x, d))[0]
