@@ -329,6 +329,22 @@ int gpx_sensitivity_second_many(gpx_handle *h, const double *U, const double *S,
  * no-op.  Handles, chunking (GPX_SENS_CHUNK), summation order and independence of the batch as gpx_sensitivity_many. */
 int gpx_sensitivity_box_many(gpx_handle *h, const double *lo, const double *hi, int box_shared, int64_t b, double *mean, double *var_mean,
                              double *first, double *total, double *quad);
+/* The second-order (pair interaction) terms of the decomposition over a box: with m_ik, E_k(i,j) and b_ij of gpx_sensitivity_box_many
+ * (the pinned coordinates' factors folded into b_ij), for active coordinates k != l
+ *   second_kl = sum_ij b_ij (prod_{q != k,l} m_iq m_jq) (E_k - m_ik m_jk) (E_l - m_il m_jl)  =  V^closed_{kl} - first_k - first_l,
+ * symmetric in (k, l); with exactly two active coordinates V = first_k + first_l + second_kl.  The Gram form of
+ * gpx_sensitivity_second_many -- second_kl = sum_ij b_ij' dh_k dh_l on the fp64 matrix cores, dh_k = exp(e1) - sg_i sg_j,
+ * e1 = (hl_i - lm_ik) + (hl_j - lm_jk) + lE_k(i,j) <= 0, hl_i = 1/2 sum_active lm_iq, sg_i = exp(hl_i) -- needs the leave-two-out product
+ * as a quotient by m_ik, which is exactly 0.0 for a point far outside the box: HERE the factors are kept as logarithms, lm_ik = log m_ik
+ * and lE_k = log E_k through log D(A, h) = log(erf(A + h) - erf(A)), finite where D underflows (scaled complementary error functions for
+ * a point outside the box, the midpoint expansion for a narrow one, the width entering as sqrt(om) L itself: csrc/log_erf_diff.h;
+ * the form, the proof of the sign and the lane map: csrc/sensitivity_box_second.hip).  No leave-two-out product is formed by division.
+ * lo, hi [b, d], or ONE [d] each for every input when box_shared != 0; second [b, d, d]: symmetric to the bit, its diagonal and every
+ * row and column of a pinned coordinate (L_k = 0) are 0.0 exactly (never computed); fewer than two active coordinates: all 0.0, no
+ * launch; a box wholly outside the data gives zeros, never a NaN.  Host or device pointers.  It reads (x, beta, v, w) alone.  Handles,
+ * refusals (lo_k > hi_k, a non-finite bound or width, a null pointer: GPX_ERR_BAD_ARG before the first launch, nothing written), b = 0,
+ * chunking (GPX_SENS_CHUNK), summation order and independence of the batch as gpx_sensitivity_box_many. */
+int gpx_sensitivity_box_second_many(gpx_handle *h, const double *lo, const double *hi, int box_shared, int64_t b, double *second);
 
 /* ---- "next" row f1: hyper-parameter likelihood at the handle's theta
  * (Covariance._negativeloglikelihood / _d_nll_d_theta, skgpuppy/Covariance.py:197-216, :266-282, :605-657) ----

@@ -613,6 +613,20 @@ int64_t sens_chunk(int64_t per, int64_t b);
 constexpr int SEN_CROWS = 6;
 static inline int64_t sens_cb_size(int d) { return (int64_t)SEN_CROWS * d + 2; }
 bool sens_constants(const double *w, const double *s, int d, double *c);   // false: a negative or non-finite variance
+// the constants of one box (sensitivity_box.hip states the rows; sensitivity_box_second.hip reads rows 0 - 4 and na): [BOX_CROWS, d], na, 0
+constexpr int BOX_CROWS = 5;
+static inline int64_t box_cb_size(int d) { return (int64_t)BOX_CROWS * d + 2; }
+int box_constants(const double *w, const double *lo, const double *hi, int d, double *c);   // 0: fine, else the offending coordinate + 1
+// the Gram frame the two second-order calls share (sensitivity_second.hip: Gaussian inputs, sensitivity_box_second.hip: a box): the
+// variant (NB blocks of 16 slots, PACK pair groups on the 16 rows) of an input with na active slots, its accumulator columns, the scatter
+constexpr int S2_R = 16;                  // rows per workgroup
+constexpr int S2_NV = 6;                  // variants (NB, PACK): (1, 4), (1, 2), (1, 1), (2, 1), (3, 1), (4, 1)
+static inline int s2_variant(int na) { return na <= 1 ? -1 : na <= 4 ? 0 : na <= 8 ? 1 : na <= 16 ? 2 : 2 + (na - 1) / 16; }
+static inline int s2_nb(int var) { return var <= 2 ? 1 : var - 1; }
+static inline int s2_pack(int var) { return var == 0 ? 4 : (var == 1 ? 2 : 1); }
+static inline int s2_cols(int var) { return var < 0 ? 0 : 256 * (s2_nb(var) * (s2_nb(var) + 1) / 2); }
+// one input's [d, d] from its summed accumulators o [s2_cols(var)] through the slot map (slot by coordinate, < 0: inactive)
+void sens2_scatter(const double *o, int var, const double *slot_of, int d, double *out);
 
 int fetch_small(double *dst, const double *src, size_t n);   // a few doubles from a caller's pointer (host or device) into host memory (runtime.hip)
 int ensure_Z(gpx_handle *h, int64_t rows);

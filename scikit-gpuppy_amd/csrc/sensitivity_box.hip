@@ -40,8 +40,7 @@
 constexpr int BOX_NC = 2 * SEN_KC + 2;    // sums per sweep: V, first and total of the sweep's slots, quad (sweep 0)
 // the constants of one input (host, box_constants): rows [d] each -- 0 slot_l (-1: inactive) by coordinate l; 1 sqrt(om), 2 1/2 sqrt(pi / om) / L,
 // 3 sqrt(pi / (2 om)) / L, 4 the scaled width sqrt(om) L (the h of erf_diff: from L itself, never from two rounded offsets) by active slot q; then na
-constexpr int BOX_CROWS = 5;
-static inline int64_t box_cb_size(int d) { return (int64_t)BOX_CROWS * d + 2; }
+// (BOX_CROWS = 5 rows, box_cb_size: common.h, shared with sensitivity_box_second.hip)
 
 // per (input z, point i): alT / mT / loT [z][slot][npad], g / bw / kw [z][npad]; mpart [block][input] = the block's share of the mean
 __global__ __launch_bounds__(256) void box_build_kernel(const double *__restrict__ x, long n, long npad, int d, const double *__restrict__ lo_all,
@@ -212,7 +211,7 @@ __global__ __launch_bounds__(256, 2) void box_pair_kernel(const double *__restri
 
 // the host side of one input's constants; 0: fine, else the offending coordinate + 1 (lo > hi, a non-finite bound, or a width whose
 // normalisers 1 / L are not finite)
-static int box_constants(const double *w, const double *lo, const double *hi, int d, double *c)
+int box_constants(const double *w, const double *lo, const double *hi, int d, double *c)
 {
     int na = 0;
     for (int l = 0; l < d; ++l) {

@@ -43,14 +43,8 @@
 
 #include "common.h"
 
-constexpr int S2_R = 16;                  // rows per workgroup
+// S2_R rows per workgroup, the S2_NV variants (NB, PACK) and their column arithmetic: common.h (shared with sensitivity_box_second.hip)
 constexpr int S2_CQ = 3 * GPX_MAX_D + 2;  // an input's pair constants: cc, cD, cS by active slot [GPX_MAX_D each], na, 0
-constexpr int S2_NV = 6;                  // variants (NB, PACK): (1, 4), (1, 2), (1, 1), (2, 1), (3, 1), (4, 1)
-
-static inline int s2_variant(int na) { return na <= 1 ? -1 : na <= 4 ? 0 : na <= 8 ? 1 : na <= 16 ? 2 : 2 + (na - 1) / 16; }
-static inline int s2_nb(int var) { return var <= 2 ? 1 : var - 1; }
-static inline int s2_pack(int var) { return var == 0 ? 4 : (var == 1 ? 2 : 1); }
-static inline int s2_cols(int var) { return var < 0 ? 0 : 256 * (s2_nb(var) * (s2_nb(var) + 1) / 2); }
 
 // per (input z, point i): a [z][npad][W] by slot (zero from na on), pt [z][3][npad] = hl, sg, bw
 __global__ __launch_bounds__(256) void sens2_build_kernel(const double *__restrict__ x, long n, long npad, int d, int W, const double *__restrict__ U,
@@ -185,8 +179,8 @@ static void sens2_launch(dim3 grid, hipStream_t s, const double *a2, const doubl
     hipLaunchKernelGGL((sens2_pair_kernel<NB, PACK>), grid, dim3(256), 0, s, a2, pt, cq, cq_stride, zl, n, npad, W, partial, ncols);
 }
 
-// one input's [d, d] from its summed accumulators o [s2_cols(var)] through the slot map (row 2 of its sens_constants)
-static void sens2_scatter(const double *o, int var, const double *slot_of, int d, double *out)
+// one input's [d, d] from its summed accumulators o [s2_cols(var)] through the slot map (row 2 of its sens_constants, row 0 of a box's)
+void sens2_scatter(const double *o, int var, const double *slot_of, int d, double *out)
 {
     const int pack = s2_pack(var), sl = 16 / pack;
     int coord[GPX_MAX_D];

@@ -15,7 +15,8 @@ NOT first_k: that pins the other inputs at u instead of averaging over them.
 
 SensitivityAnalysis(gp, distribution="uniform") reads the same (u, Sigma_x) as the centre and the variance of independent UNIFORM inputs,
 x_k ~ U(u_k - sqrt(3 s_k), u_k + sqrt(3 s_k)) -- the design-box setting of global sensitivity analysis (gpx_sensitivity_box_many); the
-*_box methods take the bounds themselves, whatever the distribution argument."""
+*_box methods take the bounds themselves, whatever the distribution argument; second_order_box* are the pair interactions over such a box
+(gpx_sensitivity_box_second_many)."""
 import numpy as np
 
 from . import _gpx
@@ -128,6 +129,43 @@ class SensitivityAnalysis(object):
         d = self.gp.d
         f, t = self.indices_box_many(_gpx.f64(lo).reshape(1, d), _gpx.f64(hi).reshape(1, d))
         return f[0], t[0]
+
+    # ---- second order over a box (gpx_sensitivity_box_second_many); whatever the distribution argument, as the *_box methods above ----
+    def _box_bounds(self, LO, HI):
+        """(lo, hi) as [b, d] float64 after the checks of _box_many"""
+        d = self.gp.d
+        lo, hi = (_gpx.f64(a) for a in np.broadcast_arrays(np.atleast_2d(_gpx.f64(LO)), np.atleast_2d(_gpx.f64(HI))))
+        if lo.ndim != 2 or lo.shape[-1] != d:
+            raise ValueError("lo and hi must be (b, %d) or (%d,), got %s" % (d, d, lo.shape))
+        if not (np.all(np.isfinite(lo)) and np.all(np.isfinite(hi)) and np.all(lo <= hi)):
+            raise ValueError("the bounds must be finite with lo <= hi")
+        return lo, hi
+
+    def second_order_box_many(self, LO, HI):
+        """second [b, d, d] under x_k ~ U(LO_ik, HI_ik): second[i, k, l] = V^closed_{kl} - first_k - first_l of variances_box_many;
+        symmetric, zero on the diagonal and in the rows and columns of a pinned coordinate (LO == HI)"""
+        lo, hi = self._box_bounds(LO, HI)
+        second = np.empty((len(lo), self.gp.d, self.gp.d))
+        st = _gpx.lib.gpx_sensitivity_box_second_many(self.gp._dev().handle, _gpx.ptr(lo), _gpx.ptr(hi), 0, len(lo), _gpx.ptr(second))
+        _gpx.check(st, "gpx_sensitivity_box_second_many")
+        return second
+
+    def second_order_box(self, lo, hi):
+        """second [d, d] under x_k ~ U(lo_k, hi_k)"""
+        d = self.gp.d
+        return self.second_order_box_many(_gpx.f64(lo).reshape(1, d), _gpx.f64(hi).reshape(1, d))[0]
+
+    def second_order_indices_box_many(self, LO, HI):
+        """second / V [b, d, d] with V of variances_box_many; zeros where V == 0"""
+        lo, hi = self._box_bounds(LO, HI)
+        second = self.second_order_box_many(lo, hi)
+        V = self._box_many(lo, hi, want_total=False)[1]
+        return self._ratio(second.reshape(len(V), -1), V).reshape(second.shape)
+
+    def second_order_indices_box(self, lo, hi):
+        """second / V [d, d]; zeros where V == 0"""
+        d = self.gp.d
+        return self.second_order_indices_box_many(_gpx.f64(lo).reshape(1, d), _gpx.f64(hi).reshape(1, d))[0]
 
     def variances_many(self, U, Sigma_x):
         """(means with meant [b], V [b], first [b, d], total [b, d]) for the rows of U (b, d); Sigma_x: [d] or a diagonal [d, d] for all of

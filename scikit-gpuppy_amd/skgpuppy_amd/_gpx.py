@@ -98,6 +98,7 @@ SIGNATURES = {
     "gpx_sensitivity_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp, _dp, _dp, _dp]),
     "gpx_sensitivity_second_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp]),
     "gpx_sensitivity_box_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp, _dp, _dp, _dp, _dp]),
+    "gpx_sensitivity_box_second_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp]),
     "gpx_nll": (_int, [_hp, ctypes.POINTER(_dbl)]),
     "gpx_nll_grad": (_int, [_hp, _dp]),
     "gpx_periodic_gram": (_int, [_dp, _i64, _dp, _i64, _int, _dp, _int, _dp]),
