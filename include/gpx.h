@@ -86,8 +86,8 @@ int gpx_spd_inverse(const double *K, int64_t n, double *Kinv_out, double *logdet
  * (skgpuppy/Covariance.py:167-187, +1e-5 I retry :180-185).  gpx_fit_matrix is that route on the device: K [n,n] (symmetric, the
  * operator's own cov_matrix(x, theta); host or device pointer) is Cholesky-factored with the same look-ahead schedule and the same
  * single +1e-5 I retry, alpha = K^-1 t_centered is solved.  The handle answers gpx_predict_kv, gpx_alpha, gpx_solve, gpx_chol_mul,
- * gpx_kinv, gpx_chol*, gpx_logdet, gpx_nll, gpx_nll_grad_matrix, gpx_jitter_used; entry points that evaluate the GaussianCovariance
- * kernel itself (gpx_predict, gpx_cjh, gpx_propagate_*, gpx_exact_mean, gpx_nll_grad) return GPX_ERR_STATE on it. */
+ * gpx_kinv, gpx_chol*, gpx_logdet, gpx_nll, gpx_loo, gpx_nll_grad_matrix, gpx_jitter_used; entry points that evaluate the GaussianCovariance
+ * kernel itself (gpx_predict, gpx_cjh, gpx_propagate_*, gpx_exact_mean, gpx_nll_grad, gpx_loo_grad) return GPX_ERR_STATE on it. */
 int gpx_fit_matrix(const double *K, const double *t_centered, int64_t n, void *stream, gpx_handle **out);
 /* estimate_many / estimate from the operator's own cross-covariance (GaussianProcess.py:68-80, :94-111): kv [m,n] =
  * cov.cov_matrix_ij(x_star, x), kdiag [m] = diag(cov.cov_matrix(x_star)) (for estimate: cov(x_star, x_star));
@@ -355,6 +355,19 @@ int gpx_nll_grad(gpx_handle *h, double *grad_out);
 /* One entry of Covariance._d_nll_d_theta for ANY operator (skgpuppy/Covariance.py:266-282): dK [n,n] = the operator's own
  * _d_cov_matrix_d_theta(x, theta, j); *grad_out = 1/2 tr(K^-1 dK) - 1/2 alpha^T dK alpha in one pass over K^-1 and dK.  Any handle. */
 int gpx_nll_grad_matrix(gpx_handle *h, const double *dK, double *grad_out);
+
+/* ---- leave-one-out cross-validation at the handle's theta (Rasmussen & Williams 5.4.2; no reference counterpart) ----
+ * With P = K^-1 (K as fitted: vt and any jitter included), alpha = P t and the target mean held fixed, the LOO predictive of point i is
+ *   mean_out[i] = t_i - alpha_i / P_ii (centred, like t),  var_out[i] = 1 / P_ii,
+ * and *nlp_out = L = N/2 log 2pi + sum_i (-1/2 log P_ii + 1/2 alpha_i^2 / P_ii), the negative log predictive probability.  Any output
+ * may be NULL.  Any handle that owns a factor and targets (gpx_fit, gpx_fit_matrix, gpx_periodic_fit, gpx_matern_fit, gpx_adopt_factor);
+ * GPX_ERR_STATE on a pseudo-input handle, whose "K^-1" is not the inverse of a training covariance.  Builds K^-1 if it is not resident. */
+int gpx_loo(gpx_handle *h, double *mean_out, double *var_out, double *nlp_out);
+/* grad_out[2 + d] = dL / dtheta.  With c_i = 1/2 (1 / P_ii + alpha_i^2 / P_ii^2), a_i = alpha_i / P_ii and g = P a,
+ *   dL / dtheta_j = sum_kl W_kl (dK / dtheta_j)_kl,  W = P diag(c) P - 1/2 (g alpha^T + alpha g^T):
+ * one symmetric N^3 product for all parameters, contracted tile by tile on the fp64 matrix cores and reduced against the kernel's
+ * derivative factors in the same launch (W is never stored).  Gaussian-kernel handles only (GPX_ERR_STATE otherwise, as gpx_nll_grad). */
+int gpx_loo_grad(gpx_handle *h, double *grad_out);
 /* out[r] = M V[r] for a supplied symmetric matrix M [n,n] and nrhs <= 64 vectors V [nrhs,n] (rows): the device route for the
  * explicit `Kinv` argument of UncertaintyPropagationApprox._get_sigma2 / _get_variance_rest
  * (skgpuppy/UncertaintyPropagation.py:412-481) when it is not the fitted model's own. */

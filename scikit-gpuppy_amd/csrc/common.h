@@ -461,6 +461,14 @@ int launch_sum_columns(const double *partial, int64_t nb, int nc, double *out_de
 int launch_kinv_pass(const double *Kinv, int64_t ld, int64_t npad, int nc, const double *V, double *KV, hipStream_t s,
                      Profiler *prof, int64_t nrows = 0);
 int launch_dot_pairs(const std::vector<std::pair<const double *, const double *>> &pr, long n, double *out_dev, hipStream_t s);
+// ---- leave-one-out cross-validation (loo.hip) ----
+// vec [5, npad] from the diagonal of K^-1: c, a, mu_-i (centred), sigma^2_-i, the terms of L; zeros at i >= n
+int launch_loo_point(const double *Kinv, int64_t ld, int64_t n, int64_t npad, const double *alpha, const double *t, double *vec, hipStream_t s);
+int64_t loo_tiles(int64_t npad);   // lower 128-tiles = rows of launch_loo_grad's partial
+// out_dev [d + 2] = S_0, S_1..S_d, T of W = P diag(c) P - 1/2 (g alpha^T + alpha g^T) against the Gaussian kernel's derivative factors;
+// scratch: gv [npad], Pc [npad, npad], partial [loo_tiles(npad), d + 2]
+int launch_loo_grad(const double *Kinv, int64_t n, int64_t npad, int d, const double *alpha, const double *xw, double v, const double *vec,
+                    double *gv, double *Pc, double *partial, double *out_dev, hipStream_t s, Profiler *prof);
 int launch_exact_sum(const double *Kinv, int64_t ld, int64_t npad, int d, const double *beta, const double *aT,
                      const double *bT, const double *e, const double *F, double *partial, double *out_dev, hipStream_t s,
                      Profiler *prof, int64_t row0 = 0, int64_t row1 = 0);

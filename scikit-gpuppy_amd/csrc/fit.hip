@@ -589,6 +589,59 @@ extern "C" int gpx_nll_grad(gpx_handle *h, double *grad_out)
     return 0;
 }
 
+// ---- leave-one-out cross-validation (loo.hip states the formulas): mu_-i = t_i - alpha_i / P_ii, sigma^2_-i = 1 / P_ii,
+// L = N/2 log 2pi + sum_i (-1/2 log P_ii + 1/2 alpha_i^2 / P_ii) from the diagonal of K^-1 alone ----
+extern "C" int gpx_loo(gpx_handle *h, double *mean_out, double *var_out, double *nlp_out)
+{
+    CHECK_H(h);
+    GPX_TRY(ensure_kinv(h));
+    hipStream_t s = h->stream;
+    const int64_t n = h->n, np = h->npad;
+    Scratch sc(s);
+    double *vec = nullptr;
+    GPX_TRY(sc.take(&vec, 5 * np + 1));
+    GPX_TRY(launch_loo_point(h->Kinv, np, n, np, h->alpha, h->t, vec, s));
+    GPX_TRY(launch_sum_columns(vec + 4 * np, np, 1, vec + 5 * np, s));
+    double sum = 0.0;
+    if (mean_out) GPX_HIP(hipMemcpyAsync(mean_out, vec + 2 * np, sizeof(double) * n, hipMemcpyDefault, s));
+    if (var_out) GPX_HIP(hipMemcpyAsync(var_out, vec + 3 * np, sizeof(double) * n, hipMemcpyDefault, s));
+    GPX_HIP(hipMemcpyAsync(&sum, vec + 5 * np, sizeof(double), hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipStreamSynchronize(s));
+    const double nlp = 0.5 * (double)n * log(2.0 * M_PI) + sum;
+    if (nlp_out) GPX_HIP(hipMemcpy(nlp_out, &nlp, sizeof(double), hipMemcpyDefault));
+    return 0;
+}
+
+// dL / dtheta = sum_kl W_kl (dK / dtheta)_kl, W = P diag(c) P - 1/2 (g alpha^T + alpha g^T) (loo.hip): the sums S_0, S_k, T of
+// loo_grad_kernel against dK/dtheta_0 = Kf, dK/dtheta_1 = vt I, dK/dtheta_{2+k} = -1/2 Kf w_k dx_k^2 (no 1/2 outside, unlike gpx_nll_grad)
+extern "C" int gpx_loo_grad(gpx_handle *h, double *grad_out)
+{
+    CHECK_H(h);
+    NEED_KERNEL(h, "gpx_loo_grad");
+    if (!grad_out) { gpx_set_error("null argument"); return GPX_ERR_BAD_ARG; }
+    GPX_TRY(ensure_kinv(h));
+    hipStream_t s = h->stream;
+    const int d = h->d;
+    const int64_t np = h->npad;
+    Scratch sc(s);
+    double *vec = nullptr, *Pc = nullptr, *partial = nullptr;
+    GPX_TRY(sc.take(&vec, 6 * np));
+    GPX_TRY(sc.take(&Pc, np * np));
+    GPX_TRY(sc.take(&partial, (loo_tiles(np) + 1) * (d + 2)));
+    double *outd = partial + loo_tiles(np) * (d + 2);
+    GPX_TRY(launch_loo_point(h->Kinv, np, h->n, np, h->alpha, h->t, vec, s));
+    GPX_TRY(launch_loo_grad(h->Kinv, h->n, np, d, h->alpha, h->xs_w, h->v, vec, vec + 5 * np, Pc, partial, outd, s, &h->prof));
+    double o[GPX_MAX_D + 2];
+    GPX_HIP(hipMemcpyAsync(o, outd, sizeof(double) * (d + 2), hipMemcpyDeviceToHost, s));
+    GPX_HIP(hipStreamSynchronize(s));
+    std::vector<double> g(d + 2);
+    g[0] = o[0];
+    g[1] = h->vt * o[d + 1];
+    for (int k = 0; k < d; ++k) g[2 + k] = -0.5 * o[1 + k];
+    GPX_HIP(hipMemcpy(grad_out, g.data(), sizeof(double) * (d + 2), hipMemcpyDefault));
+    return 0;
+}
+
 // d nll / d theta_j for ANY operator from its derivative matrix dK = d cov_matrix / d theta_j [n, n] (Covariance._d_nll_d_theta,
 // skgpuppy/Covariance.py:266-282): 1/2 tr(K^-1 dK) - 1/2 alpha^T dK alpha as ONE pass over K^-1 and dK (K^-1 from the factor is
 // exactly symmetric, so tr(K^-1 dK) = sum_ij Kinv_ij dK_ij); one wave per row, per-row partials, fixed-order final sum.

@@ -278,6 +278,30 @@ class Covariance(object):
         theta_min = fmin_l_bfgs_b(func, theta_start, bounds=None, approx_grad=False, fprime=fprime)
         return np.array(theta_min[0])
 
+    # ---- leave-one-out cross-validation (no reference counterpart; Rasmussen & Williams 5.4.2) ----------------
+    def _loo_nlp(self, x, t, theta):
+        """L = N/2 log 2pi + sum_i (-1/2 log P_ii + 1/2 alpha_i^2 / P_ii), P = K^-1, alpha = P t: the negative log predictive
+        probability of every training point under the model fitted without it (gpx_loo), on the cached model of the likelihood --
+        value and gradient at one theta share one fit and one K^-1.  1e20 when K cannot be factored."""
+        try:
+            fused = getattr(self, "_fused", None)      # the built-in kernels' fused model; any other operator's own matrix
+            model = self._model_at(x, t, theta) if fused is not None and fused() else self._matrix_model_at(x, t, theta)
+            out = np.empty(1)
+            _gpx.check(_gpx.lib.gpx_loo(model.handle, None, None, _gpx.ptr(out)), "gpx_loo")
+            return float(out[0])
+        except (np.linalg.LinAlgError, ValueError, ZeroDivisionError):
+            return 1.0e+20
+
+    def _d_loo_nlp_d_theta(self, x, t, theta):
+        raise NotImplementedError("the LOO gradient exists for the Gaussian kernel (GaussianCovariance) only")
+
+    def loo_estimate(self, x, t):
+        """theta that minimises _loo_nlp by L-BFGS-B with the analytic gradient, from get_theta: ml_estimate's twin"""
+        from scipy.optimize import fmin_l_bfgs_b
+        theta_min = fmin_l_bfgs_b(lambda th: self._loo_nlp(x, t, th), self.get_theta(x, t), bounds=None, approx_grad=False,
+                                  fprime=lambda th: self._d_loo_nlp_d_theta(x, t, th))
+        return np.array(theta_min[0])
+
     def __getstate__(self):
         state = dict(self.__dict__)
         state.pop("_mm_cache", None)     # device handles never enter a pickle
@@ -444,6 +468,16 @@ class GaussianCovariance(Covariance):
         model = self._model_at(x, t, theta)
         g = np.empty(len(theta))
         _gpx.check(_gpx.lib.gpx_nll_grad(model.handle, _gpx.ptr(g)), "gpx_nll_grad")
+        return g
+
+    def _d_loo_nlp_d_theta(self, x, t, theta):
+        """d _loo_nlp / d theta = sum_kl W_kl (dK / d theta)_kl, W = P diag(c) P - 1/2 (g alpha^T + alpha g^T): one symmetric product
+        for all 2 + d entries, contracted and reduced against the derivative Grams in one launch (gpx_loo_grad)."""
+        if not self._fused():
+            return Covariance._d_loo_nlp_d_theta(self, x, t, theta)
+        model = self._model_at(x, t, theta)
+        g = np.empty(len(theta))
+        _gpx.check(_gpx.lib.gpx_loo_grad(model.handle, _gpx.ptr(g)), "gpx_loo_grad")
         return g
 
     def get_Hessian(self, u, xi, theta):

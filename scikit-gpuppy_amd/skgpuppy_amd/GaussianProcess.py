@@ -291,8 +291,11 @@ class PseudoInputGP(object):
 class GaussianProcess(object):
     """GP regression object (skgpuppy/GaussianProcess.py:11-191)."""
 
-    def __init__(self, x, t, cov, theta_min=None):
+    def __init__(self, x, t, cov, theta_min=None, objective="ml"):
         # (GaussianProcess.py:19-41): x stored as given, targets centred, Kinv <- factorisation on the GPU
+        # objective (when theta_min is None): "ml" = the marginal likelihood (the reference's), "loo" = leave-one-out cross-validation
+        if objective not in ("ml", "loo"):
+            raise ValueError("objective must be 'ml' or 'loo'")
         self.x = x
         self.n, self.d = np.shape(x)
         self.meant = np.mean(t)
@@ -300,6 +303,10 @@ class GaussianProcess(object):
         self.cov = cov
         if theta_min is not None:
             self.theta_min = theta_min
+        elif objective == "loo":
+            if not (isinstance(cov, GaussianCovariance) and cov._fused()):
+                raise NotImplementedError("objective='loo' needs the LOO gradient, which exists for the Gaussian kernel (GaussianCovariance) only")
+            self.theta_min = self.cov.loo_estimate(self.x, self.t)
         else:
             self.theta_min = self.cov.ml_estimate(self.x, self.t)
         self._model = None
@@ -445,6 +452,24 @@ class GaussianProcess(object):
         xs = _gpx.f64(np.atleast_2d(np.array(x_star)))
         mean, var = self._dev().predict(xs)
         return mean[0] + self.meant, var[0]
+
+    # ---- leave-one-out cross-validation (no reference counterpart; Rasmussen & Williams 5.4.2) ----
+    def _loo(self, want_points):
+        if self._route() == "spgp":
+            raise NotImplementedError("leave-one-out cross-validation is not available for SPGPCovariance")
+        mean, var, nlp = (np.empty(self.n), np.empty(self.n), None) if want_points else (None, None, np.empty(1))
+        _gpx.check(_gpx.lib.gpx_loo(self._dev().handle, _gpx.ptr(mean) if want_points else None, _gpx.ptr(var) if want_points else None,
+                                    None if want_points else _gpx.ptr(nlp)), "gpx_loo")
+        return (mean + self.meant, var) if want_points else float(nlp[0])
+
+    def loo(self):
+        """(mean [N], variance [N]): the prediction of every training point from the model fitted without it, theta and the target mean
+        held fixed -- t_i - alpha_i / Kinv_ii (+ meant) and 1 / Kinv_ii from the resident K^-1, no refit (gpx_loo)"""
+        return self._loo(True)
+
+    def loo_nlp(self):
+        """the negative log predictive probability of the training targets under loo(): N/2 log 2pi + 1/2 sum_i (log var_i + (t_i - mean_i)^2 / var_i)"""
+        return self._loo(False)
 
     # ---- input gradients of the predictor (no reference counterpart: UncertaintyPropagation.py:214-227 takes central differences) ----
     def estimate_many_gradient(self, x_stars, variance=True, h=1e-5):

@@ -101,6 +101,8 @@ SIGNATURES = {
     "gpx_sensitivity_box_second_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp]),
     "gpx_nll": (_int, [_hp, ctypes.POINTER(_dbl)]),
     "gpx_nll_grad": (_int, [_hp, _dp]),
+    "gpx_loo": (_int, [_hp, _dp, _dp, _dp]),
+    "gpx_loo_grad": (_int, [_hp, _dp]),
     "gpx_periodic_gram": (_int, [_dp, _i64, _dp, _i64, _int, _dp, _int, _dp]),
     "gpx_periodic_fit": (_int, [_dp, _dp, _i64, _int, _dp, ctypes.c_void_p, ctypes.POINTER(_hp)]),
     "gpx_periodic_predict": (_int, [_hp, _dp, _i64, _dp, _dp]),
