@@ -305,6 +305,30 @@ int gpx_sensitivity_many(gpx_handle *h, const double *U, const double *S, int s_
  * pointers.  Handles, refusals (nothing written), b = 0, chunking (GPX_SENS_CHUNK), summation order and independence of the batch as
  * gpx_sensitivity_many. */
 int gpx_sensitivity_second_many(gpx_handle *h, const double *U, const double *S, int s_shared, int64_t b, double *second);
+/* Which DIRECTIONS of the input space matter: the second moment of the gradient under the same input law, the active-subspace matrix
+ * C = E[grad f grad f^T] (closed form: Wycoff, Binois and Wild, "Sequential learning of active subspaces", 2021; no reference counterpart).
+ * Its eigenvectors are the rotated inputs, its diagonal the derivative-based global sensitivity measures nu_k = C_kk, and by the Gaussian
+ * Poincare inequality total_k <= s_k nu_k.  With x_k ~ N(u_k, s_k), mu and the PLAIN kernel c_i as above, per coordinate k
+ * a_i = x_ik - u_k, om = w_k, sg = s_k:
+ *   rho_k = om sg / (1 + 2 om sg)        tau_k = sg / (1 + 2 om sg)
+ *   lE_k(i,j) = -1/2 log1p(2 om sg) - 1/4 om (a_i - a_j)^2 - 1/4 om (a_i + a_j)^2 / (1 + 2 om sg)      (<= 0, the form evaluated above)
+ *   G_ij     = v^2 exp(sum_k lE_k(i,j))                                                   ONE exponential a pair, exponent <= 0
+ *   p_k(i,j) = om (rho_k (a_i + a_j) - a_i)        q_k(i,j) = om (rho_k (a_i + a_j) - a_j) = p_k(j,i)
+ *   J_ij,kl  = G_ij (p_k(i,j) q_l(i,j) + delta_kl om^2 tau_k)
+ *   gmean_k  = E[d_k mu]               = v sum_i beta_i exp(sum_l lm_il) om a_i / (1 + om sg)
+ *   cmean_kl = E[d_k mu d_l mu]        = sum_ij beta_i beta_j J_ij,kl
+ *   cpost_kl = E[Cov(d_k f, d_l f)]    = delta_kl v w_k - sum_ij Kinv_ij J_ij,kl
+ * Over the pairs j <= i a pair below the diagonal contributes p q^T + q p^T: the device accumulates D = sum wgt p q^T over the lower half
+ * on the fp64 matrix cores (the coordinates enter through the two linear factors, whose outer product the matrix core forms; a diagonal
+ * pair weighs 1 as p p^T) and the result is D + D^T, symmetric to the bit.  s_k = 0 needs no special case (rho = tau = 0); with every
+ * s_k = 0, cmean = grad mu(u) grad mu(u)^T.  cpost concerns the latent f: vt does not enter it.  The posterior expectation of
+ * grad f grad f^T (Wycoff's matrix) is cmean + cpost; the covariance of grad mu is cmean - gmean gmean^T.
+ * U [b, d]; S [b, d] or ONE [d] when s_shared != 0; gmean [b, d]; cmean [b, d, d]; cpost [b, d, d] may be NULL: K^-1 is then neither built
+ * nor read and gmean and cmean keep their bits; otherwise a gpx_fit handle's lazily materialised inverse (built by the call if need be), a
+ * pseudo-input handle's P.  Host or device pointers.  Handles, refusals (nothing written), b = 0, chunking (GPX_SENS_CHUNK), summation
+ * order and independence of the batch as gpx_sensitivity_second_many (csrc/sensitivity_gradient.hip: the lane map). */
+int gpx_sensitivity_gradient_many(gpx_handle *h, const double *U, const double *S, int s_shared, int64_t b, double *gmean, double *cmean,
+                                  double *cpost);
 /* The same decomposition, and the two moments a propagation needs, under independent UNIFORM inputs over a box (Oakley and O'Hagan's
  * setting; no reference counterpart: the reference integrates with nquad).  x_k ~ U(lo_k, hi_k), lo_k <= hi_k, L_k = hi_k - lo_k; c_i the
  * PLAIN kernel as above; D(A, B) = erf(B) - erf(A) for A <= B.  For an active coordinate (L_k > 0), om = w_k:

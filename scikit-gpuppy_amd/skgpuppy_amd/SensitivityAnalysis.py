@@ -8,6 +8,8 @@ skgpuppy/UncertaintyPropagation.py:135-210.
   total_k  = E[Var_{x_k}(mu | x_~k)]          what is left when everything but x_k is known: first_k plus every interaction with x_k
   sum_k first_k <= V <= sum_k total_k;  the Sobol indices are first / V and total / V.
   second_kl = V_kl - first_k - first_l        with WHICH other input x_k interacts (second_order*; gpx_sensitivity_second_many)
+  C = E[grad f grad f^T]                      which DIRECTIONS matter: the active-subspace matrix, its diagonal the DGSM nu_k with
+                                              total_k <= s_k nu_k (gradient_moments*, dgsm*, active_subspace; gpx_sensitivity_gradient_many)
 
 The call reads (x, beta, v, w) alone -- no K^-1, no factor, no solve: a GaussianProcess on the fused GaussianCovariance route costs N^2 d
 per input, a PseudoInputGP (GaussianProcess.pseudo_gp() of an SPGP model) m^2 d.  Setting all but one Sigma_kk to zero in propagate_GA is
@@ -231,3 +233,44 @@ class SensitivityAnalysis(object):
         """second / V [d, d]; zeros where V == 0"""
         d = self.gp.d
         return self.second_order_indices_many(_gpx.f64(u).reshape(1, d), self._variances_of(Sigma_x, d))[0]
+
+    # ---- which DIRECTIONS matter: the second moment of the gradient, the active-subspace matrix (gpx_sensitivity_gradient_many) ----
+    def gradient_moments_many(self, U, Sigma_x, posterior=False):
+        """(gmean [b, d], C [b, d, d]): gmean = E[grad mu(x)], C = E[grad mu grad mu^T] of the predictor mean, or with posterior=True the
+        posterior expectation E[grad f grad f^T] = that plus E[Cov grad f] (reads K^-1; Wycoff, Binois and Wild 2021).  C is symmetric; the
+        covariance of grad mu is C - gmean gmean^T.  Gaussian inputs only."""
+        if self.distribution != "gaussian":
+            raise NotImplementedError("gradient_moments*, dgsm*, active_subspace: the closed form serves distribution='gaussian' (the Gaussian "
+                                      "law) only, not %r" % (self.distribution,))
+        d = self.gp.d
+        UU = _gpx.f64(U)
+        if UU.ndim != 2 or UU.shape[1] != d:
+            raise ValueError("U must be (b, %d)" % d)
+        b = len(UU)
+        s = self._variances_of(Sigma_x, d, b)
+        gmean, cmean = np.empty((b, d)), np.empty((b, d, d))
+        cpost = np.empty((b, d, d)) if posterior else None
+        st = _gpx.lib.gpx_sensitivity_gradient_many(self.gp._dev().handle, _gpx.ptr(UU), _gpx.ptr(s), int(s.ndim == 1), b, _gpx.ptr(gmean),
+                                                    _gpx.ptr(cmean), _gpx.ptr(cpost) if posterior else None)
+        _gpx.check(st, "gpx_sensitivity_gradient_many")
+        return gmean, (cmean + cpost if posterior else cmean)
+
+    def gradient_moments(self, u, Sigma_x, posterior=False):
+        """(gmean [d], C [d, d]) at one input u [d]; Sigma_x: the variances [d] or a diagonal [d, d]"""
+        d = self.gp.d
+        g, C = self.gradient_moments_many(_gpx.f64(u).reshape(1, d), self._variances_of(Sigma_x, d), posterior)
+        return g[0], C[0]
+
+    def dgsm_many(self, U, Sigma_x, posterior=False):
+        """nu [b, d] = the diagonal of C: the derivative-based global sensitivity measures; total_k <= s_k nu_k (Gaussian Poincare)"""
+        return np.array(np.diagonal(self.gradient_moments_many(U, Sigma_x, posterior)[1], axis1=1, axis2=2))
+
+    def dgsm(self, u, Sigma_x, posterior=False):
+        """nu [d] at one input u [d]"""
+        return np.array(np.diagonal(self.gradient_moments(u, Sigma_x, posterior)[1]))
+
+    def active_subspace(self, u, Sigma_x, posterior=True):
+        """(eigenvalues [d] in descending order, eigenvectors [d, d] as columns) of C at one input u [d]: the leading columns span the
+        directions along which the GP varies most under the input law"""
+        lam, vec = np.linalg.eigh(self.gradient_moments(u, Sigma_x, posterior)[1])
+        return lam[::-1].copy(), vec[:, ::-1].copy()
