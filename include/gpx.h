@@ -291,6 +291,25 @@ int  gpx_propagate_exact_model(gpx_kinv_model *m, const double *x, int d, const 
  * gives finite, tiny or zero outputs. */
 int gpx_sensitivity_many(gpx_handle *h, const double *U, const double *S, int s_shared, int64_t b, double *mean, double *var_mean,
                          double *first, double *total);
+/* The same decomposition of the GP ITSELF, in posterior expectation (Oakley and O'Hagan 2004; Marrel et al. 2009): f = mu + g with g the
+ * zero-mean posterior residual process of covariance c(x, x') - k(x)^T Kinv k(x').  Every term is quadratic in f, so E*[Q(f)] = Q(mu) +
+ * E*[Q(g)]: the outputs of gpx_sensitivity_many plus a posterior part each.  With the notation above and r_k = (1 + 2 om sg)^-1/2:
+ *   var_post     = v (1 - prod_l r_l)                 - v^2 sum_ij Kinv_ij (prod_l E_l - prod_l m_l)
+ *   first_post_k = v (prod_{l != k} r_l) (1 - r_k)    - v^2 sum_ij Kinv_ij (prod_{l != k} m_l) (E_k - m_k)
+ *   total_post_k = v (1 - r_k)                        - v^2 sum_ij Kinv_ij (prod_{l != k} E_l) (E_k - m_k)
+ * E*[Var_x f] = var_mean + var_post, E*[first_k of f] = first_k + first_post_k, E*[total_k of f] = total_k + total_post_k.  The three sums
+ * are those of V, first_k and total_k with Kinv_ij for beta_i beta_j, formed in the SAME pair pass from the same exponentials (a second
+ * weight and a second set of accumulators; 8 bytes of K^-1 a visited pair, lower triangle only); the prior constants are formed as
+ * -expm1 of sums of log r.  They concern the latent f: vt does not enter.  Each post part is a Sobol quantity of g in expectation:
+ * var_post, first_post_k, total_post_k >= 0; sum_k first_post_k <= var_post <= sum_k total_post_k; with one uncertain coordinate the three
+ * coincide; s_k = 0 gives first_post_k = total_post_k = 0.0 exactly, every s_k = 0 gives var_post = 0.0 and no pair launch.
+ * mean, var_mean, first and total are gpx_sensitivity_many's outputs BIT FOR BIT; var_post [b]; first_post, total_post [b, d].  total and
+ * total_post are NULL together (the total sums are then not formed, every other output keeps its bits) or not at all: exactly one of them
+ * NULL is GPX_ERR_BAD_ARG.  K^-1: a gpx_fit handle's lazily materialised inverse (built by the call if need be), a pseudo-input handle's
+ * P.  Host or device pointers.  Handles, refusals (nothing written), b = 0, chunking (GPX_SENS_CHUNK), summation order and independence
+ * of the batch as gpx_sensitivity_many. */
+int gpx_sensitivity_post_many(gpx_handle *h, const double *U, const double *S, int s_shared, int64_t b, double *mean, double *var_mean,
+                              double *first, double *total, double *var_post, double *first_post, double *total_post);
 /* The second-order (pair interaction) terms of the same decomposition: with the notation above, for k != l
  *   second_kl = sum_ij b_ij (prod_{q != k,l} m_q) (E_k - m_k) (E_l - m_l)  =  V^closed_{kl} - first_k - first_l,
  * the variance of the ANOVA term of mu in (x_k, x_l): with which other input x_k interacts.  Symmetric in (k, l).  With exactly two

@@ -33,6 +33,27 @@
 // the first / total sums of its own slots; grid.z = the chunk's inputs.  Partials go per block into scratch [row block][input, sweep,
 // SEN_NC], then ONE launch_sum_columns per chunk.  No atomics; an input's arithmetic reads nothing of another input's and its sums run
 // in a fixed order: the result does not depend on its place in the batch or on the chunking.
+//
+// THE POSTERIOR PART (gpx_sensitivity_post_many; Oakley and O'Hagan 2004).  f = mu + g with g the zero-mean posterior residual of covariance
+// c(x, x') - k(x)^T Kinv k(x'); every Sobol quantity Q is quadratic in f, so E*[Q(f)] = Q(mu) + E*[Q(g)], and E*[Q(g)] is the SAME sum over
+// the pairs with -v^2 Kinv_ij for b_ij, plus a constant of the prior kernel (r_k = exp(c0_k) = (1 + 2 om sg)^-1/2):
+//   var_post     = v (1 - prod r)                   - v^2 sum_ij Kinv_ij (prod E - g_i g_j)
+//   first_post_k = v (prod_{l != k} r_l) (1 - r_k)  - v^2 sum_ij Kinv_ij lo_ik lo_jk (E_k - m_ik m_jk)
+//   total_post_k = v (1 - r_k)                      - v^2 sum_ij Kinv_ij (prod_{l != k} E_l) (E_k - m_ik m_jk)
+// The exponentials are all of the pass's time and are shared: sens_post_pair_kernel is the same cell (sens_pair_cells<TOTAL, POST = true>,
+// ONE copy of E, dl and the prefix / suffix products) with a twin of every accumulation under the weight kw = (pw_i pw_j Kinv_ij) wgt,
+// pw_i = v prod_inactive (the build kernel's second point weight).  What the lane carries more:
+//   * 2 SEN_NC = 34 accumulators instead of 17.  The frame runs two workgroups a CU by its LDS footprint (70 KiB each), that is two waves
+//     a SIMD and 256 vector registers a wave: the 34 accumulators and the eight exponentials in flight fit at SEN_KC = 8 without scratch, so
+//     the sweep is NOT narrowed -- a narrower sweep would have to form all na exponentials once more per extra sweep, which is the whole cost.
+//   * ONE element of K^-1 in flight, loaded a row AHEAD: Kinv[i0][j] at the top of the j step, before the slot loop, Kinv[i0 + r + 1][j] at
+//     the top of row r, so its latency sits under row r's exponentials.  (All R values at the top of the step would be R registers indexed
+//     by the rolled row loop's counter, i.e. scratch, or 16 KB more LDS, i.e. one workgroup a CU.)  A wave reads 64 consecutive words of a
+//     row of K^-1; of the lower triangle only, but for the lanes right of the diagonal inside the diagonal block, whose loads stay
+//     unconditional (see the loop) and whose values are dropped.
+// The beta-weighted accumulations run the same instructions in the same order in both kernels (contraction off), the partials of the two
+// weights lie side by side ([beta set (SEN_NC), Kinv set (SEN_NC)] per input and sweep) and launch_sum_columns adds each column in an order
+// that does not depend on the column count: mean, V, first and total of the posterior call are gpx_sensitivity_many's bits.
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -45,11 +66,13 @@ constexpr int SEN_NC = 2 * SEN_KC + 1;    // sums per sweep: V, first of the swe
 //   3 c0_q = -1/2 log1p(2 om sg), 4 P_q = om / 4, 5 Q_q = om / 4 / (1 + 2 om sg)              by active slot q
 // then na
 
-// per (input z, point i): aT / mT / loT [z][slot][npad], g / bw [z][npad]; mpart [block][input] = the block's share of the mean
+// per (input z, point i): aT / mT / loT [z][slot][npad], g / bw [z][npad]; mpart [block][input] = the block's share of the mean;
+// pw [z][npad] = v prod_inactive (0.0 for a padded point), or null: not written
 __global__ __launch_bounds__(256) void sens_build_kernel(const double *__restrict__ x, long n, long npad, int d, const double *__restrict__ U,
                                                          const double *__restrict__ cb, long cb_stride, const double *__restrict__ beta, double v,
                                                          double *__restrict__ aT, double *__restrict__ mT, double *__restrict__ loT,
-                                                         double *__restrict__ g, double *__restrict__ bw, double *__restrict__ mpart)
+                                                         double *__restrict__ g, double *__restrict__ bw, double *__restrict__ mpart,
+                                                         double *__restrict__ pw)
 {
     __shared__ double ws[4];
     const int t = threadIdx.x;
@@ -77,7 +100,9 @@ __global__ __launch_bounds__(256) void sens_build_kernel(const double *__restric
         }
         const double b0 = real ? v * beta[i] : 0.0;
         g[z * npad + i] = exp_nonpos(lact);
-        bw[z * npad + i] = b0 * exp_nonpos(fmin(lall - lact, 0.0));   // the inactive coordinates' plain kernel factors
+        const double pin = exp_nonpos(fmin(lall - lact, 0.0));        // the inactive coordinates' plain kernel factors
+        bw[z * npad + i] = b0 * pin;
+        if (pw) pw[z * npad + i] = (real ? v : 0.0) * pin;
         mine = b0 * exp_nonpos(lall);
     }
     mine = wave_sum(mine);
@@ -93,19 +118,23 @@ static __device__ __forceinline__ double sens_log_e(double ai, double aj, double
     return fma(-Q * sm, sm, fma(-P * dm, dm, c0));
 }
 
-// partial [row block][ncols], ncols = inputs * sweeps * SEN_NC: this block's [V, first (SEN_KC), total (SEN_KC)] at (z * sweeps + y) * SEN_NC
-template <bool TOTAL>
-__global__ __launch_bounds__(256, 2) void sens_pair_kernel(const double *__restrict__ aT, const double *__restrict__ mT,
-                                                           const double *__restrict__ loT, const double *__restrict__ g,
-                                                           const double *__restrict__ bw, const double *__restrict__ cb, long cb_stride,
-                                                           long n, long npad, int d, double *__restrict__ partial, long ncols)
+// The cells of one workgroup: SEN_R rows against the columns j <= i, for both pair kernels.
+// partial [row block][ncols], ncols = inputs * sweeps * NW * SEN_NC (NW = 2 with POST): this block's [V, first (SEN_KC), total (SEN_KC)] under
+// b_ij at (z * sweeps + y) * NW * SEN_NC and, with POST, the same sums under pw_i pw_j Kinv_ij right behind them
+template <bool TOTAL, bool POST>
+static __device__ __forceinline__ void sens_pair_cells(const double *__restrict__ aT, const double *__restrict__ mT,
+                                                       const double *__restrict__ loT, const double *__restrict__ g,
+                                                       const double *__restrict__ bw, const double *__restrict__ pw,
+                                                       const double *__restrict__ Kinv, long ldk, const double *__restrict__ cb, long cb_stride,
+                                                       long n, long npad, int d, double *__restrict__ partial, long ncols)
 {
-#pragma clang fp contract(off)   // the TOTAL and the first-only instantiation must give V and first the same bits
-    constexpr int R = SEN_R, KC = SEN_KC, NC = SEN_NC;
+#pragma clang fp contract(off)   // every instantiation must give the sums it shares with another the same bits
+    constexpr int R = SEN_R, KC = SEN_KC, NC = SEN_NC, NA = POST ? 2 * NC : NC;
     __shared__ double as[R][GPX_MAX_D];       // a_i of the block's rows, by slot (broadcast reads)
     __shared__ double os[R][KC][2];           // m_i, lo_i of the sweep's own slots
     __shared__ double rs[R][2];               // g_i, bw_i
-    __shared__ double red[4][NC];
+    __shared__ double ps[POST ? R : 1];       // pw_i
+    __shared__ double red[4][NA];
     // what a lane carries from the slot loop into the row loop, parked in LDS (each lane reads its own words back) so that the row loop
     // stays rolled and its 8 exponentials in flight fit the register budget beside the 17 accumulators
     __shared__ double pe[R][256];             // prod E outside the sweep, per row
@@ -117,9 +146,9 @@ __global__ __launch_bounds__(256, 2) void sens_pair_kernel(const double *__restr
     const double *c = cb + z * cb_stride;
     const int na = (int)c[SEN_CROWS * d];
     const double *c0 = c + 3 * d, *cP = c + 4 * d, *cQ = c + 5 * d;
-    double *pout = partial + (long)rb * ncols + (z * sweeps + y) * NC;
+    double *pout = partial + (long)rb * ncols + (z * sweeps + y) * NA;
     if (k0 >= na && y > 0) {                  // an input with fewer active slots than the chunk's widest: nothing in this sweep
-        if (t < NC) pout[t] = 0.0;
+        if (t < NA) pout[t] = 0.0;
         return;
     }
     const long base = z * (long)d * npad;
@@ -135,14 +164,21 @@ __global__ __launch_bounds__(256, 2) void sens_pair_kernel(const double *__restr
         os[r][kk][1] = own ? loZ[(long)(k0 + kk) * npad + i0 + r] : 0.0;
     }
     if (t < R) { rs[t][0] = g[z * npad + i0 + t]; rs[t][1] = bw[z * npad + i0 + t]; }
+    if (POST && t < R) ps[t] = pw[z * npad + i0 + t];
     __syncthreads();
 
-    double acc[NC];
+    double acc[NA];
 #pragma unroll
-    for (int q = 0; q < NC; ++q) acc[q] = 0.0;
+    for (int q = 0; q < NA; ++q) acc[q] = 0.0;
     const int k1 = (k0 + KC < na) ? k0 + KC : na;
     const long jend = (i0 + R < n) ? i0 + R : n;
     for (long j = t; j < jend; j += 256) {
+        // the element of K^-1 of row i0 for this column, in flight under the slot loop; the rows after it one row ahead.  The loads are
+        // UNCONDITIONAL (any row < npad, column j < n lies inside Kinv) and what is not a pair j <= i < n is dropped by a select where the
+        // value is used: behind a conditional load the compiler cannot count the loads in flight and waits for all of them, the one just
+        // issued included, and a select at the load waits for it on the spot
+        double kraw = 0.0;
+        if (POST) kraw = Kinv[i0 * ldk + j];
         // prod E over the slots outside the sweep, for the block's R rows at once
         double PE[R];
 #pragma unroll
@@ -165,11 +201,18 @@ __global__ __launch_bounds__(256, 2) void sens_pair_kernel(const double *__restr
                 oj[kk][2][t] = loZ[at];
             }
         const double gj = g[z * npad + j], bj = bw[z * npad + j];
+        double pj = 0.0;
+        if (POST) pj = pw[z * npad + j];
 #pragma unroll 1
         for (int r = 0; r < R; ++r) {
             const long i = i0 + r;
             const double wgt = (j < i) ? 2.0 : ((j == i) ? 1.0 : 0.0);
             const double b = (rs[r][1] * bj) * wgt;
+            double kw = 0.0;                  // the twin weight of the pair: (pw_i pw_j Kinv_ij) wgt
+            if (POST) {
+                kw = ((ps[r] * pj) * ((j <= i && i < n) ? kraw : 0.0)) * wgt;
+                kraw = Kinv[((r + 1 < R) ? i + 1 : i0) * ldk + j];   // the next row's element (row i0 again behind the last, unused)
+            }
             double E[KC], dl[KC];
 #pragma unroll
             for (int kk = 0; kk < KC; ++kk) {
@@ -178,7 +221,9 @@ __global__ __launch_bounds__(256, 2) void sens_pair_kernel(const double *__restr
                 if (k0 + kk < na) {
                     E[kk] = exp_nonpos(sens_log_e(as[r][k0 + kk], oj[kk][0][t], c0[k0 + kk], cP[k0 + kk], cQ[k0 + kk]));
                     dl[kk] = E[kk] - os[r][kk][0] * oj[kk][1][t];
-                    acc[1 + kk] = fma(b * (os[r][kk][1] * oj[kk][2][t]), dl[kk], acc[1 + kk]);
+                    const double lo2 = os[r][kk][1] * oj[kk][2][t];
+                    acc[1 + kk] = fma(b * lo2, dl[kk], acc[1 + kk]);
+                    if (POST) acc[NC + 1 + kk] = fma(kw * lo2, dl[kk], acc[NC + 1 + kk]);
                 }
             }
             double pre = pe[r][t];
@@ -189,23 +234,47 @@ __global__ __launch_bounds__(256, 2) void sens_pair_kernel(const double *__restr
                 for (int kk = KC - 2; kk >= 0; --kk) suf[kk] = suf[kk + 1] * E[kk + 1];
 #pragma unroll
                 for (int kk = 0; kk < KC; ++kk) {
-                    acc[1 + KC + kk] = fma(b * (pre * suf[kk]), dl[kk], acc[1 + KC + kk]);
+                    const double loo = pre * suf[kk];
+                    acc[1 + KC + kk] = fma(b * loo, dl[kk], acc[1 + KC + kk]);
+                    if (POST) acc[NC + 1 + KC + kk] = fma(kw * loo, dl[kk], acc[NC + 1 + KC + kk]);
                     pre *= E[kk];
                 }
             } else {
 #pragma unroll
                 for (int kk = 0; kk < KC; ++kk) pre *= E[kk];
             }
-            acc[0] = fma(b, pre - rs[r][0] * gj, acc[0]);
+            const double dv = pre - rs[r][0] * gj;
+            acc[0] = fma(b, dv, acc[0]);
+            if (POST) acc[NC] = fma(kw, dv, acc[NC]);
         }
     }
 #pragma unroll
-    for (int q = 0; q < NC; ++q) {
+    for (int q = 0; q < NA; ++q) {
         const double s = wave_sum(acc[q]);
         if (lane == 0) red[wave][q] = s;
     }
     __syncthreads();
-    if (t < NC) pout[t] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+    if (t < NA) pout[t] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);
+}
+
+template <bool TOTAL>
+__global__ __launch_bounds__(256, 2) void sens_pair_kernel(const double *__restrict__ aT, const double *__restrict__ mT,
+                                                           const double *__restrict__ loT, const double *__restrict__ g,
+                                                           const double *__restrict__ bw, const double *__restrict__ cb, long cb_stride,
+                                                           long n, long npad, int d, double *__restrict__ partial, long ncols)
+{
+    sens_pair_cells<TOTAL, false>(aT, mT, loT, g, bw, nullptr, nullptr, 0, cb, cb_stride, n, npad, d, partial, ncols);
+}
+
+// the same cells with the twin sums under K^-1 (Kinv [*, ldk], read at j <= i < n alone; pw: the build kernel's second point weight)
+template <bool TOTAL>
+__global__ __launch_bounds__(256, 2) void sens_post_pair_kernel(const double *__restrict__ aT, const double *__restrict__ mT,
+                                                                const double *__restrict__ loT, const double *__restrict__ g,
+                                                                const double *__restrict__ bw, const double *__restrict__ pw,
+                                                                const double *__restrict__ Kinv, long ldk, const double *__restrict__ cb,
+                                                                long cb_stride, long n, long npad, int d, double *__restrict__ partial, long ncols)
+{
+    sens_pair_cells<TOTAL, true>(aT, mT, loT, g, bw, pw, Kinv, ldk, cb, cb_stride, n, npad, d, partial, ncols);
 }
 
 // the host side of one input's constants; false: a negative or non-finite variance
@@ -250,21 +319,19 @@ int64_t sens_chunk(int64_t per, int64_t b)
     return std::min(chunk, b);
 }
 
-// GPX_SENS_CHUNK (read at every call): the most inputs of a chunk; default: what 2^27 doubles (1 GiB) of per-point data hold, at most 4096
-extern "C" int gpx_sensitivity_many(gpx_handle *h, const double *U, const double *S, int s_shared, int64_t b, double *mean, double *var_mean,
-                                    double *first, double *total)
+// GPX_SENS_CHUNK (read at every call): the most inputs of a chunk; default: what 2^27 doubles (1 GiB) of per-point data hold, at most 4096.
+// The body of both entry points; post: var_post, first_post and total_post are formed as well (the caller has checked them), K^-1 is read.
+static int sens_many(gpx_handle *h, const char *name, const double *U, const double *S, int s_shared, int64_t b, double *mean, double *var_mean,
+                     double *first, double *total, bool post, double *var_post, double *first_post, double *total_post)
 {
-    CHECK_H_PSEUDO_OK(h);
-    NEED_KERNEL(h, "gpx_sensitivity_many");   // the closed form is the ARD squared-exponential kernel's: names the kernel the handle holds
-    if (b < 0 || (b > 0 && (!U || !S || !mean || !var_mean || !first))) { gpx_set_error("gpx_sensitivity_many: bad arguments"); return GPX_ERR_BAD_ARG; }
-    if (b == 0) return 0;
     const int d = h->d;
     const int64_t n = h->n, np = h->npad, cbs = sens_cb_size(d), ns = s_shared ? 1 : b;
     const bool want_total = total != nullptr;
+    const int NW = post ? 2 : 1, NCW = NW * SEN_NC;   // the sums of one input and sweep: the beta set, then the Kinv set
     hipStream_t s = h->stream;
 
     // every variance is checked, and every input's constants formed, before the first launch
-    std::vector<double> Sh, cbh, rm, rv, rf, rt, oh;
+    std::vector<double> Sh, cbh, rm, rv, rf, rt, oh, pv, pf, pt;
     std::vector<int> nah;
     try {
         Sh.resize((size_t)(ns * d));
@@ -274,20 +341,26 @@ extern "C" int gpx_sensitivity_many(gpx_handle *h, const double *U, const double
         rv.assign((size_t)b, 0.0);
         rf.assign((size_t)(b * d), 0.0);
         if (want_total) rt.assign((size_t)(b * d), 0.0);
-    } catch (const std::bad_alloc &) { gpx_set_error("gpx_sensitivity_many: out of host memory"); return GPX_ERR_HIP; }
+        if (post) {
+            pv.assign((size_t)b, 0.0);
+            pf.assign((size_t)(b * d), 0.0);
+            if (want_total) pt.assign((size_t)(b * d), 0.0);
+        }
+    } catch (const std::bad_alloc &) { gpx_set_error("%s: out of host memory", name); return GPX_ERR_HIP; }
     GPX_TRY(fetch_small(Sh.data(), S, Sh.size()));
     for (int64_t i = 0; i < ns; ++i) {
         if (!sens_constants(h->w, &Sh[(size_t)(i * d)], d, &cbh[(size_t)(i * cbs)])) {
-            gpx_set_error("gpx_sensitivity_many: the variances of input %ld are not all finite and >= 0", (long)i);
+            gpx_set_error("%s: the variances of input %ld are not all finite and >= 0", name, (long)i);
             return GPX_ERR_BAD_ARG;
         }
         nah[(size_t)i] = (int)cbh[(size_t)(i * cbs + SEN_CROWS * d)];
     }
+    if (post) GPX_TRY(ensure_kinv(h));        // a pseudo-input handle holds P there from the start
 
-    const int64_t per = (3 * (int64_t)d + 2) * np, nrb = np / SEN_R, nbb = (np + 255) / 256;
+    const int64_t per = (3 * (int64_t)d + 2 + (post ? 1 : 0)) * np, nrb = np / SEN_R, nbb = (np + 255) / 256;
     const int64_t chunk = sens_chunk(per, b);
     const int max_sweeps = (d + SEN_KC - 1) / SEN_KC;
-    const int64_t max_cols = chunk * max_sweeps * SEN_NC;
+    const int64_t max_cols = chunk * max_sweeps * NCW;
 
     Scratch sc(s);
     double *pd = nullptr, *cbd = nullptr, *ud = nullptr, *part = nullptr, *mpart = nullptr, *od = nullptr;
@@ -297,23 +370,24 @@ extern "C" int gpx_sensitivity_many(gpx_handle *h, const double *U, const double
     GPX_TRY(sc.take(&part, nrb * max_cols));
     GPX_TRY(sc.take(&mpart, nbb * chunk));
     GPX_TRY(sc.take(&od, max_cols + chunk));
-    try { oh.resize((size_t)(max_cols + chunk)); } catch (const std::bad_alloc &) { gpx_set_error("gpx_sensitivity_many: out of host memory"); return GPX_ERR_HIP; }
+    try { oh.resize((size_t)(max_cols + chunk)); } catch (const std::bad_alloc &) { gpx_set_error("%s: out of host memory", name); return GPX_ERR_HIP; }
     GPX_HIP(hipMemcpyAsync(cbd, cbh.data(), sizeof(double) * cbh.size(), hipMemcpyHostToDevice, s));
     for (int64_t b0 = 0; b0 < b; b0 += chunk) {
         const int64_t bc = std::min(chunk, b - b0);
         double *aT = pd, *mT = aT + bc * d * np, *loT = mT + bc * d * np, *g = loT + bc * d * np, *bw = g + bc * np;
+        double *pw = post ? bw + bc * np : nullptr;
         const double *cbc = s_shared ? cbd : cbd + b0 * cbs;
         const long cb_stride = s_shared ? 0 : (long)cbs;
         int na_max = 0;
         for (int64_t i = 0; i < bc; ++i) na_max = std::max(na_max, nah[(size_t)(s_shared ? 0 : b0 + i)]);
         const int sweeps = (na_max + SEN_KC - 1) / SEN_KC;
-        const int64_t ncols = bc * sweeps * SEN_NC;
+        const int64_t ncols = bc * sweeps * NCW;
         GPX_HIP(hipMemcpyAsync(ud, U + b0 * d, sizeof(double) * bc * d, hipMemcpyDefault, s));
         {
             // the build is timed in the class of the N-fold builders' sums (GPX_K_QUAD), the pair pass in GPX_K_EXACT: tools/probe_sensitivity.py
             ProfScope ps(&h->prof, s, GPX_K_QUAD, (double)n * (double)bc * (60.0 * d + 60.0));
             hipLaunchKernelGGL(sens_build_kernel, dim3((unsigned)nbb, (unsigned)bc), dim3(256), 0, s, (const double *)h->x, (long)n, (long)np, d,
-                               (const double *)ud, cbc, cb_stride, (const double *)h->alpha, h->v, aT, mT, loT, g, bw, mpart);
+                               (const double *)ud, cbc, cb_stride, (const double *)h->alpha, h->v, aT, mT, loT, g, bw, mpart, pw);
             GPX_HIP(hipGetLastError());
         }
         GPX_TRY(launch_sum_columns(mpart, nbb, (int)bc, od + ncols, s));
@@ -322,7 +396,15 @@ extern "C" int gpx_sensitivity_many(gpx_handle *h, const double *U, const double
                 // na exponentials per visited pair and sweep
                 ProfScope ps(&h->prof, s, GPX_K_EXACT, 0.5 * (double)n * (double)n * (double)bc * sweeps * (25.0 * na_max + 40.0));
                 const dim3 grid((unsigned)nrb, (unsigned)sweeps, (unsigned)bc);
-                if (want_total)
+                if (post && want_total)
+                    hipLaunchKernelGGL(sens_post_pair_kernel<true>, grid, dim3(256), 0, s, (const double *)aT, (const double *)mT, (const double *)loT,
+                                       (const double *)g, (const double *)bw, (const double *)pw, (const double *)h->Kinv, (long)np, cbc, cb_stride,
+                                       (long)n, (long)np, d, part, (long)ncols);
+                else if (post)
+                    hipLaunchKernelGGL(sens_post_pair_kernel<false>, grid, dim3(256), 0, s, (const double *)aT, (const double *)mT, (const double *)loT,
+                                       (const double *)g, (const double *)bw, (const double *)pw, (const double *)h->Kinv, (long)np, cbc, cb_stride,
+                                       (long)n, (long)np, d, part, (long)ncols);
+                else if (want_total)
                     hipLaunchKernelGGL(sens_pair_kernel<true>, grid, dim3(256), 0, s, (const double *)aT, (const double *)mT, (const double *)loT,
                                        (const double *)g, (const double *)bw, cbc, cb_stride, (long)n, (long)np, d, part, (long)ncols);
                 else
@@ -339,22 +421,58 @@ extern "C" int gpx_sensitivity_many(gpx_handle *h, const double *U, const double
             const int na = nah[(size_t)(s_shared ? 0 : b0 + i)];
             rm[(size_t)(b0 + i)] = oh[(size_t)(ncols + i)];
             if (na == 0) continue;               // no uncertain coordinate: V, first and total stay 0.0
-            const double *o = &oh[(size_t)(i * sweeps * SEN_NC)];
+            const double *o = &oh[(size_t)(i * sweeps * NCW)];
             rv[(size_t)(b0 + i)] = o[0];         // sweep 0's V (every sweep forms the same sum)
+            double lr = 0.0;                     // log prod r over the active slots; the prior constants without cancellation
+            for (int q = 0; q < na; ++q) lr += c[3 * d + q];
+            if (post) pv[(size_t)(b0 + i)] = h->v * -expm1(lr) - o[SEN_NC];
             for (int l = 0; l < d; ++l) {
                 const int q = (int)c[2 * d + l];
                 if (q < 0) continue;
-                const double *oq = o + (q / SEN_KC) * SEN_NC;
+                const double *oq = o + (q / SEN_KC) * NCW;
                 rf[(size_t)((b0 + i) * d + l)] = oq[1 + q % SEN_KC];
                 if (want_total) rt[(size_t)((b0 + i) * d + l)] = oq[1 + SEN_KC + q % SEN_KC];
+                if (!post) continue;
+                const double c0q = c[3 * d + q], one_r = -expm1(c0q);
+                pf[(size_t)((b0 + i) * d + l)] = h->v * exp(lr - c0q) * one_r - oq[SEN_NC + 1 + q % SEN_KC];
+                if (want_total) pt[(size_t)((b0 + i) * d + l)] = h->v * one_r - oq[SEN_NC + 1 + SEN_KC + q % SEN_KC];
             }
         }
     }
     const hipError_t e = sc.wait_and_free();
-    if (e != hipSuccess) { gpx_set_error("gpx_sensitivity_many: %s", hipGetErrorString(e)); return GPX_ERR_HIP; }
+    if (e != hipSuccess) { gpx_set_error("%s: %s", name, hipGetErrorString(e)); return GPX_ERR_HIP; }
     GPX_HIP(hipMemcpy(mean, rm.data(), sizeof(double) * b, hipMemcpyDefault));
     GPX_HIP(hipMemcpy(var_mean, rv.data(), sizeof(double) * b, hipMemcpyDefault));
     GPX_HIP(hipMemcpy(first, rf.data(), sizeof(double) * b * d, hipMemcpyDefault));
     if (want_total) GPX_HIP(hipMemcpy(total, rt.data(), sizeof(double) * b * d, hipMemcpyDefault));
+    if (post) {
+        GPX_HIP(hipMemcpy(var_post, pv.data(), sizeof(double) * b, hipMemcpyDefault));
+        GPX_HIP(hipMemcpy(first_post, pf.data(), sizeof(double) * b * d, hipMemcpyDefault));
+        if (want_total) GPX_HIP(hipMemcpy(total_post, pt.data(), sizeof(double) * b * d, hipMemcpyDefault));
+    }
     return 0;
+}
+
+extern "C" int gpx_sensitivity_many(gpx_handle *h, const double *U, const double *S, int s_shared, int64_t b, double *mean, double *var_mean,
+                                    double *first, double *total)
+{
+    CHECK_H_PSEUDO_OK(h);
+    NEED_KERNEL(h, "gpx_sensitivity_many");   // the closed form is the ARD squared-exponential kernel's: names the kernel the handle holds
+    if (b < 0 || (b > 0 && (!U || !S || !mean || !var_mean || !first))) { gpx_set_error("gpx_sensitivity_many: bad arguments"); return GPX_ERR_BAD_ARG; }
+    if (b == 0) return 0;
+    return sens_many(h, "gpx_sensitivity_many", U, S, s_shared, b, mean, var_mean, first, total, false, nullptr, nullptr, nullptr);
+}
+
+// total and total_post are null together or not at all
+extern "C" int gpx_sensitivity_post_many(gpx_handle *h, const double *U, const double *S, int s_shared, int64_t b, double *mean, double *var_mean,
+                                         double *first, double *total, double *var_post, double *first_post, double *total_post)
+{
+    CHECK_H_PSEUDO_OK(h);                     // reads (x, alpha, Kinv, v, w) alone
+    NEED_KERNEL(h, "gpx_sensitivity_post_many");
+    if (b < 0 || (b > 0 && (!U || !S || !mean || !var_mean || !first || !var_post || !first_post || (total == nullptr) != (total_post == nullptr)))) {
+        gpx_set_error("gpx_sensitivity_post_many: bad arguments (total and total_post are null together or not at all)");
+        return GPX_ERR_BAD_ARG;
+    }
+    if (b == 0) return 0;
+    return sens_many(h, "gpx_sensitivity_post_many", U, S, s_shared, b, mean, var_mean, first, total, true, var_post, first_post, total_post);
 }

@@ -8,6 +8,8 @@ skgpuppy/UncertaintyPropagation.py:135-210.
   total_k  = E[Var_{x_k}(mu | x_~k)]          what is left when everything but x_k is known: first_k plus every interaction with x_k
   sum_k first_k <= V <= sum_k total_k;  the Sobol indices are first / V and total / V.
   second_kl = V_kl - first_k - first_l        with WHICH other input x_k interacts (second_order*; gpx_sensitivity_second_many)
+  posterior=True                              the same terms of the GP f itself, in posterior expectation: each plus the term of the
+                                              posterior residual (variances*, indices*; gpx_sensitivity_post_many, reads K^-1)
   C = E[grad f grad f^T]                      which DIRECTIONS matter: the active-subspace matrix, its diagonal the DGSM nu_k with
                                               total_k <= s_k nu_k (gradient_moments*, dgsm*, active_subspace; gpx_sensitivity_gradient_many)
 
@@ -71,8 +73,12 @@ class SensitivityAnalysis(object):
             raise ValueError("Sigma_x has a non-zero off-diagonal entry: the variance decomposition needs independent inputs")
         return np.array(np.diagonal(S))
 
-    def _many(self, U, Sigma_x, want_total=True):
-        """(mean WITHOUT meant [b], V [b], first [b, d], total [b, d] or None)"""
+    def _many(self, U, Sigma_x, want_total=True, posterior=False):
+        """(mean WITHOUT meant [b], V [b], first [b, d], total [b, d] or None); posterior: V, first and total of the GP itself in posterior
+        expectation, the mean part plus the posterior part of ONE gpx_sensitivity_post_many call"""
+        if posterior and self.distribution != "gaussian":
+            raise NotImplementedError("posterior=True: the closed form serves distribution='gaussian' (the Gaussian law) only, not %r"
+                                      % (self.distribution,))
         d = self.gp.d
         UU = _gpx.f64(U)
         if UU.ndim != 2 or UU.shape[1] != d:
@@ -84,6 +90,14 @@ class SensitivityAnalysis(object):
             return self._box_many(UU - half, UU + half, want_total)[:4]
         mean, V, first = np.empty(b), np.empty(b), np.empty((b, d))
         total = np.empty((b, d)) if want_total else None
+        if posterior:
+            vp, fp = np.empty(b), np.empty((b, d))
+            tp = np.empty((b, d)) if want_total else None
+            st = _gpx.lib.gpx_sensitivity_post_many(self.gp._dev().handle, _gpx.ptr(UU), _gpx.ptr(s), int(s.ndim == 1), b, _gpx.ptr(mean), _gpx.ptr(V),
+                                                    _gpx.ptr(first), _gpx.ptr(total) if want_total else None, _gpx.ptr(vp), _gpx.ptr(fp),
+                                                    _gpx.ptr(tp) if want_total else None)
+            _gpx.check(st, "gpx_sensitivity_post_many")
+            return mean, V + vp, first + fp, (total + tp if want_total else None)
         st = _gpx.lib.gpx_sensitivity_many(self.gp._dev().handle, _gpx.ptr(UU), _gpx.ptr(s), int(s.ndim == 1), b, _gpx.ptr(mean), _gpx.ptr(V),
                                            _gpx.ptr(first), _gpx.ptr(total) if want_total else None)
         _gpx.check(st, "gpx_sensitivity_many")
@@ -169,17 +183,19 @@ class SensitivityAnalysis(object):
         d = self.gp.d
         return self.second_order_indices_box_many(_gpx.f64(lo).reshape(1, d), _gpx.f64(hi).reshape(1, d))[0]
 
-    def variances_many(self, U, Sigma_x):
+    def variances_many(self, U, Sigma_x, posterior=False):
         """(means with meant [b], V [b], first [b, d], total [b, d]) for the rows of U (b, d); Sigma_x: [d] or a diagonal [d, d] for all of
-        them, or [b, d] / diagonal [b, d, d]"""
-        mean, V, first, total = self._many(U, Sigma_x)
+        them, or [b, d] / diagonal [b, d, d].  posterior=True: the terms of the GP f itself in posterior expectation, E*[Var f], E*[first_k
+        of f], E*[total_k of f] (Oakley and O'Hagan 2004): the terms of the mean plus those of the posterior residual, which are what the
+        plug-in terms miss where the emulator is uncertain (reads K^-1; Gaussian inputs only)."""
+        mean, V, first, total = self._many(U, Sigma_x, posterior=posterior)
         return mean + self.gp._get_mean_t(), V, first, total
 
-    def variances(self, u, Sigma_x):
+    def variances(self, u, Sigma_x, posterior=False):
         """(mean with meant, V, first [d], total [d]) at one input u [d]; Sigma_x: the variances [d] or a diagonal [d, d]"""
         d = self.gp.d
         s = self._variances_of(Sigma_x, d)
-        mean, V, first, total = self._many(_gpx.f64(u).reshape(1, d), s)
+        mean, V, first, total = self._many(_gpx.f64(u).reshape(1, d), s, posterior=posterior)
         return np.float64(mean[0] + self.gp._get_mean_t()), np.float64(V[0]), first[0], total[0]
 
     @staticmethod
@@ -189,15 +205,16 @@ class SensitivityAnalysis(object):
         out[live] = part[live] / V[live][..., None]
         return out
 
-    def indices_many(self, U, Sigma_x):
-        """(first / V, total / V), each [b, d]; zeros where V == 0"""
-        _mean, V, first, total = self._many(U, Sigma_x)
+    def indices_many(self, U, Sigma_x, posterior=False):
+        """(first / V, total / V), each [b, d]; zeros where V == 0.  posterior=True: the ratios of the posterior EXPECTATIONS of
+        variances_many(posterior=True) -- Oakley and O'Hagan's estimate of the indices of f, not the expectation of the ratio."""
+        _mean, V, first, total = self._many(U, Sigma_x, posterior=posterior)
         return self._ratio(first, V), self._ratio(total, V)
 
-    def indices(self, u, Sigma_x):
+    def indices(self, u, Sigma_x, posterior=False):
         """(first / V, total / V), each [d]; zeros where V == 0"""
         d = self.gp.d
-        f, t = self.indices_many(_gpx.f64(u).reshape(1, d), self._variances_of(Sigma_x, d))
+        f, t = self.indices_many(_gpx.f64(u).reshape(1, d), self._variances_of(Sigma_x, d), posterior)
         return f[0], t[0]
 
     # ---- second order: with WHICH other input x_k interacts (gpx_sensitivity_second_many) ----

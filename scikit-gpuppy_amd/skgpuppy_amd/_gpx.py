@@ -96,6 +96,7 @@ SIGNATURES = {
     "gpx_kinv_model_free": (None, [_hp]),
     "gpx_propagate_exact_model": (_int, [_hp, _dp, _int, _dp, _dp, _dp, _dp, _dbl, ctypes.POINTER(_dbl), ctypes.POINTER(_dbl)]),
     "gpx_sensitivity_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp, _dp, _dp, _dp]),
+    "gpx_sensitivity_post_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "gpx_sensitivity_second_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp]),
     "gpx_sensitivity_gradient_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp, _dp, _dp]),
     "gpx_sensitivity_box_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp, _dp, _dp, _dp, _dp]),
