@@ -324,6 +324,27 @@ int gpx_sensitivity_post_many(gpx_handle *h, const double *U, const double *S, i
  * pointers.  Handles, refusals (nothing written), b = 0, chunking (GPX_SENS_CHUNK), summation order and independence of the batch as
  * gpx_sensitivity_many. */
 int gpx_sensitivity_second_many(gpx_handle *h, const double *U, const double *S, int s_shared, int64_t b, double *second);
+/* EVERY term of the same decomposition, all interaction orders: where the variance that first_k, total_k and second_kl leave unexplained
+ * sits, and the Shapley effects (Owen 2014; Song, Nelson and Staum 2016).  With the notation above, per pair of training points and
+ * coordinate M_k = exp(lm_ik) exp(lm_jk), E_k = exp(lE_k(i,j)), dE_k = E_k - M_k; the coordinates with s_k > 0 are compacted into slots
+ * 0..na-1 in increasing coordinate order, the others folded into b_ij.  For a non-empty subset S of the slots
+ *   D_S = sum_ij b_ij prod_{q in S} dE_q prod_{q not in S, active} M_q
+ * is the variance of the ANOVA component of mu in x_S:
+ *   D_{k} = first_k,  D_{k,l} = second_kl,  sum_{S != {}} D_S = V,  sum_{S contains k} D_S = total_k,
+ *   V^closed_S = sum_{{} != T subset of S} D_T                                      the closed index of a set
+ *   Sh_k = sum_{S contains k} D_S / |S|,  sum_k Sh_k = V                             the Shapley effect
+ * The device forms the D_S themselves -- no closed second moment that mean^2 would have to be taken from -- so everything derived from
+ * them is a plain sum.  Every exponent evaluated is non-positive (lE_k by its completed square, M_k from per-point exp(lm_ik)); no
+ * quotient is formed.  The 2^na sums are ONE product on the fp64 matrix cores over the pairs: the slots are split in two halves, a pair's
+ * subset products over the first are the A operand, over the second the B operand (csrc/sensitivity_anova.hip: the lane map).
+ * U [b, d]; S [b, d] or ONE [d] when s_shared != 0; terms [b, tstride]: entry `mask` of a row is D_S with bit q of mask the q-th coordinate
+ * with s_k > 0 in increasing coordinate order; entry 0 and every entry from 2^na on are 0.0 exactly; na = 0: a row of zeros, no launch.
+ * At most GPX_ANOVA_MAX_ACTIVE uncertain coordinates per input, whatever d.  tstride < 2^na for any input, na > GPX_ANOVA_MAX_ACTIVE, a
+ * negative or non-finite variance, or a null required pointer: GPX_ERR_BAD_ARG before the first launch, nothing written; the text names
+ * the input.  Host or device pointers.  Handles, b = 0, chunking (GPX_SENS_CHUNK), summation order and independence of the batch as
+ * gpx_sensitivity_second_many. */
+#define GPX_ANOVA_MAX_ACTIVE 10
+int gpx_sensitivity_anova_many(gpx_handle *h, const double *U, const double *S, int s_shared, int64_t b, double *terms, int64_t tstride);
 /* Which DIRECTIONS of the input space matter: the second moment of the gradient under the same input law, the active-subspace matrix
  * C = E[grad f grad f^T] (closed form: Wycoff, Binois and Wild, "Sequential learning of active subspaces", 2021; no reference counterpart).
  * Its eigenvectors are the rotated inputs, its diagonal the derivative-based global sensitivity measures nu_k = C_kk, and by the Gaussian

@@ -8,6 +8,8 @@ skgpuppy/UncertaintyPropagation.py:135-210.
   total_k  = E[Var_{x_k}(mu | x_~k)]          what is left when everything but x_k is known: first_k plus every interaction with x_k
   sum_k first_k <= V <= sum_k total_k;  the Sobol indices are first / V and total / V.
   second_kl = V_kl - first_k - first_l        with WHICH other input x_k interacts (second_order*; gpx_sensitivity_second_many)
+  D_S, Sh_k                                   EVERY interaction order and the Shapley effects, sum_k Sh_k = V, for up to ten uncertain
+                                              inputs (anova*, shapley*, closed_variance; gpx_sensitivity_anova_many)
   posterior=True                              the same terms of the GP f itself, in posterior expectation: each plus the term of the
                                               posterior residual (variances*, indices*; gpx_sensitivity_post_many, reads K^-1)
   C = E[grad f grad f^T]                      which DIRECTIONS matter: the active-subspace matrix, its diagonal the DGSM nu_k with
@@ -250,6 +252,72 @@ class SensitivityAnalysis(object):
         """second / V [d, d]; zeros where V == 0"""
         d = self.gp.d
         return self.second_order_indices_many(_gpx.f64(u).reshape(1, d), self._variances_of(Sigma_x, d))[0]
+
+    # ---- every interaction order: the full ANOVA decomposition and the Shapley effects (gpx_sensitivity_anova_many) ----
+    def _anova_terms(self, U, Sigma_x):
+        """(terms [b, 2^na_max] by mask, active: b lists of the uncertain coordinates in increasing order): terms[i, mask] = D_S of input i
+        with bit q of mask the coordinate active[i][q]; the raw call's bits"""
+        if self.distribution != "gaussian":
+            raise NotImplementedError("anova*, shapley*, closed_variance: the closed form serves distribution='gaussian' (the Gaussian law) "
+                                      "only, not %r" % (self.distribution,))
+        d = self.gp.d
+        UU = _gpx.f64(U)
+        if UU.ndim != 2 or UU.shape[1] != d:
+            raise ValueError("U must be (b, %d)" % d)
+        b = len(UU)
+        s = self._variances_of(Sigma_x, d, b)
+        rows = s[None, :] if s.ndim == 1 else s
+        active = [[int(k) for k in np.flatnonzero(rows[0 if s.ndim == 1 else i] > 0)] for i in range(b)]
+        na = max([len(a) for a in active] + [0])
+        if na > _gpx.GPX_ANOVA_MAX_ACTIVE:
+            raise ValueError("%d uncertain coordinates: the full decomposition serves at most GPX_ANOVA_MAX_ACTIVE = %d per input"
+                             % (na, _gpx.GPX_ANOVA_MAX_ACTIVE))
+        terms = np.empty((b, 1 << na))
+        st = _gpx.lib.gpx_sensitivity_anova_many(self.gp._dev().handle, _gpx.ptr(UU), _gpx.ptr(s), int(s.ndim == 1), b, _gpx.ptr(terms), 1 << na)
+        _gpx.check(st, "gpx_sensitivity_anova_many")
+        return terms, active
+
+    def anova_many(self, U, Sigma_x):
+        """b dicts {tuple of coordinate indices: D_S} over the non-empty subsets S of each input's uncertain coordinates: D_S is the variance
+        of the ANOVA component of mu in x_S.  D_(k,) = first_k, D_(k, l) = second_kl, the values sum to V, those with k in S to total_k.  At
+        most GPX_ANOVA_MAX_ACTIVE uncertain coordinates per input.  Gaussian inputs only."""
+        terms, active = self._anova_terms(U, Sigma_x)
+        return [{tuple(a[q] for q in range(len(a)) if mask >> q & 1): terms[i, mask] for mask in range(1, 1 << len(a))}
+                for i, a in enumerate(active)]
+
+    def anova(self, u, Sigma_x):
+        """{tuple of coordinate indices: D_S} at one input u [d]; Sigma_x: the variances [d] or a diagonal [d, d]"""
+        d = self.gp.d
+        return self.anova_many(_gpx.f64(u).reshape(1, d), self._variances_of(Sigma_x, d))[0]
+
+    def shapley_many(self, U, Sigma_x):
+        """Sh [b, d]: the Shapley effects Sh_k = sum_{S contains k} D_S / |S| (Owen 2014), one attribution per input with sum_k Sh_k = V;
+        0.0 for a coordinate without variance.  The masks are summed in ascending order."""
+        terms, active = self._anova_terms(U, Sigma_x)
+        out = np.zeros((len(active), self.gp.d))
+        for i, a in enumerate(active):
+            for mask in range(1, 1 << len(a)):
+                share = terms[i, mask] / bin(mask).count("1")
+                for q, k in enumerate(a):
+                    if mask >> q & 1:
+                        out[i, k] += share
+        return out
+
+    def shapley(self, u, Sigma_x):
+        """Sh [d] at one input u [d]"""
+        d = self.gp.d
+        return self.shapley_many(_gpx.f64(u).reshape(1, d), self._variances_of(Sigma_x, d))[0]
+
+    def closed_variance(self, u, Sigma_x, subset):
+        """V^closed_S = Var(E[mu | x_S]) = sum of D_T over the non-empty T inside `subset` (coordinate indices; one without variance adds
+        nothing), the masks in ascending order"""
+        d = self.gp.d
+        subset = set(int(k) for k in subset)
+        if not all(0 <= k < d for k in subset):
+            raise ValueError("subset must hold coordinate indices in [0, %d)" % d)
+        terms, active = self._anova_terms(_gpx.f64(u).reshape(1, d), self._variances_of(Sigma_x, d))
+        inside = sum(1 << q for q, k in enumerate(active[0]) if k in subset)
+        return np.float64(sum(terms[0, mask] for mask in range(1, 1 << len(active[0])) if mask & ~inside == 0))
 
     # ---- which DIRECTIONS matter: the second moment of the gradient, the active-subspace matrix (gpx_sensitivity_gradient_many) ----
     def gradient_moments_many(self, U, Sigma_x, posterior=False):

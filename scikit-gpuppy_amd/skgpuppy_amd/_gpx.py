@@ -14,6 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GPX_LIB", os.path.join(_HERE, "libgpx.so"))   # GPX_LIB: diagnostic builds only
 
 GPX_ERR_BAD_ARG, GPX_ERR_HIP, GPX_ERR_NO_DEVICE, GPX_ERR_STATE = -1, -2, -3, -4
+GPX_ANOVA_MAX_ACTIVE = 10      # include/gpx.h: the uncertain coordinates gpx_sensitivity_anova_many serves per input
 K_GRAM, K_GEMM, K_POTRF_LEAF, K_TRSV, K_REDUCE, K_QUAD, K_EXACT, K_GEMM_SMALL, K_TRSV_RIDE, K_GEMM_EMU = range(10)
 KERNEL_CLASS_NAMES = ["gram", "gemm_f64_mfma", "potrf_leaf", "trsv", "predict_reduce", "approx_quad", "exact_sum",
                       "gemm_f64_mfma_small_tiles", "trsv_under_factorisation", "gemm_f64_emulated_int8"]
@@ -98,6 +99,7 @@ SIGNATURES = {
     "gpx_sensitivity_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp, _dp, _dp, _dp]),
     "gpx_sensitivity_post_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "gpx_sensitivity_second_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp]),
+    "gpx_sensitivity_anova_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp, _i64]),
     "gpx_sensitivity_gradient_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp, _dp, _dp]),
     "gpx_sensitivity_box_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp, _dp, _dp, _dp, _dp]),
     "gpx_sensitivity_box_second_many": (_int, [_hp, _dp, _dp, _int, _i64, _dp]),
